@@ -9,16 +9,20 @@ oracle implements).
       N = 1 runs in this process.  N > 1: this process touches no GPU; it starts N child ranks (one per GPU, RANK / LOCAL_RANK /
       WORLD_SIZE / MASTER_* in their environment), prints rank 0's JSON line and exits non-zero if any rank fails.  Started
       under torch.distributed.run (WORLD_SIZE already in the environment) the process IS a rank and starts nothing.
+      A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step` = wall time of one
+      timed step).  --full adds everything else below: the kernel's HIP-event time and roofline block, `profile_key`, the
+      layout steps, extra.* and `cpu_baseline` (--no-extra / --no-cpu leave the last parts out again).
+      --dump-outputs DIR writes C of the last timed step (dump_outputs), after the timing.
 
   primary line (`value`): BASELINE.json's metric configuration — 4096^3 Qgemul, int<8,8> signed operands (configs[2]) in the
       linear class (QgemulMulArgs<intBits<17>,fracBits<16>>, QgemulAddArgs<Qu<intBits<29>,fracBits<16>>>, C = Qu<23,8>) on the
       3 x 3 int8-limb MFMA kernel; N > 1: every rank computes its own 4096 rows of a (4096 N) x 4096 x 4096 product (B
       replicated) and ONE gather of the packed C shards to rank 0 per step is the only collective — the
       LIBRARY's RCCL gather (qgemul_comm_*, include/qgemul.h); scaling = "weak".
-  extra.c4 (every N): BASELINE.json configs[3] — 16384 x 16384 x 4096 int<4,3>, linear class, STRONG scaling: rank r owns
+  extra.c4 (--full, every N): BASELINE.json configs[3] — 16384 x 16384 x 4096 int<4,3>, linear class, STRONG scaling: rank r owns
       16384 / N rows (whole 256-row packed tiles), B replicated, packed 1-byte C, gathered to rank 0; reported without the
       gather, with one gather per step, and with the gather cut into row chunks that travel while later chunks compute.
-  extra.c3T / c3Td / c2L / c2T / c5TF / c5B / c5L / reduce / long_k / w16 / u8 (N = 1): the remaining BASELINE configurations and
+  extra.c3T / c3Td / c2L / c2T / c5TF / c5B / c5L / reduce / long_k / w16 / u8 (--full, N = 1): the remaining BASELINE configurations and
       the round's other paths (w16, u8: 16-bit words and unsigned bytes, stored centred), each with its own roofline block against its declared bound.
 
 No PyTorch anywhere: device memory comes from the engine (qgemul_dev_alloc), the collective is the library's, timing uses HIP
@@ -48,6 +52,8 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
+MFMA_KERNELS = ("mfma_i8", "mfma_i8_limb", "mfma_cplx")
+DUMP_MAX_VALUES = 1 << 22      # --dump-outputs: at most this many float64 values over all parts of C (32 MiB)
 INT8_DENSE_PEAK_OPS = 5.0e15   # MI355X dense int8 MFMA, /opt/skills/guides/MI355X_MICROARCH.md (I8 = 2x BF16 ~2.5 PF)
 HBM_PEAK = 8.0e12
 N_SIMD, LANES, CYCLES_PER_VALU_INSTR = 256 * 4, 64, 4.0
@@ -72,7 +78,13 @@ def parse_args(argv=None):
     ap.add_argument("--launch-timeout", type=float, default=1500.0, help="--gpus N parent: seconds to wait for rank 0 before killing every rank")
     ap.add_argument("--c4-steps", type=int, default=20)
     ap.add_argument("--c4-chunks", type=int, default=0, help="row chunks of a rank's configuration-4 shard gathered while later chunks compute (0 = one per 256 tiles)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true", help="besides the headline: the kernel's HIP-event times and roofline block, profile key, layout steps, "
+                                                        "configuration 4, the other configurations and the CPU baseline (--no-extra / --no-cpu leave parts out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write C of the last timed step to DIR/<name>.npy (float64 values, see dump_outputs)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------------- launcher
@@ -165,12 +177,21 @@ REDUCE_TEXT = "batched Qreduce: 65536 vectors of 4096 int<8,8> elements (TRN::TC
 REDUCEW_TEXT = "batched Qreduce: 65536 vectors of 4096 int<15,16> elements (32-bit words, default modes), every tree node one saturating 32-bit add; one wave per row"
 
 
+def reduce_elem(name):
+    """element type of the Qreduce workloads"""
+    from qublas_amd.desc import Qu, SAT, TRN
+    return Qu(8, 8, True, TRN.TCPL, SAT.ZERO) if name == "reduce" else Qu(15, 16)
+
+
+def result_elem(name, wls, K):
+    from qublas_amd.desc import reduce_result_type
+    return wls[name]["c"] if name in wls else reduce_result_type(reduce_elem(name), [], K)
+
+
 def make_desc(name, wls, M, N, K):
-    from qublas_amd.desc import Qu, SAT, TRN, lower, lower_reduce
-    if name == "reduce":
-        return lower_reduce(Qu(8, 8, True, TRN.TCPL, SAT.ZERO), M, K)
-    if name == "reduceW":
-        return lower_reduce(Qu(15, 16), M, K)
+    from qublas_amd.desc import lower, lower_reduce
+    if name in ("reduce", "reduceW"):
+        return lower_reduce(reduce_elem(name), M, K)
     wl = wls[name]
     return lower(wl["a"], wl["b"], wl["c"], M, N, K, mul_args=wl["mul"], add_args=wl["add"])
 
@@ -269,7 +290,7 @@ def roofline_block(name, info, M, N, K, kms, singles, capi, cb):
     if prof:
         r["kernel_symbol"] = prof.get("kernel_symbol")
         r["traffic_source"] = f"{prof['profile']}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE of an earlier run of the same command on the same kernel (HEAD {prof.get('head')}), not this run"
-    if kernel in ("mfma_i8", "mfma_i8_limb", "mfma_cplx"):
+    if kernel in MFMA_KERNELS:
         limbs = max(1, info.limbs[0] * info.limbs[1])
         r.update({"bound": "mfma", "achieved": achieved / 1e12, "peak": INT8_DENSE_PEAK_OPS / 1e12, "unit": "TOP/s (int8-equivalent, algorithmic 2*M*N*K)",
                   "frac": achieved / INT8_DENSE_PEAK_OPS, "limbs": [info.limbs[0], info.limbs[1]], "mfma_issue_frac": achieved * limbs / INT8_DENSE_PEAK_OPS,
@@ -323,6 +344,35 @@ def measure_config(ctx, name, wls, capi, iters, flags=0):
         p.close()
         bufs.free()
     return rec
+
+
+def dump_outputs(out_dir, ctx, plan, c_elem, packed_cs, M, N):
+    """--dump-outputs: C as a caller receives it, i.e. unpacked into the reference's host layout (column-major, one M x N band per
+    rank in `packed_cs`, rank by rank), each part written as DIR/C.npy (complex: C_real.npy, C_imag.npy) of float64 values
+    raw * 2^-fracBits, exact up to 53 significant bits.  Above DUMP_MAX_VALUES in all, a fixed, seeded sample of positions
+    (ascending) is written, the same on every run with the same arguments."""
+    import numpy as np
+    from oracle.qoracle import WIDE, host_dtype
+    from qublas_amd.desc import Qcomplex
+    dt = host_dtype(c_elem)
+    if dt.itemsize != plan.info.host_elem_bytes[2]:      # the unpack writes M N host_elem_bytes[2] bytes into hC
+        raise RuntimeError(f"host element of C: {dt.itemsize} bytes here, {plan.info.host_elem_bytes[2]} in the plan")
+    host = np.empty(len(packed_cs) * M * N, dt)
+    hC = ctx.alloc(M * N * dt.itemsize)
+    try:
+        for r, pc in enumerate(packed_cs):
+            plan.unpack_c(pc, hC)
+            ctx.d2h(host[r * M * N:(r + 1) * M * N], hC)      # (same stream as the unpack, synchronised)
+    finally:
+        ctx.free(hC)
+    parts = [("C_real", c_elem.real, host["re"]), ("C_imag", c_elem.imag, host["im"])] if isinstance(c_elem, Qcomplex) else [("C", c_elem, host)]
+    cap = DUMP_MAX_VALUES // len(parts)
+    idx = np.sort(np.random.default_rng(0).choice(host.size, cap, replace=False)) if host.size > cap else None
+    os.makedirs(out_dir, exist_ok=True)
+    for nm, e, raw in parts:
+        raw = raw if idx is None else raw[idx]
+        v = raw["hi"].astype(np.float64) * 2.0 ** 64 + raw["lo"] if raw.dtype == WIDE else raw.astype(np.float64)
+        np.save(os.path.join(out_dir, nm + ".npy"), np.ldexp(v, -e.fracBits))
 
 
 # ---------------------------------------------------------------------------------------------------------------- the c4 leg
@@ -541,25 +591,21 @@ def main(argv=None):
 
     out = None
     if rank == 0:
-        # dominant kernel, HIP events on the engine's own stream; SURVEY.md §8-d asks for median and min beside the mean
-        kms = plan.time_execute(tC, tA, tB, 3, max(10, min(args.steps, 100)))
-        singles = sorted(plan.time_execute(tC, tA, tB, 0, 1) for _ in range(30))
-        roof = roofline_block(name, info, M, N, K, kms, singles, capi, c_container_bytes(wls[name]["c"]) if name in wls else 4)
-        mfma = roof["bound"] == "mfma"
+        if args.dump_outputs:           # C of the last timed step (rank 0 holds every rank's band after the last gather)
+            last = ((state["i"] - 1) & 1) if use_dist else 0
+            dump_outputs(args.dump_outputs, ctx, plan, result_elem(name, wls, K), land[last] if use_dist else [tC], M, N)
         wtext = wls[name]["text"] if name in wls else (REDUCEW_TEXT if name == "reduceW" else REDUCE_TEXT)
+        ms_step = dt / args.steps * 1e3
         out = {"metric": "int-MAC/s (2*M*N*K/s) for Qgemul 4096^3 int<8,8>; % of MI355X int8 peak", "value": value,
                "unit": "int-op/s (2*M*N*K/s)", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-               "ms_per_step": dt / args.steps * 1e3, "ms_per_step_events": kms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-               "dtype": "i8 limbs -> i32/i64" if mfma else "i32", "data": "synthetic",
+               "ms_per_step": ms_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+               "dtype": "i8 limbs -> i32/i64" if capi.KERNEL_NAMES[info.kernel] in MFMA_KERNELS else "i32", "data": "synthetic",
                "config": {"workload": wtext, "baseline_config": wls[name]["cfg"] if name in wls else "SURVEY.md 8-f #1", "M_per_gpu": M, "N": N, "K": K,
                           "class": "linear" if info.cls == 1 else "tree",
                           "sharding": f"rows of A/C over {world} rank(s), B replicated, one RCCL gather of C to rank 0" if world > 1 else "single GPU"},
                "prewarm_launches": PREWARM,
-               "pct_of_int8_peak": 100.0 * value / (INT8_DENSE_PEAK_OPS * world),
-               "roofline": roof,
-               "profile_key": profmeta.profile_key(roof["kernel"], roof["kernel_form"], ops_rank / 2.0)}
+               "pct_of_int8_peak": 100.0 * value / (INT8_DENSE_PEAK_OPS * world)}
         if use_dist:
-            out["value_without_gather"] = ops_rank / (kms * 1e-3) * world   # the curve with and without the gather
             out["gather_bytes_per_step_per_rank"] = cbytes
             out["rccl_world_size"] = net.reported_world()    # rccl: ncclCommCount of the library's communicator
             out["backend"] = net.name
@@ -567,11 +613,21 @@ def main(argv=None):
                 out["backend_note"] = backend_note
             if net.name == "rccl":
                 out["rccl_version"] = net.comm.info()[2]
-            ms_step = dt / args.steps * 1e3
-            out["gather_exposed_ms"] = max(0.0, ms_step - kms)
-            out["gather_GBps_into_root_exposed"] = (cbytes * (world - 1) / (max(ms_step - kms, 1e-6) * 1e-3) / 1e9) if world > 1 else None
+        if args.full:
+            from qublas_amd import profmeta
+            # dominant kernel, HIP events on the engine's own stream; SURVEY.md §8-d asks for median and min beside the mean
+            kms = plan.time_execute(tC, tA, tB, 3, max(10, min(args.steps, 100)))
+            singles = sorted(plan.time_execute(tC, tA, tB, 0, 1) for _ in range(30))
+            roof = roofline_block(name, info, M, N, K, kms, singles, capi, c_container_bytes(wls[name]["c"]) if name in wls else 4)
+            out["ms_per_step_events"] = kms
+            out["roofline"] = roof
+            out["profile_key"] = profmeta.profile_key(roof["kernel"], roof["kernel_form"], ops_rank / 2.0)
+            if use_dist:
+                out["value_without_gather"] = ops_rank / (kms * 1e-3) * world   # the curve with and without the gather
+                out["gather_exposed_ms"] = max(0.0, ms_step - kms)
+                out["gather_GBps_into_root_exposed"] = (cbytes * (world - 1) / (max(ms_step - kms, 1e-6) * 1e-3) / 1e9) if world > 1 else None
     extra = {}
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         # configuration 4 runs on every rank count (strong scaling); collective inside: every rank takes part
         try:
             c4 = c4_leg(args, ctx, wls, capi, net, world, rank)
@@ -581,7 +637,7 @@ def main(argv=None):
             if use_dist:
                 raise              # a rank that drops out of a collective must not leave the others waiting
             extra["c4"] = {"error": f"{type(e).__name__}: {e}"}
-    if rank == 0 and world == 1 and not args.no_extra:
+    if args.full and rank == 0 and world == 1 and not args.no_extra:
         # the layout steps either side of the hot path, timed separately (never part of `value`)
         try:
             hb = info.host_elem_bytes
@@ -629,7 +685,7 @@ def main(argv=None):
                 extra[nm] = {"error": f"{type(e).__name__}: {e}"}
     if rank == 0 and extra:
         out["extra"] = extra
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         try:
             out["cpu_baseline"] = cpu_baseline((wls[name]["ref"] if name in wls else None) or "c3L")
         except Exception as e:

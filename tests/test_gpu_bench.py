@@ -2,13 +2,14 @@
 and starts the two ranks itself; on the one-GPU test box both ranks share the card and the packed bands travel over the host
 transport (`--backend host`: RCCL refuses two ranks on one device; that run is the driver's).  The RCCL branch — the library's
 communicator, the gather on its own stream, device-side ordering against the GEMMs, barrier and max — runs here with a world of
-ONE rank.  Both legs of the JSON line are checked: the metric workload and extra.c4 (configuration 4, strong scaling, with and
+ONE rank.  Both legs of the --full JSON line are checked: the metric workload and extra.c4 (configuration 4, strong scaling, with and
 without the gather).  bench.py imports no PyTorch."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -38,7 +39,7 @@ def check_common(j, world):
 
 
 def test_self_launcher_two_ranks_host_transport():
-    j = run_bench("--gpus", "2", "--backend", "host", "--steps", "5", "--warmup", "2", "--prewarm", "20", "--no-cpu", "--c4-steps", "3")
+    j = run_bench("--full", "--gpus", "2", "--backend", "host", "--steps", "5", "--warmup", "2", "--prewarm", "20", "--no-cpu", "--c4-steps", "3")
     c4 = check_common(j, 2)
     assert j["rccl_world_size"] == 2 and j["backend"] == "host" and j["gather_bytes_per_step_per_rank"] == 4096 * 4096 * 4
     assert c4["rows_per_rank"] == [8192, 8192] and c4["rccl_world_size"] == 2
@@ -66,14 +67,14 @@ def test_two_ranks_under_torch_distributed_run_as_the_driver_launches_them():
 
 def test_self_launcher_three_ranks_ragged_partition():
     """16384 rows over 3 ranks: 64 blocks of 256 rows do not divide — bands of 22 / 21 / 21 blocks; the gather pads to the largest."""
-    j = run_bench("--gpus", "3", "--backend", "host", "--steps", "3", "--warmup", "1", "--prewarm", "10", "--no-cpu", "--c4-steps", "2")
+    j = run_bench("--full", "--gpus", "3", "--backend", "host", "--steps", "3", "--warmup", "1", "--prewarm", "10", "--no-cpu", "--c4-steps", "2")
     c4 = check_common(j, 3)
     assert c4["rows_per_rank"] == [5632, 5376, 5376] and c4["gather_bytes_per_rank"] == 5632 * 16384
     assert c4["value_one_gather"] > 0
 
 
 def test_rccl_branch_with_one_rank():
-    j = run_bench("--gpus", "1", "--force-dist", "--steps", "5", "--warmup", "2", "--prewarm", "20", "--no-cpu", "--c4-steps", "3")
+    j = run_bench("--full", "--gpus", "1", "--force-dist", "--steps", "5", "--warmup", "2", "--prewarm", "20", "--no-cpu", "--c4-steps", "3")
     c4 = check_common(j, 1)
     assert j["rccl_world_size"] == 1 and j["backend"] == "rccl" and j["rccl_version"] > 20000     # ncclCommCount / ncclGetVersion of the library's communicator
     assert c4["rccl_world_size"] == 1 and c4["backend"] == "rccl" and c4["value_one_gather"] > 1e14
@@ -96,7 +97,7 @@ def test_a_failing_rank_fails_the_launcher():
 
 
 def test_single_gpu_line_carries_every_baseline_configuration():
-    j = run_bench("--steps", "10", "--warmup", "3", "--prewarm", "50", "--c4-steps", "5", timeout=900)
+    j = run_bench("--full", "--steps", "10", "--warmup", "3", "--prewarm", "50", "--c4-steps", "5", timeout=900)
     check_common(j, 1)
     assert j["cpu_baseline"]["value"] and j["cpu_baseline"]["kind"] in ("reference", "port")
     ex = j["extra"]
@@ -115,3 +116,24 @@ def test_single_gpu_line_carries_every_baseline_configuration():
     assert ex["c3T"]["launches_timed"] >= 10 and ex["reduce"]["roofline"]["frac"] > 0.3
     assert j["ms_per_step_events"] > 0 and j["profile_key"]["engine_kernel"] == "mfma_i8_limb"
     assert j["roofline"]["traffic"] is None or "traffic_source" in j["roofline"]
+
+
+@pytest.mark.parametrize("gpus", [1, 2])
+def test_plain_line_and_dumped_outputs(oracle, tmp_path, gpus):
+    """A plain run prints the headline only (no per-kernel timing, extras or CPU baseline).  --dump-outputs writes C of the last
+    timed step: the oracle's product of the operands bench.py generated (rank r's A from seed 1 + 1000 r, B from seed 2), rank by
+    rank, as float64 values."""
+    from bench import workloads
+    from qublas_amd.desc import lower
+    S = 256
+    j = run_bench("--gpus", str(gpus), "--backend", "host", "--size", str(S), "--steps", "3", "--warmup", "1", "--prewarm", "0",
+                  "--dump-outputs", str(tmp_path))
+    assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["value"] > 0 and j["dtype"] == "i8 limbs -> i32/i64"
+    assert not {"roofline", "ms_per_step_events", "profile_key", "extra", "cpu_baseline", "layout_steps"} & set(j)
+    wl = workloads()["c3L"]
+    d = lower(wl["a"], wl["b"], wl["c"], S, S, S, mul_args=wl["mul"], add_args=wl["add"])
+    B = oracle.fill(wl["b"], S * S, 2)
+    exp = np.concatenate([oracle.gemm(d, oracle.fill(wl["a"], S * S, 1 + 1000 * r), B, wl["c"], nthreads=8) for r in range(gpus)])
+    assert os.listdir(tmp_path) == ["C.npy"]
+    got = np.load(tmp_path / "C.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, exp.astype(np.float64) * 2.0 ** -wl["c"].fracBits)

@@ -104,12 +104,17 @@ def _probe(src, extra_inc, tmp_path):
     return [json.loads(l) for l in out.splitlines() if l.strip()]
 
 
-@pytest.mark.skipif(not (os.path.exists(CLANG) and os.path.isdir("/root/reference/include")),
-                    reason="needs AMD clang and the reference header (build container)")
-def test_reference_binding_lowering(tmp_path):
-    """include/qgemul_reference_binding.hpp compiled against the REAL reference header."""
+REF_BINDING_PROBE = os.path.join(ROOT, "oracle", "_ref", "ref_binding_probe")
+
+
+@pytest.mark.skipif(not os.path.exists(REF_BINDING_PROBE),
+                    reason="oracle/_ref/ref_binding_probe was not built (build() makes it where the reference header is present)")
+def test_reference_binding_lowering():
+    """include/qgemul_reference_binding.hpp compiled against the REAL reference header (tests/binding/ref_binding_probe.cpp,
+    built into oracle/_ref/ by oracle/Makefile)."""
     gold = golden_by_name()
-    recs = _probe("ref_binding_probe.cpp", ["-I/root/reference/include"], tmp_path)
+    out = subprocess.check_output([REF_BINDING_PROBE], text=True)
+    recs = [json.loads(l) for l in out.splitlines() if l.strip()]
     eps = [r for r in recs if "epilogue" in r]
     epcs = [r for r in recs if "epilogue_cplx" in r]
     recs = [r for r in recs if "epilogue" not in r and "epilogue_cplx" not in r]
