@@ -87,6 +87,7 @@ struct qgemul_plan {
     QCGeom pc;
     QHostElem ha, hb, hc;
     QTreeTable* dev_table;
+    QTreeChoice tc;       // the tree kernels' step form that launches (qg_tree_choice: the diagnostic library's A/B switches applied)
     int64_t* workspace;   // complex linear class: raw dot products [2Mh x 2Nh] int64
     QMfmaCfg cfg;
     // element-wise epilogue (qgemul_epilogue): pc then describes packed D; pc_c is the kernel's own packed C, which
@@ -353,12 +354,19 @@ static int plan_geometry(const qgemul_desc* d, uint32_t flags, QAnalysis* an, qg
         }
     } else {
         const bool fast = !(flags & QG_OPT_GENERIC_TREE);
-        // 32-bit words on the one-column kernel (QAnalysis::gemv_w32): rows of at least 256 leaves; like fast_mode 10 it has no
-        // run-time-mode form, QG_OPT_RUNTIME_MODES keeps the 64-bit-value form (the tests' second opinion)
-        const bool gemv_w32 = an->gemv_wide_ok && an->gemv_w32 && !(flags & QG_OPT_RUNTIME_MODES) && an->tree.n_levels_k >= 8;
-        kernel = an->wide ? QG_KERNEL_TREE_I128 : d->is_complex ? ((an->cplx_fast_ok && fast) ? QG_KERNEL_TREE_CPLX_I32 : QG_KERNEL_TREE_CPLX)
-                               : (((an->gemv_ok || gemv_w32) && fast) ? QG_KERNEL_GEMV_I32 : (an->gemv_wide_ok && fast) ? QG_KERNEL_GEMV_I64
-                                  : (an->tree_fast_ok && fast && !(an->fast_mode == 10 && (flags & QG_OPT_RUNTIME_MODES))) ? QG_KERNEL_TREE_I32 : QG_KERNEL_TREE_I64);   // (fast_mode 10, 32-bit words: no run-time-mode form on that kernel)
+        const QTreeChoice tc = qg_tree_choice(an, d, flags, false);
+        kernel = tc.kernel;
+        // which form of the kernel's steps this descriptor gets (tests assert their coverage through it)
+        if (kernel == QG_KERNEL_TREE_I128)
+            snprintf(info->reason, sizeof info->reason, "exact tree evaluation on 128-bit values (intermediates of %d bits)", an->max_bits);
+        if (kernel == QG_KERNEL_TREE_I32)
+            snprintf(info->reason, sizeof info->reason, "exact tree evaluation; tree kernel steps: %s", qg_form_name(tc.tree));
+        if (kernel == QG_KERNEL_GEMV_I64)
+            snprintf(info->reason, sizeof info->reason, "exact tree evaluation; one-column kernel steps: run-time modes, 64-bit values");
+        if (kernel == QG_KERNEL_GEMV_I32)
+            snprintf(info->reason, sizeof info->reason, "exact tree evaluation; one-column kernel steps: %s", qg_form_name(tc.gemv));
+        if (kernel == QG_KERNEL_TREE_CPLX_I32)
+            snprintf(info->reason, sizeof info->reason, "exact tree evaluation; complex kernel steps: %s", qg_form_name(tc.cplx));
         // the 32-bit tree kernels walk a perfect binary tree: their operands are zero-padded along K to 2^n_levels leaves
         // (a node whose right child is a zero leaf / zero subtree is the reference's converting copy of an odd leftover)
         const bool t64 = kernel == QG_KERNEL_TREE_I64 && an->tree64_ok && fast;   // the 2x2-per-lane 64-bit kernel, not the general one
@@ -371,26 +379,6 @@ static int plan_geometry(const qgemul_desc* d, uint32_t flags, QAnalysis* an, qg
         pc->tm = pc->tn = 0;
     }
     info->kernel = kernel;
-    if (kernel == QG_KERNEL_TREE_I128)
-        snprintf(info->reason, sizeof info->reason, "exact tree evaluation on 128-bit values (intermediates of %d bits)", an->max_bits);
-    if (kernel == QG_KERNEL_TREE_I32) {
-        const int fm = (flags & QG_OPT_RUNTIME_MODES) ? 0 : an->fast_mode;
-        snprintf(info->reason, sizeof info->reason, "exact tree evaluation; tree kernel steps: %s",
-                 fm == 10 ? (an->tree.lj.e[1] ? "one 32-bit format, WRP::TCPL, wrapping word adds" : an->tree.lj.e[0] > 0 ? "one format, SAT::TCPL, justified words" : "one 32-bit format, SAT::TCPL, saturating word adds") : fm >= 8 ? "one format, SAT::TCPL, left-justified, packed nodes" : fm == 7 ? "one format, SAT::TCPL, left-justified, packed 16-bit" : fm == 6 ? "one format, SAT::TCPL, left-justified" : fm == 1 ? "one format, SAT::ZERO" : fm == 2 ? "one format, SAT::TCPL" : fm == 3 ? "per-level formats, compact (clamps)" : fm == 4 ? "per-level formats, compact" : fm == 5 ? "per-level formats, compact (unbiased)" : "run-time modes");
-    }
-    if (kernel == QG_KERNEL_GEMV_I64)
-        snprintf(info->reason, sizeof info->reason, "exact tree evaluation; one-column kernel steps: run-time modes, 64-bit values");
-    if (kernel == QG_KERNEL_GEMV_I32) {
-        const int fm = (flags & QG_OPT_RUNTIME_MODES) ? 0 : an->gemv_fixed;
-        snprintf(info->reason, sizeof info->reason, "exact tree evaluation; one-column kernel steps: %s",
-                 fm == 1 ? "one format, SAT::ZERO" : fm == 2 ? "one format, SAT::TCPL" : fm == 3 ? "per-level formats, compact (clamps)" : fm == 5 ? "per-level formats, compact" : (fm == 6 || fm == 7) ? "one 32-bit format, saturating adds" : "run-time modes");
-    }
-    if (kernel == QG_KERNEL_TREE_CPLX_I32) {
-        // which form of the complex kernel's steps this descriptor gets (tests assert their coverage through it)
-        const int fx = (flags & QG_OPT_RUNTIME_MODES) ? 0 : an->cplx_fixed_ok;
-        snprintf(info->reason, sizeof info->reason, "exact tree evaluation; complex kernel steps: %s",
-                 fx >= 8 ? "compact, branch-free rounding / overflow kinds" : fx == 6 ? "fixed modes, one clamp, packed 16-bit" : fx == 5 ? "fixed modes, one clamp, left-justified" : fx == 4 ? "fixed modes, one clamp for the whole loop" : fx == 3 ? "compact, rounding / overflow kinds" : fx == 2 ? "fixed modes, compact" : fx == 1 ? "fixed modes, table" : "run-time modes");
-    }
     info->limbs[0] = LA;
     info->limbs[1] = LB;
     info->packed_bytes[0] = (int64_t)parts * (pa->limbs ? pa->limbs : 1) * pa->rows_p * pa->K_p * pa->cbytes;
@@ -734,6 +722,7 @@ static int plan_create_view(qgemul_ctx* c, const qgemul_desc* d, const EpView* e
                            ev, &p->ept, &p->pc_c, &p->ept_im, &p->comp);
     if (st != QG_OK) { delete p; return st; }
     p->variant = p->cfg.variant;
+    p->tc = qg_tree_choice(&p->an, d, opt_flags, true);
     DeviceScope scope(c->device);
     if (scope.err != hipSuccess || hipMalloc((void**)&p->dev_table, sizeof(QTreeTable)) != hipSuccess) {
         delete p;
@@ -1218,35 +1207,21 @@ static int execute_kernel(qgemul_plan* p, void* packedC, const void* packedA, co
         QG_HIP(qg_launch_cplx_combine(g, st));
         return QG_OK;
     }
-    case QG_KERNEL_TREE_I32: {
-        static const bool no_lj = QG_DIAG_ENV("QG_NO_LEFT_JUSTIFIED");   // A/B switch (diagnostic library): the form such a descriptor had before
-        static const bool no_pk = QG_DIAG_ENV("QG_NO_PACKED16");
-        int fm = (p->an.fast_mode >= 6 && p->an.fast_mode <= 9 && no_lj) ? p->an.fast_mode_base : (p->an.fast_mode >= 7 && p->an.fast_mode <= 9 && no_pk) ? 6 : p->an.fast_mode;
-        if (fm == 10) {   // 32-bit words: product shift 10 ... 23 -> k_tree_fast<., 18>; justified words (lj.e[0] > 0) -> <., 19 / 20>
-            const bool mad = p->an.tree.lj.s >= 10 && p->an.tree.lj.s <= 23;
-            fm = p->an.tree.lj.e[1] ? 14 : p->an.tree.lj.e[0] > 0 ? (mad ? 13 : 12) : (mad ? 11 : 10);   // (14: a wrapping word, k_tree_fast<., 21>)
-        }
-        if (fm >= 6 && fm <= 9 && p->an.lj_unsigned) fm += 16;   // (the unsigned counterparts: qg_launch_tree_fast)
-        QG_HIP(qg_launch_tree_fast(p->dev_table, p->an.tree.n_levels_k, p->an.split_s, p->an.mul24_ok,
-                                   (p->flags & QG_OPT_RUNTIME_MODES) ? 0 : fm, packedA, packedB, packedC,
+    case QG_KERNEL_TREE_I32:
+        QG_HIP(qg_launch_tree_fast(p->dev_table, p->an.tree.n_levels_k, p->an.split_s, p->an.mul24_ok, p->tc.tree, packedA, packedB, packedC,
                                    p->desc.M, p->desc.N, p->pa.K_p, pcg.cbytes, st));
         return QG_OK;
-    }
     case QG_KERNEL_GEMV_I64:
-        QG_HIP(qg_launch_gemv(p->dev_table, p->an.tree.n_levels_k, p->an.gemv_b_bit, 0, packedA, packedB, packedC, p->desc.M, p->pa.K_p,
+        QG_HIP(qg_launch_gemv(p->dev_table, p->an.tree.n_levels_k, p->an.gemv_b_bit, QGF_RUNTIME, packedA, packedB, packedC, p->desc.M, p->pa.K_p,
                               pcg.cbytes, st, 1));
         return QG_OK;
     case QG_KERNEL_GEMV_I32:
-        QG_HIP(qg_launch_gemv(p->dev_table, p->an.tree.n_levels_k, p->an.gemv_b_bit, (p->flags & QG_OPT_RUNTIME_MODES) ? 0 : p->an.gemv_fixed,
-                              packedA, packedB, packedC, p->desc.M, p->pa.K_p,
+        QG_HIP(qg_launch_gemv(p->dev_table, p->an.tree.n_levels_k, p->an.gemv_b_bit, p->tc.gemv, packedA, packedB, packedC, p->desc.M, p->pa.K_p,
                               pcg.cbytes, st));
         return QG_OK;
     case QG_KERNEL_TREE_CPLX_I32:
-        // (the justified forms carry, in the second byte, the form the descriptor has without them: the diagnostic library's A/B switches)
-        QG_HIP(qg_launch_tree_cplx_fast(p->dev_table, p->an.tree.n_levels_k,
-                                        (p->flags & QG_OPT_RUNTIME_MODES) ? 0 : p->an.cplx_fixed_ok >= 5 ? (p->an.cplx_fixed_ok | p->an.cplx_fixed_base << 8) : p->an.cplx_fixed_ok,
-                                        p->desc.cmul == QG_CMUL_TF ? 1 : 0, packedA, packedB, packedC, p->desc.M, p->desc.N,
-                                        p->pa.K_p, pcg.cbytes, st));
+        QG_HIP(qg_launch_tree_cplx_fast(p->dev_table, p->an.tree.n_levels_k, p->tc.cplx, p->desc.cmul == QG_CMUL_TF ? 1 : 0, packedA, packedB, packedC,
+                                        p->desc.M, p->desc.N, p->pa.K_p, pcg.cbytes, st));
         return QG_OK;
     case QG_KERNEL_TREE_I64:
         if (p->an.tree64_ok && !(p->flags & QG_OPT_GENERIC_TREE)) {

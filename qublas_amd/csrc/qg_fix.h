@@ -120,7 +120,7 @@ __device__ __forceinline__ void fx_finish(int (&v)[N], const QFix& f)
 #pragma unroll
     for (int o = 0; o < N; ++o) asm("v_med3_i32 %0, %0, %1, %2" : "+v"(v[o]) : "s"(f.lo), "v"(hi));
 }
-// BIASED records (the real kernel's fast_mode 4, qg_plan.cpp): the value is u = v - lo >= 0 of its own format; after the shift
+// BIASED records (the real kernel's QTF_REC_BIASED, qg_plan.cpp): the value is u = v - lo >= 0 of its own format; after the shift
 // the overflow kind of the record (QFix::kb) acts on u with span = hi - lo (QFix::hi) and the biased zero B = -lo (QFix::lo):
 // 0 clamp = med3(u, 0, span); 1 SAT::ZERO = one unsigned compare + select; 2 WRP::TCPL = u & span; 4 none.  Wave-uniform.
 template <int N>
@@ -141,7 +141,7 @@ __device__ __forceinline__ void fx_finish_biased(int (&v)[N], const QFix& f)
         for (int o = 0; o < N; ++o) v[o] &= f.hi;
     }
 }
-// UNBIASED records with an overflow kind (the real kernel's fast_mode 5: formats too wide for the biased form), QFix::kb: 0 one clamp (SAT::TCPL, SAT::SMGN), 1 out of range -> 0 (SAT::ZERO), 2 wrap, signed (WRP::TCPL: keep the low
+// UNBIASED records with an overflow kind (the real kernel's QTF_REC_KINDS: formats too wide for the biased form), QFix::kb: 0 one clamp (SAT::TCPL, SAT::SMGN), 1 out of range -> 0 (SAT::ZERO), 2 wrap, signed (WRP::TCPL: keep the low
 // W + 1 bits, sign-extended; hi = 2^W - 1), 3 wrap, unsigned (v & hi).  Wave-uniform.
 // ... and a rounding kind (QFix::skip of such a record) for the modes whose addend depends on the value: 0 the constant
 // addend is already in (TRN::TCPL, RND::POS_INF, RND::NEG_INF); else the record's t is 0 and, with half = 2^(d-1) and c = QFix::ka,

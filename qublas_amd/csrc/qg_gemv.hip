@@ -22,6 +22,7 @@
 #include <stdlib.h>
 #include <type_traits>
 
+#include "qg_forms.h"
 #include "qg_kernels.h"
 #include "qg_fix.h"
 #include "qg_step_all.h"
@@ -35,7 +36,7 @@ struct QGemvArgs {
     char* C;            // [M] containers of cbytes
     int64_t M, K;
     int32_t cbytes, n_levels, b_is_bit;
-    int32_t pad_;       // fixed-mode selector: 0 run-time modes, 1 one format + SAT::ZERO, 2 one format + SAT::TCPL (QAnalysis::gemv_fixed)
+    int32_t pad_;
 };
 
 typedef int v4i __attribute__((ext_vector_type(4)));
@@ -71,22 +72,22 @@ __device__ __forceinline__ void node_all(T (&acc)[N], const T (&x)[N], CTab tab,
 }
 
 // in-lane levels: v[0..CNT) -> v[0..CNT/2) ... -> v[0]
-// MODE 1 / 2: every level has ONE format with no rounding shift and SAT::ZERO / SAT::TCPL overflow (what default tags
-// produce; QAnalysis::fast_mode) — a node is an add and a range test / a clamp against two constants, with no per-level
+// MODE (QGemvForm, qg_forms.h) QGF_ONE_*: every level has ONE format (what default tags produce) — a node is an add and a
+// range test / a clamp against two constants, with no per-level
 // table read and no scalar branch ladder.  The counters of the run-time-mode kernel showed more scalar than vector
 // instructions per launch (65 M SALU vs 48 M VALU at 65536 x 4096) and 56 % of the wave cycles waiting.
 template <int MODE>
 __device__ __forceinline__ int node_fixed(int a, int b, int lo, int hi)
 {
-    if (MODE == 6 || MODE == 7) return sat_add(a, b);   // 32-bit words (QAnalysis::gemv_w32): the format's range IS the int32 range — one v_add_i32 ... clamp
+    if (MODE == QGF_WORD || MODE == QGF_WORD_RND) return sat_add(a, b);   // 32-bit words: the format's range IS the int32 range — one v_add_i32 ... clamp
     const int t = a + b;
-    if (MODE == 1) return ((unsigned)(t - lo) > (unsigned)(hi - lo)) ? 0 : t;
+    if (MODE == QGF_ONE_ZERO) return ((unsigned)(t - lo) > (unsigned)(hi - lo)) ? 0 : t;
     return qg_clamp_i32(t, lo, hi);
 }
 
-// MODE 3 / 5: per-level formats in the compact records of qg_plan.h (QFix; QAnalysis::gemv_fixed): acc = acc + x + the rounding
-// addend, a left shift where the level has more fraction bits, then a right shift and one clamp (3: every level clamps) or what
-// the record's overflow kind asks for (5: SAT::ZERO / WRP::TCPL levels exist) — no mode ladder, one scalar load per level.
+// QGF_REC_*: per-level formats in the compact records of qg_plan.h (QFix): acc = acc + x + the rounding addend, a left shift where
+// the level has more fraction bits, then a right shift and one clamp (QGF_REC_CLAMP) or what the record's overflow kind asks for
+// (QGF_REC_KINDS: SAT::ZERO / WRP::TCPL levels exist) — no mode ladder, one scalar load per level.
 template <int MODE, int N>
 __device__ __forceinline__ void node_rec(int (&acc)[N], const int (&x)[N], const QTreeTable* t, int level)
 {
@@ -97,7 +98,7 @@ __device__ __forceinline__ void node_rec(int (&acc)[N], const int (&x)[N], const
 #pragma unroll
         for (int o = 0; o < N; ++o) acc[o] = (int)((unsigned)acc[o] << f.ls);
     }
-    if (MODE == 5) fx_finish_any<N>(acc, f);
+    if (MODE == QGF_REC_KINDS) fx_finish_any<N>(acc, f);
     else fx_finish<N>(acc, f);
 }
 
@@ -108,11 +109,11 @@ __device__ __forceinline__ T lane_tree(T (&v)[CNT], CTab tab, int level, int lo,
         return v[0];
     } else {
         T h[CNT / 2];   // (arrays of exact size, indexed only by unrolled loops: registers, never scratch)
-        if constexpr (MODE == 0) {
+        if constexpr (MODE == QGF_RUNTIME) {
 #pragma unroll
             for (int o = 0; o < CNT / 2; ++o) h[o] = v[2 * o] + v[2 * o + 1];   // left child + right child, in the tree's order
             qg_step_all<T, CNT / 2>(h, load_step(&tab->level_add[0][level].q));
-        } else if constexpr (MODE == 3 || MODE == 5) {
+        } else if constexpr (MODE == QGF_REC_CLAMP || MODE == QGF_REC_KINDS) {
             int r[CNT / 2];
 #pragma unroll
             for (int o = 0; o < CNT / 2; ++o) { h[o] = v[2 * o]; r[o] = v[2 * o + 1]; }
@@ -125,13 +126,13 @@ __device__ __forceinline__ T lane_tree(T (&v)[CNT], CTab tab, int level, int lo,
     }
 }
 
-// T = int64_t (MODE 0 only): the tree's values need more than 31 bits — sums of 32-bit words, wide level types — while the
+// T = int64_t (QGF_RUNTIME only): the tree's values need more than 31 bits — sums of 32-bit words, wide level types — while the
 // elements still come in 4-byte containers; the same streaming structure on 64-bit nodes (still HBM-bound by far: the general
 // 64-bit tree kernel, built for square output tiles, ran a 65 536 x 4096 reduction of Q15.16 at 140 GB/s).
-template <int CH, int MODE, class T = int>   // leaves per lane and segment; MODE: 0 run-time modes, 1 / 2 fixed (see node_fixed)
+template <int CH, int MODE, class T = int>   // leaves per lane and segment; MODE: QGemvForm
 __global__ __launch_bounds__(64 * WAVES) void k_gemv(QGemvArgs g)
 {
-    static_assert(sizeof(T) == 4 || MODE == 0, "64-bit values: run-time modes");
+    static_assert(sizeof(T) == 4 || MODE == QGF_RUNTIME, "64-bit values: run-time modes");
     constexpr int Q = CH == 32 ? 5 : CH == 16 ? 4 : CH == 8 ? 3 : 2;
     static_assert(CH <= 32 && CH >= 4, "leaves per lane");
     constexpr int SEG = 64 * CH;                 // leaves per segment
@@ -175,12 +176,12 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv(QGemvArgs g)
     pnode.sa = pnode.sb = 0;
     pnode.q = load_step(&tab->mul[0].q);
     const QStep c_cvt = load_step(&tab->c_cvt[0]);
-    const int flo = (int)tab->level_add[0][0].q.lo, fhi = (int)tab->level_add[0][0].q.hi;   // MODE 1 / 2: the one level format
-    // MODE 7: the product's shift, its rounding addend (TRN::TCPL 0, RND::POS_INF 2^(d-1), RND::NEG_INF 2^(d-1) - 1) and the range test's constants
-    const int w_d = MODE == 7 ? pnode.q.d : 0;
-    const int w_t = MODE == 7 ? (pnode.q.Q == QG_RND_POS_INF ? 1 << ((w_d - 1) & 31) : pnode.q.Q == QG_RND_NEG_INF ? (1 << ((w_d - 1) & 31)) - 1 : 0) : 0;
-    unsigned w_half = MODE == 7 ? 1u << ((w_d - 1) & 31) : 0u, w_lim = MODE == 7 ? 1u << (w_d & 31) : 0u;
-    if (MODE == 7) asm volatile("" : "+s"(w_lim));   // (opaque: see k_tree_fast)
+    const int flo = (int)tab->level_add[0][0].q.lo, fhi = (int)tab->level_add[0][0].q.hi;   // QGF_ONE_*: the one level format
+    // QGF_WORD_RND: the product's shift, its rounding addend (TRN::TCPL 0, RND::POS_INF 2^(d-1), RND::NEG_INF 2^(d-1) - 1) and the range test's constants
+    const int w_d = MODE == QGF_WORD_RND ? pnode.q.d : 0;
+    const int w_t = MODE == QGF_WORD_RND ? (pnode.q.Q == QG_RND_POS_INF ? 1 << ((w_d - 1) & 31) : pnode.q.Q == QG_RND_NEG_INF ? (1 << ((w_d - 1) & 31)) - 1 : 0) : 0;
+    unsigned w_half = MODE == QGF_WORD_RND ? 1u << ((w_d - 1) & 31) : 0u, w_lim = MODE == QGF_WORD_RND ? 1u << (w_d & 31) : 0u;
+    if (MODE == QGF_WORD_RND) asm volatile("" : "+s"(w_lim));   // (opaque: see k_tree_fast)
     for (; row < g.M; row += wstride) {
         T root = 0;
         for (int64_t s = 0; s < nseg; ++s) {
@@ -210,8 +211,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv(QGemvArgs g)
                     v4i b;
                     if (b_in_lds) b = *(const v4i*)(bimg + lane * CHUNK + t * 16);
                     else b = *(const v4i*)(g.B + s * SEG + lane * CH + t * 4);
-                    if constexpr (MODE == 7) {
-                        // 32-bit words, product "add a constant, shift right by 1 ... 31, saturate to the word" (QAnalysis::gemv_fixed 7):
+                    if constexpr (MODE == QGF_WORD_RND) {
+                        // 32-bit words, product "add a constant, shift right by 1 ... 31, saturate to the word" (QGF_WORD_RND):
                         // the steps of k_tree_fast<., 17> — v_mad_i64_i32, v_alignbit, range test of the high half, select
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
@@ -235,8 +236,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv(QGemvArgs g)
 #pragma unroll
             for (int i = 0; i < 6; ++i) {
                 T y[1] = {__shfl_down(x[0], 1 << i)};
-                if constexpr (MODE == 0) node_all<1, T>(x, y, tab, Q + i);
-                else if constexpr (MODE == 3 || MODE == 5) node_rec<MODE, 1>(x, y, g.tab, Q + i);
+                if constexpr (MODE == QGF_RUNTIME) node_all<1, T>(x, y, tab, Q + i);
+                else if constexpr (MODE == QGF_REC_CLAMP || MODE == QGF_REC_KINDS) node_rec<MODE, 1>(x, y, g.tab, Q + i);
                 else x[0] = node_fixed<MODE>(x[0], y[0], flo, fhi);
             }
             // x[0] in lane 0 = the segment's node of level Q + 6; carry it into the counter
@@ -245,11 +246,11 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv(QGemvArgs g)
             for (int u = 0; u < MAXUP && !parked; ++u) {
                 if (base + u >= g.n_levels) { root = x[0]; parked = true; }
                 else if (((s >> u) & 1) == 0) { if (lane == 0) up[u] = x[0]; parked = true; }
-                else if constexpr (MODE == 0) {
+                else if constexpr (MODE == QGF_RUNTIME) {
                     T l[1] = {up[u]};
                     node_all<1, T>(l, x, tab, base + u);
                     x[0] = l[0];
-                } else if constexpr (MODE == 3 || MODE == 5) {
+                } else if constexpr (MODE == QGF_REC_CLAMP || MODE == QGF_REC_KINDS) {
                     int l[1] = {up[u]};
                     node_rec<MODE, 1>(l, x, g.tab, base + u);
                     x[0] = l[0];
@@ -258,8 +259,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv(QGemvArgs g)
                 }
             }
         }
-        typename std::conditional<MODE == 6 || MODE == 7, int64_t, T>::type r[1] = {root};   // (MODE 6 / 7: a rounding addend on a full 32-bit word needs the 64-bit step)
-        qg_step_all<typename std::conditional<MODE == 6 || MODE == 7, int64_t, T>::type, 1>(r, c_cvt);
+        typename std::conditional<MODE == QGF_WORD || MODE == QGF_WORD_RND, int64_t, T>::type r[1] = {root};   // (the words: a rounding addend on a full 32-bit word needs the 64-bit step)
+        qg_step_all<typename std::conditional<MODE == QGF_WORD || MODE == QGF_WORD_RND, int64_t, T>::type, 1>(r, c_cvt);
         if (lane == 0) {
             switch (g.cbytes) {
             case 1: ((int8_t*)g.C)[row] = (int8_t)r[0]; break;
@@ -274,10 +275,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv(QGemvArgs g)
 // Short rows (K = 16 .. 128): a row is K/4 lanes wide, so one 16-byte load per lane covers 256/K whole rows and the lane's
 // four values are already consecutive leaves — no LDS.  Two levels inside the lane, log2(K) - 2 across the lanes of the
 // row's group; U row groups are processed together so that the (wave-uniform) mode switches are paid once per U values.
-template <int KK, int MODE, class T = int>   // MODE: see node_fixed; T = int64_t (MODE 0): see k_gemv
+template <int KK, int MODE, class T = int>   // MODE: QGemvForm; T = int64_t (QGF_RUNTIME): see k_gemv
 __global__ __launch_bounds__(256) void k_gemv_short(QGemvArgs g)
 {
-    static_assert(sizeof(T) == 4 || MODE == 0, "64-bit values: run-time modes");
+    static_assert(sizeof(T) == 4 || MODE == QGF_RUNTIME, "64-bit values: run-time modes");
     constexpr int LPR = KK / 4;        // lanes per row
     constexpr int RPL = 64 / LPR;      // rows per wave-wide load
     constexpr int U = 4;               // loads in flight per lane
@@ -291,7 +292,7 @@ __global__ __launch_bounds__(256) void k_gemv_short(QGemvArgs g)
     pnode.sa = pnode.sb = 0;
     pnode.q = load_step(&tab->mul[0].q);
     const QStep c_cvt = load_step(&tab->c_cvt[0]);
-    const int flo = (int)tab->level_add[0][0].q.lo, fhi = (int)tab->level_add[0][0].q.hi;   // MODE 1 / 2: the one level format
+    const int flo = (int)tab->level_add[0][0].q.lo, fhi = (int)tab->level_add[0][0].q.hi;   // QGF_ONE_*: the one level format
     const int64_t groups = (g.M + RPL - 1) / RPL;            // groups of RPL rows
     for (int64_t g0 = wave * U; g0 < groups; g0 += nwaves * U) {
         v4i a[U];
@@ -318,7 +319,7 @@ __global__ __launch_bounds__(256) void k_gemv_short(QGemvArgs g)
 #pragma unroll
                 for (int o = 0; o < 4 * U; ++o) p[o] = (T)w[o];
             }
-            if constexpr (MODE >= 3) {
+            if constexpr (MODE >= QGF_REC_CLAMP) {
                 int r0[2 * U];
 #pragma unroll
                 for (int o = 0; o < 2 * U; ++o) { l0[o] = p[2 * o]; r0[o] = p[2 * o + 1]; }
@@ -326,14 +327,14 @@ __global__ __launch_bounds__(256) void k_gemv_short(QGemvArgs g)
             } else {
 #pragma unroll
                 for (int o = 0; o < 2 * U; ++o) {
-                    if constexpr (MODE == 0) l0[o] = p[2 * o] + p[2 * o + 1];
-                    else l0[o] = node_fixed<(MODE == 1 || MODE == 2) ? MODE : 1>(p[2 * o], p[2 * o + 1], flo, fhi);
+                    if constexpr (MODE == QGF_RUNTIME) l0[o] = p[2 * o] + p[2 * o + 1];
+                    else l0[o] = node_fixed<(MODE == QGF_ONE_ZERO || MODE == QGF_ONE_TCPL) ? MODE : QGF_ONE_ZERO>(p[2 * o], p[2 * o + 1], flo, fhi);
                 }
             }
         }
-        if constexpr (MODE == 0) qg_step_all<T, 2 * U>(l0, load_step(&tab->level_add[0][0].q));
+        if constexpr (MODE == QGF_RUNTIME) qg_step_all<T, 2 * U>(l0, load_step(&tab->level_add[0][0].q));
         T x[U];
-        if constexpr (MODE >= 3) {
+        if constexpr (MODE >= QGF_REC_CLAMP) {
             int r1[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) { x[u] = l0[2 * u]; r1[u] = l0[2 * u + 1]; }
@@ -341,21 +342,21 @@ __global__ __launch_bounds__(256) void k_gemv_short(QGemvArgs g)
         } else {
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                if constexpr (MODE == 0) x[u] = l0[2 * u] + l0[2 * u + 1];
-                else x[u] = node_fixed<(MODE == 1 || MODE == 2) ? MODE : 1>(l0[2 * u], l0[2 * u + 1], flo, fhi);
+                if constexpr (MODE == QGF_RUNTIME) x[u] = l0[2 * u] + l0[2 * u + 1];
+                else x[u] = node_fixed<(MODE == QGF_ONE_ZERO || MODE == QGF_ONE_TCPL) ? MODE : QGF_ONE_ZERO>(l0[2 * u], l0[2 * u + 1], flo, fhi);
             }
         }
-        if constexpr (MODE == 0) qg_step_all<T, U>(x, load_step(&tab->level_add[0][1].q));
+        if constexpr (MODE == QGF_RUNTIME) qg_step_all<T, U>(x, load_step(&tab->level_add[0][1].q));
 #pragma unroll
         for (int i = 0; i < XL; ++i) {
             T y[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) y[u] = __shfl_down(x[u], 1 << i);
-            if constexpr (MODE == 0) node_all<U, T>(x, y, tab, 2 + i);
-            else if constexpr (MODE >= 3) node_rec<MODE, U>(x, y, g.tab, 2 + i);
+            if constexpr (MODE == QGF_RUNTIME) node_all<U, T>(x, y, tab, 2 + i);
+            else if constexpr (MODE >= QGF_REC_CLAMP) node_rec<MODE, U>(x, y, g.tab, 2 + i);
             else {
 #pragma unroll
-                for (int u = 0; u < U; ++u) x[u] = node_fixed<(MODE == 1 || MODE == 2) ? MODE : 1>(x[u], y[u], flo, fhi);
+                for (int u = 0; u < U; ++u) x[u] = node_fixed<(MODE == QGF_ONE_ZERO || MODE == QGF_ONE_TCPL) ? MODE : QGF_ONE_ZERO>(x[u], y[u], flo, fhi);
             }
         }
         qg_step_all<T, U>(x, c_cvt);
@@ -376,21 +377,28 @@ __global__ __launch_bounds__(256) void k_gemv_short(QGemvArgs g)
     }
 }
 
-template <int KK, int MODE = 0>
+template <int KK, int MODE>
 hipError_t launch_gemv_short(const QGemvArgs& g, hipStream_t st)
 {
-    if constexpr (MODE == 0) {
-        if (g.pad_ == 1) return launch_gemv_short<KK, 1>(g, st);
-        if (g.pad_ == 2) return launch_gemv_short<KK, 2>(g, st);
-        if (g.pad_ == 3) return launch_gemv_short<KK, 3>(g, st);
-        if (g.pad_ == 5) return launch_gemv_short<KK, 5>(g, st);
-    }
     constexpr int RPL = 64 / (KK / 4);
     const int64_t groups = (g.M + RPL - 1) / RPL;
     int64_t blocks = (groups + 15) / 16;          // 4 waves x U = 4 groups per block pass
     if (blocks > 256 * 16) blocks = 256 * 16;
     hipLaunchKernelGGL((k_gemv_short<KK, MODE>), dim3((unsigned)blocks), dim3(256), 0, st, g);
     return hipGetLastError();
+}
+
+template <int KK>   // (no 32-bit words: long rows only, qg_api.hip keeps short rows on the 64-bit form)
+hipError_t launch_gemv_short(QGemvForm form, const QGemvArgs& g, hipStream_t st)
+{
+    switch (form) {
+    case QGF_ONE_ZERO: return launch_gemv_short<KK, QGF_ONE_ZERO>(g, st);
+    case QGF_ONE_TCPL: return launch_gemv_short<KK, QGF_ONE_TCPL>(g, st);
+    case QGF_REC_CLAMP: return launch_gemv_short<KK, QGF_REC_CLAMP>(g, st);
+    case QGF_REC_KINDS: return launch_gemv_short<KK, QGF_REC_KINDS>(g, st);
+    case QGF_RUNTIME: return launch_gemv_short<KK, QGF_RUNTIME>(g, st);
+    default: return hipErrorInvalidValue;
+    }
 }
 
 template <int KK>
@@ -418,17 +426,9 @@ hipError_t launch_gemv_wide(const QGemvArgs& g, hipStream_t st)   // 64-bit valu
     return hipGetLastError();
 }
 
-template <int CH, int MODE = 0>
+template <int CH, int MODE>
 hipError_t launch_gemv(const QGemvArgs& g, hipStream_t st)
 {
-    if constexpr (MODE == 0) {
-        if (g.pad_ == 1) return launch_gemv<CH, 1>(g, st);
-        if (g.pad_ == 2) return launch_gemv<CH, 2>(g, st);
-        if (g.pad_ == 3) return launch_gemv<CH, 3>(g, st);
-        if (g.pad_ == 5) return launch_gemv<CH, 5>(g, st);
-        if (g.pad_ == 6) return launch_gemv<CH, 6>(g, st);
-        if (g.pad_ == 7) return launch_gemv<CH, 7>(g, st);
-    }
     constexpr int IMG = 64 * (CH * 4 + 16);
     const int64_t nseg = g.K / (64 * CH);
     const int lds = IMG * ((nseg == 1 ? 1 : 0) + WAVES);
@@ -440,14 +440,29 @@ hipError_t launch_gemv(const QGemvArgs& g, hipStream_t st)
     return hipGetLastError();
 }
 
+template <int CH>
+hipError_t launch_gemv(QGemvForm form, const QGemvArgs& g, hipStream_t st)
+{
+    switch (form) {
+    case QGF_ONE_ZERO: return launch_gemv<CH, QGF_ONE_ZERO>(g, st);
+    case QGF_ONE_TCPL: return launch_gemv<CH, QGF_ONE_TCPL>(g, st);
+    case QGF_REC_CLAMP: return launch_gemv<CH, QGF_REC_CLAMP>(g, st);
+    case QGF_REC_KINDS: return launch_gemv<CH, QGF_REC_KINDS>(g, st);
+    case QGF_WORD: return launch_gemv<CH, QGF_WORD>(g, st);
+    case QGF_WORD_RND: return launch_gemv<CH, QGF_WORD_RND>(g, st);
+    case QGF_RUNTIME: return launch_gemv<CH, QGF_RUNTIME>(g, st);
+    default: return hipErrorInvalidValue;
+    }
+}
+
 } // namespace
 
-hipError_t qg_launch_gemv(const QTreeTable* dev_table, int n_levels, int b_is_bit, int fixed_mode, const void* A, const void* B, void* C,
+hipError_t qg_launch_gemv(const QTreeTable* dev_table, int n_levels, int b_is_bit, QGemvForm form, const void* A, const void* B, void* C,
                           int64_t M, int64_t K, int cbytes, hipStream_t st, int wide)
 {
     if (M <= 0) return hipSuccess;
     if (K < 16 || (K & (K - 1)) || n_levels < 4 || n_levels > 10 + MAXUP) return hipErrorInvalidValue;
-    QGemvArgs g{dev_table, (const int32_t*)A, (const int32_t*)B, (char*)C, M, K, cbytes, n_levels, b_is_bit, wide ? 0 : fixed_mode};
+    QGemvArgs g{dev_table, (const int32_t*)A, (const int32_t*)B, (char*)C, M, K, cbytes, n_levels, b_is_bit, 0};
     if (wide) {   // 64-bit tree values on 4-byte elements: 8 leaves per lane and segment (16 would hold 64 registers of values alone)
         if (K >= 1024) return launch_gemv_wide<16>(g, st);
         if (K >= 512) return launch_gemv_wide<8>(g, st);
@@ -459,12 +474,11 @@ hipError_t qg_launch_gemv(const QTreeTable* dev_table, int n_levels, int b_is_bi
         default: return launch_gemv_short_wide<128>(g, st);
         }
     }
-    if ((fixed_mode == 6 || fixed_mode == 7) && K < 256) return hipErrorInvalidValue;   // (32-bit words: long rows only — qg_api.hip keeps short rows on the 64-bit form)
     switch (K) {
-    case 16: return launch_gemv_short<16>(g, st);
-    case 32: return launch_gemv_short<32>(g, st);
-    case 64: return launch_gemv_short<64>(g, st);
-    case 128: return launch_gemv_short<128>(g, st);
+    case 16: return launch_gemv_short<16>(form, g, st);
+    case 32: return launch_gemv_short<32>(form, g, st);
+    case 64: return launch_gemv_short<64>(form, g, st);
+    case 128: return launch_gemv_short<128>(form, g, st);
     default: break;
     }
     // (64 leaves per lane were measured first: v[64] plus the 64 prefetch registers spill, 0.68 ms for 65536 x 4096)
@@ -476,8 +490,8 @@ hipError_t qg_launch_gemv(const QTreeTable* dev_table, int n_levels, int b_is_bi
     constexpr int force_ch = 0;
 #endif
     const int ch = force_ch ? force_ch : 16;
-    if (ch >= 32 && K >= 2048) return launch_gemv<32>(g, st);
-    if (ch >= 16 && K >= 1024) return launch_gemv<16>(g, st);
-    if (ch >= 8 && K >= 512) return launch_gemv<8>(g, st);
-    return launch_gemv<4>(g, st);
+    if (ch >= 32 && K >= 2048) return launch_gemv<32>(form, g, st);
+    if (ch >= 16 && K >= 1024) return launch_gemv<16>(form, g, st);
+    if (ch >= 8 && K >= 512) return launch_gemv<8>(form, g, st);
+    return launch_gemv<4>(form, g, st);
 }

@@ -137,8 +137,9 @@ hipError_t qg_launch_tree_generic(const QTreeTable* dev_table, int parts, const 
                                   int64_t N, int64_t K, const QPackedGeom& pa, const QPackedGeom& pb, const QCGeom& pc,
                                   hipStream_t st, int wide = 0);   // wide: 128-bit values (C containers of up to 16 bytes)
 
-// exact tree evaluation, real descriptors with K = 2^p >= 32 and 32-bit intermediates (A, B packed as int32)
-hipError_t qg_launch_tree_fast(const QTreeTable* dev_table, int n_levels, int split_s, int mul24, int mode, const void* A, const void* B,
+// exact tree evaluation, real descriptors with K = 2^p >= 32 and 32-bit intermediates (A, B packed as int32); an unknown form is
+// hipErrorInvalidValue
+hipError_t qg_launch_tree_fast(const QTreeTable* dev_table, int n_levels, int split_s, int mul24, QTreeForm form, const void* A, const void* B,
                                void* C, int64_t M, int64_t N, int64_t K, int cbytes, hipStream_t st);
 
 // exact tree evaluation, real descriptors with 5..16 levels and 64-bit values (A, B packed as int32 or int64, K = 2^n_levels)
@@ -146,11 +147,11 @@ hipError_t qg_launch_tree64(const QTreeTable* dev_table, int n_levels, const voi
                             int64_t K, int abytes, int bbytes, int cbytes, hipStream_t st);
 
 // exact tree evaluation of ONE output column (batched Qreduce / GEMV): A [M][K] int32, B [K] int32
-hipError_t qg_launch_gemv(const QTreeTable* dev_table, int n_levels, int b_is_bit, int fixed_mode, const void* A, const void* B, void* C,
+hipError_t qg_launch_gemv(const QTreeTable* dev_table, int n_levels, int b_is_bit, QGemvForm form, const void* A, const void* B, void* C,
                           int64_t M, int64_t K, int cbytes, hipStream_t st, int wide = 0);   // wide: 64-bit tree values (4-byte elements)
 
 // exact tree evaluation, complex descriptors with K = 2^p >= 32 and 32-bit intermediates
-hipError_t qg_launch_tree_cplx_fast(const QTreeTable* dev_table, int n_levels, int fixed_modes, int tf, const void* A, const void* B, void* C,
+hipError_t qg_launch_tree_cplx_fast(const QTreeTable* dev_table, int n_levels, QCplxForm form, int tf, const void* A, const void* B, void* C,
                                     int64_t M, int64_t N, int64_t K, int cbytes, hipStream_t st);
 
 // linear class on int8 MFMA with LA x LB limbs

@@ -2,6 +2,7 @@
 #include "qg_plan.h"
 
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include <vector>
 
@@ -608,26 +609,26 @@ void qg_analyze(const qgemul_desc* d, QAnalysis* out)
     }
     // fixed-mode variants of the 32-bit tree kernel: product and all levels in one format, truncating
     // product, SAT::ZERO or SAT::TCPL overflow (the shapes default tags produce)
-    out->fast_mode = 0;
+    out->tree_form = QTF_RUNTIME;
     if (out->tree_fast_ok && out->mul24_ok) {
         const qfmt pf = d->mul[0];
         bool one = (pf.Q == QG_TRN_TCPL || T.mul[0].q.d <= 0) && T.mul[0].q.d >= 0 && (pf.O == QG_SAT_ZERO || pf.O == QG_SAT_TCPL);
         for (uint32_t l = 0; l < d->n_levels && one; ++l) one = same(d->level[0][l], pf) && same(d->level_add[0][l], pf);
         const int W = (int)pf.I + (int)pf.F;
-        if (one && W + 1 + T.mul[0].q.d <= 30) out->fast_mode = pf.O == QG_SAT_ZERO ? 1 : 2;
+        if (one && W + 1 + T.mul[0].q.d <= 30) out->tree_form = pf.O == QG_SAT_ZERO ? QTF_ONE_ZERO : QTF_ONE_TCPL;
     }
     // one-column kernel (qg_gemv.hip): products are formed in 64 bits, everything else in 32
     out->gemv_ok = (!cx && !out->wide && !out->generic_only && d->N == 1 && d->n_levels <= 30 && c.max_bits_np <= 31 && c.max_fmt_bits <= 31) ? 1 : 0;
     // ... with 64-bit tree values when only the ELEMENTS fit 32 storage bits (sums of 32-bit words, wide level types)
     out->gemv_wide_ok = (!cx && !out->wide && !out->generic_only && !out->gemv_ok && d->N == 1 && d->n_levels <= 30 &&
                          1 + (int)d->a[0].I + (int)d->a[0].F <= 32 && 1 + (int)d->b[0].I + (int)d->b[0].F <= 32) ? 1 : 0;
-    // fast_mode 3: per-level formats, but every step "add a constant, shift right, clamp" (QFix, qg_plan.h): TRN::TCPL /
+    // QTF_REC_CLAMP: per-level formats, but every step "add a constant, shift right, clamp" (QFix, qg_plan.h): TRN::TCPL /
     // RND::POS_INF / RND::NEG_INF rounding; SAT::TCPL / SAT::SMGN (one clamp), SAT::ZERO (range test + select) or WRP::TCPL
     // (sign extension / mask) overflow — e.g. default modes with a wider level type in QgemulAddArgs, which used to take the
     // run-time-mode form (4.3x slower at 2048^3)
-    int rec_form = 0;   // 3 / 5: the unbiased records are valid (every level clamps / overflow kinds), for the one-column kernel
-    if (((out->tree_fast_ok && out->mul24_ok && out->fast_mode == 0) || out->gemv_ok)) {
-        const bool for_tree = out->tree_fast_ok && out->mul24_ok && out->fast_mode == 0 && !out->gemv_ok;
+    bool recs = false, rec_clamps = false;   // the unbiased records are valid (every level clamps / overflow kinds), for the one-column kernel
+    if (((out->tree_fast_ok && out->mul24_ok && out->tree_form == QTF_RUNTIME) || out->gemv_ok)) {
+        const bool for_tree = out->tree_fast_ok && out->mul24_ok && out->tree_form == QTF_RUNTIME && !out->gemv_ok;
         auto okq = [](const QStep& q) {   // (every QuMode: the value-dependent ones as a rounding kind of the unbiased form)
             return q.identity || (q.d >= -22 && q.d <= 29 && (q.O == QG_SAT_TCPL || q.O == QG_SAT_SMGN || q.O == QG_SAT_ZERO || (q.O == QG_WRP_TCPL && q.W >= 1)));
         };
@@ -671,13 +672,14 @@ void qg_analyze(const qgemul_desc* d, QAnalysis* out)
                 clamps = clamps && T.fadd[0][l].kb == 0 && rk_of(T.level_add[0][l].q) == 0;
                 plain_rounding = plain_rounding && rk_of(T.level_add[0][l].q) == 0;
             }
-            rec_form = clamps ? 3 : 5;
-            if (for_tree) out->fast_mode = rec_form;   // 3: every step clamps (one v_med3 per value, no branch on the overflow kind);
-                                                       // 5: the records' overflow kinds on unbiased values (any format the kernel admits)
+            recs = true;
+            rec_clamps = clamps;
+            if (for_tree) out->tree_form = clamps ? QTF_REC_CLAMP : QTF_REC_KINDS;   // every step clamps (one v_med3 per value, no branch on the
+                                                                                     // overflow kind), or the records' overflow kinds on unbiased values
             if (!clamps && for_tree && plain_rounding) {
                 QFix keep_mul = T.fmul[0];
                 std::vector<QFix> keep_add(T.fadd[0], T.fadd[0] + (uint32_t)T.n_levels_k);
-                // 4: some step tests the range (SAT::ZERO) or wraps.  The running value is then kept BIASED by -lo of its own
+                // QTF_REC_BIASED: some step tests the range (SAT::ZERO) or wraps.  The running value is then kept BIASED by -lo of its own
                 // format, u = v - lo >= 0 (as the one-format SAT::ZERO form does): the range test is ONE unsigned compare
                 // against span = hi - lo with the biased zero as the select's other operand, a clamp is med3(u, 0, span) with
                 // no register for a bound, a wrap is u & span; the change of bias from level to level, the rounding addend and
@@ -719,7 +721,7 @@ void qg_analyze(const qgemul_desc* d, QAnalysis* out)
                 }
                 T.fmul[0].ka = (int32_t)cur.B;   // the root's bias, removed once per output
                 if (fits) {
-                    out->fast_mode = 4;
+                    out->tree_form = QTF_REC_BIASED;
                 } else {   // too wide for the bias arithmetic: the unbiased records stand
                     T.fmul[0] = keep_mul;
                     for (uint32_t l = 0; l < (uint32_t)T.n_levels_k; ++l) T.fadd[0][l] = keep_add[l];
@@ -727,17 +729,17 @@ void qg_analyze(const qgemul_desc* d, QAnalysis* out)
             }
         }
     }
-    // fast_mode 6, left-justified values (qg_fix.h): the product and every level clamp into ONE signed SAT::TCPL format of
+    // QTF_LJ, left-justified values (qg_fix.h): the product and every level clamp into ONE signed SAT::TCPL format of
     // Wt = W + 1 bits, the product rounds by "add a constant, shift right by d" (TRN::TCPL, RND::POS_INF, RND::NEG_INF) and the
     // nodes do not shift.  Values are held as x * 2^s, s = 32 - Wt: the operands are staged with factors 2^ea, 2^eb,
     // ea + eb = s - d, so that a * b * 2^(s-d) + t * 2^(s-d), saturated by the multiply-add itself and its low s bits cleared,
-    // is the quantised product; a node is one saturating add.  fast_mode_base keeps the form such a descriptor had before.
-    out->fast_mode_base = out->fast_mode;
-    if (out->tree_fast_ok && (out->fast_mode == 2 || out->fast_mode == 3)) {
+    // is the quantised product; a node is one saturating add.  tree_form_base keeps the form such a descriptor had before.
+    out->tree_form_base = out->tree_form;
+    if (out->tree_fast_ok && (out->tree_form == QTF_ONE_TCPL || out->tree_form == QTF_REC_CLAMP)) {
         const QStep& pq = T.mul[0].q;
         const int bitsA = 1 + (int)d->a[0].I + (int)d->a[0].F, bitsB = 1 + (int)d->b[0].I + (int)d->b[0].F;
         // (unsigned: every operand, the product and the levels unsigned — nothing ever goes below 0 — and [0, 2^W - 1] is the uint32
-        //  range of x * 2^(32 - W): the unsigned multiply-add / add with the clamp bit, QAnalysis::lj_unsigned)
+        //  range of x * 2^(32 - W): the unsigned multiply-add / add with the clamp bit, QTF_LJ_U)
         const bool uns = !pq.S && !d->a[0].S && !d->b[0].S && pq.lo == 0;
         bool lj = !pq.identity && pq.O == QG_SAT_TCPL && (uns || (pq.S && pq.lo == -pq.hi - 1)) && pq.d >= 0 && ((pq.hi + 1) & pq.hi) == 0 && pq.hi > 0 &&
                   (pq.d == 0 || pq.Q == QG_TRN_TCPL || pq.Q == QG_RND_POS_INF || pq.Q == QG_RND_NEG_INF);
@@ -764,9 +766,8 @@ void qg_analyze(const qgemul_desc* d, QAnalysis* out)
                 T.lj.s = sj;
                 T.lj.e[0] = ea;
                 T.lj.e[1] = eb;
-                out->fast_mode = 6;
-                out->lj_unsigned = uns ? 1 : 0;
-                // 7: ... in 16-bit halves, two outputs per register (k_tree_pk16): the format has at most 16 bits and the justified
+                out->tree_form = uns ? QTF_LJ_U : QTF_LJ;
+                // QTF_PK16: ... in 16-bit halves, two outputs per register (k_tree_pk16): the format has at most 16 bits and the justified
                 // operands fit int16 (QTreeTable::lj16).
                 const int s16 = 16 - Wt;
                 if (s16 >= 1 && s16 - pq.d >= 0) {
@@ -780,29 +781,30 @@ void qg_analyze(const qgemul_desc* d, QAnalysis* out)
                         T.lj16.e[0] = ea16;
                         T.lj16.e[1] = eb16;
                         T.lj16.t[0] = (int32_t)(t << (s16 - pq.d));
-                        out->fast_mode = 7;
+                        out->tree_form = uns ? QTF_PK16_U : QTF_PK16;
                     }
                 }
-                // 8: the format has at most 16 bits but its product does not fit the halves (bits + shift > 16): MODE 6's 32-bit justified
-                // product, whose high half is the value justified in 16 bits, and the tree on packed halves (k_tree_pk16<., true>)
-                if (out->fast_mode == 6 && Wt >= 2 && Wt <= 16) out->fast_mode = Wt == 16 ? 9 : 8;   // (9: no bits below the unit in a half)
+                // QTF_PK16_HYB: the format has at most 16 bits but its product does not fit the halves (bits + shift > 16): QTF_LJ's 32-bit
+                // justified product, whose high half is the value justified in 16 bits, and the tree on packed halves
+                if ((out->tree_form == QTF_LJ || out->tree_form == QTF_LJ_U) && Wt >= 2 && Wt <= 16)   // (HYB16: no bits below the unit in a half)
+                    out->tree_form = Wt == 16 ? (uns ? QTF_PK16_HYB16_U : QTF_PK16_HYB16) : (uns ? QTF_PK16_HYB_U : QTF_PK16_HYB);
             }
         }
     }
-    // fast_mode 10, 32-BIT WORDS (Q15.16 with default tags, the 32-bit fixed-point format of most code): the product and every level
+    // QTF_WORD, 32-BIT WORDS (Q15.16 with default tags, the 32-bit fixed-point format of most code): the product and every level
     // clamp into ONE signed SAT::TCPL format of exactly 32 bits — whose range is the int32 range as it stands, no justification and
     // no bits below the unit — the nodes do not shift, and the product rounds by "add a constant, shift right by d" out of the
     // exact 64-bit product of two elements of at most 32 bits.  Then a node is ONE v_add_i32 ... clamp, where the 64-bit tree
     // kernel spends a 64-bit add and a 64-bit clamp; the product is v_mul_hi / v_mul_lo, the shift and a saturation to the word.
-    // Runs on the 32-bit tree kernel's frame (k_tree_fast<., 17>), which has no run-time-mode form for such a format: the plan
+    // Runs on the 32-bit tree kernel's frame, which has no run-time-mode form for such a format: the plan
     // flag QG_OPT_RUNTIME_MODES sends the descriptor to the 64-bit kernel (qg_api.hip).
     if (!out->tree_fast_ok && !cx && !out->wide && !out->generic_only && d->n_levels <= 16 && T.n_levels_k <= 16) {
         const QStep& pq = T.mul[0].q;
         const int bitsA = 1 + (int)d->a[0].I + (int)d->a[0].F, bitsB = 1 + (int)d->b[0].I + (int)d->b[0].F;
         // ... and JUSTIFIED WORDS: a signed SAT::TCPL format of Wt < 32 bits (Q11.12: 24-bit words) held as x * 2^sj, sj = 32 - Wt, as
-        // fast_mode 6 holds it, when the product needs a net RIGHT shift dn = d - sj >= 1 (fast_mode 6 needs a left one, and 24-bit
+        // QTF_LJ holds it, when the product needs a net RIGHT shift dn = d - sj >= 1 (QTF_LJ needs a left one, and 24-bit
         // factors): the word is floor((a b + t) / 2^dn) of the same exact 64-bit product with its low sj bits cleared, the nodes
-        // are fast_mode 6's (T.lj.e[0] = sj; k_tree_fast<., 19 / 20>).  Such descriptors ran on the 64-bit tree kernel.
+        // are QTF_LJ's (T.lj.e[0] = sj; QTF_JWORD / QTF_JWORD_MAD).  Such descriptors ran on the 64-bit tree kernel.
         int Wt = 1;
         while (Wt < 33 && pq.S && ((int64_t)1 << (Wt - 1)) <= pq.hi) ++Wt;      // hi = 2^(Wt-1) - 1
         const int sj = 32 - Wt, dn = pq.d - sj;
@@ -819,7 +821,7 @@ void qg_analyze(const qgemul_desc* d, QAnalysis* out)
         // the root is converted into C by the kernel's 32-bit step: C's bounds must be words too, and no left shift
         const QStep& cq = T.c_cvt[0];
         w32 = w32 && (cq.identity || (cq.d >= 0 && 1 + (int)d->c[0].I + (int)d->c[0].F <= 32));
-        // ... and WRAPPING words: the same frame for a signed WRP::TCPL format of exactly 32 bits (T.lj.e[1] = 1; k_tree_fast<., 21>) — the
+        // ... and WRAPPING words: the same frame for a signed WRP::TCPL format of exactly 32 bits (T.lj.e[1] = 1; QTF_WORD_WRAP) — the
         // product's word is the low 32 bits of floor((a b + t) / 2^d), 0 <= d <= 31, a node a plain 32-bit add
         bool wrap32 = !w32 && !pq.identity && pq.O == QG_WRP_TCPL && pq.S && pq.W == 31 && pq.d >= 0 && pq.d <= 31 &&
                       (pq.d == 0 || pq.Q == QG_TRN_TCPL || pq.Q == QG_RND_POS_INF || pq.Q == QG_RND_NEG_INF) && bitsA <= 32 && bitsB <= 32 &&
@@ -839,7 +841,7 @@ void qg_analyze(const qgemul_desc* d, QAnalysis* out)
             out->tree_fast_ok = 1;
             out->split_s = 0;
             out->mul24_ok = 0;
-            out->fast_mode = out->fast_mode_base = 10;
+            out->tree_form = out->tree_form_base = QTF_WORD_WRAP;
         }
         if (w32) {
             memset(&T.lj, 0, sizeof T.lj);
@@ -849,14 +851,19 @@ void qg_analyze(const qgemul_desc* d, QAnalysis* out)
             out->tree_fast_ok = 1;
             out->split_s = 0;
             out->mul24_ok = 0;
-            out->fast_mode = out->fast_mode_base = 10;
+            // a product shift of 10 ... 23: the multiply-add form
+            const bool mad = dn >= 10 && dn <= 23;
+            out->tree_form = out->tree_form_base = sj > 0 ? (mad ? QTF_JWORD_MAD : QTF_JWORD) : (mad ? QTF_WORD_MAD : QTF_WORD);
         }
     }
     out->tree64_ok = (!cx && !out->wide && !out->generic_only && d->n_levels <= 16) ? 1 : 0;   // (64-bit values: not a wide plan)
     // QG_DESC_LEFTOVER0_COPY with an odd K: the zero-padded kernels would form the leftover as x + 0 in level 0's type — a
     // conversion, where the reference copies — so only the general kernel, which has the leftover step itself, may run it
     const bool copy0 = (d->flags & QG_DESC_LEFTOVER0_COPY) && (d->K & 1) && d->K > 1;
-    if (copy0) out->tree_fast_ok = out->fast_mode = out->tree64_ok = out->gemv_ok = out->gemv_wide_ok = 0;
+    if (copy0) {
+        out->tree_fast_ok = out->tree64_ok = out->gemv_ok = out->gemv_wide_ok = 0;
+        out->tree_form = QTF_RUNTIME;
+    }
     // (the Qreduce lowering: a * 1 into a's own format.  That is the identity for every raw value EXCEPT -2^W of a signed
     // SAT::SMGN format, which the conversion clamps to -(2^W - 1); the lowerings therefore name a's format with SAT::TCPL
     // as the leaf format of such element types, and only that form takes the shortcut)
@@ -882,12 +889,12 @@ void qg_analyze(const qgemul_desc* d, QAnalysis* out)
         }
         out->gemv_w32 = w32 ? 1 : 0;
     }
-    out->gemv_fixed = out->gemv_w32 ? 6 : 0;   // (6: only with gemv_wide_ok, i.e. never together with the forms below)
-    if (out->gemv_w32 && !out->gemv_b_bit) {    // 7: ... and the product itself is fast_mode 10's "add a constant, shift right, saturate to the word"
+    out->gemv_form = out->gemv_w32 ? QGF_WORD : QGF_RUNTIME;   // (only with gemv_wide_ok, i.e. never together with the forms below)
+    if (out->gemv_w32 && !out->gemv_b_bit) {    // ... and the product itself is QTF_WORD's "add a constant, shift right, saturate to the word"
         const QStep& pq = T.mul[0].q;
         if (!pq.identity && pq.O == QG_SAT_TCPL && pq.S && pq.lo == -((int64_t)1 << 31) && pq.hi == ((int64_t)1 << 31) - 1 && pq.d >= 1 && pq.d <= 31 &&
             (pq.Q == QG_TRN_TCPL || pq.Q == QG_RND_POS_INF || pq.Q == QG_RND_NEG_INF))
-            out->gemv_fixed = 7;
+            out->gemv_form = QGF_WORD_RND;
     }
     if (out->gemv_ok) {
         // all levels one format (the product's), exact alignment (d == 0), SAT::ZERO or SAT::TCPL
@@ -895,14 +902,14 @@ void qg_analyze(const qgemul_desc* d, QAnalysis* out)
         bool one = (lf.O == QG_SAT_ZERO || lf.O == QG_SAT_TCPL) && same(lf, d->mul[0]) && (int)lf.I + (int)lf.F <= 29;
         for (uint32_t l = 0; l < d->n_levels && one; ++l)
             one = same(d->level_add[0][l], lf) && same(d->level[0][l], lf) && T.level_add[0][l].q.d == 0;
-        if (one) out->gemv_fixed = lf.O == QG_SAT_ZERO ? 1 : 2;
-        else if (rec_form) out->gemv_fixed = rec_form;   // per-level formats in compact records (3: every level clamps, 5: kinds)
+        if (one) out->gemv_form = lf.O == QG_SAT_ZERO ? QGF_ONE_ZERO : QGF_ONE_TCPL;
+        else if (recs) out->gemv_form = rec_clamps ? QGF_REC_CLAMP : QGF_REC_KINDS;   // per-level formats in compact records
     }
     out->cplx_fast_ok = (cx && !out->wide && !out->generic_only && !copy0 && d->n_levels <= 16 && c.max_bits <= 31 && c.max_fmt_bits <= 31) ? 1 : 0;
     // fixed-mode variant of the complex kernel (BASELINE configuration 5's "RND + SAT"): every sub-operation and every tree
     // step either the identity, or an exact left shift / a rounding shift with RND::POS_INF, followed by SAT::TCPL, so a
     // step is (v + 2^(d-1)) >> d (or v << -d) and one clamp
-    out->cplx_fixed_ok = 0;
+    out->cplx_form = QCF_RUNTIME;
     if (out->cplx_fast_ok) {
         auto ok = [](const QStep& q) {
             return q.identity || (q.d >= -29 && q.d <= 29 && q.O == QG_SAT_TCPL && (q.d <= 0 || q.Q == QG_RND_POS_INF));
@@ -912,13 +919,13 @@ void qg_analyze(const qgemul_desc* d, QAnalysis* out)
         for (int i = 0; i < ns; ++i) all = all && ok(T.mul[i].q);
         for (int p = 0; p < 2; ++p)
             for (uint32_t l = 0; l < d->n_levels; ++l) all = all && ok(T.level_add[p][l].q) && ok(T.level_cvt[p][l]);
-        out->cplx_fixed_ok = all ? 1 : 0;
-        // ... and 2 when every step fits the branch-free forms of QFix (qg_plan.h): a rounding that is "add a constant, shift
+        out->cplx_form = all ? QCF_TABLE : QCF_RUNTIME;
+        // ... and QCF_COMPACT when every step fits the branch-free forms of QFix (qg_plan.h): a rounding that is "add a constant, shift
         // right" — TRN::TCPL (+0; the reference's default QuMode), RND::POS_INF (+2^(d-1)), RND::NEG_INF (+2^(d-1) - 1) — and an
         // overflow that is one clamp — SAT::TCPL (the reference's default OfMode) or SAT::SMGN ([-hi, hi]); the values that
         // enter a multiplication or an alignment fit 24 bits (v_mad_i32_i24), alignment and exact left shifts are folded
         // into power-of-two factors of at most 2^22
-        auto ok2 = [](const QStep& q) {   // (the other modes as rounding / overflow kinds: cplx_fixed_ok = 3, 8 + features)
+        auto ok2 = [](const QStep& q) {   // (the other modes as rounding / overflow kinds: QCF_KINDS, QCF_KINDS_*)
             return q.identity || (q.d >= -22 && q.d <= 29 && (q.O == QG_SAT_TCPL || q.O == QG_SAT_SMGN || q.O == QG_SAT_ZERO || (q.O == QG_WRP_TCPL && q.W >= 1)));
         };
         bool kinds = false;
@@ -1006,15 +1013,15 @@ void qg_analyze(const qgemul_desc* d, QAnalysis* out)
                     }
                 if (!kinds || feat <= 0) break;   // plain compact records, or the branching form: the first packing stands
             }
-            if (reg) out->cplx_fixed_ok = !kinds ? 2 : feat > 0 ? 8 + feat : 3;
-            // 4 ("one clamp for the whole loop"): the plain compact form where, in addition, every value made in the k loop — the
+            if (reg) out->cplx_form = !kinds ? QCF_COMPACT : feat > 0 ? qcf_kinds(feat) : QCF_KINDS;
+            // QCF_UNIFORM ("one clamp for the whole loop"): the plain compact form where, in addition, every value made in the k loop — the
             // products, their sum / differences and every tree node of both parts — is clamped into ONE range, the sums and the
             // nodes neither shift nor round (equal fraction bits throughout), and the level buffers do not convert.  That is what
             // default tags give on operands whose parts merge into one format (BASELINE configuration 5: everything is int<6,3>
             // RND::POS_INF / SAT::TCPL inside the loop).  The kernel then keeps (lo, hi) and the products' (t, d) in registers for
             // the whole launch — no record loads, no moves of bounds — and the products' exact left shifts are folded into the
             // staged operand planes: 18 vector instructions per complex MAC instead of 24.8 (TF), 21 instead of 27.4 (Basic).
-            if (reg && out->cplx_fixed_ok == 2) {
+            if (reg && out->cplx_form == QCF_COMPACT) {
                 const int re = tf ? QG_T_RE : QG_B_RE, im = tf ? QG_T_IM : QG_B_IM;
                 const QFix& r0 = T.fmul[re];
                 bool uni = r0.lo > INT32_MIN && r0.hi < INT32_MAX;
@@ -1077,7 +1084,7 @@ void qg_analyze(const qgemul_desc* d, QAnalysis* out)
                         }
                     }
                 }
-                if (uni) out->cplx_fixed_ok = 4;
+                if (uni) out->cplx_form = QCF_UNIFORM;
                 // The justified forms below also take products with FEWER fraction bits than the common format but the same integer
                 // bits (BasicComplexMul on Qcomplex<int<6,3>, int<6,-3>>: b d lives in int<6,-3>, RE = ac - 64 bd): left-justified, such
                 // a product's range ends where the common range does, its alignment factor in RE / IM is implicit, and only its mask
@@ -1104,8 +1111,8 @@ void qg_analyze(const qgemul_desc* d, QAnalysis* out)
                             ru = (fc.skip & 1) && (ident || (same_clamp(fa) && fa.t == 0 && fa.d == 0 && fa.ls == 0));
                         }
                 }
-                out->cplx_fixed_base = uni ? 4 : 2;
-                // 5: ... and that one range is a signed SAT::TCPL format: left-justified values (qg_fix.h).  The planes are staged with the
+                out->cplx_form_base = uni ? QCF_UNIFORM : QCF_COMPACT;
+                // QCF_LJ: ... and that one range is a signed SAT::TCPL format: left-justified values (qg_fix.h).  The planes are staged with the
                 // left shifts that justify each product exactly (x y 2^(s + ls - d), the addend scaled alike), so a product is one
                 // saturating multiply-add + v_and, RE / IM one saturating add / subtract, a node one saturating add (+ v_and at the
                 // even levels): 12.5 instead of 18 vector instructions per complex MAC (TF).
@@ -1155,9 +1162,9 @@ void qg_analyze(const qgemul_desc* d, QAnalysis* out)
                         return lj;
                     };
                     if (justify(32, 24, &T.lj)) {
-                        out->cplx_fixed_ok = 5;
-                        // 6: ... in packed 16-bit halves, two outputs per register (k_tree_cplx_pk16)
-                        if (justify(16, 16, &T.lj16)) out->cplx_fixed_ok = 6;
+                        out->cplx_form = QCF_LJ;
+                        // QCF_PK16: ... in packed 16-bit halves, two outputs per register
+                        if (justify(16, 16, &T.lj16)) out->cplx_form = QCF_PK16;
                     }
                 }
             }
@@ -1166,4 +1173,85 @@ void qg_analyze(const qgemul_desc* d, QAnalysis* out)
     if (!out->linear_ok)
         snprintf(out->reason, sizeof out->reason, "%s",
                  "a product or tree node may round or overflow: exact tree evaluation");
+}
+
+QTreeChoice qg_tree_choice(const QAnalysis* an, const qgemul_desc* d, uint32_t flags, bool ab)
+{
+    const bool fast = !(flags & QG_OPT_GENERIC_TREE), rt = (flags & QG_OPT_RUNTIME_MODES) != 0;
+#ifdef QG_DIAG
+    // A/B switches (diagnostic library): the form such a descriptor had before
+    static const bool no_lj = getenv("QG_NO_LEFT_JUSTIFIED"), no_pk = getenv("QG_NO_PACKED16"), no_uniform = getenv("QG_NO_UNIFORM_CLAMP");
+#else
+    const bool no_lj = false, no_pk = false, no_uniform = false;
+#endif
+    QTreeChoice c{QG_KERNEL_TREE_I64, QTF_RUNTIME, QGF_RUNTIME, QCF_RUNTIME};
+    if (an->wide) {
+        c.kernel = QG_KERNEL_TREE_I128;
+    } else if (d->is_complex) {
+        c.kernel = an->cplx_fast_ok && fast ? QG_KERNEL_TREE_CPLX_I32 : QG_KERNEL_TREE_CPLX;
+        c.cplx = rt ? QCF_RUNTIME : an->cplx_form;
+        if (ab && no_uniform && (c.cplx == QCF_UNIFORM || c.cplx == QCF_LJ || c.cplx == QCF_PK16)) c.cplx = QCF_COMPACT;
+        else if (ab && no_lj && (c.cplx == QCF_LJ || c.cplx == QCF_PK16)) c.cplx = an->cplx_form_base;
+        else if (ab && no_pk && c.cplx == QCF_PK16) c.cplx = QCF_LJ;
+    } else if ((an->gemv_ok || (an->gemv_wide_ok && an->gemv_w32 && !rt && an->tree.n_levels_k >= 8)) && fast) {
+        // (32-bit words on the one-column kernel, QAnalysis::gemv_w32: rows of at least 256 leaves; like QTF_WORD they have no
+        //  run-time-mode form, QG_OPT_RUNTIME_MODES keeps the 64-bit-value form — the tests' second opinion)
+        c.kernel = QG_KERNEL_GEMV_I32;
+        c.gemv = rt ? QGF_RUNTIME : an->gemv_form;
+    } else if (an->gemv_wide_ok && fast) {
+        c.kernel = QG_KERNEL_GEMV_I64;
+    } else if (an->tree_fast_ok && fast && !(rt && an->tree_form >= QTF_WORD && an->tree_form <= QTF_WORD_WRAP)) {
+        // (the 32-bit words have no run-time-mode form on that kernel: QG_OPT_RUNTIME_MODES takes the 64-bit one)
+        c.kernel = QG_KERNEL_TREE_I32;
+        c.tree = rt ? QTF_RUNTIME : an->tree_form;
+        const bool pk = c.tree == QTF_PK16 || c.tree == QTF_PK16_HYB || c.tree == QTF_PK16_HYB16, pku = c.tree == QTF_PK16_U || c.tree == QTF_PK16_HYB_U || c.tree == QTF_PK16_HYB16_U;
+        if (ab && no_lj && (c.tree == QTF_LJ || c.tree == QTF_LJ_U || pk || pku)) c.tree = an->tree_form_base;
+        else if (ab && no_pk && (pk || pku)) c.tree = pku ? QTF_LJ_U : QTF_LJ;
+    }
+    return c;
+}
+
+const char* qg_form_name(QTreeForm f)
+{
+    switch (f) {
+    case QTF_ONE_ZERO: return "one format, SAT::ZERO";
+    case QTF_ONE_TCPL: return "one format, SAT::TCPL";
+    case QTF_REC_CLAMP: return "per-level formats, compact (clamps)";
+    case QTF_REC_BIASED: return "per-level formats, compact";
+    case QTF_REC_KINDS: return "per-level formats, compact (unbiased)";
+    case QTF_LJ: case QTF_LJ_U: return "one format, SAT::TCPL, left-justified";
+    case QTF_PK16: case QTF_PK16_U: return "one format, SAT::TCPL, left-justified, packed 16-bit";
+    case QTF_PK16_HYB: case QTF_PK16_HYB16: case QTF_PK16_HYB_U: case QTF_PK16_HYB16_U: return "one format, SAT::TCPL, left-justified, packed nodes";
+    case QTF_WORD: case QTF_WORD_MAD: return "one 32-bit format, SAT::TCPL, saturating word adds";
+    case QTF_JWORD: case QTF_JWORD_MAD: return "one format, SAT::TCPL, justified words";
+    case QTF_WORD_WRAP: return "one 32-bit format, WRP::TCPL, wrapping word adds";
+    default: return "run-time modes";
+    }
+}
+
+const char* qg_form_name(QGemvForm f)
+{
+    switch (f) {
+    case QGF_ONE_ZERO: return "one format, SAT::ZERO";
+    case QGF_ONE_TCPL: return "one format, SAT::TCPL";
+    case QGF_REC_CLAMP: return "per-level formats, compact (clamps)";
+    case QGF_REC_KINDS: return "per-level formats, compact";
+    case QGF_WORD: case QGF_WORD_RND: return "one 32-bit format, saturating adds";
+    default: return "run-time modes";
+    }
+}
+
+const char* qg_form_name(QCplxForm f)
+{
+    switch (f) {
+    case QCF_TABLE: return "fixed modes, table";
+    case QCF_COMPACT: return "fixed modes, compact";
+    case QCF_KINDS: return "compact, rounding / overflow kinds";
+    case QCF_UNIFORM: return "fixed modes, one clamp for the whole loop";
+    case QCF_LJ: return "fixed modes, one clamp, left-justified";
+    case QCF_PK16: return "fixed modes, one clamp, packed 16-bit";
+    case QCF_KINDS_R: case QCF_KINDS_Z: case QCF_KINDS_RZ: case QCF_KINDS_W: case QCF_KINDS_RW: case QCF_KINDS_ALL:
+        return "compact, branch-free rounding / overflow kinds";
+    default: return "run-time modes";
+    }
 }

@@ -5,20 +5,21 @@
 #include <stdint.h>
 
 #include "../../include/qgemul.h"
+#include "qg_forms.h"
 #include "qg_ops.h"
 
-// One fixed-mode step of the complex kernel (qg_tree_cplx.hip, QAnalysis::cplx_fixed_ok == 2) in the form the kernel
+// One fixed-mode step of the complex kernel (qg_tree_cplx.hip, QCF_COMPACT) in the form the kernel
 // executes without a branch, 8 dwords = one scalar load:
 //   add / sub slot:  v = (x * ka + t) +/- y * kb;   v >>= d;   v = clamp(v, lo, hi)       (ka, kb = 2^alignment shift)
 //   multiply slot:   v = (x * ka) * y + t;          v >>= d;   v = clamp(v, lo, hi)       (ka = 2^(left shift of an exact product))
 //   tree node:       v = x + v + t;   v <<= ls;     v >>= d;   v = clamp(v, lo, hi)       (ls: a level type with MORE fraction bits)
 // t = the rounding mode's addend (TRN::TCPL 0, RND::POS_INF 2^(d-1), RND::NEG_INF 2^(d-1) - 1); an identity step is d = 0,
-// t = 0 and the full int32 range.  cplx_fixed_ok == 3 / >= 8: `skip` also packs the step's rounding / overflow kind
+// t = 0 and the full int32 range.  QCF_KINDS / QCF_KINDS_*: `skip` also packs the step's rounding / overflow kind
 // (qg_fix.h: fx_finish_packed / fx_finish_feat; the latter's rounding factor is `ls` of a slot, `ka` of a node).
-// Records of the REAL kernel (product, nodes) have no factors.  fast_mode 3 (every step clamps): as above.  fast_mode 4 (a step
+// Records of the REAL kernel (product, nodes) have no factors.  QTF_REC_CLAMP (every step clamps): as above.  QTF_REC_BIASED (a step
 // tests the range or wraps): the value is kept biased by -lo of its format, and the fields mean: t = the node's one constant
 // (rounding addend, change of bias), kb = overflow kind (0 clamp, 1 SAT::ZERO, 2 WRP::TCPL, 4 none), hi = span = hi - lo,
-// lo = the bias B = -lo (the biased zero); fmul[0].ka = the root's bias (qg_plan.cpp).  fast_mode 5 (a format too wide for that):
+// lo = the bias B = -lo (the biased zero); fmul[0].ka = the root's bias (qg_plan.cpp).  QTF_REC_KINDS (a format too wide for that):
 // unbiased values, lo / hi = the bounds, kb = 0 clamp, 1 SAT::ZERO, 2 / 3 WRP::TCPL signed / unsigned.
 struct QFix {
     int32_t ka, kb, t, d, lo, hi, skip, ls;
@@ -42,19 +43,19 @@ struct QTreeTable {
     QStep level_cvt[2][QG_MAX_LEVELS];    // store into the level buffer (identity for real GEMMs)
     QStep leftover[2][QG_MAX_LEVELS];     // odd-leftover copy into level l's buffer
     QStep c_cvt[2];                       // root -> C, valid when the tree has all n_levels levels
-    // complex fixed-mode kernel, register-lean form (valid when QAnalysis::cplx_fixed_ok == 2)
+    // complex fixed-mode kernel, register-lean form (valid from QCF_COMPACT on)
     QFix fmul[8];
     QFix fadd[2][QG_MAX_LEVELS];
     QFix fcvt[2][QG_MAX_LEVELS];
-    // ... its "one clamp for the whole loop" form (cplx_fixed_ok == 4): the common range, then per product (TF: A, B, C; Basic: ac,
+    // ... its "one clamp for the whole loop" form (QCF_UNIFORM): the common range, then per product (TF: A, B, C; Basic: ac,
     // bd, ad, bc) the rounding addend and the right shift, then the factors (powers of two) the operand planes are staged with
     // (TF: (a+b), (c+d), (b-a); Basic: a, b, c, d) — which carry the products' exact left shifts, the shifts growing to match
     struct { int32_t lo, hi, t[4], d[4], k[4], pad_[2]; } uni;
-    // LEFT-JUSTIFIED forms (qg_fix.h: one signed SAT::TCPL format held as x * 2^s; real fast_mode 6, complex cplx_fixed_ok 5): the
+    // LEFT-JUSTIFIED forms (qg_fix.h: one signed SAT::TCPL format held as x * 2^s; QTF_LJ, QCF_LJ): the
     // shift s, per product the rounding addend scaled to the justified product, and the left shifts the operand planes are staged
     // with (real: A, B; TF: (a+b), b, (b-a), c, (c+d), d; Basic: a, b, c, d), which justify the products
     QJustify lj;
-    // ... and in packed 16-bit halves (x * 2^s, s = 16 - width; real fast_mode 7, complex cplx_fixed_ok 6), the same fields
+    // ... and in packed 16-bit halves (x * 2^s, s = 16 - width; QTF_PK16, QCF_PK16), the same fields
     QJustify lj16;
 };
 
@@ -78,16 +79,15 @@ struct QAnalysis {
     int split_s;             // > 0: product evaluated split at its rounding shift
     int mul24_ok;            // multiplies fit v_mul_i32_i24
     int cplx_fast_ok;        // the 32-bit complex tree kernel applies
-    int cplx_fixed_ok;       // ... and every step on the path is RND::POS_INF (or exact) + SAT::TCPL: fixed-mode variant (2: compact records; 3: ... with rounding / overflow kinds; 8 + f: ... of the branch-free feature set f; 4: one clamp for the whole loop; 5: ... on left-justified values; 6: ... in packed 16-bit halves)
-    int cplx_fixed_base;     // cplx_fixed_ok 5 / 6: the form the descriptor has without the justified values (4 when the strict one-clamp form holds, else 2)
-    int fast_mode;           // 0 runtime modes; 1 one format everywhere, TCPL + SAT::ZERO; 2 TCPL + SAT::TCPL; 3 / 4 / 5 per-level formats, compact steps (QFix; 3: every step clamps, 4: biased values, 5: unbiased); 6 one signed SAT::TCPL format on left-justified values, 7 ... in packed 16-bit halves, 8 ... 32-bit products, packed 16-bit nodes
-    int fast_mode_base;      // fast_mode 6 / 7 (one signed SAT::TCPL format, left-justified saturating steps): the form (2 / 3) the descriptor has without it
-    int lj_unsigned;         // fast_mode 6 ... 9 on an unsigned format (all operands unsigned): the unsigned saturating instructions
+    QCplxForm cplx_form;     // ... and its step form (qg_forms.h), the one that launches
+    QCplxForm cplx_form_base;   // QCF_LJ / QCF_PK16: the form the descriptor has without the justified values (QCF_UNIFORM when the strict one-clamp form holds, else QCF_COMPACT)
+    QTreeForm tree_form;     // the 32-bit tree kernel's step form (qg_forms.h), the one that launches
+    QTreeForm tree_form_base;   // the justified forms (QTF_LJ ... QTF_PK16_HYB16_U): the form (QTF_ONE_TCPL / QTF_REC_CLAMP) the descriptor has without them
     int tree64_ok;           // the 2x2-outputs-per-lane 64-bit tree kernel applies (real, 5..16 levels)
     int gemv_ok;             // the one-column 32-bit tree kernel applies (N = 1, K = 2^p >= 16)
     int gemv_wide_ok;        // ... or its 64-bit-value form: elements of at most 32 storage bits, wider sums / level types
-    int gemv_fixed;          // 1 / 2: every tree level has one format, no rounding shift, SAT::ZERO / SAT::TCPL (fixed-mode nodes); 3 / 5: per-level formats in compact records
-    int gemv_w32;            // gemv_wide_ok descriptors whose product and every level live in ONE signed SAT::TCPL format of exactly 32 bits: values stay 32-bit words, a node is one saturating add (k_gemv<., 6>)
+    QGemvForm gemv_form;     // the one-column kernel's step form (qg_forms.h)
+    int gemv_w32;            // gemv_wide_ok descriptors whose product and every level live in ONE signed SAT::TCPL format of exactly 32 bits: values stay 32-bit words, a node is one saturating add (QGF_WORD)
     int gemv_b_bit;          // ... and B is a 0/1 vector whose product with a is a itself (the Qreduce lowering)
     int wide;                // an intermediate, a level / product format or C needs more than 62 bits: 128-bit kernels (qg_ops.h: qg_step_w)
     int generic_only;        // C's WRP::TCPL_SAT can let the root through unclamped: the general kernels / the composite plan's combine pass only
@@ -98,6 +98,21 @@ struct QAnalysis {
 };
 
 void qg_analyze(const qgemul_desc* d, QAnalysis* out);
+
+// the tree kernel of an analysed descriptor that is not on the MFMA path, and its step form, under the plan flags
+// QG_OPT_GENERIC_TREE / QG_OPT_RUNTIME_MODES; ab: with the diagnostic library's A/B switches (QG_NO_LEFT_JUSTIFIED,
+// QG_NO_PACKED16, QG_NO_UNIFORM_CLAMP) applied — the form that launches, where the plan's reason names the form without them
+struct QTreeChoice {
+    int kernel;        // QG_KERNEL_TREE_* / QG_KERNEL_GEMV_*
+    QTreeForm tree;    // QG_KERNEL_TREE_I32
+    QGemvForm gemv;    // QG_KERNEL_GEMV_I32
+    QCplxForm cplx;    // QG_KERNEL_TREE_CPLX_I32
+};
+QTreeChoice qg_tree_choice(const QAnalysis* an, const qgemul_desc* d, uint32_t flags, bool ab);
+// the step form as the plan's reason names it
+const char* qg_form_name(QTreeForm f);
+const char* qg_form_name(QGemvForm f);
+const char* qg_form_name(QCplxForm f);
 
 // fused element-wise epilogue (qgemul_epilogue), pre-resolved for the device: stage k combines the running value x
 // with its operand e (node.sa shifts the FIRST operand of the Qop, node.sb the second), node.q rounds/overflows into

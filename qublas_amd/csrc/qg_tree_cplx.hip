@@ -20,6 +20,7 @@
 #include <stddef.h>
 
 #include "qg_fix.h"
+#include "qg_forms.h"
 #include "qg_kernels.h"
 #include "qg_step_all.h"
 
@@ -30,7 +31,7 @@ constexpr int TMB = 32, TNB = 32;  // 16x16 threads x (2x2)
 constexpr int PITCH = KC + 4;
 
 // one quantising step on N values.  FIXED: the planner has shown every step of this descriptor to be the identity or
-// "RND::POS_INF by d >= 0 bits, then SAT::TCPL" (QAnalysis::cplx_fixed_ok) — round-half-up is (v + 2^(d-1)) >> d and the
+// "RND::POS_INF by d >= 0 bits, then SAT::TCPL" (QAnalysis::cplx_form) — round-half-up is (v + 2^(d-1)) >> d and the
 // saturation one clamp, 3 VALU instructions instead of the 6-7 of the runtime-mode form and no scalar branch ladder.
 template <bool FIXED, int N>
 __device__ __forceinline__ void step_n(int (&v)[N], const QStep& s)
@@ -80,7 +81,7 @@ __device__ __forceinline__ void node_n(int (&v)[N], const int (&x)[N], const QTr
     step_n<FIXED, N>(v, t->level_cvt[part][l]);
 }
 
-// ---- MODE 2: the compact fixed-mode steps (qg_fix.h, QFix of qg_plan.h) ----
+// ---- QCF_COMPACT: the compact fixed-mode steps (qg_fix.h, QFix of qg_plan.h) ----
 // KIND 0: every step adds a constant and clamps; 1: the records carry rounding / overflow kinds (fx_finish_packed, a branch
 // ladder per step); 8 + FEAT: kinds of the branch-free feature set FEAT (fx_finish_feat; k: the rounding's factor)
 template <int KIND, int N>
@@ -133,31 +134,30 @@ __device__ __forceinline__ void fx_node(int (&v)[N], const int (&x)[N], const QF
     }
 }
 
-// MODE: 0 run-time modes, 1 fixed modes read from the step table, 2 fixed modes in the compact branch-free form, 4 the same with
-// ONE clamp range for the whole k loop held in registers (k_tree_cplx), 3 the compact
-// form with rounding / overflow kinds (SAT::ZERO, WRP::TCPL, RND::ZERO / INF / CONV, TRN::SMGN) behind a branch per step,
-// 8 + FEAT the same without the branch for the kinds of FEAT (qg_fix.h, fx_finish_feat)
+// MODE: the step form, QCplxForm (qg_forms.h).  The rounding / overflow kinds of QCF_KINDS (SAT::ZERO, WRP::TCPL, RND::ZERO /
+// INF / CONV, TRN::SMGN) sit behind a branch per step; QCF_KINDS_* (8 + FEAT) have no branch for the kinds of FEAT (qg_fix.h,
+// fx_finish_feat).  A record's KIND (qg_fix.h) is 0 for QCF_COMPACT, 1 for QCF_KINDS and the form itself for QCF_KINDS_*.
 template <int MODE, int N>
 __device__ __forceinline__ void op_addsub(int (&out)[N], const int (&x)[N], const int (&y)[N], const QTreeTable* __restrict__ t, int slot, bool sub)
 {
-    if constexpr (MODE >= 2) fx_addsub<(MODE >= 8 ? MODE : MODE == 3), N>(out, x, y, fx_at(t, FX_OFF_MUL(slot)), sub);
-    else addsub_n<MODE == 1, N>(out, x, y, t->mul[slot], sub);
+    if constexpr (MODE >= QCF_COMPACT) fx_addsub<(MODE >= QCF_KINDS_R ? MODE : MODE == QCF_KINDS), N>(out, x, y, fx_at(t, FX_OFF_MUL(slot)), sub);
+    else addsub_n<MODE == QCF_TABLE, N>(out, x, y, t->mul[slot], sub);
 }
 template <int MODE, int N>
 __device__ __forceinline__ void op_mul(int (&out)[N], const int (&x)[N], const int (&y)[N], const QTreeTable* __restrict__ t, int slot)
 {
-    if constexpr (MODE >= 2) fx_mul<(MODE >= 8 ? MODE : MODE == 3), N>(out, x, y, fx_at(t, FX_OFF_MUL(slot)));
-    else mul_n<MODE == 1, N>(out, x, y, t->mul[slot]);
+    if constexpr (MODE >= QCF_COMPACT) fx_mul<(MODE >= QCF_KINDS_R ? MODE : MODE == QCF_KINDS), N>(out, x, y, fx_at(t, FX_OFF_MUL(slot)));
+    else mul_n<MODE == QCF_TABLE, N>(out, x, y, t->mul[slot]);
 }
 template <int MODE, int N>
 __device__ __forceinline__ void op_node(int (&v)[N], const int (&x)[N], const QTreeTable* __restrict__ t, int part, int l)
 {
-    if constexpr (MODE >= 2) {
+    if constexpr (MODE >= QCF_COMPACT) {
         QFix fa, fc;
         fx_at2(t, FX_OFF_ADD(part, l), FX_OFF_CVT(part, l), fa, fc);
-        fx_node<(MODE >= 8 ? MODE : MODE == 3), N>(v, x, fa, fc);
+        fx_node<(MODE >= QCF_KINDS_R ? MODE : MODE == QCF_KINDS), N>(v, x, fa, fc);
     } else {
-        node_n<MODE == 1, N>(v, x, t, part, l);
+        node_n<MODE == QCF_TABLE, N>(v, x, t, part, l);
     }
 }
 
@@ -165,14 +165,14 @@ __device__ __forceinline__ void op_node(int (&v)[N], const int (&x)[N], const QT
 template <int MODE, int N>
 __device__ __forceinline__ void op_node2(int (&v0)[N], int (&v1)[N], const int (&x0)[N], const int (&x1)[N], const QTreeTable* __restrict__ t, int l)
 {
-    if constexpr (MODE >= 2) {
+    if constexpr (MODE >= QCF_COMPACT) {
         QFix fa0, fc0, fa1, fc1;
         fx_at4(t, FX_OFF_ADD(0, l), FX_OFF_CVT(0, l), FX_OFF_ADD(1, l), FX_OFF_CVT(1, l), fa0, fc0, fa1, fc1);
-        fx_node<(MODE >= 8 ? MODE : MODE == 3), N>(v0, x0, fa0, fc0);
-        fx_node<(MODE >= 8 ? MODE : MODE == 3), N>(v1, x1, fa1, fc1);
+        fx_node<(MODE >= QCF_KINDS_R ? MODE : MODE == QCF_KINDS), N>(v0, x0, fa0, fc0);
+        fx_node<(MODE >= QCF_KINDS_R ? MODE : MODE == QCF_KINDS), N>(v1, x1, fa1, fc1);
     } else {
-        node_n<MODE == 1, N>(v0, x0, t, 0, l);
-        node_n<MODE == 1, N>(v1, x1, t, 1, l);
+        node_n<MODE == QCF_TABLE, N>(v0, x0, t, 0, l);
+        node_n<MODE == QCF_TABLE, N>(v1, x1, t, 1, l);
     }
 }
 
@@ -189,7 +189,7 @@ struct QTreeCplxArgs {
 // for one wave per SIMD more than their natural register count gives (4 at MAXL 12, 3 at MAXL 16; 10-20 spilled registers outside
 // the hot values) — except Basic's forms whose spill count would be 30-40 (the branching kinds form and the SAT::ZERO feature).
 template <int MODE, bool TF>
-constexpr bool cplx_dense_waves = MODE >= 2 && (TF || (MODE != 3 && !(MODE >= 8 && ((MODE - 8) & 2))));
+constexpr bool cplx_dense_waves = MODE >= QCF_COMPACT && (TF || (MODE != QCF_KINDS && !(MODE >= QCF_KINDS_R && ((MODE - 8) & 2))));   // (no SAT::ZERO kinds)
 template <int MAXL, int MODE, bool TF>   // TF: TFComplexMul (3 multiplications), else BasicComplexMul (4)
 __global__ __launch_bounds__(256, ((cplx_dense_waves<MODE, TF>) ? (MAXL == 12 ? 4 : 3) : 1)) void k_tree_cplx(QTreeCplxArgs g)
 {
@@ -216,20 +216,20 @@ __global__ __launch_bounds__(256, ((cplx_dense_waves<MODE, TF>) ? (MAXL == 12 ? 
     const int64_t gsz = (tiles_m - first_m) < GMT ? (tiles_m - first_m) : GMT;
     const int64_t m0 = (first_m + (bid % (GMT * tiles_n)) % gsz) * TMB, n0 = ((bid % (GMT * tiles_n)) / gsz) * TNB;
     const int nl = tab->n_levels_k;   // (a tree shorter than 5 levels is continued with identity levels: qg_plan.h)
-    // MODE 4 ("one clamp for the whole loop", qg_plan.cpp): ONE range for every value of the k loop and no shift / rounding at the
+    // QCF_UNIFORM ("one clamp for the whole loop", qg_plan.cpp): ONE range for every value of the k loop and no shift / rounding at the
     // sums and the tree nodes: the bounds and the products' (addend, shift) live in registers for the whole launch; the products'
     // exact left shifts are factors of the operand planes, applied while the tile is staged (QTreeTable::uni)
     int u_lo = 0, u_hi = 0, u_t[4] = {0, 0, 0, 0}, u_d[4] = {0, 0, 0, 0}, u_k[4] = {1, 1, 1, 1};
-    if constexpr (MODE == 4) {
+    if constexpr (MODE == QCF_UNIFORM) {
         u_lo = tab->uni.lo;
         u_hi = fx_vgpr(tab->uni.hi);
 #pragma unroll
         for (int i = 0; i < 4; ++i) { u_t[i] = tab->uni.t[i]; u_d[i] = tab->uni.d[i]; u_k[i] = tab->uni.k[i]; }
     }
-    // MODE 5: ... and that range is a signed SAT::TCPL format: LEFT-JUSTIFIED values (qg_fix.h, QTreeTable::lj) — the planes are
+    // QCF_LJ: ... and that range is a signed SAT::TCPL format: LEFT-JUSTIFIED values (qg_fix.h, QTreeTable::lj) — the planes are
     // staged with the shifts that justify each product; the clamp bit of the multiply-add, the add and the subtract saturates
     int j_s = 0, j_mask = -1, j_t[4] = {0, 0, 0, 0}, j_e[6] = {0, 0, 0, 0, 0, 0}, j_pm[4] = {-1, -1, -1, -1};   // j_pm: a product's own mask (QJustify::g)
-    if constexpr (MODE == 5) {
+    if constexpr (MODE == QCF_LJ) {
         j_s = tab->lj.s;
         j_mask = (int)(~0u << j_s);
 #pragma unroll
@@ -273,15 +273,15 @@ __global__ __launch_bounds__(256, ((cplx_dense_waves<MODE, TF>) ? (MAXL == 12 ? 
                 const int ar4[4] = {x[0].x, x[0].y, x[0].z, x[0].w}, ai4[4] = {x[1].x, x[1].y, x[1].z, x[1].w};
                 const int br4[4] = {y[0].x, y[0].y, y[0].z, y[0].w}, bi4[4] = {y[1].x, y[1].y, y[1].z, y[1].w};
                 int ab[4], ba[4], cd[4];
-                constexpr int SM = (MODE == 4 || MODE == 5) ? 2 : MODE;   // (the staged sums keep their own compact records)
+                constexpr int SM = (MODE == QCF_UNIFORM || MODE == QCF_LJ) ? QCF_COMPACT : MODE;   // (the staged sums keep their own compact records)
                 op_addsub<SM, 4>(ab, ar4, ai4, tab, QG_T_AB, false);  // (a+b), per A element
                 op_addsub<SM, 4>(ba, ai4, ar4, tab, QG_T_BA, true);   // (b-a), per A element
                 op_addsub<SM, 4>(cd, br4, bi4, tab, QG_T_CD, false);  // (c+d), per B element
-                if constexpr (MODE == 4) {   // the products' exact left shifts, once per element: A = (a+b) c, B = (c+d) b, C = (b-a) d
+                if constexpr (MODE == QCF_UNIFORM) {   // the products' exact left shifts, once per element: A = (a+b) c, B = (c+d) b, C = (b-a) d
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { ab[e] = __mul24(ab[e], u_k[0]); cd[e] = __mul24(cd[e], u_k[1]); ba[e] = __mul24(ba[e], u_k[2]); }
                 }
-                if constexpr (MODE == 5) {   // planes (a+b), b, (b-a) / c, (c+d), d with the shifts that justify A, B, C
+                if constexpr (MODE == QCF_LJ) {   // planes (a+b), b, (b-a) / c, (c+d), d with the shifts that justify A, B, C
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { ab[e] <<= j_e[0]; ba[e] <<= j_e[2]; cd[e] <<= j_e[4]; }
                     x[1] = make_int4(x[1].x << j_e[1], x[1].y << j_e[1], x[1].z << j_e[1], x[1].w << j_e[1]);
@@ -295,14 +295,14 @@ __global__ __launch_bounds__(256, ((cplx_dense_waves<MODE, TF>) ? (MAXL == 12 ? 
                 *(int4*)&sB[1][r][q * 4] = make_int4(cd[0], cd[1], cd[2], cd[3]);
                 *(int4*)&sB[2][r][q * 4] = y[1];
             } else {
-                if constexpr (MODE == 5) {   // planes a, b, c, d with the shifts that justify ac, bd, ad, bc
+                if constexpr (MODE == QCF_LJ) {   // planes a, b, c, d with the shifts that justify ac, bd, ad, bc
 #pragma unroll
                     for (int p = 0; p < 2; ++p) {
                         x[p] = make_int4(x[p].x << j_e[p], x[p].y << j_e[p], x[p].z << j_e[p], x[p].w << j_e[p]);
                         y[p] = make_int4(y[p].x << j_e[2 + p], y[p].y << j_e[2 + p], y[p].z << j_e[2 + p], y[p].w << j_e[2 + p]);
                     }
                 }
-                if constexpr (MODE == 4) {   // planes a, b, c, d with their factors
+                if constexpr (MODE == QCF_UNIFORM) {   // planes a, b, c, d with their factors
 #pragma unroll
                     for (int p = 0; p < 2; ++p) {
                         x[p] = make_int4(__mul24(x[p].x, u_k[p]), __mul24(x[p].y, u_k[p]), __mul24(x[p].z, u_k[p]), __mul24(x[p].w, u_k[p]));
@@ -357,7 +357,7 @@ __global__ __launch_bounds__(256, ((cplx_dense_waves<MODE, TF>) ? (MAXL == 12 ? 
                                 ab[i * 2 + j] = a0[i]; xi[i * 2 + j] = a1[i]; ba[i * 2 + j] = a2[i];
                                 yr[i * 2 + j] = b0[j]; cd[i * 2 + j] = b1[j]; yi[i * 2 + j] = b2[j];
                             }
-                        if constexpr (MODE == 5) {
+                        if constexpr (MODE == QCF_LJ) {
 #pragma unroll
                             for (int o = 0; o < 4; ++o) {
                                 PA[o] = sat_mad24_vvs(ab[o], yr[o], j_t[0]) & j_pm[0];
@@ -366,7 +366,7 @@ __global__ __launch_bounds__(256, ((cplx_dense_waves<MODE, TF>) ? (MAXL == 12 ? 
                             }
 #pragma unroll
                             for (int o = 0; o < 4; ++o) { v[0][o] = sat_sub(PA[o], PB[o]); v[1][o] = sat_sub(PB[o], PC[o]); }   // (clean subtrahends)
-                        } else if constexpr (MODE == 4) {
+                        } else if constexpr (MODE == QCF_UNIFORM) {
 #pragma unroll
                             for (int o = 0; o < 4; ++o) { PA[o] = mad24_vvs(ab[o], yr[o], u_t[0]); PB[o] = mad24_vvs(cd[o], xi[o], u_t[1]); PC[o] = mad24_vvs(ba[o], yi[o], u_t[2]); }
 #pragma unroll
@@ -378,8 +378,8 @@ __global__ __launch_bounds__(256, ((cplx_dense_waves<MODE, TF>) ? (MAXL == 12 ? 
                             for (int o = 0; o < 4; ++o) { v[0][o] = PA[o] - PB[o]; v[1][o] = PB[o] - PC[o]; }
                             uclamp4(v[0]);
                             uclamp4(v[1]);
-                        } else if constexpr (MODE >= 2) {   // records of steps that follow each other share a wait (qg_fix.h)
-                            constexpr int KIND = MODE >= 8 ? MODE : MODE == 3;
+                        } else if constexpr (MODE >= QCF_COMPACT) {   // records of steps that follow each other share a wait (qg_fix.h)
+                            constexpr int KIND = MODE >= QCF_KINDS_R ? MODE : MODE == QCF_KINDS;
                             QFix fA, fB, fC, fR, fI;
                             fx_at5(tab, FX_OFF_MUL(QG_T_A), FX_OFF_MUL(QG_T_B), FX_OFF_MUL(QG_T_C), FX_OFF_MUL(QG_T_RE), FX_OFF_MUL(QG_T_IM), fA, fB, fC, fR, fI);
                             fx_mul<KIND, 4>(PA, ab, yr, fA);
@@ -404,7 +404,7 @@ __global__ __launch_bounds__(256, ((cplx_dense_waves<MODE, TF>) ? (MAXL == 12 ? 
                                 yr[i * 2 + j] = b0[j]; yi[i * 2 + j] = b1[j];
                             }
                         int ac[4], bd[4], ad[4], bc[4];
-                        if constexpr (MODE == 5) {
+                        if constexpr (MODE == QCF_LJ) {
 #pragma unroll
                             for (int o = 0; o < 4; ++o) {
                                 ac[o] = sat_mad24_vvs(xr[o], yr[o], j_t[0]) & j_pm[0];
@@ -414,7 +414,7 @@ __global__ __launch_bounds__(256, ((cplx_dense_waves<MODE, TF>) ? (MAXL == 12 ? 
                             }
 #pragma unroll
                             for (int o = 0; o < 4; ++o) { v[0][o] = sat_sub(ac[o], bd[o]); v[1][o] = sat_add(ad[o], bc[o]); }
-                        } else if constexpr (MODE == 4) {
+                        } else if constexpr (MODE == QCF_UNIFORM) {
 #pragma unroll
                             for (int o = 0; o < 4; ++o) {
                                 ac[o] = mad24_vvs(xr[o], yr[o], u_t[0]) >> u_d[0];
@@ -430,8 +430,8 @@ __global__ __launch_bounds__(256, ((cplx_dense_waves<MODE, TF>) ? (MAXL == 12 ? 
                             for (int o = 0; o < 4; ++o) { v[0][o] = ac[o] - bd[o]; v[1][o] = ad[o] + bc[o]; }
                             uclamp4(v[0]);
                             uclamp4(v[1]);
-                        } else if constexpr (MODE >= 2) {
-                            constexpr int KIND = MODE >= 8 ? MODE : MODE == 3;
+                        } else if constexpr (MODE >= QCF_COMPACT) {
+                            constexpr int KIND = MODE >= QCF_KINDS_R ? MODE : MODE == QCF_KINDS;
                             QFix f0, f1, f2, f3;
                             fx_at2(tab, FX_OFF_MUL(QG_B_AC), FX_OFF_MUL(QG_B_BD), f0, f1);
                             fx_mul<KIND, 4>(ac, xr, yr, f0);
@@ -463,13 +463,13 @@ __global__ __launch_bounds__(256, ((cplx_dense_waves<MODE, TF>) ? (MAXL == 12 ? 
 #pragma unroll
                                         for (int o = 0; o < 4; ++o) low[p][l][o] = v[p][o];
                                     parked_low = true;
-                                } else if constexpr (MODE == 5) {
+                                } else if constexpr (MODE == QCF_LJ) {
                                     // RE / IM come from one saturating operation on clean values: 2^31 - 1 or clean.  One more
                                     // saturating add keeps floor(v / 2^s) right; before the next one the low bits are cleared
 #pragma unroll
                                     for (int o = 0; o < 4; ++o) { v[0][o] = sat_add(low[0][l][o], v[0][o]); v[1][o] = sat_add(low[1][l][o], v[1][o]); }
                                     if ((l & 1) == 0) { jmask4(v[0]); jmask4(v[1]); }
-                                } else if constexpr (MODE == 4) {
+                                } else if constexpr (MODE == QCF_UNIFORM) {
 #pragma unroll
                                     for (int o = 0; o < 4; ++o) { v[0][o] += low[0][l][o]; v[1][o] += low[1][l][o]; }
                                     uclamp4(v[0]);
@@ -493,11 +493,11 @@ __global__ __launch_bounds__(256, ((cplx_dense_waves<MODE, TF>) ? (MAXL == 12 ? 
 #pragma unroll
                             for (int o = 0; o < 4; ++o) up[p][u][o] = v[p][o];
                         parked = true;
-                    } else if constexpr (MODE == 5) {
+                    } else if constexpr (MODE == QCF_LJ) {
 #pragma unroll
                         for (int o = 0; o < 4; ++o) { v[0][o] = sat_add(up[0][u][o], v[0][o]); v[1][o] = sat_add(up[1][u][o], v[1][o]); }
                         if ((u & 1) == 0) { jmask4(v[0]); jmask4(v[1]); }   // (level 4 + u: the even ones)
-                    } else if constexpr (MODE == 4) {
+                    } else if constexpr (MODE == QCF_UNIFORM) {
 #pragma unroll
                         for (int o = 0; o < 4; ++o) { v[0][o] += up[0][u][o]; v[1][o] += up[1][u][o]; }
                         uclamp4(v[0]);
@@ -509,7 +509,7 @@ __global__ __launch_bounds__(256, ((cplx_dense_waves<MODE, TF>) ? (MAXL == 12 ? 
             }
         }
     }
-    if constexpr (MODE == 5) {   // floor(v / 2^s): the value
+    if constexpr (MODE == QCF_LJ) {   // floor(v / 2^s): the value
 #pragma unroll
         for (int o = 0; o < 4; ++o) { v[0][o] >>= j_s; v[1][o] >>= j_s; }
     }
@@ -535,11 +535,11 @@ __global__ __launch_bounds__(256, ((cplx_dense_waves<MODE, TF>) ? (MAXL == 12 ? 
             }
 }
 
-// ---- packed 16-bit form (cplx_fixed_ok 6): MODE 5's left-justified steps for a common format of at most 16 bits, TWO outputs
+// ---- packed 16-bit form (QCF_PK16): QCF_LJ's left-justified steps for a common format of at most 16 bits, TWO outputs
 // per register.  A lane owns 4 rows x 2 columns (tx, tx + 16; low half: column tx) of both parts; the A-side planes are staged
 // as 16-bit values (two k per dword), the B-side planes as (column tx, column tx + 16) pairs per k; a pair of products is one
 // v_pk_mad_i16 ... clamp whose A operand is broadcast by op_sel, + v_and; RE / IM one v_pk_sub_i16 / v_pk_add_i16 ... clamp; a
-// node pair one v_pk_add_i16 ... clamp, + v_and at the even levels: 6.3 vector instructions per complex MAC (TF) where MODE 5
+// node pair one v_pk_add_i16 ... clamp, + v_and at the even levels: 6.3 vector instructions per complex MAC (TF) where QCF_LJ
 // spends 12.9 (BASELINE configuration 5 as literally configured).
 constexpr int TM16 = 64;    // rows of C per block (16 thread rows x 4)
 constexpr int PKP = 18;     // dwords per A-plane row: 16 + 2 (8-byte reads stay aligned)
@@ -753,7 +753,20 @@ __global__ __launch_bounds__(256, 3) void k_tree_cplx_pk16(QTreeCplxArgs g)
 
 } // namespace
 
-hipError_t qg_launch_tree_cplx_fast(const QTreeTable* dev_table, int n_levels, int fixed, int tf, const void* A, const void* B, void* C, int64_t M,
+template <int MODE>
+static hipError_t launch_cplx(int n_levels, int tf, dim3 grid, hipStream_t st, const QTreeCplxArgs& g)
+{
+    if (tf) {
+        if (n_levels <= 12) hipLaunchKernelGGL((k_tree_cplx<12, MODE, true>), grid, dim3(256), 0, st, g);
+        else hipLaunchKernelGGL((k_tree_cplx<16, MODE, true>), grid, dim3(256), 0, st, g);
+    } else {
+        if (n_levels <= 12) hipLaunchKernelGGL((k_tree_cplx<12, MODE, false>), grid, dim3(256), 0, st, g);
+        else hipLaunchKernelGGL((k_tree_cplx<16, MODE, false>), grid, dim3(256), 0, st, g);
+    }
+    return hipGetLastError();
+}
+
+hipError_t qg_launch_tree_cplx_fast(const QTreeTable* dev_table, int n_levels, QCplxForm form, int tf, const void* A, const void* B, void* C, int64_t M,
                                     int64_t N, int64_t K, int cbytes, hipStream_t st)
 {
     if (K % KC != 0 || n_levels < 5 || n_levels > 16) return hipErrorInvalidValue;
@@ -761,56 +774,31 @@ hipError_t qg_launch_tree_cplx_fast(const QTreeTable* dev_table, int n_levels, i
     const int64_t blocks = ((M + TMB - 1) / TMB) * ((N + TNB - 1) / TNB);
     if (blocks <= 0) return hipSuccess;
     if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
-    // fixed: 0 run-time modes; 1 fixed modes, steps read from the step table; 2 fixed modes, compact branch-free steps; 3 compact
-    // steps with a branch on the rounding / overflow kind; 8 + f compact steps, branch-free kinds of the feature set f (1 R, 2 Z,
-    // 3 RZ, 4 W, 5 RW; the other ones run the full set)
-#define QG_CPLX_LAUNCH(MODE)                                                                                                      \
-    do {                                                                                                                          \
-        if (tf) {                                                                                                                 \
-            if (n_levels <= 12) hipLaunchKernelGGL((k_tree_cplx<12, MODE, true>), dim3((unsigned)blocks), dim3(256), 0, st, g);   \
-            else hipLaunchKernelGGL((k_tree_cplx<16, MODE, true>), dim3((unsigned)blocks), dim3(256), 0, st, g);                  \
-        } else {                                                                                                                  \
-            if (n_levels <= 12) hipLaunchKernelGGL((k_tree_cplx<12, MODE, false>), dim3((unsigned)blocks), dim3(256), 0, st, g);  \
-            else hipLaunchKernelGGL((k_tree_cplx<16, MODE, false>), dim3((unsigned)blocks), dim3(256), 0, st, g);                 \
-        }                                                                                                                         \
-    } while (0)
-    const int base = fixed >> 8;   // (forms 5 / 6: 4 when the strict one-clamp form holds as well, else 2)
-    fixed &= 255;
-    switch (fixed) {
-    case 0: QG_CPLX_LAUNCH(0); break;
-    case 1: QG_CPLX_LAUNCH(1); break;
-    case 2: QG_CPLX_LAUNCH(2); break;
-    case 3: QG_CPLX_LAUNCH(3); break;
-    case 6:     // ... in packed 16-bit halves
-    case 5:     // ... on left-justified values
-    case 4: {   // one clamp for the whole loop (qg_plan.cpp)
-        static const bool no_uniform = QG_DIAG_ENV("QG_NO_UNIFORM_CLAMP");   // A/B switch (diagnostic library): the compact form such a descriptor had before
-        static const bool no_lj = QG_DIAG_ENV("QG_NO_LEFT_JUSTIFIED");
-        static const bool no_pk = QG_DIAG_ENV("QG_NO_PACKED16");
-        if (no_uniform) QG_CPLX_LAUNCH(2);
-        else if (fixed == 6 && !no_lj && !no_pk) {
-            const int64_t blocks16 = ((M + TM16 - 1) / TM16) * ((N + TNB - 1) / TNB);
-            if (tf) {
-                if (n_levels <= 12) hipLaunchKernelGGL((k_tree_cplx_pk16<12, true>), dim3((unsigned)blocks16), dim3(256), 0, st, g);
-                else hipLaunchKernelGGL((k_tree_cplx_pk16<16, true>), dim3((unsigned)blocks16), dim3(256), 0, st, g);
-            } else {
-                if (n_levels <= 12) hipLaunchKernelGGL((k_tree_cplx_pk16<12, false>), dim3((unsigned)blocks16), dim3(256), 0, st, g);
-                else hipLaunchKernelGGL((k_tree_cplx_pk16<16, false>), dim3((unsigned)blocks16), dim3(256), 0, st, g);
-            }
-        } else if (fixed >= 5 && !no_lj) QG_CPLX_LAUNCH(5);
-        else if (fixed >= 5 && base != 4) QG_CPLX_LAUNCH(2);
-        else QG_CPLX_LAUNCH(4);
-        break;
+    const dim3 grid((unsigned)blocks);
+    switch (form) {
+    case QCF_RUNTIME: return launch_cplx<QCF_RUNTIME>(n_levels, tf, grid, st, g);
+    case QCF_TABLE: return launch_cplx<QCF_TABLE>(n_levels, tf, grid, st, g);
+    case QCF_COMPACT: return launch_cplx<QCF_COMPACT>(n_levels, tf, grid, st, g);
+    case QCF_KINDS: return launch_cplx<QCF_KINDS>(n_levels, tf, grid, st, g);
+    case QCF_PK16: {
+        const dim3 grid16((unsigned)(((M + TM16 - 1) / TM16) * ((N + TNB - 1) / TNB)));
+        if (tf) {
+            if (n_levels <= 12) hipLaunchKernelGGL((k_tree_cplx_pk16<12, true>), grid16, dim3(256), 0, st, g);
+            else hipLaunchKernelGGL((k_tree_cplx_pk16<16, true>), grid16, dim3(256), 0, st, g);
+        } else {
+            if (n_levels <= 12) hipLaunchKernelGGL((k_tree_cplx_pk16<12, false>), grid16, dim3(256), 0, st, g);
+            else hipLaunchKernelGGL((k_tree_cplx_pk16<16, false>), grid16, dim3(256), 0, st, g);
+        }
+        return hipGetLastError();
     }
-    case 9: QG_CPLX_LAUNCH(9); break;
-    case 10: QG_CPLX_LAUNCH(10); break;
-    case 11: QG_CPLX_LAUNCH(11); break;
-    case 12: QG_CPLX_LAUNCH(12); break;
-    case 13: QG_CPLX_LAUNCH(13); break;
-    case 14:
-    case 15: QG_CPLX_LAUNCH(15); break;
-    default: return hipErrorInvalidValue;
+    case QCF_LJ: return launch_cplx<QCF_LJ>(n_levels, tf, grid, st, g);
+    case QCF_UNIFORM: return launch_cplx<QCF_UNIFORM>(n_levels, tf, grid, st, g);
+    case QCF_KINDS_R: return launch_cplx<QCF_KINDS_R>(n_levels, tf, grid, st, g);
+    case QCF_KINDS_Z: return launch_cplx<QCF_KINDS_Z>(n_levels, tf, grid, st, g);
+    case QCF_KINDS_RZ: return launch_cplx<QCF_KINDS_RZ>(n_levels, tf, grid, st, g);
+    case QCF_KINDS_W: return launch_cplx<QCF_KINDS_W>(n_levels, tf, grid, st, g);
+    case QCF_KINDS_RW: return launch_cplx<QCF_KINDS_RW>(n_levels, tf, grid, st, g);
+    case QCF_KINDS_ALL: return launch_cplx<QCF_KINDS_ALL>(n_levels, tf, grid, st, g);
     }
-#undef QG_CPLX_LAUNCH
-    return hipGetLastError();
+    return hipErrorInvalidValue;
 }

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "qg_fix.h"
+#include "qg_forms.h"
 #include "qg_kernels.h"
 
 namespace {
@@ -114,7 +115,7 @@ __device__ __forceinline__ void step_all(int (&v)[NOUT], const QStep& s)
 template <int MODE>
 __device__ __forceinline__ void node_fixed(int (&v)[NOUT], const int (&x)[NOUT], int flo, int fhi, int bias, unsigned span)
 {
-    if (MODE == 1) {
+    if (MODE == QTF_ONE_ZERO) {
 #pragma unroll
         for (int o = 0; o < NOUT; ++o) {
             const int t = x[o] + v[o] - bias;               // biased sum (v_add3_u32)
@@ -196,32 +197,22 @@ struct QTreeFastArgs {
     int32_t split_s;    // SPLIT: rounding shift of the product (= bits split off B)
 };
 
-// MODE 0: per-node formats and modes are runtime values (any real descriptor the planner admits).
-// MODE 1 / 2: the product and every tree level share ONE format, rounding is TRN::TCPL and the overflow mode is
-//   SAT::ZERO (1) or SAT::TCPL (2) — the default-tag shapes (configurations 1 and 3 as literally configured).  Then
-//   a node is 3 (ZERO, on values biased by -lo so that the range test is one unsigned compare) or 2 (TCPL:
-//   v_add + v_med3) VALU instructions and the leaf needs no separate rounding step.
-// MODE 3 / 4: per-level formats, every step in the compact form of qg_fix.h (QAnalysis::fast_mode): the node's record is one
-//   scalar load, the node itself v_add3 (+ the rounding addend), a shift where the level has fewer fraction bits, and one
-//   v_med3 (3: every step of the descriptor clamps), or — 4: SAT::ZERO / WRP::TCPL steps exist — values biased by -lo of their
-//   format and the overflow by the record's kind: one unsigned compare + select, med3(u, 0, span), or u & span (qg_fix.h);
-//   5: the same kinds on unbiased values (a subtraction more per range test) where a format is too wide for the biased form.
-// MODE 6: one signed SAT::TCPL format for the product and every level, held LEFT-JUSTIFIED (qg_fix.h): the product is one
-//   saturating v_mad_i32_i24 (operands staged with the factors that justify it, rounding addend included) + v_and, a node one
-//   saturating v_add_i32, + v_and at the odd levels: 3.3 instead of 5 vector instructions per MAC, and no split product
-//   (the hardware saturates from the full 48-bit product).
+// MODE: the step form, QTreeForm (qg_forms.h).  The one-format forms (QTF_ONE_*) are the default-tag shapes (configurations 1 and 3
+// as literally configured), whose leaf needs no separate rounding step.  QTF_LJ: the operands are staged with the factors that
+// justify the product (rounding addend included): 3.3 instead of 5 vector instructions per MAC, and no split product (the
+// hardware saturates from the full 48-bit product).
 #define NODE(X, L)                                                         \
     do {                                                                   \
-        if (MODE == 21) {                                                  \
+        if (MODE == QTF_WORD_WRAP) {                                       \
             _Pragma("unroll") for (int o_ = 0; o_ < NOUT; ++o_) v[o_] = (int)((unsigned)X[o_] + (unsigned)v[o_]);   \
-        } else if (MODE >= 17 && MODE <= 20) {                             \
+        } else if (W32) {                                                  \
             _Pragma("unroll") for (int o_ = 0; o_ < NOUT; ++o_) v[o_] = sat_add(X[o_], v[o_]);   \
-            if ((MODE == 19 || MODE == 20) && ((L) & 1)) { _Pragma("unroll") for (int o_ = 0; o_ < NOUT; ++o_) v[o_] &= w_mask; }   \
-        } else if (MODE == 6 || MODE == 16) {                              \
-            _Pragma("unroll") for (int o_ = 0; o_ < NOUT; ++o_) v[o_] = MODE == 16 ? usat_add(X[o_], v[o_]) : sat_add(X[o_], v[o_]);   \
+            if (WJ && ((L) & 1)) { _Pragma("unroll") for (int o_ = 0; o_ < NOUT; ++o_) v[o_] &= w_mask; }   \
+        } else if (LJ) {                                                   \
+            _Pragma("unroll") for (int o_ = 0; o_ < NOUT; ++o_) v[o_] = MODE == QTF_LJ_U ? usat_add(X[o_], v[o_]) : sat_add(X[o_], v[o_]);   \
             if ((L) & 1) { _Pragma("unroll") for (int o_ = 0; o_ < NOUT; ++o_) v[o_] &= lj_mask; }               \
-        } else if (MODE >= 3) { if ((L) < 4) node_fx_rec<MODE>(v, X, flow[(L) < 4 ? (L) : 0]); else node_fx<MODE>(v, X, tab, L); } \
-        else if (MODE != 0) node_fixed<MODE>(v, X, flo, fhi, bias, span);  \
+        } else if (MODE >= QTF_REC_CLAMP) { if ((L) < 4) node_fx_rec<MODE>(v, X, flow[(L) < 4 ? (L) : 0]); else node_fx<MODE>(v, X, tab, L); } \
+        else if (MODE != QTF_RUNTIME) node_fixed<MODE>(v, X, flo, fhi, bias, span);   \
         else node_all(v, X, tab, L);                                       \
     } while (0)
 
@@ -250,29 +241,29 @@ __global__ __launch_bounds__(256) void k_tree_fast(QTreeFastArgs g)
     const int s = g.split_s;
     const int smask = SPLIT ? ((1 << s) - 1) : 0;
     const QStep pstep = tab->mul[0].q;
-    // MODE 1/2 constants: the shared format's bounds
+    // QTF_ONE_* constants: the shared format's bounds
     const int flo = (int)pstep.lo, fhi = (int)pstep.hi;
-    const int bias = MODE == 1 ? -flo : 0;
+    const int bias = MODE == QTF_ONE_ZERO ? -flo : 0;
     const unsigned span = (unsigned)(fhi - flo);
     const int pd = pstep.d > 0 ? pstep.d : 0;  // DIRECT: TCPL shift of the product
-    // MODE 3: the product's own compact step (rounding addend, shift, clamp; the upper bound lives in a VGPR for v_med3_i32)
+    // QTF_REC_*: the product's own compact step (rounding addend, shift, clamp; the upper bound lives in a VGPR for v_med3_i32)
     const QFix fp = tab->fmul[0];
-    const int phi_v = MODE >= 3 ? fx_vgpr(fp.hi) : 0;
+    const int phi_v = MODE >= QTF_REC_CLAMP ? fx_vgpr(fp.hi) : 0;
     // ... and the records of the four lowest levels (15 of 16 nodes) stay in registers; the upper levels load theirs per node
     QFix flow[4];
 #pragma unroll
     for (int l = 0; l < 4; ++l) flow[l] = tab->fadd[0][l];
-    // MODE 6 (QTreeTable::lj): shift of the justified values, their mask, the product's scaled rounding addend, the operands' factors
-    // 21: a WRAPPING 32-bit word (signed WRP::TCPL — what `(int32_t)(((int64_t)a * b) >> 16)` and a plain `+=` compute): the word is
-    // v_alignbit of the exact product's halves and a node a plain 32-bit add, nothing is tested or selected
-    constexpr bool W32 = MODE >= 17 && MODE <= 21;   // 19 / 20: 17 / 18 on JUSTIFIED words (formats of fewer than 32 bits held as x * 2^sj, qg_plan.cpp)
-    constexpr bool WJ = MODE == 19 || MODE == 20, WCMP = MODE == 17 || MODE == 19, WMAD = MODE == 18 || MODE == 20;
+    // the word forms (QTreeTable::lj: the product's shift and rounding addend; QTF_WORD_WRAP — what `(int32_t)(((int64_t)a * b) >> 16)`
+    // and a plain `+=` compute — tests and selects nothing)
+    constexpr bool W32 = MODE >= QTF_WORD && MODE <= QTF_WORD_WRAP;
+    constexpr bool WJ = MODE == QTF_JWORD || MODE == QTF_JWORD_MAD, WCMP = MODE == QTF_WORD || MODE == QTF_JWORD, WMAD = MODE == QTF_WORD_MAD || MODE == QTF_JWORD_MAD;
     const int w_d = W32 ? tab->lj.s : 0, w_t = W32 ? tab->lj.t[0] : 0;   // the product's shift and rounding addend
     unsigned w_half = WCMP ? 1u << ((w_d - 1) & 31) : 0u, w_lim = WCMP ? 1u << (w_d & 31) : 0u;
     const int w_f = WMAD ? 1 << ((32 - w_d) & 31) : 0;                   // 2^(32 - d), the weight of the product's high half in the word
-    const int w_j = WJ ? tab->lj.e[0] : 0, w_mask = WJ ? (int)(~0u << w_j) : -1;   // bits below the unit in a justified word, cleared as MODE 6 clears them
+    const int w_j = WJ ? tab->lj.e[0] : 0, w_mask = WJ ? (int)(~0u << w_j) : -1;   // bits below the unit in a justified word, cleared as QTF_LJ clears them
     if (WCMP) asm volatile("" : "+s"(w_lim));   // (opaque: the compiler would rewrite "x < 2^d" as a shift and a compare with 0 — one instruction more per product)
-    constexpr bool LJ = MODE == 6 || MODE == 16;   // (16: the unsigned counterpart — uint32 range, v_mad_u32_u24 / v_add_u32 ... clamp)
+    // QTF_LJ / QTF_LJ_U (QTreeTable::lj): shift of the justified values, their mask, the product's scaled rounding addend, the operands' factors
+    constexpr bool LJ = MODE == QTF_LJ || MODE == QTF_LJ_U;
     const int lj_s = LJ ? tab->lj.s : 0, lj_mask = LJ ? (int)(~0u << lj_s) : -1, lj_t = LJ ? tab->lj.t[0] : 0;
     const int lj_ea = LJ ? tab->lj.e[0] : 0, lj_eb = LJ ? tab->lj.e[1] : 0;
 
@@ -333,7 +324,7 @@ __global__ __launch_bounds__(256) void k_tree_fast(QTreeFastArgs g)
                         if (SPLIT) blv[j] = e == 0 ? bl4[j].x : e == 1 ? bl4[j].y : e == 2 ? bl4[j].z : bl4[j].w;
                     }
                     // ---- leaves: 8 quantised products
-                    if (MODE == 21) {
+                    if (MODE == QTF_WORD_WRAP) {
 #pragma unroll
                         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -346,7 +337,7 @@ __global__ __launch_bounds__(256) void k_tree_fast(QTreeFastArgs g)
                         // bit of v_mad_i32_i24 saturates exactly that sum to the word (the hardware clamps the full-width result,
                         // tools/ubench/sat_semantics.hip).  hi enters as a 24-bit factor: every in-range hi is within 2^(d-1) <= 2^22, and one
                         // clamped to +-2^23 still carries the sum past the word's range (d <= 23) — 4 instructions per product where the
-                        // range test and select of MODE 17 take 7
+                        // range test and select of QTF_WORD take 7
 #pragma unroll
                         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -356,7 +347,7 @@ __global__ __launch_bounds__(256) void k_tree_fast(QTreeFastArgs g)
                                 asm("v_med3_i32 %0, %0, %1, %2" : "+v"(ph) : "s"(-(1 << 23)), "v"((1 << 23) - 1));
                                 v[i * 2 + j] = sat_mad24_vsv(ph, w_f, (int)((unsigned)p >> w_d)) & w_mask;   // (w_mask: -1 unless justified — folded away)
                             }
-                    } else if (WCMP) {   // 32-bit words (fast_mode 10): floor((a b + t) / 2^d) of the exact 64-bit product, saturated to the word
+                    } else if (WCMP) {   // 32-bit words (QTF_WORD): floor((a b + t) / 2^d) of the exact 64-bit product, saturated to the word
 #pragma unroll
                         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -373,8 +364,8 @@ __global__ __launch_bounds__(256) void k_tree_fast(QTreeFastArgs g)
 #pragma unroll
                         for (int i = 0; i < 4; ++i)
 #pragma unroll
-                            for (int j = 0; j < 2; ++j) v[i * 2 + j] = (MODE == 16 ? usat_mad24_vvs(av[i], bhv[j], lj_t) : sat_mad24_vvs(av[i], bhv[j], lj_t)) & lj_mask;
-                    } else if (MODE == 5 && fp.skip != 0) {
+                            for (int j = 0; j < 2; ++j) v[i * 2 + j] = (MODE == QTF_LJ_U ? usat_mad24_vvs(av[i], bhv[j], lj_t) : sat_mad24_vvs(av[i], bhv[j], lj_t)) & lj_mask;
+                    } else if (MODE == QTF_REC_KINDS && fp.skip != 0) {
                         // a product whose rounding looks at the value's sign or parity (RND::ZERO / INF / CONV, TRN::SMGN)
                         if (SPLIT) {
                             int lw[NOUT];
@@ -397,7 +388,7 @@ __global__ __launch_bounds__(256) void k_tree_fast(QTreeFastArgs g)
                                 for (int j = 0; j < 2; ++j) v[i * 2 + j] = __mul24(av[i], bhv[j]);
                             fx_finish_any<NOUT>(v, fp);   // (d > 0: the rounding kind, the shift, the overflow kind)
                         }
-                    } else if (MODE >= 3) {
+                    } else if (MODE >= QTF_REC_CLAMP) {
 #pragma unroll
                         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -416,20 +407,20 @@ __global__ __launch_bounds__(256) void k_tree_fast(QTreeFastArgs g)
                                 for (int o = 0; o < NOUT; ++o) v[o] >>= fp.d;
                             } else if (fp.ls) {
 #pragma unroll
-                                for (int o = 0; o < NOUT; ++o) v[o] = (int)((unsigned)v[o] << fp.ls) + (MODE == 4 ? fp.lo : 0);
+                                for (int o = 0; o < NOUT; ++o) v[o] = (int)((unsigned)v[o] << fp.ls) + (MODE == QTF_REC_BIASED ? fp.lo : 0);
                             }
                         }
-                        if (MODE == 3) {
+                        if (MODE == QTF_REC_CLAMP) {
 #pragma unroll
                             for (int o = 0; o < NOUT; ++o) asm("v_med3_i32 %0, %0, %1, %2" : "+v"(v[o]) : "s"(fp.lo), "v"(phi_v));
                         } else {
                             QFix f0 = fp;
                             f0.d = 0;   // (the shift is done)
                             f0.skip = 0;
-                            if (MODE == 4) fx_finish_biased<NOUT>(v, f0);
+                            if (MODE == QTF_REC_BIASED) fx_finish_biased<NOUT>(v, f0);
                             else fx_finish_any<NOUT>(v, f0);
                         }
-                    } else if (MODE != 0) {
+                    } else if (MODE != QTF_RUNTIME) {
 #pragma unroll
                         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -442,7 +433,7 @@ __global__ __launch_bounds__(256) void k_tree_fast(QTreeFastArgs g)
                                 } else {
                                     p = (__mul24(av[i], bhv[j]) + (bias << pd)) >> pd;
                                 }
-                                if (MODE == 1) p = ((unsigned)p > span) ? bias : p;
+                                if (MODE == QTF_ONE_ZERO) p = ((unsigned)p > span) ? bias : p;
                                 else p = qg_clamp_i32(p, flo, fhi);
                                 v[i * 2 + j] = p;
                             }
@@ -511,17 +502,17 @@ __global__ __launch_bounds__(256) void k_tree_fast(QTreeFastArgs g)
         }
     }
     // after the last block the counter has carried through every level: v holds the root
-    if (MODE == 1) {
+    if (MODE == QTF_ONE_ZERO) {
 #pragma unroll
         for (int o = 0; o < NOUT; ++o) v[o] -= bias;
     }
-    if (MODE == 4) {   // the root's bias
+    if (MODE == QTF_REC_BIASED) {   // the root's bias
 #pragma unroll
         for (int o = 0; o < NOUT; ++o) v[o] -= fp.ka;
     }
     if (LJ) {   // floor(v / 2^s): the value
 #pragma unroll
-        for (int o = 0; o < NOUT; ++o) v[o] = MODE == 16 ? (int)((unsigned)v[o] >> lj_s) : v[o] >> lj_s;
+        for (int o = 0; o < NOUT; ++o) v[o] = MODE == QTF_LJ_U ? (int)((unsigned)v[o] >> lj_s) : v[o] >> lj_s;
     }
     if (WJ) {
 #pragma unroll
@@ -546,19 +537,19 @@ __global__ __launch_bounds__(256) void k_tree_fast(QTreeFastArgs g)
         }
 }
 
-// ---- packed 16-bit form (fast_mode 7): the left-justified form of MODE 6 for formats of at most 16 bits, TWO outputs per
+// ---- packed 16-bit form (QTF_PK16): the left-justified form of QTF_LJ for formats of at most 16 bits, TWO outputs per
 // register.  A lane owns 4 rows x 2 columns (tx, tx + 16) as 4 registers (low half: column tx); a product pair is ONE
 // v_pk_mad_i16 ... clamp (the hardware saturates a * b + t from the exact product, tools/ubench/sat_semantics.hip) whose A
 // operand is broadcast to both halves by op_sel (A is staged as 16-bit values, two k per dword; B as (column tx, column
 // tx + 16) pairs per k), + v_and; a node pair is one v_pk_add_i16 ... clamp, + v_and at the odd levels: 1.9 vector
-// instructions per MAC where MODE 6 spends 3.8 and the v_med3 form 5.3 (BASELINE configuration 2 as literally configured).
+// instructions per MAC where QTF_LJ spends 3.8 and the v_med3 form 5.3 (BASELINE configuration 2 as literally configured).
 constexpr int PKP = 18;   // dwords per sA16 row (16 + 2: 8-byte reads stay aligned)
-// HYB (fast_mode 8): formats of 9 ... 16 bits whose PRODUCT does not fit the halves (format bits + the product's rounding shift
-// > 16: int<7,8>, the 16-bit words of most fixed-point code).  The product is MODE 6's — one saturating v_mad_i32_i24 per output
+// HYB (QTF_PK16_HYB, _HYB16): formats of 9 ... 16 bits whose PRODUCT does not fit the halves (format bits + the product's rounding shift
+// > 16: int<7,8>, the 16-bit words of most fixed-point code).  The product is QTF_LJ's — one saturating v_mad_i32_i24 per output
 // on x * 2^(32 - bits) — and its HIGH half is the value justified in 16 bits: one v_perm_b32 packs the high halves of a lane's two
 // columns and drops the low ones — for a 16-bit format that IS the rounding's floor and no low bits exist to be cleared anywhere
 // (2.0 vector instructions per MAC); narrower formats clear the rest of the fraction with one v_and per pair and then follow the
-// packed form's rule (2.7 per MAC) — where MODE 6 spends 3.5.
+// packed form's rule (2.7 per MAC) — where QTF_LJ spends 3.5.
 #define NODE16(X, L)                                                                                     \
     do {                                                                                                 \
         _Pragma("unroll") for (int o_ = 0; o_ < 4; ++o_) v[o_] = UNS ? pk_add_usat(X[o_], v[o_]) : pk_add_sat(X[o_], v[o_]);   \
@@ -743,13 +734,37 @@ __global__ __launch_bounds__(256) void k_tree_pk16(QTreeFastArgs g)
 } // namespace
 
 template <bool SPLIT, bool MUL24, int MODE>
-static void launch_tf(int n_levels, dim3 grid, hipStream_t st, const QTreeFastArgs& g)
+static hipError_t launch_tf(int n_levels, dim3 grid, hipStream_t st, const QTreeFastArgs& g)
 {
     if (n_levels <= 12) hipLaunchKernelGGL((k_tree_fast<SPLIT, MUL24, 12, MODE>), grid, dim3(256), 0, st, g);
     else hipLaunchKernelGGL((k_tree_fast<SPLIT, MUL24, 16, MODE>), grid, dim3(256), 0, st, g);
+    return hipGetLastError();
 }
 
-hipError_t qg_launch_tree_fast(const QTreeTable* dev_table, int n_levels, int split_s, int mul24, int mode, const void* A, const void* B,
+// the forms that split the product at its rounding shift where it needs one (QAnalysis::split_s)
+template <bool SPLIT>
+static hipError_t launch_tf_split(QTreeForm form, int mul24, int n_levels, dim3 grid, hipStream_t st, const QTreeFastArgs& g)
+{
+    switch (form) {
+    case QTF_ONE_ZERO: return launch_tf<SPLIT, true, QTF_ONE_ZERO>(n_levels, grid, st, g);
+    case QTF_ONE_TCPL: return launch_tf<SPLIT, true, QTF_ONE_TCPL>(n_levels, grid, st, g);
+    case QTF_REC_CLAMP: return launch_tf<SPLIT, true, QTF_REC_CLAMP>(n_levels, grid, st, g);
+    case QTF_REC_BIASED: return launch_tf<SPLIT, true, QTF_REC_BIASED>(n_levels, grid, st, g);
+    case QTF_REC_KINDS: return launch_tf<SPLIT, true, QTF_REC_KINDS>(n_levels, grid, st, g);
+    case QTF_RUNTIME: return mul24 ? launch_tf<SPLIT, true, QTF_RUNTIME>(n_levels, grid, st, g) : launch_tf<SPLIT, false, QTF_RUNTIME>(n_levels, grid, st, g);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+template <int HYB, bool UNS>
+static hipError_t launch_pk16(int n_levels, dim3 grid, hipStream_t st, const QTreeFastArgs& g)
+{
+    if (n_levels <= 12) hipLaunchKernelGGL((k_tree_pk16<12, HYB, UNS>), grid, dim3(256), 0, st, g);
+    else hipLaunchKernelGGL((k_tree_pk16<16, HYB, UNS>), grid, dim3(256), 0, st, g);
+    return hipGetLastError();
+}
+
+hipError_t qg_launch_tree_fast(const QTreeTable* dev_table, int n_levels, int split_s, int mul24, QTreeForm form, const void* A, const void* B,
                                void* C, int64_t M, int64_t N, int64_t K, int cbytes, hipStream_t st)
 {
     if (K % KC != 0 || n_levels < 5 || n_levels > 16) return hipErrorInvalidValue;
@@ -758,58 +773,23 @@ hipError_t qg_launch_tree_fast(const QTreeTable* dev_table, int n_levels, int sp
     if (blocks <= 0) return hipSuccess;
     if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
     dim3 grid((unsigned)blocks);
-    if (mode == 10) {   // 32-bit words: exact 64-bit products, saturating adds (qg_plan.cpp, fast_mode 10)
-        launch_tf<false, false, 17>(n_levels, grid, st, g);
-        return hipGetLastError();
+    // (the word forms form exact 64-bit products; the others are built for 24-bit multiplies, except the run-time-mode form)
+    if (!mul24 && form != QTF_RUNTIME && !(form >= QTF_WORD && form <= QTF_WORD_WRAP)) return hipErrorInvalidValue;
+    switch (form) {
+    case QTF_WORD: return launch_tf<false, false, QTF_WORD>(n_levels, grid, st, g);
+    case QTF_WORD_WRAP: return launch_tf<false, false, QTF_WORD_WRAP>(n_levels, grid, st, g);
+    case QTF_JWORD: return launch_tf<false, false, QTF_JWORD>(n_levels, grid, st, g);
+    case QTF_JWORD_MAD: return launch_tf<false, false, QTF_JWORD_MAD>(n_levels, grid, st, g);
+    case QTF_WORD_MAD: return launch_tf<false, false, QTF_WORD_MAD>(n_levels, grid, st, g);
+    case QTF_PK16_U: return launch_pk16<0, true>(n_levels, grid, st, g);
+    case QTF_PK16_HYB_U: return launch_pk16<1, true>(n_levels, grid, st, g);
+    case QTF_PK16_HYB16_U: return launch_pk16<2, true>(n_levels, grid, st, g);
+    case QTF_PK16: return launch_pk16<0, false>(n_levels, grid, st, g);
+    case QTF_PK16_HYB: return launch_pk16<1, false>(n_levels, grid, st, g);
+    case QTF_PK16_HYB16: return launch_pk16<2, false>(n_levels, grid, st, g);
+    case QTF_LJ_U: return launch_tf<false, true, QTF_LJ_U>(n_levels, grid, st, g);
+    case QTF_LJ: return launch_tf<false, true, QTF_LJ>(n_levels, grid, st, g);   // (the left-justified forms are never split)
+    default:
+        return split_s > 0 ? launch_tf_split<true>(form, mul24, n_levels, grid, st, g) : launch_tf_split<false>(form, mul24, n_levels, grid, st, g);
     }
-    if (mode == 14) {   // a wrapping 32-bit word (signed WRP::TCPL)
-        launch_tf<false, false, 21>(n_levels, grid, st, g);
-        return hipGetLastError();
-    }
-    if (mode == 12 || mode == 13) {   // ... on justified words (formats of fewer than 32 bits): 12 the compare form, 13 the multiply-add form
-        if (mode == 12) launch_tf<false, false, 19>(n_levels, grid, st, g);
-        else launch_tf<false, false, 20>(n_levels, grid, st, g);
-        return hipGetLastError();
-    }
-    if (mode == 11) {   // ... with a product shift of 10 ... 23 (qg_api.hip reads it from the table): the product's word from one saturating multiply-add
-        launch_tf<false, false, 18>(n_levels, grid, st, g);
-        return hipGetLastError();
-    }
-    if (mode != 0 && !mul24) mode = 0;  // the fixed-mode variants are built for 24-bit multiplies only
-    const bool uns = mode >= 16;   // (+ 16: the unsigned counterparts)
-    if (uns) mode -= 16;
-    if (mode >= 7 && mode <= 9) {   // packed 16-bit halves (7); 32-bit justified products, packed 16-bit nodes (8: fewer than 16 bits; 9: exactly 16)
-#define QG_PK16_LAUNCH(H, U)                                                                                   \
-        do {                                                                                                       \
-            if (n_levels <= 12) hipLaunchKernelGGL((k_tree_pk16<12, H, U>), grid, dim3(256), 0, st, g);            \
-            else hipLaunchKernelGGL((k_tree_pk16<16, H, U>), grid, dim3(256), 0, st, g);                           \
-        } while (0)
-        if (uns) { if (mode == 7) QG_PK16_LAUNCH(0, true); else if (mode == 8) QG_PK16_LAUNCH(1, true); else QG_PK16_LAUNCH(2, true); }
-        else { if (mode == 7) QG_PK16_LAUNCH(0, false); else if (mode == 8) QG_PK16_LAUNCH(1, false); else QG_PK16_LAUNCH(2, false); }
-#undef QG_PK16_LAUNCH
-        return hipGetLastError();
-    }
-    if (mode == 6) {   // left-justified saturating form: never split (the planner checked the scaled operands against 24 bits)
-        if (uns) launch_tf<false, true, 16>(n_levels, grid, st, g);
-        else launch_tf<false, true, 6>(n_levels, grid, st, g);
-        return hipGetLastError();
-    }
-    if (split_s > 0) {
-        if (mode == 1) launch_tf<true, true, 1>(n_levels, grid, st, g);
-        else if (mode == 2) launch_tf<true, true, 2>(n_levels, grid, st, g);
-        else if (mode == 3) launch_tf<true, true, 3>(n_levels, grid, st, g);
-        else if (mode == 4) launch_tf<true, true, 4>(n_levels, grid, st, g);
-        else if (mode == 5) launch_tf<true, true, 5>(n_levels, grid, st, g);
-        else if (mul24) launch_tf<true, true, 0>(n_levels, grid, st, g);
-        else launch_tf<true, false, 0>(n_levels, grid, st, g);
-    } else {
-        if (mode == 1) launch_tf<false, true, 1>(n_levels, grid, st, g);
-        else if (mode == 2) launch_tf<false, true, 2>(n_levels, grid, st, g);
-        else if (mode == 3) launch_tf<false, true, 3>(n_levels, grid, st, g);
-        else if (mode == 4) launch_tf<false, true, 4>(n_levels, grid, st, g);
-        else if (mode == 5) launch_tf<false, true, 5>(n_levels, grid, st, g);
-        else if (mul24) launch_tf<false, true, 0>(n_levels, grid, st, g);
-        else launch_tf<false, false, 0>(n_levels, grid, st, g);
-    }
-    return hipGetLastError();
 }

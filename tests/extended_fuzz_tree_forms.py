@@ -2,7 +2,7 @@
 """Opt-in fuzz of the real 32-bit tree kernel's step forms on an MI355X (not collected by pytest): tree-class descriptors
 whose roundings are "add a constant, shift right" (TRN::TCPL, RND::POS_INF, RND::NEG_INF) and whose overflows are a clamp
 (SAT::TCPL, SAT::SMGN), a range test (SAT::ZERO) or a wrap (WRP::TCPL), with product tags and 0..3 level types of other widths / fracBits, any K >= 17, split and direct
-products — so that the planner picks the compact per-level form (fast_mode 3) or one of the one-format forms.  Each case:
+products — so that the planner picks the compact per-level forms (QTF_REC_*) or one of the one-format forms.  Each case:
 GPU against the oracle, and against the same plan with run-time modes (QG_OPT_RUNTIME_MODES).
 usage: python tests/extended_fuzz_tree_forms.py [cases] [seed]"""
 import json

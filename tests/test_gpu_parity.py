@@ -436,7 +436,7 @@ def test_justified_word_tree_form(oracle, K):
 def test_32_bit_word_tree_form(oracle, K):
     """Q15.16 with default tags — every product and every tree node quantised into the 32-bit word — and relatives: the product
     from the exact 64-bit product (truncating and rounding shifts, operands of other widths), a node one saturating 32-bit add
-    (`fast_mode` 10 on the 32-bit tree kernel's frame).  Against the oracle, with full-range operands (the sums saturate) and
+    (`QTF_WORD` ... `QTF_WORD_WRAP` on the 32-bit tree kernel's frame).  Against the oracle, with full-range operands (the sums saturate) and
     small ones (they do not), and against the 64-bit tree kernel the same descriptor takes with QG_OPT_RUNTIME_MODES."""
     q = Qu(15, 16)
     cases = [(q, q, q, {}), (Qu(15, 16, True, RND.POS_INF, SAT.TCPL), Qu(15, 16, True, RND.POS_INF, SAT.TCPL), Qu(20, 4), {}),

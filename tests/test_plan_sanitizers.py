@@ -59,7 +59,8 @@ def random_descs(n, seed):
 
 def compact_form_descs(n, seed):
     """descriptors whose roundings add a constant and whose overflows clamp / test / wrap: the planner's compact step records
-    (QFix: fast_mode 3 / 4 / 5, cplx_fixed_ok 2 / 3 / 8 + features, gemv_fixed 3 / 5) are built for most of them"""
+    (QFix: QTF_REC_CLAMP / _BIASED / _KINDS, QCF_COMPACT / QCF_KINDS / QCF_KINDS_*, QGF_REC_CLAMP / _KINDS; qublas_amd/csrc/qg_forms.h) are
+    built for most of them"""
     from qublas_amd.desc import BasicComplexMul, Qcomplex, TFComplexMul, lower_reduce
     rng = random.Random(seed)
     QM, OM = [5, 0, 1], [0, 0, 2, 1, 3]     # TRN::TCPL, RND::POS_INF, RND::NEG_INF; SAT::TCPL, SAT::SMGN, SAT::ZERO, WRP::TCPL
@@ -98,7 +99,7 @@ def compact_form_descs(n, seed):
     return out
 
 
-def test_planner_under_asan_ubsan(tmp_path):
+def test_planner_and_tree_choice_under_asan_ubsan(tmp_path):
     exe = build_driver(str(tmp_path))
     descs = [desc_from_dict(j) for j in G.gemm_cases("real") + G.gemm_cases("cplx")] + random_descs(3000, 5) + compact_form_descs(1500, 6)
     blob = bytearray()
@@ -115,14 +116,29 @@ def test_planner_under_asan_ubsan(tmp_path):
     L = capi.lib()
     n_ok = 0
     forms = {"fast": set(), "cplx": set(), "gemv": set()}
+    tree_kernels = {3, 4, 5, 6, 8, 9, 10}            # QG_KERNEL_TREE_* / QG_KERNEL_GEMV_*: the plans qg_tree_choice decides
+    named = {3: "tree kernel", 6: "complex kernel", 8: "one-column kernel"}
+    n_tree = 0
     for ln, d in zip(lines, descs):
-        _, st, cls, bits, _, _, _, fm, cf, gf = ln.split()
+        head, *choices = ln.split("|")
+        _, st, cls, bits, _, _, _, fm, cf, gf = head.split()
         forms["fast"].add(int(fm)); forms["cplx"].add(int(cf)); forms["gemv"].add(int(gf))
         info = capi.qgemul_info()
         assert L.qgemul_classify(C.byref(d), 0, C.byref(info)) == int(st)
         if int(st) == 0:
             assert info.cls == int(cls) and info.max_bits == int(bits)
             n_ok += 1
-    assert n_ok > 500
+            # the resolver's kernel and form name are the product library's kernel and reason, under each plan flag set
+            assert len(choices) == 3, ln
+            for fl, ch in zip((0, capi.OPT_RUNTIME_MODES, capi.OPT_GENERIC_TREE), choices):
+                kernel, name = ch.split(" ", 1)
+                info = capi.qgemul_info()
+                if L.qgemul_classify(C.byref(d), fl, C.byref(info)) != 0 or info.kernel not in tree_kernels:
+                    continue
+                n_tree += 1
+                assert info.kernel == int(kernel), (ln, fl)
+                if info.kernel in named:
+                    assert info.reason.decode() == f"exact tree evaluation; {named[info.kernel]} steps: {name}", (ln, fl)
+    assert n_ok > 500 and n_tree > 1000, (n_ok, n_tree)
     # the record-building code ran under the sanitizers for every form
     assert {1, 2, 3, 4, 5} <= forms["fast"] and {1, 2, 3} <= forms["cplx"] and any(f >= 8 for f in forms["cplx"]) and {1, 2, 3, 5} <= forms["gemv"], forms

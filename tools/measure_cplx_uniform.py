@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A/B of the complex tree kernel's "one clamp for the whole loop" form (qg_tree_cplx.hip, MODE 4) against the compact
+"""A/B of the complex tree kernel's "one clamp for the whole loop" form (qg_tree_cplx.hip, QCF_UNIFORM) against the compact
 per-step-record form the same descriptors had before, at BASELINE configuration 5 (2048^3 Qcomplex<int<6,3>, int<6,-3>>
 RND::POS_INF + SAT::TCPL, TFComplexMul) and with the reference's default modes.  Run with the diagnostic library:
     QUBLAS_AMD_DIAG=1 python tools/measure_cplx_uniform.py                       # the new form
