@@ -584,7 +584,11 @@ int qoracle_eltwise(const qgemul_epilogue* ep, qfmt c, int64_t n, const int64_t*
  * Synthetic operands: raw value of host element e, part p is drawn from the
  * counter-based generator below, so host and device produce identical tensors without sharing
  * state.  dist 0: uniform over the whole representable range, as Qu::fill() does
- * (QuBLAS.h:526-536); dist 1: |raw| < 2^(W/2) ("small", keeps narrow accumulators unsaturated).
+ * (QuBLAS.h:526-536); dist 1: |raw| < 2^(W/2) ("small", keeps narrow accumulators unsaturated);
+ * dist 2 ("edges", host only: the device fill knows dist 0 and 1): the lowest bit of the random value picks, about half the
+ * time, an entry of the format's edge set (qo_edges) chosen by the other bits, else the dist-0 value.  The edge set puts exact
+ * boundary products (-1 * min, 1 * max, (1 + ulp) * max), rounding ties (1/2 * odd) and boundary node sums into every
+ * reduction of a few dozen leaves.  oracle/ref_driver.hpp restates all of this bit for bit.
  */
 static inline uint64_t qo_rand(uint64_t seed, uint64_t idx)
 {
@@ -594,6 +598,35 @@ static inline uint64_t qo_rand(uint64_t seed, uint64_t idx)
     return z ^ (z >> 31);
 }
 
+/* E(f): the sorted, distinct values of  lo, lo+1, -2^F-1, -2^F, -2^(F-1), -1, 0, 1, 2^(F-1), 2^F-1, 2^F, 2^F+1, hi-1, hi
+ * that lie in the format's raw range [lo, hi] (clipped to int64); terms that are not integers (F <= 0) are left out.
+ * 2^F is the format's one.  Returns the count (at most 14). */
+static int qo_edges(qfmt f, int64_t out[14])
+{
+    const int W = (int)f.I + (int)f.F, F = (int)f.F;
+    const __int128 lo = f.S ? (W >= 64 ? (__int128)INT64_MIN : -((__int128)1 << W)) : 0;
+    const __int128 hi = W >= 63 ? (__int128)INT64_MAX : ((__int128)1 << W) - 1;
+    __int128 c[14];
+    int n = 0;
+    c[n++] = lo; c[n++] = lo + 1; c[n++] = -1; c[n++] = 0; c[n++] = 1; c[n++] = hi - 1; c[n++] = hi;
+    if (F >= 0 && F <= 63) {
+        const __int128 one = (__int128)1 << F;
+        c[n++] = -one - 1; c[n++] = -one; c[n++] = one - 1; c[n++] = one; c[n++] = one + 1;
+        if (F >= 1) { c[n++] = -(one >> 1); c[n++] = one >> 1; }
+    }
+    int m = 0;
+    for (int i = 0; i < n; ++i) {
+        if (c[i] < lo || c[i] > hi) continue;
+        int j = m;                                  /* insertion into the sorted, distinct list */
+        while (j > 0 && out[j - 1] > (int64_t)c[i]) --j;
+        if (j > 0 && out[j - 1] == (int64_t)c[i]) continue;
+        for (int k = m; k > j; --k) out[k] = out[k - 1];
+        out[j] = (int64_t)c[i];
+        ++m;
+    }
+    return m;
+}
+
 int64_t qoracle_synth(qfmt f, uint64_t seed, int dist, uint64_t elem, int part)
 {
     int W = (int)f.I + (int)f.F;
@@ -601,6 +634,11 @@ int64_t qoracle_synth(qfmt f, uint64_t seed, int dist, uint64_t elem, int part)
     int bits = b + (f.S ? 1 : 0);
     if (bits <= 0) return 0;
     uint64_t r = qo_rand(seed, elem * 2 + (uint64_t)part);
+    if (dist == 2 && (r & 1)) {
+        int64_t e[14];
+        const int n = qo_edges(f, e);
+        return e[(r >> 1) % (uint64_t)n];
+    }
     uint64_t v = bits >= 64 ? r : (r >> (64 - bits));
     uint64_t lo = f.S ? (uint64_t)0 - ((uint64_t)1 << b) : 0;   /* unsigned arithmetic: well defined for b = 63 too */
     return (int64_t)(lo + v);

@@ -153,7 +153,8 @@ def _f2(e):
 
 
 def fill(e, n: int, seed: int, dist: int = 0) -> np.ndarray:
-    """Synthetic tight host tensor of n elements (same generator as the engine's fill kernel)."""
+    """Synthetic tight host tensor of n elements (same generator as the engine's fill kernel for dist 0 and 1; dist 2, the
+    edge-heavy distribution of oracle/qoracle.c, is host-only: build such operands here and pass them to capi.run)."""
     out = np.zeros(n, dtype=host_dtype(e))
     lib().qoracle_fill(_f2(e), int(isinstance(e, Qcomplex)), seed, dist, n, out.ctypes.data_as(C.c_void_p))
     return out

@@ -27,6 +27,16 @@ static Inputs syn(int dist, uint64_t sa = 11, uint64_t sb = 12)
     return in;
 }
 
+// dist 2 (edge-heavy operands, oracle/qoracle.c: qo_edges): one case with K <= 3, one with an odd K
+template <class E, class EC, class Mul, class Add, size_t KS, size_t KL, bool TL>
+static void form_pair(const char* name, FILE* out)
+{
+    std::string a = std::string(name) + "_9x7xK" + std::to_string(KS) + "_edges";
+    std::string b = std::string(name) + "_5x6xK" + std::to_string(KL) + (TL ? "_tn" : "") + "_edges";
+    run_case<E, E, EC, Mul, Add, false, 9, 7, KS>(a.c_str(), syn(2, 31, 32), out);
+    run_case<E, E, EC, Mul, Add, TL, 5, 6, KL>(b.c_str(), syn(2, 33, 34), out);
+}
+
 int main(int argc, char** argv)
 {
     int part = argc > 1 ? std::atoi(argv[1]) : 0;
@@ -91,6 +101,49 @@ int main(int argc, char** argv)
         run_case<c5, c5, cn, TypeList<BL>, TypeList<lw>, true, 5, 7, 128>("c5_basic_L_tn_5x7x128_full_narrowC", syn(0), out);
         run_case<c5, c5, c5, TypeList<BL>, TypeList<lw>, false, 2, 2, 2048>("c5_basic_L_2x2x2048_full", syn(0), out);
         run_case<c5, c5, cw, TypeList<BL>, TypeList<lw>, false, 3, 3, 100>("c5_basic_L_K100_small_wideC", syn(1), out);
+        break;
+    }
+    case 4: { // dist 2 (edge-heavy operands) for each step form of the complex 32-bit kernel (qublas_amd/csrc/qg_forms.h: QCplxForm), once
+              // with K <= 3 and once with an odd K
+        using P63 = r63;
+        using P84 = Qu<intBits<8>, fracBits<4>, QuMode<RND::POS_INF>, OfMode<SAT::TCPL>>;
+        using P124 = Qu<intBits<12>, fracBits<4>, QuMode<RND::POS_INF>, OfMode<SAT::TCPL>>;
+        using P102 = Qu<intBits<10>, fracBits<2>, QuMode<RND::POS_INF>, OfMode<SAT::TCPL>>;
+        using cC = Qcomplex<P124, P102>;
+        using c84 = Qcomplex<P84, P84>;
+        using n63s = Qu<intBits<6>, fracBits<3>, QuMode<RND::NEG_INF>, OfMode<SAT::SMGN>>;
+        using cS = Qcomplex<n63s, n63s>;
+        using c9 = Qcomplex<Qu<intBits<9>, fracBits<3>>, Qu<intBits<9>, fracBits<1>>>;
+        using d = TypeList<>;
+        form_pair<c5, c5, TypeList<TFComplexMul<>>, d, 2, 37, true>("cpk16_c5_tf", out);                                        // QCF_PK16
+        form_pair<c5, c5, TypeList<TFComplexMul<ABT<intBits<7>, fracBits<3>>>>, d, 3, 37, false>("ccompact_c5_tf", out);      // QCF_COMPACT
+        form_pair<c84, c5, TypeList<TFComplexMul<>>, d, 1, 37, false>("clj_c84_tf", out);                                      // QCF_LJ
+        form_pair<cS, c5, TypeList<BasicComplexMul<>>, d, 2, 37, true>("cuniform_smgn_basic", out);                           // QCF_UNIFORM
+        form_pair<c5, cC, TypeList<BasicComplexMul<acT<intBits<20>, fracBits<8>>>>, d, 3, 37, false>("ctable_c5_basic", out);  // QCF_TABLE
+        using cR = Qcomplex<Qu<intBits<6>, fracBits<3>, QuMode<RND::CONV>>, Qu<intBits<6>, fracBits<3>, QuMode<RND::CONV>>>;
+        form_pair<cR, c9, TypeList<TFComplexMul<>>, d, 2, 37, false>("ckindsR_conv_tf", out);                                  // QCF_KINDS_R
+        using z63 = Qu<intBits<6>, fracBits<3>, QuMode<TRN::TCPL>, OfMode<SAT::ZERO>>;
+        using z6m3 = Qu<intBits<6>, fracBits<-3>, QuMode<TRN::TCPL>, OfMode<SAT::ZERO>>;
+        using cZ = Qcomplex<z63, z6m3>;
+        using cZC = Qcomplex<Qu<intBits<9>, fracBits<3>, QuMode<TRN::TCPL>, OfMode<SAT::ZERO>>, Qu<intBits<9>, fracBits<1>, QuMode<TRN::TCPL>, OfMode<SAT::ZERO>>>;
+        form_pair<cZ, cZC, TypeList<TFComplexMul<>>, d, 1, 37, true>("ckindsZ_zero_tf", out);                                  // QCF_KINDS_Z
+        using cW = Qcomplex<Qu<intBits<6>, fracBits<3>, QuMode<TRN::TCPL>, OfMode<WRP::TCPL>>, Qu<intBits<6>, fracBits<1>, QuMode<TRN::TCPL>, OfMode<WRP::TCPL>>>;
+        using cWC = Qcomplex<Qu<intBits<7>, fracBits<3>, QuMode<TRN::TCPL>, OfMode<WRP::TCPL>>, Qu<intBits<5>, fracBits<1>, QuMode<TRN::TCPL>, OfMode<WRP::TCPL>>>;
+        form_pair<cW, cWC, TypeList<TFComplexMul<>>, d, 2, 37, false>("ckindsW_wrap_tf", out);                                 // QCF_KINDS_W
+        using cRZ = Qcomplex<Qu<intBits<6>, fracBits<3>, QuMode<RND::CONV>, OfMode<SAT::ZERO>>, Qu<intBits<6>, fracBits<3>, QuMode<RND::CONV>, OfMode<SAT::ZERO>>>;
+        form_pair<cRZ, c9, TypeList<TFComplexMul<>>, d, 3, 37, false>("ckindsRZ_tf", out);                                     // QCF_KINDS_RZ
+        using cRW = Qcomplex<Qu<intBits<6>, fracBits<3>, QuMode<RND::CONV>, OfMode<WRP::TCPL>>, Qu<intBits<6>, fracBits<3>, QuMode<RND::CONV>, OfMode<WRP::TCPL>>>;
+        form_pair<cRW, c9, TypeList<TFComplexMul<>>, d, 2, 37, true>("ckindsRW_tf", out);                                      // QCF_KINDS_RW
+        using cI = Qcomplex<Qu<intBits<6>, fracBits<3>, QuMode<RND::INF>>, Qu<intBits<6>, fracBits<1>, QuMode<RND::INF>, OfMode<SAT::ZERO>>>;
+        using cIC = Qcomplex<Qu<intBits<7>, fracBits<1>, QuMode<RND::INF>>, Qu<intBits<5>, fracBits<0>, QuMode<RND::INF>, OfMode<WRP::TCPL>>>;
+        using cIL = Qcomplex<Qu<intBits<12>, fracBits<2>, QuMode<RND::INF>>, Qu<intBits<12>, fracBits<1>, QuMode<RND::INF>, OfMode<SAT::ZERO>>>;
+        form_pair<cI, cIC, TypeList<BasicComplexMul<acT<intBits<8>, fracBits<4>>>>, TypeList<cIL>, 1, 37, false>("ckindsALL_inf_basic", out);   // QCF_KINDS_ALL
+        using cU = Qcomplex<Qu<intBits<5>, fracBits<4>, QuMode<RND::INF>, OfMode<WRP::TCPL>>, Qu<intBits<6>, fracBits<2>, isSigned<false>, QuMode<RND::ZERO>, OfMode<WRP::TCPL>>>;
+        using cUC = Qcomplex<Qu<intBits<6>, fracBits<2>, QuMode<RND::INF>, OfMode<SAT::ZERO>>, Qu<intBits<5>, fracBits<1>, isSigned<false>, QuMode<RND::CONV>, OfMode<WRP::TCPL>>>;
+        using cUL1 = Qcomplex<Qu<intBits<9>, fracBits<3>, QuMode<RND::INF>, OfMode<WRP::TCPL>>, Qu<intBits<8>, fracBits<1>, isSigned<false>, QuMode<TRN::SMGN>, OfMode<WRP::TCPL>>>;
+        using cUL2 = Qcomplex<Qu<intBits<7>, fracBits<2>, QuMode<RND::ZERO>, OfMode<SAT::ZERO>>, Qu<intBits<9>, fracBits<3>, QuMode<RND::CONV>, OfMode<SAT::SMGN>>>;
+        form_pair<cU, cUC, TypeList<TFComplexMul<>>, TypeList<cUL1, cUL2>, 2, 37, true>("ckinds_unsignedwrap_tf", out);       // QCF_KINDS
+        run_case<c5, c5, c5, TypeList<TFComplexMul<>>, TypeList<>, false, 3, 2, 2>("cpk16_c5_tf_3x2x2_edges_explicit", explicit_synth<c5, c5>(3 * 2, 2 * 2, 35, 36, 2), out);
         break;
     }
     default:

@@ -37,6 +37,33 @@ inline uint64_t qrand(uint64_t seed, uint64_t idx)
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return z ^ (z >> 31);
 }
+// dist 2: the format's edge set E(f) (qo_edges), picked when the random value's lowest bit is set
+template <class T>
+int edges(int64_t out[14])
+{
+    constexpr int W = T::intB + T::fracB, F = T::fracB;
+    const __int128 lo = T::isS ? (W >= 64 ? __int128(INT64_MIN) : -(__int128(1) << (W & 127))) : 0;
+    const __int128 hi = W >= 63 ? __int128(INT64_MAX) : (__int128(1) << (W & 127)) - 1;
+    __int128 c[14];
+    int n = 0;
+    c[n++] = lo; c[n++] = lo + 1; c[n++] = -1; c[n++] = 0; c[n++] = 1; c[n++] = hi - 1; c[n++] = hi;
+    if (F >= 0 && F <= 63) {
+        const __int128 one = __int128(1) << (F & 127);
+        c[n++] = -one - 1; c[n++] = -one; c[n++] = one - 1; c[n++] = one; c[n++] = one + 1;
+        if (F >= 1) { c[n++] = -(one >> 1); c[n++] = one >> 1; }
+    }
+    int m = 0;
+    for (int i = 0; i < n; ++i) {
+        if (c[i] < lo || c[i] > hi) continue;
+        int j = m;
+        while (j > 0 && out[j - 1] > int64_t(c[i])) --j;
+        if (j > 0 && out[j - 1] == int64_t(c[i])) continue;
+        for (int k = m; k > j; --k) out[k] = out[k - 1];
+        out[j] = int64_t(c[i]);
+        ++m;
+    }
+    return m;
+}
 template <class T>
 int64_t synth(uint64_t seed, int dist, uint64_t elem, int part)
 {
@@ -45,6 +72,11 @@ int64_t synth(uint64_t seed, int dist, uint64_t elem, int part)
     int bits = b + (T::isS ? 1 : 0);
     if (bits <= 0) return 0;
     uint64_t r = qrand(seed, elem * 2 + uint64_t(part));
+    if (dist == 2 && (r & 1)) {
+        int64_t e[14];
+        const int n = edges<T>(e);
+        return e[(r >> 1) % uint64_t(n)];
+    }
     uint64_t v = bits >= 64 ? r : (r >> (64 - bits));
     uint64_t lo = T::isS ? uint64_t(0) - (uint64_t(1) << b) : 0;   // unsigned arithmetic: well defined for b = 63 too
     return int64_t(lo + v);
@@ -256,7 +288,27 @@ struct Inputs {
     uint64_t seedA = 1, seedB = 2;
     int dist = 0;
     std::vector<int64_t> A, B; // explicit raw values, host linear order, complex interleaved re,im
+    bool from_seeds = false;   // explicit values that the generator drew from (seedA, seedB, dist): printed with both
 };
+
+// the generator's values of a case written out explicitly, so that a test can pin oracle/qoracle.c's restatement to this one
+template <class EA, class EB>
+Inputs explicit_synth(size_t nA, size_t nB, uint64_t sa, uint64_t sb, int dist)
+{
+    Inputs in;
+    in.synthetic = false;
+    in.from_seeds = true;
+    in.seedA = sa; in.seedB = sb; in.dist = dist;
+    for (size_t e = 0; e < nA; ++e) {
+        in.A.push_back(synth<typename parts<EA>::re>(sa, dist, e, 0));
+        if (is_cplx<EA>) in.A.push_back(synth<typename parts<EA>::im>(sa, dist, e, 1));
+    }
+    for (size_t e = 0; e < nB; ++e) {
+        in.B.push_back(synth<typename parts<EB>::re>(sb, dist, e, 0));
+        if (is_cplx<EB>) in.B.push_back(synth<typename parts<EB>::im>(sb, dist, e, 1));
+    }
+    return in;
+}
 
 // one dot product through the reference primitives
 template <class EA, class EB, class EC, class MulList, class AddList, size_t K>
@@ -348,7 +400,11 @@ void run_case(const char* name, const Inputs& in, FILE* out)
         for (size_t e = 0; e < in.A.size(); ++e) std::fprintf(out, "%s%lld", e ? "," : "", (long long)in.A[e]);
         std::fprintf(out, "],\"B\":[");
         for (size_t e = 0; e < in.B.size(); ++e) std::fprintf(out, "%s%lld", e ? "," : "", (long long)in.B[e]);
-        std::fprintf(out, "]},\n");
+        if (in.from_seeds)
+            std::fprintf(out, "],\"from\":{\"seedA\":%llu,\"seedB\":%llu,\"dist\":%d}},\n", (unsigned long long)in.seedA,
+                         (unsigned long long)in.seedB, in.dist);
+        else
+            std::fprintf(out, "]},\n");
     }
     std::fprintf(out, " \"C\":[");
     for (size_t e = 0; e < C.size(); ++e) std::fprintf(out, "%s%s", e ? "," : "", dec(C[e]).c_str());

@@ -287,9 +287,15 @@ int qg_analyze_ep(qfmt cfmt, const qgemul_epilogue* ep, QEpTable* out, int* max_
         while (r < b) r *= 2;
         return r;
     };
+    // the chain kernels are 64-bit only: make_step gives a step bounds only up to 62 value bits
+    auto chain_fmt_ok = [&c](qfmt f) {
+        if (!fmt_ok(c, f)) return false;
+        if ((int)f.I + (int)f.F > 62) { c.fail(QG_EUNSUPPORTED, "element-wise chain format wider than 62 value bits"); return false; }
+        return true;
+    };
     do {
         if (!ep || ep->n_stages > QG_MAX_EW) { c.fail(QG_EINVAL, "null epilogue or too many stages"); break; }
-        if (!fmt_ok(c, cfmt) || !fmt_ok(c, ep->d)) break;
+        if (!chain_fmt_ok(cfmt) || !chain_fmt_ok(ep->d)) break;
         Val x;
         x.f = cfmt;
         x.r = fmt_range(cfmt);
@@ -308,12 +314,12 @@ int qg_analyze_ep(qfmt cfmt, const qgemul_epilogue* ep, QEpTable* out, int* max_
                 t.node.q.identity = 1;
                 t.cvt.identity = 1;
                 if (k + 1 < ep->n_stages) {
-                    if (!fmt_ok(c, s.t)) { ok = false; break; }
+                    if (!chain_fmt_ok(s.t)) { ok = false; break; }
                     x = do_cvt(c, x, s.t, &t.cvt);
                 }
                 continue;
             }
-            if (!fmt_ok(c, s.e) || !fmt_ok(c, s.r)) { ok = false; break; }
+            if (!chain_fmt_ok(s.e) || !chain_fmt_ok(s.r)) { ok = false; break; }
             Val e;
             e.f = s.e;
             e.r = fmt_range(s.e);
@@ -328,7 +334,7 @@ int qg_analyze_ep(qfmt cfmt, const qgemul_epilogue* ep, QEpTable* out, int* max_
             memset(&t.cvt, 0, sizeof t.cvt);
             t.cvt.identity = 1;
             if (k + 1 < ep->n_stages) {
-                if (!fmt_ok(c, s.t)) { ok = false; break; }
+                if (!chain_fmt_ok(s.t)) { ok = false; break; }
                 x = do_cvt(c, x, s.t, &t.cvt);
             }
         }

@@ -82,7 +82,7 @@ def main():
         k = capi.KERNEL_NAMES[info.kernel]
         form = (("one column: " if k == "gemv_i32" else "") + info.reason.decode().split("steps: ")[-1]) if k in ("tree_i32", "gemv_i32") else k
         forms[form] = forms.get(form, 0) + 1
-        dist = rng.randint(0, 1)
+        dist = rng.randint(0, 2)                    # (2: edge-heavy operands, oracle/qoracle.c qo_edges)
         A = oracle.fill(ea, M * K, rng.randint(1, 1 << 30), dist)
         B = np.ones(K, dtype=np.int32) if reduce_form else oracle.fill(eb, K * N, rng.randint(1, 1 << 30), dist)
         out = np.zeros(M * N, dtype=oracle.host_dtype(ec))

@@ -81,9 +81,10 @@ def main():
         if dry:
             ran += 1
             continue
-        dist = rng.randint(0, 2)
-        A = oracle.fill(ea, M * K, rng.randint(1, 1 << 30), dist % 2)
-        B = np.ones(K, dtype=np.int32) if reduce_form else oracle.fill(eb, K * N, rng.randint(1, 1 << 30), dist % 2)
+        dist = rng.randint(0, 3)
+        gen = 2 if dist == 3 else dist % 2          # (3: the generator's edge-heavy distribution, oracle/qoracle.c qo_edges)
+        A = oracle.fill(ea, M * K, rng.randint(1, 1 << 30), gen)
+        B = np.ones(K, dtype=np.int32) if reduce_form else oracle.fill(eb, K * N, rng.randint(1, 1 << 30), gen)
         if dist == 2:                     # small values: nothing saturates
             A = (A >> rng.randint(4, 12)).astype(A.dtype)
             if not reduce_form:

@@ -174,3 +174,34 @@ def test_config1_known_answer(oracle):
                                        21248, 28160, 35072, 0]
     assert by["c1_tn_classT"]["C"] == [7680, 17920, 28160, 38400, 17920, 44544, 0, 0, 28160, 0, 46336, 0, 38400, 0,
                                        0, 57600]
+
+
+def test_edge_distribution_matches_the_reference_driver(oracle):
+    """The dist-2 (edge-heavy) generator exists twice, in oracle/qoracle.c and restated in oracle/ref_driver.hpp, which drew
+    every seeded dist-2 record.  One record per new fixture file carries the driver's values explicitly with the seeds they
+    came from: oracle.fill must reproduce them bit for bit, or the seeded records would be compared on different operands."""
+    recs = [j for j in G.gemm_cases("real") + G.gemm_cases("cplx") if "from" in j["inputs"]]
+    assert len(recs) >= 5
+    for j in recs:
+        src = j["inputs"]["from"]
+        assert src["dist"] == 2
+        A, B = G.case_inputs(j, oracle)
+        ea, eb, _ = G.case_elems(j)
+        assert A.tobytes() == oracle.fill(ea, j["M"] * j["K"], src["seedA"], 2).tobytes(), j["name"]
+        assert B.tobytes() == oracle.fill(eb, j["K"] * j["N"], src["seedB"], 2).tobytes(), j["name"]
+
+
+def test_edge_distribution_reaches_the_edges(oracle):
+    """dist 2 draws about half of its values from the format's edge set (lo, lo + 1, -one - 1 ... one + 1, hi - 1, hi), the rest
+    as dist 0 does; dist 0 and 1 are unchanged by it"""
+    for e, one in ((Qu(15, 16), 1 << 16), (Qu(4, 3), 8), (Qu(0, 31), 1 << 31), (Qu(6, -3), None), (Qu(8, 0, False), 1)):
+        a = oracle.fill(e, 4000, 9, 2).astype(np.int64)
+        lo, hi = e.raw_min, e.raw_max
+        edges = {lo, lo + 1, -1, 0, 1, hi - 1, hi}
+        if one is not None:
+            edges |= {-one - 1, -one, one - 1, one, one + 1} | ({-one // 2, one // 2} if one > 1 else set())
+        edges = {v for v in edges if lo <= v <= hi}
+        hit = np.isin(a, sorted(edges))
+        assert hit.mean() > 0.45 and set(np.unique(a[hit]).tolist()) == edges, str(e)
+        d0 = oracle.fill(e, 4000, 9, 0)
+        assert np.array_equal(a[~hit], d0[~hit].astype(np.int64)) and (a == d0).mean() > 0.45
