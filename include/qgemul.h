@@ -160,6 +160,10 @@ enum {
     QG_OPT_UNFUSED_EPILOGUE = 32u, /* never fuse: always the pass after the kernel */
     /* result-identical kernel choices, for equivalence tests and same-process A/B timing */
     QG_OPT_GENERIC_LAYOUT = 64u,   /* pack / unpack with the any-format kernels even where a fast path exists */
+    /* operands of 17 / 18 value+sign bits: keep the balanced base-256 limbs and the 9-product two-group kernel (k_mfma_ppl) where the
+     * default stores three unsigned base-64 digits and takes 6 products (k_mfma_k6).  Decided at plan time: the packed layouts
+     * differ.  QG_OPT_LOCKSTEP_TILES implies it (the lock-step kernel reads balanced limbs). */
+    QG_OPT_SCHOOLBOOK_LIMBS = 2048u,
     /* qgemul_pack_f64 on an element whose QuMode is RND::CONV: the reference's Qu_s(double) takes a 2400-bit path whose CONV
      * branch returns a multi-word artefact (the format maximum for every negative input; tests/test_from_double.py), so by
      * default such a pack is REJECTED (QG_EUNSUPPORTED).  With this flag the engine converts with the arithmetic definition

@@ -333,6 +333,21 @@ static int plan_geometry(const qgemul_desc* d, uint32_t flags, QAnalysis* an, qg
     pc->ldc = d->M;
     pc->elem_bytes = hc->size;
     for (int p = 0; p < 2; ++p) { pc->off[p] = hc->off[p]; pc->sb[p] = hc->sb[p]; }
+    // Three-digit Karatsuba (qg_mfma_k6.hip): both operands of 17 / 18 value+sign bits (3 limbs each; operands of 2 limbs take 4 or
+    // 6 schoolbook products already), real, not centred, no element-wise chain, a shape the two-group 3 x 3 kernel takes, C in a 4-
+    // or 8-byte container, and ONE product per int32 accumulator exact: K * 126^2 < 2^31.  The planes then hold the unsigned base-64
+    // digits of x + bias on 96-row tiles of A; QG_OPT_SCHOOLBOOK_LIMBS / QG_OPT_LOCKSTEP_TILES keep the balanced limbs.
+    bool k6 = false, ppl33 = false;
+    {
+        static const bool no_kara3 = QG_DIAG_ENV("QG_NO_KARA3");   // A/B switch
+        auto ubits = [](qfmt f) { return (int)f.I + (int)f.F + (f.S ? 1 : 0); };
+        const int cb = pow2_bytes(sbits(d->c));
+        // (what k_mfma_ppl's 3 x 3 body takes: qg_mfma_ppl_applies)
+        ppl33 = kernel == QG_KERNEL_MFMA_I8_LIMB && !comp.on && !d->is_complex && !ep && LA == 3 && LB == 3 && cfg.variant == 10 && (cb == 4 || cb == 8);
+        k6 = ppl33 && !no_kara3 && !(flags & QG_OPT_SCHOOLBOOK_LIMBS) && !centred && !an->band && ubits(d->a[0]) >= 13 && ubits(d->a[0]) <= 18 &&
+             ubits(d->b[0]) >= 13 && ubits(d->b[0]) <= 18 && d->K * (int64_t)(126 * 126) < (1ll << 31);
+        if (k6) cfg = QMfmaCfg{QG_K6_VARIANT, QG_K6_TM, QG_K6_TN, QG_K6_BK};
+    }
     if (kernel != QG_KERNEL_NONE) {
         *pa = QPackedGeom{round_up(d->M, cfg.TM), round_up(d->K, cfg.BK), 1, LA, cfg.TM, cfg.BK};
         *pb = QPackedGeom{round_up(d->N, cfg.TN), round_up(d->K, cfg.BK), 1, LB, cfg.TN, cfg.BK};
@@ -345,6 +360,10 @@ static int plan_geometry(const qgemul_desc* d, uint32_t flags, QAnalysis* an, qg
         pc->Np = pb->rows_p;
         pc->tm = cfg.TM;
         pc->tn = cfg.TN;
+        if (k6) {   // packed C keeps the 128 x 128 tiles of the other limb plans: callers that size or move packed C see no change
+            pc->Mp = round_up(d->M, 128);
+            pc->tm = 128;
+        }
         if (d->is_complex) {
             // the MFMA kernel writes the raw 2Mh x 2Nh dot products into the plan's workspace; the combine
             // pass writes the packed complex C row-major [2][M][N]
@@ -432,6 +451,19 @@ static int plan_geometry(const qgemul_desc* d, uint32_t flags, QAnalysis* an, qg
             info->packed_bytes[0] += pa->rows_p * 8;
             info->packed_bytes[1] += pb->rows_p * 8;
         }
+    }
+    if (k6) {
+        for (QPackedGeom* g : {pa, pb}) {
+            const qfmt f = g == pa ? d->a[0] : d->b[0];
+            g->digit6 = 1;
+            g->bias = f.S ? ((int64_t)1 << ((int)f.I + (int)f.F)) : 0;
+            g->rowsum_off = g->trailer + QG_TRAILER_BYTES;
+        }
+        info->packed_bytes[0] += pa->rows_p * 8;
+        info->packed_bytes[1] += pb->rows_p * 8;
+        snprintf(info->reason, sizeof info->reason, "linear class: three base-64 digits per operand, six products (two-group kernel, 96x128 tiles)");
+    } else if (ppl33) {
+        snprintf(info->reason, sizeof info->reason, "linear class: balanced base-256 limbs, nine products (two-group kernel, 128x128 tiles)");
     }
     info->packed_bytes[2] = (int64_t)parts * pc->Mp * pc->Np * pc->cbytes;
     *pLA = LA;
@@ -921,7 +953,7 @@ static bool stores_host_c(const qgemul_plan* p)
 {
     if (p->has_ep || p->desc.is_complex || wide_epilogue(p) || p->comp.on) return false;
     if (p->info.kernel != QG_KERNEL_MFMA_I8 && p->info.kernel != QG_KERNEL_MFMA_I8_LIMB) return false;
-    if (p->variant != 9 && p->variant != 10) return false;
+    if (p->variant != 9 && p->variant != 10 && p->variant != QG_K6_VARIANT) return false;
     if (p->variant == 10 && (p->pa.rows_p / p->cfg.TM) * (p->pb.rows_p / p->cfg.TN) < 256) return false;   // (falls back to the lock-step kernel)
     return (p->pc.cbytes == 4 || p->pc.cbytes == 8) && p->pc.cbytes == p->hc.size;
 }
@@ -1145,6 +1177,7 @@ static int execute_kernel(qgemul_plan* p, void* packedC, const void* packedA, co
             a.biasA = p->pa.bias;
             a.biasB = p->pb.bias;
             a.corr = p->desc.K * p->pa.bias * p->pb.bias;
+            a.Mc = pcg.Mp;
         }
         if (wide_epilogue(p)) {
             a.C = p->wide_ws;

@@ -173,6 +173,7 @@ struct QMfmaArgs {
     const int64_t* rsB;
     int64_t biasA, biasB, corr;
     int32_t kara, pad3_;
+    int64_t Mc;             // k_mfma_k6: padded rows of packed C (128-row tiles), which differ from Mp (A on 96-row tiles)
     const uint32_t* maskA;  // plane masks of the packed operands (QPackedGeom::trailer); nullptr: all planes
     const uint32_t* maskB;
     int32_t has_ep, pad_;   // fused element-wise epilogue: C below is then packed D (ep.dbytes containers)
@@ -191,6 +192,12 @@ hipError_t qg_launch_mfma_pp(const QMfmaArgs& a, hipStream_t st);
 // 3 x 3 and 2 x 2 limbs, 128x128 tiles, the two-group scheme with one A limb plane per phase (qg_mfma_ppl.hip; variant 10)
 bool qg_mfma_ppl_applies(int LA, int LB, const QMfmaArgs& a);
 hipError_t qg_launch_mfma_ppl(int limbs, const QMfmaArgs& a, hipStream_t st);   // limbs: 3 (3 x 3, plane masks) or 2 (2 x 2 on two-plane storage)
+// three unsigned base-64 digits per operand, six products, 96x128 tiles, the two-group scheme (qg_mfma_k6.hip; variant 11).  Its
+// packed operands (QPackedGeom::digit6 with 3 planes, 96-row tiles of A) belong to this kernel alone; packed C is the 128 x 128-tiled
+// layout of the other limb plans
+enum { QG_K6_VARIANT = 11, QG_K6_TM = 96, QG_K6_TN = 128, QG_K6_BK = 64 };
+bool qg_mfma_k6_applies(const QMfmaArgs& a);
+hipError_t qg_launch_mfma_k6(const QMfmaArgs& a, hipStream_t st);
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is set once per DEVICE (one process may drive several: qgemul_run_sharded);
 // `done` holds one bit per device ordinal of the calling thread's current device

@@ -884,6 +884,7 @@ static constexpr int ablation() { return 0; }
 
 hipError_t qg_launch_mfma(int LA, int LB, const QMfmaArgs& a_in, hipStream_t st)
 {
+    if (a_in.variant == QG_K6_VARIANT) return qg_launch_mfma_k6(a_in, st);
     if (a_in.variant == 10 && qg_mfma_ppl_applies(LA, LB, a_in)) return qg_launch_mfma_ppl(LA, a_in, st);
     QMfmaArgs a_v3;
     if (a_in.variant == 10) { a_v3 = a_in; a_v3.variant = 3; }   // (fused chain, narrow C: the lock-step kernel on the same packed layout)

@@ -120,7 +120,7 @@ __global__ __launch_bounds__(256) void k_pack_limb32(QOperandGeom g, QPackedGeom
     // per wave and block — 16 384 for a 4096^2 operand, all on the trailer's memory channel — cost 0.06-0.17 ms on top of a
     // 0.03 ms pack)
     const int kt = (int)(p.K_p / 64);
-    const int64_t nblk = (int64_t)kt * (p.rows_p / 64);
+    const int64_t nblk = (int64_t)kt * ((p.rows_p + 63) / 64);   // (96-row tiles: the last block may reach beyond rows_p; such rows are not stored)
     const int t = threadIdx.x;
     const int row_l = R_FAST ? (t & 63) : (t >> 2), kc = R_FAST ? (t >> 6) : (t & 3);
     const int W = g.W[0];
@@ -166,12 +166,14 @@ __global__ __launch_bounds__(256) void k_pack_limb32(QOperandGeom g, QPackedGeom
             bad |= (v[j] < lo) | (v[j] > hi);
         }
     }
-    if (p.offs) {   // centred operand (QPackedGeom::offs): x - centre, padding stays 0; row sums of the stored values through LDS
+    if (p.offs || p.digit6) {   // centred operand (QPackedGeom::offs): x - centre, padding stays 0; row sums of the stored values through LDS
+        // (three-digit layout, QPackedGeom::digit6: x + bias, non-negative and below 2^18; the same row sums)
         const int32_t bias = (int32_t)p.bias;   // (|bias| < 2^24 and W <= 24 on this path: qg_launch_pack)
         long long part = 0;
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             if (row_in && k0 + j < g.K) v[j] += bias;
+            if (p.digit6) v[j] &= (1 << 18) - 1;   // (what k_pack stores for a value outside its format)
             part += v[j];
         }
         if (p.offs != 3) {
@@ -193,6 +195,19 @@ __global__ __launch_bounds__(256) void k_pack_limb32(QOperandGeom g, QPackedGeom
     for (int l = 0; l < p.limb0; ++l)   // a limb group: the lower digits live elsewhere
 #pragma unroll
         for (int j = 0; j < 16; ++j) v[j] = (int32_t)(((int64_t)v[j] - (int32_t)(int8_t)(v[j] & 0xff)) >> 8);
+    if (r >= p.rows_p) continue;
+    if (p.digit6) {   // unsigned base-64 digits; no plane mask (a biased zero has non-zero digits)
+        for (int l = 0; l < p.limbs; ++l) {
+            uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                w[j >> 2] |= (uint32_t)(v[j] & 63) << (8 * (j & 3));
+                v[j] >>= 6;
+            }
+            *(uint4*)(out + (int64_t)l * p.tr * p.bk) = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+        continue;
+    }
     for (int l = 0; l < p.limbs; ++l) {
         uint32_t w[4] = {0, 0, 0, 0};
         uint32_t any = 0;
@@ -571,9 +586,9 @@ hipError_t qg_launch_pack(const QOperandGeom& g, const QPackedGeom& p, const voi
     if (hipError_t e = zero_trailer(p, dst, st); e != hipSuccess) return e;
     const bool no_fast = generic != 0;   // QG_OPT_GENERIC_LAYOUT: the any-format kernel (byte-identical; the equivalence test)
     const bool centred_fast = !p.offs || (g.W[0] <= 24 && p.bias > -(1ll << 24) && p.bias < (1ll << 24));   // (x - centre within int32)
-    if (!no_fast && g.parts == 1 && g.elem_bytes == 4 && g.sb[0] == 4 && g.off[0] == 0 && p.limbs >= 1 && p.limbs <= 3 && !p.digit6 && centred_fast && (p.bk == 64 || p.bk == 128) &&
-        p.tr % 64 == 0 && p.rows_p % p.tr == 0 && p.K_p % p.bk == 0 && g.W[0] <= 30 && ((uintptr_t)src & 3) == 0 && ((uintptr_t)dst & 15) == 0) {
-        const int64_t nblk = (p.K_p / 64) * (p.rows_p / 64);
+    if (!no_fast && g.parts == 1 && g.elem_bytes == 4 && g.sb[0] == 4 && g.off[0] == 0 && p.limbs >= 1 && p.limbs <= 3 && (!p.digit6 || p.limbs == 3) && centred_fast && (p.bk == 64 || p.bk == 128) &&
+        (p.tr % 64 == 0 || (p.digit6 && p.tr % 16 == 0)) && p.rows_p % p.tr == 0 && p.K_p % p.bk == 0 && g.W[0] <= 30 && ((uintptr_t)src & 3) == 0 && ((uintptr_t)dst & 15) == 0) {
+        const int64_t nblk = (p.K_p / 64) * ((p.rows_p + 63) / 64);
         const unsigned nb = (unsigned)(nblk < 2048 ? nblk : 2048);   // grid-stride beyond 8 workgroups per CU
         if (g.rs == 1 && g.ks != 1) hipLaunchKernelGGL(k_pack_limb32<true>, dim3(nb), dim3(256), 0, st, g, p, (const int32_t*)src, (int8_t*)dst, check_range, range_flag);
         else if (g.ks == 1 && g.rs % 4 == 0 && g.k0 % 4 == 0 && ((uintptr_t)src & 15) == 0)
@@ -593,9 +608,10 @@ hipError_t qg_launch_pack_f64(const QOperandGeom& g, const QPackedGeom& p, const
     if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
     if (hipError_t e = zero_trailer(p, dst, st); e != hipSuccess) return e;
     const bool centred_fast = !p.offs || (g.W[0] <= 24 && p.bias > -(1ll << 24) && p.bias < (1ll << 24));
-    if (!generic && g.parts == 1 && p.limbs >= 1 && p.limbs <= 3 && !p.digit6 && centred_fast && (p.bk == 64 || p.bk == 128) && p.tr % 64 == 0 && p.rows_p % p.tr == 0 &&
+    if (!generic && g.parts == 1 && p.limbs >= 1 && p.limbs <= 3 && (!p.digit6 || p.limbs == 3) && centred_fast && (p.bk == 64 || p.bk == 128) &&
+        (p.tr % 64 == 0 || (p.digit6 && p.tr % 16 == 0)) && p.rows_p % p.tr == 0 &&
         p.K_p % p.bk == 0 && g.W[0] <= 30 && ((uintptr_t)src & 7) == 0 && ((uintptr_t)dst & 15) == 0) {
-        const int64_t nblk = (p.K_p / 64) * (p.rows_p / 64);
+        const int64_t nblk = (p.K_p / 64) * ((p.rows_p + 63) / 64);
         const unsigned nb = (unsigned)(nblk < 2048 ? nblk : 2048);
         if (g.rs == 1 && g.ks != 1) hipLaunchKernelGGL((k_pack_limb32<true, false, true>), dim3(nb), dim3(256), 0, st, g, p, (const int32_t*)src, (int8_t*)dst, 0, (int*)nullptr);
         else if (g.ks == 1 && g.rs % 2 == 0 && g.k0 % 2 == 0 && ((uintptr_t)src & 15) == 0)
