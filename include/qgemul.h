@@ -193,7 +193,11 @@ enum {
 /* exactness class of a descriptor */
 enum {
     QG_CLASS_LINEAR = 1, /* every intermediate conversion is provably the identity: exact integer
-                            dot product + ONE round/overflow into C (MFMA / wide-int path) */
+                            dot product + ONE round/overflow into C (MFMA / wide-int path) — or a RING plan:
+                            product and every tree level wrap (WRP::TCPL) into one signed format of n <= 32
+                            bits entered by an exact left shift, so the tree is the dot product modulo 2^n,
+                            then C's conversion ("wrapping ring mod 2^n" in qgemul_info.reason; a plain C
+                            int8 / int16 / int32 GEMM is one).  QG_OPT_FORCE_TREE selects the tree plan */
     QG_CLASS_TREE = 2    /* products and tree nodes must be quantised one by one, in tree order */
 };
 

@@ -12,6 +12,7 @@
 
 #include "../../include/qgemul.h"
 #include "qg_kernels.h"
+#include "qg_ring.h"
 #include "qg_plan.h"
 
 static thread_local int g_last_hip = 0;
@@ -266,7 +267,21 @@ static int plan_geometry(const qgemul_desc* d, uint32_t flags, QAnalysis* an, qg
     int64_t centreA = 0, centreB = 0;
     bool centred = false;
     QMfmaCfg cfg = {0, 0, 0, 0};
-    if (an->linear_ok && !(flags & QG_OPT_FORCE_TREE)) {
+    // RING plans (qg_plan.cpp: ring_plan; qg_mfma_ring.hip): product and every level wrap into one signed format of n <= 32 bits, so
+    // the tree is the dot product modulo 2^n.  The operands keep their first min(L, limbs) balanced digits, L = ceil(n / 8) — no
+    // centring, no base-64 digits, no plane-mask shortcut —, and ONE launch takes any K: the accumulators may wrap.  Descriptors
+    // that are exact anyway keep their exact linear plan, one output column the one-column kernels walk stays with them, and
+    // QG_OPT_FORCE_TREE selects today's tree plan (the invariance arm of the tests).
+    const bool ring = an->ring_ok && !(flags & QG_OPT_FORCE_TREE);
+    if (ring) {
+        const int L = qg_ring_digits(an->ring_n);
+        LA = qg_limbs_for(d->a[0]) < L ? qg_limbs_for(d->a[0]) : L;
+        LB = qg_limbs_for(d->b[0]) < L ? qg_limbs_for(d->b[0]) : L;
+        cfg = QMfmaCfg{QG_RING_VARIANT, QG_RING_TM, QG_RING_TN, QG_RING_BK};
+        kernel = L == 1 ? QG_KERNEL_MFMA_I8 : QG_KERNEL_MFMA_I8_LIMB;
+        const int np = qg_ring_products(LA, LB, L);
+        snprintf(info->reason, sizeof info->reason, "linear class: wrapping ring mod 2^%d, %d limb product%s", an->ring_n, np, np == 1 ? "" : "s");
+    } else if (an->linear_ok && !(flags & QG_OPT_FORCE_TREE)) {
         LA = qg_limbs_for(d->a[0]);
         LB = qg_limbs_for(d->b[0]);
         if (d->is_complex) {  // parts are stacked along the row axis and share one limb count
@@ -554,7 +569,7 @@ static int plan_geometry(const qgemul_desc* d, uint32_t flags, QAnalysis* an, qg
 // 64-bit linear pass instead, which keeps the hot kernels' epilogue as it is.
 static bool wide_epilogue(const qgemul_plan* p)
 {
-    if (p->comp.on) return false;   // (the combine pass converts in 64-bit arithmetic anyway)
+    if (p->comp.on || p->variant == QG_RING_VARIANT) return false;   // (the combine pass / the ring kernel's epilogue convert in 64-bit arithmetic anyway)
     const QStep& q = p->an.lin.to_c[0];
     // ... and a C format beyond 31 value bits does not fit the 32-bit epilogue's clamp bounds at all (second find of the
     // extended fuzz runs: int<7,-2> x int<7,-1> into Qu<24,9>)
@@ -579,7 +594,7 @@ extern "C" void qgemul_diag_set_stamps(void* dev) { g_diag_stamps = (uint32_t*)d
 
 static bool fuses_epilogue(const qgemul_plan* p)
 {
-    if (wide_epilogue(p) || p->comp.on) return false;
+    if (wide_epilogue(p) || p->comp.on || p->variant == QG_RING_VARIANT) return false;
     if (p->flags & QG_OPT_UNFUSED_EPILOGUE) return false;
     if (!p->ept.bits32) return false;
     if (p->info.kernel == QG_KERNEL_MFMA_I8_LIMB && p->LA == 3 && p->LB == 3) return true;
@@ -1153,6 +1168,22 @@ static int execute_kernel(qgemul_plan* p, void* packedC, const void* packedA, co
     switch (p->info.kernel) {
     case QG_KERNEL_MFMA_I8:
     case QG_KERNEL_MFMA_I8_LIMB: {
+        if (p->variant == QG_RING_VARIANT) {
+            QRingArgs r;
+            memset(&r, 0, sizeof r);
+            r.A = (const int8_t*)packedA;
+            r.B = (const int8_t*)packedB;
+            r.C = packedC;
+            r.Mp = p->pa.rows_p;
+            r.Np = p->pb.rows_p;
+            r.Kp = p->pa.K_p;
+            r.cbytes = pcg.cbytes;
+            r.n = p->an.ring_n;
+            r.s = p->an.ring_s;
+            r.to_c = p->an.tree.c_cvt[0];
+            QG_HIP(qg_launch_mfma_ring(p->LA, p->LB, qg_ring_digits(p->an.ring_n), r, st));
+            return QG_OK;
+        }
         QMfmaArgs a;
         memset(&a, 0, sizeof a);
         a.A = (const int8_t*)packedA;

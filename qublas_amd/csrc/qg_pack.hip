@@ -586,8 +586,8 @@ hipError_t qg_launch_pack(const QOperandGeom& g, const QPackedGeom& p, const voi
     if (hipError_t e = zero_trailer(p, dst, st); e != hipSuccess) return e;
     const bool no_fast = generic != 0;   // QG_OPT_GENERIC_LAYOUT: the any-format kernel (byte-identical; the equivalence test)
     const bool centred_fast = !p.offs || (g.W[0] <= 24 && p.bias > -(1ll << 24) && p.bias < (1ll << 24));   // (x - centre within int32)
-    if (!no_fast && g.parts == 1 && g.elem_bytes == 4 && g.sb[0] == 4 && g.off[0] == 0 && p.limbs >= 1 && p.limbs <= 3 && (!p.digit6 || p.limbs == 3) && centred_fast && (p.bk == 64 || p.bk == 128) &&
-        (p.tr % 64 == 0 || (p.digit6 && p.tr % 16 == 0)) && p.rows_p % p.tr == 0 && p.K_p % p.bk == 0 && g.W[0] <= 30 && ((uintptr_t)src & 3) == 0 && ((uintptr_t)dst & 15) == 0) {
+    if (!no_fast && g.parts == 1 && g.elem_bytes == 4 && g.sb[0] == 4 && g.off[0] == 0 && p.limbs >= 1 && p.limbs <= 4 && (!p.digit6 || p.limbs == 3) && centred_fast && (p.bk == 64 || p.bk == 128) &&
+        (p.tr % 64 == 0 || (p.digit6 && p.tr % 16 == 0)) && p.rows_p % p.tr == 0 && p.K_p % p.bk == 0 && g.W[0] <= 31 && ((uintptr_t)src & 3) == 0 && ((uintptr_t)dst & 15) == 0) {
         const int64_t nblk = (p.K_p / 64) * ((p.rows_p + 63) / 64);
         const unsigned nb = (unsigned)(nblk < 2048 ? nblk : 2048);   // grid-stride beyond 8 workgroups per CU
         if (g.rs == 1 && g.ks != 1) hipLaunchKernelGGL(k_pack_limb32<true>, dim3(nb), dim3(256), 0, st, g, p, (const int32_t*)src, (int8_t*)dst, check_range, range_flag);
@@ -608,9 +608,9 @@ hipError_t qg_launch_pack_f64(const QOperandGeom& g, const QPackedGeom& p, const
     if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
     if (hipError_t e = zero_trailer(p, dst, st); e != hipSuccess) return e;
     const bool centred_fast = !p.offs || (g.W[0] <= 24 && p.bias > -(1ll << 24) && p.bias < (1ll << 24));
-    if (!generic && g.parts == 1 && p.limbs >= 1 && p.limbs <= 3 && (!p.digit6 || p.limbs == 3) && centred_fast && (p.bk == 64 || p.bk == 128) &&
+    if (!generic && g.parts == 1 && p.limbs >= 1 && p.limbs <= 4 && (!p.digit6 || p.limbs == 3) && centred_fast && (p.bk == 64 || p.bk == 128) &&
         (p.tr % 64 == 0 || (p.digit6 && p.tr % 16 == 0)) && p.rows_p % p.tr == 0 &&
-        p.K_p % p.bk == 0 && g.W[0] <= 30 && ((uintptr_t)src & 7) == 0 && ((uintptr_t)dst & 15) == 0) {
+        p.K_p % p.bk == 0 && g.W[0] <= 31 && ((uintptr_t)src & 7) == 0 && ((uintptr_t)dst & 15) == 0) {
         const int64_t nblk = (p.K_p / 64) * ((p.rows_p + 63) / 64);
         const unsigned nb = (unsigned)(nblk < 2048 ? nblk : 2048);
         if (g.rs == 1 && g.ks != 1) hipLaunchKernelGGL((k_pack_limb32<true, false, true>), dim3(nb), dim3(256), 0, st, g, p, (const int32_t*)src, (int8_t*)dst, 0, (int*)nullptr);

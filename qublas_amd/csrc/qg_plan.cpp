@@ -271,6 +271,44 @@ Val do_cvt(Ctx& c, Val a, qfmt to, QStep* st)
     return v;
 }
 
+
+// RING plans of the linear class (qg_mfma_ring.hip).  A real descriptor whose product format R = mul[0] is signed WRP::TCPL
+// with n = W_R + 1 <= 32 bits, whose product shift d = F_a + F_b - F_R is <= 0 (an exact left shift s = -d < n: nothing is ever
+// rounded), and whose every level_add / level format has R's (I, F, S) and WRP::TCPL (the QuMode may differ: there is nothing
+// to round), with operands of at most 32 storage bits, evaluates to
+//     C[i,j] = cvt_C( wrap_R( 2^s * sum_k a_ik b_kj ) ),      wrap_R(x) = the representative of x mod 2^n in [-2^(n-1), 2^(n-1)).
+// Proof.  wrap_R is the canonical map Z -> Z / 2^n Z followed by the choice of a representative, and
+//   * Qmul<R>(a, b) = wrap_R(a b 2^s): the product is exact (QuBLAS.h:1186-1207), the shift is exact, the overflow step wraps;
+//   * Qadd<R>(x, y) = wrap_R(x + y): equal fraction bits, no alignment, no rounding; the store into the level buffer of the same
+//     (I, F, S) and WRP::TCPL re-wraps a value that is already canonical: the identity;
+//   * the odd-leftover copy converts a value of R into the same range: the identity;
+// so by induction over the tree every node is the canonical representative of 2^s * (sum of the leaves below it) mod 2^n: the
+// class of a sum is the sum of the classes.  The root is wrap_R(2^s * sum_k a_ik b_kj) whatever the tree's shape; zero leaves
+// (padding) add the class of 0.  The operands' own modes never act inside Qgemul (they are stored values), and C's converting
+// assignment sees a value of at most 32 bits.  Kept out: an unsigned R (its 32-bit case is the reference's allOnes() artefact,
+// through() above), complex descriptors, levels of another width, any saturating level, any d > 0 — those round or clamp
+// between the additions and are no homomorphisms.  C: any format the 64-bit step converts a 32-bit value into (at most 62 value
+// bits, shifts that stay inside int64, no value that can leave its format: `c_leaves`).
+void ring_plan(const qgemul_desc* d, bool c_leaves, QAnalysis* out)
+{
+    out->ring_ok = out->ring_n = out->ring_s = 0;
+    if (d->is_complex || c_leaves) return;
+    const qfmt R = d->mul[0];
+    const int n = (int)R.I + (int)R.F + 1;
+    if (R.O != QG_WRP_TCPL || !R.S || n < 1 || n > 32) return;
+    const int s = (int)R.F - ((int)d->a[0].F + (int)d->b[0].F);
+    if (s < 0 || s >= n) return;
+    for (uint32_t l = 0; l < d->n_levels; ++l)
+        for (const qfmt f : {d->level_add[0][l], d->level[0][l]})
+            if (f.I != R.I || f.F != R.F || f.S != R.S || f.O != QG_WRP_TCPL) return;
+    if (sbits(d->a[0]) > 32 || sbits(d->b[0]) > 32) return;
+    const QStep& q = out->tree.c_cvt[0];
+    if (!q.identity && (q.W > 62 || q.d < -30 || q.d > 61 || q.O > QG_WRP_TCPL || q.refcmp)) return;
+    out->ring_ok = 1;
+    out->ring_n = n;
+    out->ring_s = s;
+}
+
 } // namespace
 
 int qg_analyze_ep(qfmt cfmt, const qgemul_epilogue* ep, QEpTable* out, int* max_bits, char* reason, size_t reason_len)
@@ -1179,6 +1217,11 @@ void qg_analyze(const qgemul_desc* d, QAnalysis* out)
     if (!out->linear_ok)
         snprintf(out->reason, sizeof out->reason, "%s",
                  "a product or tree node may round or overflow: exact tree evaluation");
+    // ring plans: decided on the formats alone (a "wide" unrounded product, 2^62 for int32 operands, is no obstacle: it is never
+    // formed).  A descriptor that is exact anyway keeps its exact linear plan, one output column the one-column kernels walk
+    // stays with them (they stream A once at HBM rate).
+    if (!out->linear_ok && !(d->N == 1 && (out->gemv_ok || out->gemv_wide_ok))) ring_plan(d, c.raw_c || c.band, out);
+    if (out->ring_ok) out->cls = QG_CLASS_LINEAR;
 }
 
 QTreeChoice qg_tree_choice(const QAnalysis* an, const qgemul_desc* d, uint32_t flags, bool ab)

@@ -92,6 +92,8 @@ struct QAnalysis {
     int wide;                // an intermediate, a level / product format or C needs more than 62 bits: 128-bit kernels (qg_ops.h: qg_step_w)
     int generic_only;        // C's WRP::TCPL_SAT can let the root through unclamped: the general kernels / the composite plan's combine pass only
     int band;                // C may hold a value outside its format (host-word containers): WRP::TCPL_SAT, or a multi-word value in [2^63, 2^64) / [-2^64, -2^63) can reach a one-word target (QStep::refcmp)
+    int ring_ok;             // a ring plan applies (qg_plan.cpp: ring_plan): product and every level wrap into ONE signed format of ring_n <= 32 bits,
+    int ring_n, ring_s;      // ... the product enters it by the exact left shift ring_s; the root -> C step is tree.c_cvt[0]
     char reason[96];
     QTreeTable tree;
     QLinearEpilogue lin;

@@ -20,8 +20,8 @@ KERNELS_JSON = os.path.join(ROOT, "profiles", "kernels.json")
 
 COMMON = ["qg_ops.h", "qg_kernels.h"]
 FAMILY_SOURCES = {
-    "mfma_i8": ["qg_mfma.hip", "qg_mfma_pp.hip", "qg_step_all.h"],
-    "mfma_i8_limb": ["qg_mfma.hip", "qg_mfma_ppl.hip", "qg_mfma_k6.hip", "qg_step_all.h"],
+    "mfma_i8": ["qg_mfma.hip", "qg_mfma_pp.hip", "qg_mfma_ring.hip", "qg_ring.h", "qg_step_all.h"],
+    "mfma_i8_limb": ["qg_mfma.hip", "qg_mfma_ppl.hip", "qg_mfma_k6.hip", "qg_mfma_ring.hip", "qg_ring.h", "qg_step_all.h"],
     "mfma_cplx": ["qg_mfma.hip", "qg_mfma_ppl.hip", "qg_step_all.h", "qg_pack.hip"],
     "tree_i32": ["qg_tree_fast.hip", "qg_fix.h", "qg_forms.h"],
     "tree_i64": ["qg_tree64.hip", "qg_tree.hip"],
