@@ -64,6 +64,21 @@ __device__ __forceinline__ void tile_of(int w, int tiles_m, int tiles_n, int& ti
     tile_n = rem / gsz;
 }
 
+// base + S00 + 2^6 c1 + 2^12 c2 + 2^18 c3 + 2^24 S22 (mod 2^64) from five unsigned 32-bit pieces: one 64-bit add and four
+// v_mad_u64_u32.  The weights pass through an empty asm so that they stay run-time scalars: written as constants hipcc turns each
+// product into v_lshlrev_b64 + v_lshl_add_u64 with a v_mov of the zero high half — 216 vector instructions more per tile, 3 us
+// more fixed cost per 4096^2 launch.
+__device__ __forceinline__ uint64_t k6_recombine(uint32_t s00, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t s22, uint64_t base)
+{
+    uint32_t m6 = 1u << 6, m12 = 1u << 12, m18 = 1u << 18, m24 = 1u << 24;
+    asm("" : "+s"(m6), "+s"(m12), "+s"(m18), "+s"(m24));
+    uint64_t x = base + s00;
+    x = (uint64_t)c1 * m6 + x;
+    x = (uint64_t)c2 * m12 + x;
+    x = (uint64_t)c3 * m18 + x;
+    return (uint64_t)s22 * m24 + x;
+}
+
 // FAST: truncation (TRN::TCPL, right shift d >= 0) + SAT::TCPL as a 64-bit shift and a clamp; otherwise the general routine.
 // CB: container bytes of C (4 or 8).
 template <bool FAST, int CB>
@@ -216,7 +231,7 @@ __global__ __launch_bounds__(512) void k_mfma_k6(QMfmaArgs g)
         if (wm == 0) __builtin_amdgcn_s_barrier();   // pairs with group 1's last barrier: both groups are level again
         __builtin_amdgcn_sched_barrier(0);
 
-        // epilogue: recombine the six sums in 64 bits, take the biases out with the row sums, one round + overflow, stores of 4
+        // epilogue: recombine the six sums into 64 bits, take the biases out with the row sums, one round + overflow, stores of 4
         // consecutive rows.  C/D of the 16x16 MFMA: col = lane & 15, rows 4 (lane >> 4) + e; packed C is column-major inside the tile
         int tile_m, tile_n;
         tile_of(w_first + ti * w_step, tiles_m, tiles_n, tile_m, tile_n);
@@ -226,19 +241,30 @@ __global__ __launch_bounds__(512) void k_mfma_k6(QMfmaArgs g)
         // one of its tiles; rows beyond its padded extent g.Mc (the tail of A's last 96-row tile) are not stored
         constexpr int CT = 128;
         [[maybe_unused]] const int sh = st.d;
+        // The recombination in 32-bit pieces.  Every accumulator is a sum of K products of two bytes <= 126, and the planner admits
+        // the form only for K * 126^2 < 2^31: all six are non-negative int32.  The Karatsuba differences are sums of digit products
+        // themselves — c1 = sum d0 e1 + d1 e0 <= 2 K 63^2, c2 = sum d0 e2 + d1 e1 + d2 e0 <= 3 K 63^2, c3 = sum d1 e2 + d2 e1
+        // <= 2 K 63^2, and 3 K 63^2 = 3/4 K 126^2 < 2^31 — so wrapping 32-bit subtraction gives them exactly and they zero-extend.
+        // What depends on the column alone (corr - biasA rsB[col]) is formed once per column of the lane, what depends on the row
+        // alone (biasB rsA[row]) once per row; the 64-bit sums are modulo 2^64, as they were.
+        uint64_t colt[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            colt[j] = (uint64_t)g.corr - (uint64_t)g.biasA * (uint64_t)g.rsB[(int64_t)tile_n * TN + wn * 32 + j * 16 + fr];
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             int64_t s[8];
+            uint64_t rowt[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) rowt[e] = (uint64_t)g.biasB * (uint64_t)g.rsA[(int64_t)tile_m * TM + wm * 48 + i * 16 + 4 * fq + e];
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const int64_t s00 = acc[S00][i][j][e], s11 = acc[S11][i][j][e], s22 = acc[S22][i][j][e];
-                    const int64_t c1 = (int64_t)acc[P01][i][j][e] - s00 - s11, c2 = (int64_t)acc[P02][i][j][e] - s00 - s22 + s11,
-                                  c3 = (int64_t)acc[P12][i][j][e] - s11 - s22;
-                    const int64_t x = s00 + (c1 << 6) + (c2 << 12) + (c3 << 18) + (s22 << 24);
-                    s[j * 4 + e] = (int64_t)((uint64_t)x + (uint64_t)g.corr - (uint64_t)g.biasA * (uint64_t)g.rsB[(int64_t)tile_n * TN + wn * 32 + j * 16 + fr] -
-                                             (uint64_t)g.biasB * (uint64_t)g.rsA[(int64_t)tile_m * TM + wm * 48 + i * 16 + 4 * fq + e]);
+                    const uint32_t s00 = (uint32_t)acc[S00][i][j][e], s11 = (uint32_t)acc[S11][i][j][e], s22 = (uint32_t)acc[S22][i][j][e];
+                    const uint32_t c1 = (uint32_t)acc[P01][i][j][e] - s00 - s11, c3 = (uint32_t)acc[P12][i][j][e] - s11 - s22,
+                                   c2 = (uint32_t)acc[P02][i][j][e] - s00 - s22 + s11;
+                    s[j * 4 + e] = (int64_t)k6_recombine(s00, c1, c2, c3, s22, colt[j] - rowt[e]);
                 }
             if constexpr (FAST) {
 #pragma unroll
