@@ -197,6 +197,9 @@ public:
     }
     double toDouble() const { return std::ldexp(double(data), -F); }
     Qu_s& fill(int64_t raw) { data = raw_t(raw); return *this; }  // raw store, no range check (QuBLAS.h:2447-2452)
+    // a constant from its raw value, usable as a template argument (the scalar is a structural type: one public integer) —
+    // how ANUS::Segment coefficients are written, see there
+    static constexpr Qu_s from_raw(int64_t raw) { Qu_s q; q.data = raw_t(raw); return q; }
 };
 
 template <typename... Args> struct QuInput {
@@ -516,10 +519,51 @@ void Qgemul(TC& C, const TA& A, const TB& B)
 // for ThenAdd / ThenSub / ThenRsub (realT<…> / imagT<…> tags), real operands for all four; no complex x complex ThenMul.
 template <class CT> struct QgemulResult {};
 
+// ------------------------------------------------------------------ piecewise-polynomial activation (the reference's ANUS helpers, QuBLAS.h:4829-4897)
+// ANUS::Segment<breakpoint, a0, a1, …> with Qu scalar constants as template arguments, exactly the reference's spelling; as a stage
+// after the GEMM:   Qgemul<…, QgemulResult<CT>>(D, A, B, ThenMul<…>(s), ThenAdd<…>(Bias), ThenApprox<Into, Segment<…>, Segment<…>…>());
+// The stage replaces the running value x by Qapprox<Segments…>(x) (x's own type; include/qgemul.h, QG_EW_APPROX).  Write a
+// coefficient as T::from_raw(r): a double would go through Qu_s(double), which this header refuses for QuMode<RND::CONV>.
+namespace ANUS {
+template <double BreakPoint, auto... as>
+struct Segment {
+    static_assert(sizeof...(as) >= 1 && sizeof...(as) <= QG_MAX_COEF, "1 .. QG_MAX_COEF coefficients");
+    static constexpr double breakpoint = BreakPoint;
+    static constexpr qgemul_approx_seg lower()
+    {
+        qgemul_approx_seg g{};
+        g.breakpoint = BreakPoint;
+        g.n_coef = sizeof...(as);
+        uint32_t i = 0;
+        ((g.f[i] = std::remove_cvref_t<decltype(as)>::fmt.c(), g.a[i] = int64_t(as.data), ++i), ...);
+        return g;
+    }
+};
+} // namespace ANUS
+
 namespace detail {
+template <class Into, class... Segs>
+struct ApproxStage {
+    static_assert(sizeof...(Segs) >= 1 && sizeof...(Segs) <= QG_MAX_SEG, "1 .. QG_MAX_SEG segments");
+    static constexpr bool approx = true;
+    static constexpr bool scalar = true;      // no tensor operand
+    static constexpr bool e_complex = false;
+    static constexpr Fmt into(Fmt r) { if constexpr (std::is_void_v<Into>) return r; else return Into::fmt; }
+    static constexpr qgemul_approx table()
+    {
+        qgemul_approx t{};
+        t.n_seg = sizeof...(Segs);
+        uint32_t g = 0;
+        ((t.seg[g++] = Segs::lower()), ...);
+        return t;
+    }
+    static constexpr qgemul_approx tab = table();
+};
+
 template <int OP, bool XFIRST, class Into, class Operand, typename... Tags>
 struct EwStage {
     const Operand& e;
+    static constexpr bool approx = false;
     static constexpr int op = OP;
     static constexpr bool x_first = XFIRST;
     static constexpr bool scalar = !requires { typename Operand::elem_t; };   // tensors have an element type
@@ -564,11 +608,16 @@ constexpr qgemul_epilogue lower_chain(Fmt c, Fmt d)
     Fmt x = c;
     uint32_t k = 0;
     ([&] {
-        const Fmt r = Stages::result(x);
-        ep.stage[k].op = uint8_t(Stages::op);
-        ep.stage[k].x_first = Stages::x_first;
-        ep.stage[k].e_scalar = Stages::scalar;
-        ep.stage[k].e = Stages::efmt.c();
+        Fmt r = x;
+        if constexpr (Stages::approx) {
+            ep.stage[k].op = uint8_t(QG_EW_APPROX);   // e, e_scalar, x_first stay zero; r = x's own format
+        } else {
+            r = Stages::result(x);
+            ep.stage[k].op = uint8_t(Stages::op);
+            ep.stage[k].x_first = Stages::x_first;
+            ep.stage[k].e_scalar = Stages::scalar;
+            ep.stage[k].e = Stages::efmt.c();
+        }
         ep.stage[k].r = r.c();
         x = Stages::into(r);
         ep.stage[k].t = x.c();
@@ -582,6 +631,7 @@ template <class... Stages>
 constexpr qgemul_epilogue_cplx lower_chain_cplx(Fmt cre, Fmt cim, Fmt dre, Fmt dim_)
 {
     static_assert(sizeof...(Stages) <= QG_MAX_EW, "at most QG_MAX_EW element-wise operators");
+    static_assert((!Stages::approx && ...), "Qapprox is defined on real values only (QuBLAS.h:4868: toDouble() of a complex value)");
     static_assert((!(Stages::e_complex && Stages::op == QG_EW_MUL) && ...), "complex x complex multiplication mixes the parts: not an element-wise stage");
     qgemul_epilogue_cplx ep{};
     ep.part[0].n_stages = ep.part[1].n_stages = sizeof...(Stages);
@@ -614,6 +664,16 @@ template <class Into = void, typename... Tags, class Operand> auto ThenMul(const
 template <class Into = void, typename... Tags, class Operand> auto ThenAdd(const Operand& e) { return detail::EwStage<QG_EW_ADD, true, Into, Operand, Tags...>{e}; }
 template <class Into = void, typename... Tags, class Operand> auto ThenSub(const Operand& e) { return detail::EwStage<QG_EW_SUB, true, Into, Operand, Tags...>{e}; }
 template <class Into = void, typename... Tags, class Operand> auto ThenRsub(const Operand& e) { return detail::EwStage<QG_EW_SUB, false, Into, Operand, Tags...>{e}; }
+template <class Into, class... Segments> auto ThenApprox() { return detail::ApproxStage<Into, Segments...>{}; }
+// the tables of a chain, in stage order: the stage's qgemul_approx, nullptr for a stage that is no ThenApprox
+template <class... Stages>
+constexpr std::array<const qgemul_approx*, QG_MAX_EW> Qgemul_lower_approx(const Stages&...)
+{
+    std::array<const qgemul_approx*, QG_MAX_EW> t{};
+    uint32_t k = 0;
+    ([&] { if constexpr (Stages::approx) t[k] = &Stages::tab; ++k; }(), ...);
+    return t;
+}
 
 // the chain's C-ABI form (pure host computation)
 template <typename... Tags, class TD, class... Stages>
@@ -645,7 +705,8 @@ void Qgemul(TD& D, const TA& A, const TB& B, const S0& s0, const Stages&... st)
     qgemul_desc d = Qgemul_lower_types<Tags...>(std::type_identity<Qu_s<typename TD::size, CT>>{}, std::type_identity<TA>{}, std::type_identity<TB>{});
     d.flags |= QgemulDescFlags();
     auto ptr = [](const auto& stage) -> const void* {
-        if constexpr (std::remove_cvref_t<decltype(stage)>::scalar) return &stage.e;   // one element as the tensors store them
+        if constexpr (std::remove_cvref_t<decltype(stage)>::approx) return nullptr;   // reads no operand
+        else if constexpr (std::remove_cvref_t<decltype(stage)>::scalar) return &stage.e;   // one element as the tensors store them
         else {
             static_assert(std::is_same_v<typename std::remove_cvref_t<decltype(stage.e)>::size, typename TD::size>, "a tensor operand has D's shape");
             return stage.e.data.data();
@@ -658,7 +719,12 @@ void Qgemul(TD& D, const TA& A, const TB& B, const S0& s0, const Stages&... st)
         rc = qgemul_run_epc(&d, &ep, D.data.data(), A.data.data(), B.data.data(), E, nullptr);
     } else {
         const qgemul_epilogue ep = Qgemul_lower_epilogue<Tags...>(D, s0, st...);
-        rc = qgemul_run_ep(&d, &ep, D.data.data(), A.data.data(), B.data.data(), E, nullptr);
+        if constexpr (S0::approx || (Stages::approx || ...)) {
+            const auto ax = Qgemul_lower_approx(s0, st...);
+            rc = qgemul_run_epx(&d, &ep, ax.data(), D.data.data(), A.data.data(), B.data.data(), E, nullptr);
+        } else {
+            rc = qgemul_run_ep(&d, &ep, D.data.data(), A.data.data(), B.data.data(), E, nullptr);
+        }
     }
     if (rc != QG_OK) throw std::runtime_error(std::string("Qgemul: ") + qgemul_strerror(rc));
 }

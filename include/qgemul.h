@@ -174,8 +174,12 @@ enum {
     QG_OPT_BALANCED_LIMBS = 1024u, /* linear class: never store an operand CENTRED (x - c in balanced int8 limbs, the centre taken back out
                                       with row sums in the epilogue: one limb fewer for signed formats of 16 / 24 / 32 bits and for
                                       unsigned formats) — the plain balanced limbs of every round before; result-identical (tests) */
-    QG_OPT_LOCKSTEP_TILES = 128u   /* large single-limb problems: the 64-byte-k-tile kernel whose waves run in lock step
+    QG_OPT_LOCKSTEP_TILES = 128u,  /* large single-limb problems: the 64-byte-k-tile kernel whose waves run in lock step
                                     * (k_mfma16) instead of the two-group kernel on 128-byte k-tiles (k_mfma_pp) */
+    /* the highest bit in use.  Chains with an APPROX stage (below): run UNIFORM tables through the general form of the pass too
+     * (segment by segment under a lane mask instead of one Horner loop with a per-lane coefficient); result-identical, for
+     * equivalence tests and A/B timing */
+    QG_OPT_APPROX_GENERAL = 4096u
 };
 
 /* status codes */
@@ -354,6 +358,16 @@ int qgemul_pack_e(qgemul_plan* p, int stage, const void* src_dev, int64_t ld, vo
 int qgemul_execute_ep(qgemul_plan* p, void* packedD, const void* packedA, const void* packedB, const qgemul_ep_args* args);
 int qgemul_time_execute_ep(qgemul_plan* p, void* packedD, const void* packedA, const void* packedB, const qgemul_ep_args* args,
                            int warmup, int iters, float* avg_ms);
+/* The plan's chain ALONE, as one linear pass over a C tensor that already exists: packed C -> packed D.  packedC is in the plan's
+ * own packed layout with C's container: qgemul_packed_c_bytes(p) bytes, written by qgemul_pack_c(p, C_dev, ld, packedC) from a
+ * device-resident tensor of the Qgemul result's element type in reference layout (plans with an epilogue only).  It is the pass
+ * that qgemul_execute_ep runs after the GEMM kernel when it does not fuse the chain; here also for plans that would fuse it.
+ * Real and complex chains, APPROX stages included.  QG_EINVAL for a plan without an epilogue.  qgemul_time_apply_epilogue times
+ * it as qgemul_time_execute times a GEMM. */
+int64_t qgemul_packed_c_bytes(const qgemul_plan* p);
+int qgemul_pack_c(qgemul_plan* p, const void* C_dev, int64_t ld, void* packedC);
+int qgemul_apply_epilogue(qgemul_plan* p, void* packedD, const void* packedC, const qgemul_ep_args* args);
+int qgemul_time_apply_epilogue(qgemul_plan* p, void* packedD, const void* packedC, const qgemul_ep_args* args, int warmup, int iters, float* avg_ms);
 /* one-shot: host pointers in reference layout; E[k] points to stage k's tensor (tight, column-major M x N) or to its
  * one scalar element; D (ldc from opts) is fully overwritten */
 int qgemul_run_ep(const qgemul_desc* d, const qgemul_epilogue* ep, void* D, const void* A, const void* B,
@@ -389,6 +403,70 @@ int qgemul_plan_create_epc(qgemul_ctx* c, const qgemul_desc* d, const qgemul_epi
  * qgemul_unpack_c serve plans of both kinds */
 int qgemul_run_epc(const qgemul_desc* d, const qgemul_epilogue_cplx* ep, void* D, const void* A, const void* B,
                    const void* const* E, const qgemul_opts* o);
+
+/* ---- piecewise-polynomial activation stage (the reference's ANUS::Qpoly / Segment / Qapprox, QuBLAS.h:4829-4897) ----
+ * A stage with op = QG_EW_APPROX replaces the running REAL value x (format X) by  X{ Qpoly<a_s0, a_s1, ...>(x) }  of the
+ * selected segment s:
+ *   selection   the first segment in list order with  x.toDouble() < seg[s].breakpoint  (:4868), the last one when none
+ *               matches (:4879-4884).  Breakpoints need not be sorted; +-infinity is legal, NaN is not.  With at most 53
+ *               value bits in X, toDouble() = raw / 2^F is exact and the test is  raw < ceil(breakpoint * 2^F).
+ *   Horner      v_n = a_sn (format f[n]);  for i = n-1 .. 0:  v_i = Qadd<f[i]>(a_si, Qmul<f[i]>(x, v_{i+1}))  (:4843-4851).
+ *               A full Qu type as tag unwraps into its five tags (:3097-3099): both results have exactly the format f[i],
+ *               modes included.  Formats may differ per level and per segment.
+ *   result      the converting constructor into X (:2398-2411), X's own QuMode and OfMode; a one-coefficient segment is a
+ *               constant converted into X.
+ * Coefficients cross this boundary as RAW integers plus format, never as doubles (Qu_s(double) with RND::CONV is an
+ * artefact for negative inputs: QG_OPT_ARITHMETIC_CONV above).
+ * In the stage record  e, e_scalar and x_first  are unused and must be zero,  r  must equal the running value's format in
+ * all five fields (Qapprox returns decltype(x)), and  t  works as for any stage.  The stage reads no run-time operand:
+ * qgemul_packed_e_bytes is 0, and the E[k] / qgemul_ep_args entries of the stage are ignored.
+ * The _epx entry points are the _ep ones plus  ax[QG_MAX_EW]:  ax[k] is non-null exactly for the APPROX stages; the plan
+ * copies the tables.  qgemul_execute_ep, qgemul_time_execute_ep, qgemul_pack_e, qgemul_unpack_c and
+ * qgemul_export_bitstream serve such plans unchanged.  The chain of such a plan always runs as one pass after the GEMM
+ * kernel (qgemul_plan_fuses_epilogue = 0).  The _ep / _epc entry points keep refusing op 5; complex chains have no such stage.
+ * QG_EINVAL: n_seg = 0 or > QG_MAX_SEG, n_coef = 0 or > QG_MAX_COEF, a NaN breakpoint, a coefficient outside its format,
+ * r != x's format, a missing or surplus table.  QG_EUNSUPPORTED: x with more than 53 value bits, a Horner format or an
+ * intermediate beyond 62 bits, and whatever the chain refuses anywhere (WRP::TCPL_SAT that can act, the 32-/64-bit shift
+ * artefacts). */
+#define QG_EW_APPROX 5
+#define QG_MAX_SEG 16
+#define QG_MAX_COEF 8
+typedef struct qgemul_approx_seg {
+    double breakpoint;
+    uint32_t n_coef;            /* 1 .. QG_MAX_COEF: a[0] + a[1] x + ... + a[n_coef-1] x^(n_coef-1) */
+    uint32_t reserved;
+    qfmt f[QG_MAX_COEF];        /* format of coefficient i = result format of Horner level i */
+    int64_t a[QG_MAX_COEF];     /* raw values */
+} qgemul_approx_seg;
+typedef struct qgemul_approx {
+    uint32_t n_seg;             /* 1 .. QG_MAX_SEG */
+    uint32_t reserved;
+    qgemul_approx_seg seg[QG_MAX_SEG];
+} qgemul_approx;
+int qgemul_classify_epx(const qgemul_desc* d, const qgemul_epilogue* ep, const qgemul_approx* const ax[QG_MAX_EW], uint32_t opt_flags,
+                        qgemul_info* out);
+int qgemul_plan_create_epx(qgemul_ctx* c, const qgemul_desc* d, const qgemul_epilogue* ep, const qgemul_approx* const ax[QG_MAX_EW],
+                           uint32_t opt_flags, qgemul_plan** out);
+int qgemul_run_epx(const qgemul_desc* d, const qgemul_epilogue* ep, const qgemul_approx* const ax[QG_MAX_EW], void* D, const void* A,
+                   const void* B, const void* const* E, const qgemul_opts* o);
+/* 1: the plan's APPROX tables are all UNIFORM (every segment has the same n_coef and the same format, all five fields, at every
+ * level: one datapath and a coefficient table — one Horner loop for all lanes); 0: a table takes the general form (segment by
+ * segment under a lane mask, several times slower when many segments meet in a wave); -1: the plan has no APPROX stage.  The
+ * formats alone decide, never the coefficient values.  (QG_OPT_APPROX_GENERAL changes the form that runs, not this answer.) */
+int qgemul_plan_approx_uniform(const qgemul_plan* p);
+/* what the planner made of a chain with APPROX stages (pure host code): whether the pass runs in 32-bit arithmetic, the widest
+ * intermediate, and per stage slot the table's form (1 uniform, 0 general, -1 no table) and the integer thresholds
+ * ceil(breakpoint * 2^F) of segments 0 .. n_seg - 2, clamped to [lo, hi + 1] of x's format (the remaining entries: hi + 1) */
+typedef struct qgemul_approx_form {
+    int32_t bits32, max_bits;
+    int32_t uniform[QG_MAX_EW];
+    int64_t threshold[QG_MAX_EW][QG_MAX_SEG];
+} qgemul_approx_form;
+int qgemul_approx_plan_form(const qgemul_desc* d, const qgemul_epilogue* ep, const qgemul_approx* const ax[QG_MAX_EW], qgemul_approx_form* out);
+/* sizeof of an ABI struct as THIS library was compiled (language bindings check their mirrors against it); 0: unknown id */
+enum { QG_SIZEOF_QFMT = 0, QG_SIZEOF_DESC = 1, QG_SIZEOF_OPTS = 2, QG_SIZEOF_INFO = 3, QG_SIZEOF_EW_STAGE = 4, QG_SIZEOF_EPILOGUE = 5,
+       QG_SIZEOF_EP_ARGS = 6, QG_SIZEOF_EPILOGUE_CPLX = 7, QG_SIZEOF_APPROX_SEG = 8, QG_SIZEOF_APPROX = 9 };
+size_t qgemul_sizeof(int which);
 
 /* ---- several GPUs in one process ----
  * The M x N outputs are independent: device i computes a band of whole 256-row blocks of C from the matching rows of A' and

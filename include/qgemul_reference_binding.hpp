@@ -15,6 +15,7 @@
 // The repository's standalone header include/QuBLAS_amd.h provides the same Qgemul on its own
 // minimal tag API for users who do not have the reference header.
 #pragma once
+#include <array>
 #include <stdexcept>
 #include <string>
 #include <type_traits>
@@ -243,11 +244,50 @@ template <class... Tags> struct pick_result { using type = void; };
 template <class CT, class... Rest> struct pick_result<QgemulResult<CT>, Rest...> { using type = CT; };
 template <class T, class... Rest> struct pick_result<T, Rest...> : pick_result<Rest...> {};
 
+// ThenApprox<Into, ANUS::Segment<…>…>(): the header's own Segment types (QuBLAS.h:4853-4863) lowered to a qgemul_approx.  The raw value
+// of a coefficient is what the header holds for it (c.data.data) — never a double.
+template <class S> struct seg_lower;
+template <double BP, auto... as>
+struct seg_lower<ANUS::Segment<BP, as...>> {
+    static_assert(sizeof...(as) >= 1 && sizeof...(as) <= QG_MAX_COEF, "1 .. QG_MAX_COEF coefficients");
+    static qgemul_approx_seg lower()
+    {
+        qgemul_approx_seg g{};
+        g.breakpoint = BP;
+        g.n_coef = sizeof...(as);
+        uint32_t i = 0;
+        ((g.f[i] = fmt_of<std::remove_cvref_t<decltype(as)>>(), g.a[i] = int64_t(as.data.data), ++i), ...);
+        return g;
+    }
+};
+template <class Into, class... Segs>
+struct ApproxStage {
+    static_assert(sizeof...(Segs) >= 1 && sizeof...(Segs) <= QG_MAX_SEG, "1 .. QG_MAX_SEG segments");
+    static constexpr bool approx = true;
+    static constexpr bool scalar = true;
+    static constexpr int op = QG_EW_APPROX;
+    template <class X> using r_t = decltype(ANUS::Qapprox<Segs...>(std::declval<X>()));   // decltype(x)
+    template <class X> using next_t = std::conditional_t<std::is_void_v<Into>, r_t<X>, Into>;
+    static const qgemul_approx* table()
+    {
+        static const qgemul_approx t = [] {
+            qgemul_approx q{};
+            q.n_seg = sizeof...(Segs);
+            uint32_t g = 0;
+            ((q.seg[g++] = seg_lower<Segs>::lower()), ...);
+            return q;
+        }();
+        return &t;
+    }
+};
+template <class S> constexpr bool is_approx = requires { requires S::approx; };
+
 // complex chains: stage k of the chain of part P (0 = real parts, 1 = imaginary parts) — include/qgemul.h's table
 template <class X> void fill_chain_cplx(qgemul_epilogue_cplx&, uint32_t) {}
 template <class X, class S0, class... Ss>
 void fill_chain_cplx(qgemul_epilogue_cplx& ep, uint32_t k)
 {
+    static_assert(!is_approx<S0>, "Qapprox is defined on real values only (QuBLAS.h:4868)");
     using e_t = typename S0::e_t;
     using r_t = typename S0::template r_t<X>;
     using n_t = typename S0::template next_t<X>;
@@ -279,9 +319,11 @@ void fill_chain(qgemul_epilogue& ep, uint32_t k)
     using r_t = typename S0::template r_t<X>;
     using n_t = typename S0::template next_t<X>;
     ep.stage[k].op = uint8_t(S0::op);
-    ep.stage[k].x_first = S0::x_first;
-    ep.stage[k].e_scalar = S0::scalar;
-    ep.stage[k].e = fmt_of<typename S0::e_t>();
+    if constexpr (!is_approx<S0>) {   // (an APPROX stage: e, e_scalar and x_first stay zero)
+        ep.stage[k].x_first = S0::x_first;
+        ep.stage[k].e_scalar = S0::scalar;
+        ep.stage[k].e = fmt_of<typename S0::e_t>();
+    }
     ep.stage[k].r = fmt_of<r_t>();
     ep.stage[k].t = fmt_of<n_t>();
     fill_chain<n_t, Ss...>(ep, k + 1);
@@ -292,6 +334,16 @@ template <class Into = void, typename... Tags, class Operand> auto ThenMul(const
 template <class Into = void, typename... Tags, class Operand> auto ThenAdd(const Operand& e) { return qgemul_detail::EwStage<QG_EW_ADD, true, Into, Operand, Tags...>{e}; }
 template <class Into = void, typename... Tags, class Operand> auto ThenSub(const Operand& e) { return qgemul_detail::EwStage<QG_EW_SUB, true, Into, Operand, Tags...>{e}; }
 template <class Into = void, typename... Tags, class Operand> auto ThenRsub(const Operand& e) { return qgemul_detail::EwStage<QG_EW_SUB, false, Into, Operand, Tags...>{e}; }
+template <class Into, class... Segments> auto ThenApprox() { return qgemul_detail::ApproxStage<Into, Segments...>{}; }
+// the tables of a chain, in stage order: the stage's qgemul_approx, nullptr for a stage that is no ThenApprox
+template <class... Stages>
+std::array<const qgemul_approx*, QG_MAX_EW> Qgemul_lower_approx(const Stages&...)
+{
+    std::array<const qgemul_approx*, QG_MAX_EW> t{};
+    uint32_t k = 0;
+    ([&] { if constexpr (qgemul_detail::is_approx<Stages>) t[k] = Stages::table(); ++k; }(), ...);
+    return t;
+}
 
 template <typename... Tags, class TD, class... Stages>
 qgemul_epilogue Qgemul_lower_epilogue(const TD&, const Stages&...)
@@ -331,7 +383,8 @@ void Qgemul(TD& D, const TA& A, const TB& B, const S0& s0, const Stages&... st)
     d.flags |= QgemulDescFlags();
     auto ptr = [](const auto& stage) -> const void* {
         // a scalar is one element as the tensors store them (ArbiInt<N>::data, QuBLAS.h:353; {real, imag} for a complex one, :2512-2513)
-        if constexpr (std::remove_cvref_t<decltype(stage)>::scalar) return &stage.e;
+        if constexpr (qgemul_detail::is_approx<std::remove_cvref_t<decltype(stage)>>) return nullptr;   // reads no operand
+        else if constexpr (std::remove_cvref_t<decltype(stage)>::scalar) return &stage.e;
         else return stage.e.data.data();
     };
     const void* E[QG_MAX_EW] = {ptr(s0), ptr(st)...};
@@ -341,7 +394,12 @@ void Qgemul(TD& D, const TA& A, const TB& B, const S0& s0, const Stages&... st)
         rc = qgemul_run_epc(&d, &ep, D.data.data(), A.data.data(), B.data.data(), E, nullptr);
     } else {
         const qgemul_epilogue ep = Qgemul_lower_epilogue<Tags...>(D, s0, st...);
-        rc = qgemul_run_ep(&d, &ep, D.data.data(), A.data.data(), B.data.data(), E, nullptr);
+        if constexpr (qgemul_detail::is_approx<S0> || (qgemul_detail::is_approx<Stages> || ...)) {
+            const auto ax = Qgemul_lower_approx(s0, st...);
+            rc = qgemul_run_epx(&d, &ep, ax.data(), D.data.data(), A.data.data(), B.data.data(), E, nullptr);
+        } else {
+            rc = qgemul_run_ep(&d, &ep, D.data.data(), A.data.data(), B.data.data(), E, nullptr);
+        }
     }
     if (rc != QG_OK) throw std::runtime_error(std::string("Qgemul: ") + qgemul_strerror(rc));
 }

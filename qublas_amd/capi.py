@@ -13,8 +13,8 @@ from typing import Optional
 
 import numpy as np
 
-from .desc import (Qcomplex, Qu, host_layout, qgemul_desc, qgemul_ep_args, qgemul_epilogue, qgemul_epilogue_cplx, qgemul_info,
-                   qgemul_opts)
+from .desc import (QG_MAX_EW, Qcomplex, Qu, host_layout, qfmt, qgemul_approx, qgemul_approx_form, qgemul_approx_seg, qgemul_desc, qgemul_ep_args, qgemul_epilogue,
+                   qgemul_epilogue_cplx, qgemul_ew_stage, qgemul_info, qgemul_opts)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # QUBLAS_AMD_DIAG=1 (tools/ only) loads the diagnostic build: environment A/B switches and ablation variants exist there and
@@ -25,6 +25,7 @@ QG_OK, QG_EINVAL, QG_EUNSUPPORTED, QG_EHIP, QG_ERCCL, QG_ERANGE, QG_ENOGPU = 0, 
 OPT_FORCE_TREE, OPT_CHECK_RANGE, OPT_GENERIC_TREE, OPT_RUNTIME_MODES, OPT_FUSED_EPILOGUE, OPT_UNFUSED_EPILOGUE = 1, 2, 4, 8, 16, 32
 OPT_GENERIC_LAYOUT, OPT_LOCKSTEP_TILES, OPT_ARITHMETIC_CONV, OPT_ALL_DEVICES = 64, 128, 256, 512
 OPT_SCHOOLBOOK_LIMBS = 2048   # 17/18-bit operands: balanced base-256 limbs and 9 products, not three base-64 digits and 6; result-identical
+OPT_APPROX_GENERAL = 4096   # chains with an APPROX stage: uniform tables through the general form of the pass; result-identical
 OPT_BALANCED_LIMBS = 1024   # never centre an operand (x - c in balanced limbs): the plain balanced limbs, result-identical
 OPERAND_A, OPERAND_B, OPERAND_C = 0, 1, 2
 BITS_ASCII, BITS_PACKED = 0, 1
@@ -41,7 +42,11 @@ EXPORTS = [
     "qgemul_bitstream_bytes", "qgemul_export_bitstream", "qgemul_run_release", "qgemul_run_sharded", "qgemul_execute_host_c", "qgemul_plan_stores_host_c",
     "qgemul_comm_unique_id", "qgemul_comm_create", "qgemul_comm_destroy", "qgemul_comm_info", "qgemul_gather_packed_c", "qgemul_comm_fence",
     "qgemul_comm_sync", "qgemul_comm_barrier", "qgemul_comm_max_f64", "qgemul_last_rccl_error", "qgemul_ctx_device",
+    "qgemul_classify_epx", "qgemul_plan_create_epx", "qgemul_run_epx", "qgemul_plan_approx_uniform", "qgemul_sizeof", "qgemul_approx_plan_form", "qgemul_apply_epilogue", "qgemul_time_apply_epilogue", "qgemul_packed_c_bytes", "qgemul_pack_c",
 ]
+# qgemul_sizeof ids (include/qgemul.h) and the ctypes mirror each one must match
+SIZEOF_MIRRORS = {0: qfmt, 1: qgemul_desc, 2: qgemul_opts, 3: qgemul_info, 4: qgemul_ew_stage, 5: qgemul_epilogue, 6: qgemul_ep_args,
+                  7: qgemul_epilogue_cplx, 8: qgemul_approx_seg, 9: qgemul_approx}
 
 _lib = None
 
@@ -123,6 +128,19 @@ def lib() -> C.CDLL:
         L.qgemul_comm_barrier.argtypes = [vp]
         L.qgemul_comm_max_f64.argtypes = [vp, C.POINTER(C.c_double)]
         L.qgemul_ctx_device.argtypes = [vp]
+        pax = C.POINTER(C.POINTER(qgemul_approx))
+        L.qgemul_classify_epx.argtypes = [pd, pe, pax, u32, C.POINTER(qgemul_info)]
+        L.qgemul_plan_create_epx.argtypes = [vp, pd, pe, pax, u32, C.POINTER(vp)]
+        L.qgemul_run_epx.argtypes = [pd, pe, pax, vp, vp, vp, C.POINTER(vp), C.POINTER(qgemul_opts)]
+        L.qgemul_plan_approx_uniform.argtypes = [vp]
+        L.qgemul_approx_plan_form.argtypes = [pd, pe, pax, C.POINTER(qgemul_approx_form)]
+        L.qgemul_packed_c_bytes.argtypes = [vp]
+        L.qgemul_packed_c_bytes.restype = i64
+        L.qgemul_pack_c.argtypes = [vp, vp, i64, vp]
+        L.qgemul_apply_epilogue.argtypes = [vp, vp, vp, pa]
+        L.qgemul_time_apply_epilogue.argtypes = [vp, vp, vp, pa, C.c_int, C.c_int, C.POINTER(C.c_float)]
+        L.qgemul_sizeof.argtypes = [C.c_int]
+        L.qgemul_sizeof.restype = C.c_size_t
         _lib = L
     return _lib
 
@@ -163,6 +181,42 @@ def run_ep(desc: qgemul_desc, ep, D_out: np.ndarray, A: np.ndarray, B: np.ndarra
     _chk(fn(C.byref(desc), C.byref(ep), D_out.ctypes.data_as(C.c_void_p), A.ctypes.data_as(C.c_void_p),
             B.ctypes.data_as(C.c_void_p), ptrs, C.byref(o)), "qgemul_run_ep")
     return D_out
+
+
+def _tables(approx):
+    """QG_MAX_EW pointers: the stage's qgemul_approx, or null for a stage that is no APPROX stage"""
+    approx = list(approx) + [None] * (QG_MAX_EW - len(approx))
+    return (C.POINTER(qgemul_approx) * QG_MAX_EW)(*[C.pointer(t) if t is not None else None for t in approx[:QG_MAX_EW]])
+
+
+def classify_epx(desc: qgemul_desc, ep: qgemul_epilogue, approx, flags: int = 0):
+    """qgemul_classify_epx: (status, info); approx[k] = stage k's qgemul_approx or None (desc.lower_epilogue_x)"""
+    info = qgemul_info()
+    st = lib().qgemul_classify_epx(C.byref(desc), C.byref(ep), _tables(approx), flags, C.byref(info))
+    return st, info
+
+
+def run_epx(desc: qgemul_desc, ep: qgemul_epilogue, approx, D_out: np.ndarray, A: np.ndarray, B: np.ndarray, E, *, lda: int = 0,
+            ldb: int = 0, ldc: int = 0, device: int = -1, flags: int = 0) -> np.ndarray:
+    """qgemul_run_epx: as run_ep; E[k] of an APPROX stage is ignored (None)"""
+    A = np.ascontiguousarray(A)
+    B = np.ascontiguousarray(B)
+    E = [None if e is None else np.ascontiguousarray(e) for e in E]
+    ptrs = (C.c_void_p * max(1, len(E)))(*[None if e is None else e.ctypes.data for e in E])
+    o = qgemul_opts(lda, ldb, ldc, device, flags)
+    _chk(lib().qgemul_run_epx(C.byref(desc), C.byref(ep), _tables(approx), D_out.ctypes.data_as(C.c_void_p), A.ctypes.data_as(C.c_void_p),
+                              B.ctypes.data_as(C.c_void_p), ptrs, C.byref(o)), "qgemul_run_epx")
+    return D_out
+
+
+def approx_plan_form(desc: qgemul_desc, ep: qgemul_epilogue, approx) -> qgemul_approx_form:
+    out = qgemul_approx_form()
+    _chk(lib().qgemul_approx_plan_form(C.byref(desc), C.byref(ep), _tables(approx), C.byref(out)), "qgemul_approx_plan_form")
+    return out
+
+
+def sizeof(which: int) -> int:
+    return int(lib().qgemul_sizeof(which))
 
 
 def classify_status(desc: qgemul_desc, flags: int = 0):
@@ -294,12 +348,14 @@ def _chk_rccl(st: int, what: str):
 
 
 class Plan:
-    def __init__(self, ctx: Context, desc: qgemul_desc, flags: int = 0, epilogue=None):
+    def __init__(self, ctx: Context, desc: qgemul_desc, flags: int = 0, epilogue=None, approx=None):
         self.ctx = ctx
         self.desc = desc
         self.epilogue = epilogue
         self.h = C.c_void_p()
-        if epilogue is None:
+        if approx is not None and any(t is not None for t in approx):
+            _chk(lib().qgemul_plan_create_epx(ctx.h, C.byref(desc), C.byref(epilogue), _tables(approx), flags, C.byref(self.h)), "qgemul_plan_create_epx")
+        elif epilogue is None:
             _chk(lib().qgemul_plan_create(ctx.h, C.byref(desc), flags, C.byref(self.h)), "qgemul_plan_create")
         elif isinstance(epilogue, qgemul_epilogue_cplx):
             _chk(lib().qgemul_plan_create_epc(ctx.h, C.byref(desc), C.byref(epilogue), flags, C.byref(self.h)), "qgemul_plan_create_epc")
@@ -350,6 +406,10 @@ class Plan:
         _chk(lib().qgemul_plan_packed_layout(self.h, operand, out), "qgemul_plan_packed_layout")
         return tuple(int(x) for x in out)
 
+    def approx_uniform(self) -> int:
+        """1: every APPROX table of the plan has the uniform form, 0: one takes the general form, -1: no APPROX stage"""
+        return int(lib().qgemul_plan_approx_uniform(self.h))
+
     def fuses_epilogue(self) -> bool:
         return bool(lib().qgemul_plan_fuses_epilogue(self.h))
 
@@ -377,6 +437,23 @@ class Plan:
         ms = C.c_float()
         _chk(lib().qgemul_time_execute_ep(self.h, C.c_void_p(pD), C.c_void_p(pA), C.c_void_p(pB), C.byref(args), warmup, iters,
                                           C.byref(ms)), "qgemul_time_execute_ep")
+        return ms.value
+
+    def packed_c_bytes(self) -> int:
+        return int(lib().qgemul_packed_c_bytes(self.h))
+
+    def pack_c(self, src_dev: int, packed_dev: int, ld: int = 0):
+        """a device-resident tensor of the Qgemul result's element type -> the packed C that apply_epilogue reads"""
+        _chk(lib().qgemul_pack_c(self.h, C.c_void_p(src_dev), ld, C.c_void_p(packed_dev)), "qgemul_pack_c")
+
+    def apply_epilogue(self, pD: int, pC: int, args: qgemul_ep_args):
+        """the chain alone: packed C (pack_c) -> packed D"""
+        _chk(lib().qgemul_apply_epilogue(self.h, C.c_void_p(pD), C.c_void_p(pC), C.byref(args)), "qgemul_apply_epilogue")
+
+    def time_apply_epilogue(self, pD: int, pC: int, args: qgemul_ep_args, warmup: int, iters: int) -> float:
+        ms = C.c_float()
+        _chk(lib().qgemul_time_apply_epilogue(self.h, C.c_void_p(pD), C.c_void_p(pC), C.byref(args), warmup, iters, C.byref(ms)),
+             "qgemul_time_apply_epilogue")
         return ms.value
 
     def unpack_c(self, pC: int, dst_dev: int, ld: int = 0):

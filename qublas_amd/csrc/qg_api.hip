@@ -14,6 +14,7 @@
 #include "qg_kernels.h"
 #include "qg_ring.h"
 #include "qg_plan.h"
+#include "qg_approx.h"
 
 static thread_local int g_last_hip = 0;
 
@@ -101,6 +102,10 @@ struct qgemul_plan {
     qgemul_epilogue ep_im;
     QEpTable ept_im;
     uint8_t e_cplx[QG_MAX_EW];
+    // APPROX stages (qg_approx.h): has_ax = the chain holds one (it then always runs as the pass of qg_approx.hip); ax_dev[k] = stage k's
+    // table on the device, ax_uniform = every table has the uniform form
+    int has_ax, ax_uniform;
+    QApproxTable* ax_dev[QG_MAX_EW];
     QCGeom pc_c;
     void* cwork;
     int32_t* wide_ws;     // single-limb MFMA with a left-shifting epilogue that leaves 32 bits: raw int32 dot products
@@ -112,7 +117,7 @@ struct qgemul_plan {
 
 struct HostC { void* C; int64_t ld; };
 // an element-wise chain as the planner sees it: a real chain (im == nullptr) or the two part chains of a complex one
-struct EpView { const qgemul_epilogue* re; const qgemul_epilogue* im; const uint8_t* e_cplx; };   // execute_kernel: store the reference layout directly (kernels that can)
+struct EpView { const qgemul_epilogue* re; const qgemul_epilogue* im; const uint8_t* e_cplx; const qgemul_approx* const* ax; };   // execute_kernel: store the reference layout directly (kernels that can)
 
 static int pow2_bytes(int storage_bits)
 {
@@ -224,7 +229,7 @@ static hipError_t comp_zero_rowsums(const qgemul_plan* p, int operand, void* pac
 static int plan_geometry(const qgemul_desc* d, uint32_t flags, QAnalysis* an, qgemul_info* info, int* pLA, int* pLB, QMfmaCfg* pVar,
                          QPackedGeom* pa, QPackedGeom* pb, QCGeom* pc, QHostElem* ha, QHostElem* hb, QHostElem* hc,
                          const EpView* ev = nullptr, QEpTable* ept = nullptr, QCGeom* pc_c = nullptr, QEpTable* ept_im = nullptr,
-                         QComposite* pcomp = nullptr)
+                         QComposite* pcomp = nullptr, QApproxTable* axt = nullptr)
 {
     QComposite comp_local;
     QComposite& comp = pcomp ? *pcomp : comp_local;
@@ -504,7 +509,7 @@ static int plan_geometry(const qgemul_desc* d, uint32_t flags, QAnalysis* an, qg
             const qgemul_epilogue* e = part ? ev->im : ep;
             int ep_bits = 0;
             char why[96];
-            const int st = qg_analyze_ep(d->c[part], e, t[part], &ep_bits, why, sizeof why);
+            const int st = qg_analyze_epx(d->c[part], e, part ? nullptr : ev->ax, t[part], part ? nullptr : axt, &ep_bits, why, sizeof why);
             if (st != QG_OK) {
                 info->supported = 0;
                 snprintf(info->reason, sizeof info->reason, "%s", why);
@@ -594,6 +599,7 @@ extern "C" void qgemul_diag_set_stamps(void* dev) { g_diag_stamps = (uint32_t*)d
 
 static bool fuses_epilogue(const qgemul_plan* p)
 {
+    if (p->has_ax) return false;   // (an APPROX stage: always the pass of qg_approx.hip)
     if (wide_epilogue(p) || p->comp.on || p->variant == QG_RING_VARIANT) return false;
     if (p->flags & QG_OPT_UNFUSED_EPILOGUE) return false;
     if (!p->ept.bits32) return false;
@@ -641,6 +647,53 @@ int qgemul_classify_ep(const qgemul_desc* d, const qgemul_epilogue* ep, uint32_t
 {
     const EpView v = {ep, nullptr, nullptr};
     return classify_view(d, ep ? &v : nullptr, opt_flags, out);
+}
+
+int qgemul_classify_epx(const qgemul_desc* d, const qgemul_epilogue* ep, const qgemul_approx* const ax[QG_MAX_EW], uint32_t opt_flags, qgemul_info* out)
+{
+    if (!ep || !ax) return QG_EINVAL;
+    const EpView v = {ep, nullptr, nullptr, ax};
+    return classify_view(d, &v, opt_flags, out);
+}
+
+int qgemul_approx_plan_form(const qgemul_desc* d, const qgemul_epilogue* ep, const qgemul_approx* const ax[QG_MAX_EW], qgemul_approx_form* out)
+{
+    if (!d || !ep || !ax || !out) return QG_EINVAL;
+    memset(out, 0, sizeof *out);
+    if (d->is_complex) return QG_EINVAL;
+    QApproxTable* axt = new (std::nothrow) QApproxTable[QG_MAX_EW];
+    if (!axt) return QG_EINVAL;
+    QEpTable t;
+    int bits = 0;
+    const int st = qg_analyze_epx(d->c[0], ep, ax, &t, axt, &bits, nullptr, 0);
+    if (st == QG_OK) {
+        out->bits32 = t.bits32;
+        out->max_bits = bits;
+        for (int k = 0; k < QG_MAX_EW; ++k) {
+            const bool on = k < t.n && t.st[k].op == QG_EW_APPROX;
+            out->uniform[k] = on ? axt[k].uniform : -1;
+            for (int g = 0; on && g < QG_MAX_SEG; ++g) out->threshold[k][g] = axt[k].thr[g];
+        }
+    }
+    delete[] axt;
+    return st;
+}
+
+size_t qgemul_sizeof(int which)
+{
+    switch (which) {
+    case QG_SIZEOF_QFMT: return sizeof(qfmt);
+    case QG_SIZEOF_DESC: return sizeof(qgemul_desc);
+    case QG_SIZEOF_OPTS: return sizeof(qgemul_opts);
+    case QG_SIZEOF_INFO: return sizeof(qgemul_info);
+    case QG_SIZEOF_EW_STAGE: return sizeof(qgemul_ew_stage);
+    case QG_SIZEOF_EPILOGUE: return sizeof(qgemul_epilogue);
+    case QG_SIZEOF_EP_ARGS: return sizeof(qgemul_ep_args);
+    case QG_SIZEOF_EPILOGUE_CPLX: return sizeof(qgemul_epilogue_cplx);
+    case QG_SIZEOF_APPROX_SEG: return sizeof(qgemul_approx_seg);
+    case QG_SIZEOF_APPROX: return sizeof(qgemul_approx);
+    default: return 0;
+    }
 }
 
 int qgemul_classify_epc(const qgemul_desc* d, const qgemul_epilogue_cplx* ep, uint32_t opt_flags, qgemul_info* out)
@@ -740,6 +793,16 @@ int qgemul_plan_create_ep(qgemul_ctx* c, const qgemul_desc* d, const qgemul_epil
     return plan_create_view(c, d, ep ? &v : nullptr, opt_flags, out);
 }
 
+int qgemul_plan_create_epx(qgemul_ctx* c, const qgemul_desc* d, const qgemul_epilogue* ep, const qgemul_approx* const ax[QG_MAX_EW], uint32_t opt_flags,
+                           qgemul_plan** out)
+{
+    if (!ep || !ax) return QG_EINVAL;
+    const EpView v = {ep, nullptr, nullptr, ax};
+    return plan_create_view(c, d, &v, opt_flags, out);
+}
+
+int qgemul_plan_approx_uniform(const qgemul_plan* p) { return p && p->has_ax ? p->ax_uniform : -1; }
+
 int qgemul_plan_create_epc(qgemul_ctx* c, const qgemul_desc* d, const qgemul_epilogue_cplx* ep, uint32_t opt_flags, qgemul_plan** out)
 {
     if (!ep) return QG_EINVAL;
@@ -764,9 +827,13 @@ static int plan_create_view(qgemul_ctx* c, const qgemul_desc* d, const EpView* e
             p->ep_im = *ev->im;
             memcpy(p->e_cplx, ev->e_cplx, sizeof p->e_cplx);
         }
+        for (int k = 0; ev->ax && k < QG_MAX_EW; ++k) p->has_ax |= ev->ax[k] != nullptr;
     }
+    QApproxTable* axt = p->has_ax ? new (std::nothrow) QApproxTable[QG_MAX_EW] : nullptr;
+    if (p->has_ax && !axt) { delete p; return QG_EINVAL; }
+    struct AxtGuard { QApproxTable* t; ~AxtGuard() { delete[] t; } } axt_guard = {axt};
     int st = plan_geometry(d, opt_flags, &p->an, &p->info, &p->LA, &p->LB, &p->cfg, &p->pa, &p->pb, &p->pc, &p->ha, &p->hb, &p->hc,
-                           ev, &p->ept, &p->pc_c, &p->ept_im, &p->comp);
+                           ev, &p->ept, &p->pc_c, &p->ept_im, &p->comp, axt);
     if (st != QG_OK) { delete p; return st; }
     p->variant = p->cfg.variant;
     p->tc = qg_tree_choice(&p->an, d, opt_flags, true);
@@ -819,6 +886,21 @@ static int plan_create_view(qgemul_ctx* c, const qgemul_desc* d, const EpView* e
             return QG_EHIP;
         }
     }
+    if (p->has_ax) {
+        // the plan's copy of the tables, pre-resolved: one device buffer per APPROX stage
+        p->ax_uniform = 1;
+        bool ok = true;
+        for (int k = 0; k < p->ept.n && ok; ++k) {
+            if (p->ept.st[k].op != QG_EW_APPROX) continue;
+            p->ax_uniform &= axt[k].uniform;
+            ok = hipMalloc((void**)&p->ax_dev[k], sizeof(QApproxTable)) == hipSuccess &&
+                 hipMemcpyAsync(p->ax_dev[k], &axt[k], sizeof(QApproxTable), hipMemcpyHostToDevice, c->stream) == hipSuccess;
+        }
+        if (!ok || hipStreamSynchronize(c->stream) != hipSuccess) {   // (the tables are host temporaries: copied before they go)
+            qgemul_plan_destroy(p);
+            return QG_EHIP;
+        }
+    }
     *out = p;
     return QG_OK;
 }
@@ -835,6 +917,7 @@ void qgemul_plan_destroy(qgemul_plan* p)
     hipFree(p->hostc_pc);
     hipFree(p->comp_slabs);
     hipFree(p->comp_acc);
+    for (int k = 0; k < QG_MAX_EW; ++k) hipFree(p->ax_dev[k]);
     delete p;
 }
 
@@ -994,21 +1077,103 @@ int qgemul_execute_host_c(qgemul_plan* p, void* C_dev, int64_t ldc, const void* 
     return QG_OK;
 }
 
-int qgemul_execute_ep(qgemul_plan* p, void* packedD, const void* packedA, const void* packedB, const qgemul_ep_args* args)
+static int ep_args_ok(const qgemul_plan* p, const qgemul_ep_args* args)
 {
-    if (!p || !packedD || !packedA || !packedB) return QG_EINVAL;
-    if (!p->has_ep) return args ? QG_EINVAL : qgemul_execute(p, packedD, packedA, packedB);
     if (!args && p->ept.n > 0) return QG_EINVAL;
     for (int k = 0; k < p->ept.n; ++k)
         if ((!p->ept.st[k].scalar || (p->ep_cplx && !p->ept_im.st[k].scalar)) && !args->e_packed[k]) return QG_EINVAL;
-    if (p->desc.M == 0 || p->desc.N == 0) return QG_OK;
-    QG_ON_DEVICE(p->ctx);
+    return QG_OK;
+}
+
+// the plan's chain as ONE linear pass: packed C (the kernel's own layout and container, pc_c) -> packed D
+static int run_chain_pass(qgemul_plan* p, const void* packedC, void* packedD, const QEpArgs& a, const qgemul_ep_args* args)
+{
+    hipStream_t st = p->ctx->stream;
+    QEltwiseArgs g;
+    memset(&g, 0, sizeof g);
+    g.C = (const char*)packedC;
+    g.D = (char*)packedD;
+    g.n = p->pc_c.Mp * p->pc_c.Np;
+    g.cbytes = p->pc_c.cbytes;
+    g.t = p->ept;
+    g.a = a;
+    if (p->has_ax) {
+        QApproxArgs x;
+        memset(&x, 0, sizeof x);
+        x.g = g;
+        for (int k = 0; k < QG_MAX_EW; ++k) x.ax[k] = p->ax_dev[k];
+        x.force_general = (p->flags & QG_OPT_APPROX_GENERAL) ? 1 : 0;   // result-identical form choice (include/qgemul.h)
+        QG_HIP(qg_launch_approx(x, st));
+        return QG_OK;
+    }
+    QG_HIP(qg_launch_eltwise(g, st));
+    if (p->ep_cplx) {
+        // the chain of the imaginary parts: the second half of packed C, of packed D and of every complex tensor operand
+        g.C += g.n * g.cbytes;
+        g.D += g.n * p->ept.dbytes;
+        g.t = p->ept_im;
+        for (int k = 0; k < p->ept_im.n; ++k) {
+            if (g.a.e[k] && p->e_cplx[k]) g.a.e[k] += g.n * p->ept_im.st[k].ebytes;
+            g.a.scalar[k] = args->e_scalar_im[k];
+        }
+        QG_HIP(qg_launch_eltwise(g, st));
+    }
+    return QG_OK;
+}
+
+static QEpArgs ep_device_args(const qgemul_plan* p, const qgemul_ep_args* args)
+{
     QEpArgs a;
     memset(&a, 0, sizeof a);
     for (int k = 0; k < p->ept.n; ++k) {
         a.e[k] = (const char*)args->e_packed[k];
         a.scalar[k] = args->e_scalar[k];
     }
+    return a;
+}
+
+int qgemul_apply_epilogue(qgemul_plan* p, void* packedD, const void* packedC, const qgemul_ep_args* args)
+{
+    if (!p || !packedD || !packedC || !p->has_ep) return QG_EINVAL;
+    if (int s = ep_args_ok(p, args)) return s;
+    if (p->desc.M == 0 || p->desc.N == 0) return QG_OK;
+    QG_ON_DEVICE(p->ctx);
+    return run_chain_pass(p, packedC, packedD, ep_device_args(p, args), args);
+}
+
+int qgemul_time_apply_epilogue(qgemul_plan* p, void* packedD, const void* packedC, const qgemul_ep_args* args, int warmup, int iters, float* avg_ms)
+{
+    if (!p || !avg_ms || iters < 1) return QG_EINVAL;
+    for (int i = 0; i < warmup; ++i)
+        if (int s = qgemul_apply_epilogue(p, packedD, packedC, args)) return s;
+    QG_ON_DEVICE(p->ctx);
+    hipStream_t st = p->ctx->stream;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    int rc = QG_OK;
+    float ms = 0;
+    hipError_t he = hipEventCreate(&e0);
+    if (he == hipSuccess) he = hipEventCreate(&e1);
+    if (he == hipSuccess) he = hipEventRecord(e0, st);
+    for (int i = 0; he == hipSuccess && rc == QG_OK && i < iters; ++i) rc = qgemul_apply_epilogue(p, packedD, packedC, args);
+    if (he == hipSuccess && rc == QG_OK) he = hipEventRecord(e1, st);
+    if (he == hipSuccess && rc == QG_OK) he = hipEventSynchronize(e1);
+    if (he == hipSuccess && rc == QG_OK) he = hipEventElapsedTime(&ms, e0, e1);
+    if (e0) hipEventDestroy(e0);
+    if (e1) hipEventDestroy(e1);
+    if (he != hipSuccess) { g_last_hip = (int)he; return QG_EHIP; }
+    if (rc != QG_OK) return rc;
+    *avg_ms = ms / (float)iters;
+    return QG_OK;
+}
+
+int qgemul_execute_ep(qgemul_plan* p, void* packedD, const void* packedA, const void* packedB, const qgemul_ep_args* args)
+{
+    if (!p || !packedD || !packedA || !packedB) return QG_EINVAL;
+    if (!p->has_ep) return args ? QG_EINVAL : qgemul_execute(p, packedD, packedA, packedB);
+    if (int s = ep_args_ok(p, args)) return s;
+    if (p->desc.M == 0 || p->desc.N == 0) return QG_OK;
+    QG_ON_DEVICE(p->ctx);
+    const QEpArgs a = ep_device_args(p, args);
     hipStream_t st = p->ctx->stream;
     if (fuses_epilogue(p)) {
         // fused: the MFMA kernel's epilogue runs the chain on the value it has just converted into C's type
@@ -1035,27 +1200,7 @@ int qgemul_execute_ep(qgemul_plan* p, void* packedD, const void* packedA, const 
     // not fused: the kernel stores C into the plan's buffer, one linear pass turns it into D
     const int s = execute_kernel(p, p->cwork, packedA, packedB, nullptr);
     if (s != QG_OK) return s;
-    QEltwiseArgs g;
-    memset(&g, 0, sizeof g);
-    g.C = (const char*)p->cwork;
-    g.D = (char*)packedD;
-    g.n = p->pc_c.Mp * p->pc_c.Np;
-    g.cbytes = p->pc_c.cbytes;
-    g.t = p->ept;
-    g.a = a;
-    QG_HIP(qg_launch_eltwise(g, st));
-    if (p->ep_cplx) {
-        // the chain of the imaginary parts: the second half of packed C, of packed D and of every complex tensor operand
-        g.C += g.n * g.cbytes;
-        g.D += g.n * p->ept.dbytes;
-        g.t = p->ept_im;
-        for (int k = 0; k < p->ept_im.n; ++k) {
-            if (g.a.e[k] && p->e_cplx[k]) g.a.e[k] += g.n * p->ept_im.st[k].ebytes;
-            g.a.scalar[k] = args->e_scalar_im[k];
-        }
-        QG_HIP(qg_launch_eltwise(g, st));
-    }
-    return QG_OK;
+    return run_chain_pass(p, p->cwork, packedD, a, args);
 }
 
 int qgemul_plan_fuses_epilogue(const qgemul_plan* p) { return p && p->has_ep && fuses_epilogue(p) ? 1 : 0; }
@@ -1077,6 +1222,23 @@ static const QEpStage* stage_tensor(const qgemul_plan* p, int k)
     if (!p->ept.st[k].scalar) return &p->ept.st[k];
     if (p->ep_cplx && !p->ept_im.st[k].scalar) return &p->ept_im.st[k];
     return nullptr;
+}
+
+int64_t qgemul_packed_c_bytes(const qgemul_plan* p)
+{
+    return p && p->has_ep ? (int64_t)p->pc_c.parts * p->pc_c.Mp * p->pc_c.Np * p->pc_c.cbytes : 0;
+}
+
+// a tensor of the GEMM result's own element type -> the packed C the chain's pass reads (qgemul_apply_epilogue)
+int qgemul_pack_c(qgemul_plan* p, const void* src_dev, int64_t ld, void* packed_dev)
+{
+    if (!p || !src_dev || !packed_dev || !p->has_ep) return QG_EINVAL;
+    if (ld && ld < p->desc.M) return QG_EINVAL;
+    QG_ON_DEVICE(p->ctx);
+    const QHostElem h = qg_host_elem(p->desc.c, p->desc.is_complex);
+    for (int part = 0; part < p->pc_c.parts; ++part)
+        QG_HIP(qg_launch_pack_e(p->pc_c, part, src_dev, ld ? ld : p->desc.M, h.size, h.off[part], h.sb[part], packed_dev, p->pc_c.cbytes, p->ctx->stream));
+    return QG_OK;
 }
 
 int64_t qgemul_packed_e_bytes(const qgemul_plan* p, int stage)
@@ -1437,6 +1599,8 @@ struct RunCache {
     qgemul_desc pd;
     qgemul_epilogue_cplx pe;          // a real chain is part[0]
     bool has_pe = false, pe_cplx = false;
+    qgemul_approx* pax = nullptr;     // QG_MAX_EW tables of the cached plan's APPROX stages (allocated at the first such plan)
+    uint8_t pax_on[QG_MAX_EW] = {};
     uint32_t pflags = 0;
     enum { NBUF = 6 + 16 };   // 0-5: host-layout A, B, C and packed A, B, C; behind them: the epilogue operands (2 per stage) or, on the
                               // root of a sharded call, the landing buffers of the other bands
@@ -1496,6 +1660,27 @@ bool same_epilogue(const qgemul_epilogue& x, const qgemul_epilogue& y)
     return true;
 }
 
+bool same_approx(const qgemul_approx& x, const qgemul_approx& y)
+{
+    if (x.n_seg != y.n_seg || x.n_seg > QG_MAX_SEG) return false;
+    for (uint32_t g = 0; g < x.n_seg; ++g) {
+        const qgemul_approx_seg &a = x.seg[g], &b = y.seg[g];
+        if (memcmp(&a.breakpoint, &b.breakpoint, sizeof a.breakpoint) || a.n_coef != b.n_coef || a.n_coef > QG_MAX_COEF) return false;
+        for (uint32_t i = 0; i < a.n_coef; ++i)
+            if (!same_fmt(a.f[i], b.f[i]) || a.a[i] != b.a[i]) return false;
+    }
+    return true;
+}
+bool same_tables(const RunCache& c, const qgemul_approx* const* ax)
+{
+    for (int k = 0; k < QG_MAX_EW; ++k) {
+        const qgemul_approx* t = ax ? ax[k] : nullptr;
+        if ((t != nullptr) != (c.pax_on[k] != 0)) return false;
+        if (t && !same_approx(*t, c.pax[k])) return false;
+    }
+    return true;
+}
+
 int cache_buffer(RunCache& c, int i, size_t bytes, void** out)   // (the caller has made the cache's device current)
 {
     if (bytes > c.cap[i]) {
@@ -1527,6 +1712,9 @@ static void release_cache(RunCache& c)
     c.plan = nullptr;
     c.ctx = nullptr;
     c.device = -2;
+    delete[] c.pax;
+    c.pax = nullptr;
+    memset(c.pax_on, 0, sizeof c.pax_on);
 }
 
 namespace {
@@ -1559,6 +1747,14 @@ int qgemul_run_ep(const qgemul_desc* d, const qgemul_epilogue* ep, void* C, cons
 {
     const EpView v = {ep, nullptr, nullptr};
     return run_view(d, ep ? &v : nullptr, C, A, B, E, o);
+}
+
+int qgemul_run_epx(const qgemul_desc* d, const qgemul_epilogue* ep, const qgemul_approx* const ax[QG_MAX_EW], void* C, const void* A, const void* B,
+                   const void* const* E, const qgemul_opts* o)
+{
+    if (!ep || !ax) return QG_EINVAL;
+    const EpView v = {ep, nullptr, nullptr, ax};
+    return run_view(d, &v, C, A, B, E, o);
 }
 
 int qgemul_run_epc(const qgemul_desc* d, const qgemul_epilogue_cplx* ep, void* C, const void* A, const void* B, const void* const* E,
@@ -1596,7 +1792,8 @@ static int run_view(const qgemul_desc* d, const EpView* ev, void* C, const void*
     }
     const bool same_plan = c.plan && c.pflags == opts.flags && same_desc(c.pd, *d) && c.has_pe == (ep != nullptr) &&
                            (!ep || (same_epilogue(c.pe.part[0], *ep) && c.pe_cplx == (ev->im != nullptr) &&
-                                    (!ev->im || (same_epilogue(c.pe.part[1], *ev->im) && !memcmp(c.pe.e_complex, ev->e_cplx, ep->n_stages))))) &&
+                                    (!ev->im || (same_epilogue(c.pe.part[1], *ev->im) && !memcmp(c.pe.e_complex, ev->e_cplx, ep->n_stages))) &&
+                                    same_tables(c, ev->ax))) &&
                            (opts.device < 0 || opts.device == c.device);
     if (!same_plan) {
         // validate before touching the device so that descriptor errors are reported without a GPU
@@ -1606,7 +1803,7 @@ static int run_view(const qgemul_desc* d, const EpView* ev, void* C, const void*
     }
     if (ep)
         for (uint32_t k = 0; k < ep->n_stages; ++k)
-            if (!E || !E[k]) return QG_EINVAL;
+            if (ep->stage[k].op != QG_EW_APPROX && (!E || !E[k])) return QG_EINVAL;   // (an APPROX stage reads no operand)
     if (d->M == 0 || d->N == 0) return QG_OK;
     int st = QG_OK;
     if (!c.ctx || (opts.device >= 0 && opts.device != c.device)) {
@@ -1627,6 +1824,13 @@ static int run_view(const qgemul_desc* d, const EpView* ev, void* C, const void*
         c.pe_cplx = ev && ev->im;
         if (ep) c.pe.part[0] = *ep;
         if (c.pe_cplx) { c.pe.part[1] = *ev->im; memcpy(c.pe.e_complex, ev->e_cplx, sizeof c.pe.e_complex); }
+        memset(c.pax_on, 0, sizeof c.pax_on);
+        for (int k = 0; ev && ev->ax && k < QG_MAX_EW; ++k) {
+            if (!ev->ax[k]) continue;
+            if (!c.pax) c.pax = new qgemul_approx[QG_MAX_EW];
+            c.pax[k] = *ev->ax[k];
+            c.pax_on[k] = 1;
+        }
         c.pflags = opts.flags;
     }
     qgemul_plan* p = c.plan;
@@ -1666,6 +1870,7 @@ static int run_view(const qgemul_desc* d, const EpView* ev, void* C, const void*
                 const qgemul_ew_stage& sr = ep->stage[k];
                 const qgemul_ew_stage* si = ev->im ? &ev->im->stage[k] : nullptr;
                 const bool cplx = si && ev->e_cplx[k];
+                if (sr.op == QG_EW_APPROX) continue;
                 const bool t_re = sr.op != QG_EW_PASS && !sr.e_scalar, t_im = si && si->op != QG_EW_PASS && !si->e_scalar;
                 if (!t_re && !t_im) {
                     // scalar operand: one element ({re, im} for a complex one); a real scalar feeds both parts, except where the

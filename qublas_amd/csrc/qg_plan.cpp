@@ -1,6 +1,8 @@
 // qg_plan.cpp — descriptor analysis (host only).  See qg_plan.h.
 #include "qg_plan.h"
+#include "qg_approx.h"
 
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -313,7 +315,115 @@ void ring_plan(const qgemul_desc* d, bool c_leaves, QAnalysis* out)
 
 int qg_analyze_ep(qfmt cfmt, const qgemul_epilogue* ep, QEpTable* out, int* max_bits, char* reason, size_t reason_len)
 {
+    return qg_analyze_epx(cfmt, ep, nullptr, out, nullptr, max_bits, reason, reason_len);
+}
+
+namespace {
+
+// One APPROX stage (include/qgemul.h): validates the table, walks every segment's Horner chain through the same range tracking as
+// any other node, fills the device table.  x: the running value, replaced by the stage's result (x's own format; the hull of the
+// segments' result ranges).  ok32: cleared when a step or a constant of the stage does not fit the 32-bit form of the pass.
+bool approx_stage(Ctx& c, const qgemul_ew_stage& s, const qgemul_approx& A, Val& x, QApproxTable* T, bool* ok32)
+{
+    static const qfmt zero = {0, 0, 0, 0, 0, 0};
+    if (s.x_first || s.e_scalar || !same(s.e, zero)) { c.fail(QG_EINVAL, "APPROX stage: e, e_scalar and x_first must be zero"); return false; }
+    if (!same(s.r, x.f)) { c.fail(QG_EINVAL, "APPROX stage: r must be the running value's own format (Qapprox returns decltype(x))"); return false; }
+    if (A.n_seg < 1 || A.n_seg > QG_MAX_SEG) { c.fail(QG_EINVAL, "APPROX table: n_seg outside 1..16"); return false; }
+    for (uint32_t g = 0; g < A.n_seg; ++g) {
+        const qgemul_approx_seg& sg = A.seg[g];
+        if (sg.n_coef < 1 || sg.n_coef > QG_MAX_COEF) { c.fail(QG_EINVAL, "APPROX table: n_coef outside 1..8"); return false; }
+        if (sg.breakpoint != sg.breakpoint) { c.fail(QG_EINVAL, "APPROX table: a NaN breakpoint"); return false; }
+        for (uint32_t i = 0; i < sg.n_coef; ++i) {
+            if (!fmt_ok(c, sg.f[i])) return false;
+            if ((int)sg.f[i].I + (int)sg.f[i].F > 62) { c.fail(QG_EUNSUPPORTED, "APPROX table: a Horner format wider than 62 value bits"); return false; }
+            const Rng r = fmt_range(sg.f[i]);
+            if (sg.a[i] < r.lo || sg.a[i] > r.hi) { c.fail(QG_EINVAL, "APPROX table: a coefficient outside its format"); return false; }
+            if (sbits(sg.f[i]) > 32) *ok32 = false;
+        }
+    }
+    const int Wx = (int)x.f.I + (int)x.f.F;
+    // x.toDouble() is double(raw) / 2^F (QuBLAS.h:2413-2416): exact, and the comparison an integer one, up to 53 value bits
+    if (Wx > 53) { c.fail(QG_EUNSUPPORTED, "APPROX stage: x has more than 53 value bits (toDouble() rounds)"); return false; }
+    if (Wx > 30) *ok32 = false;   // (the clamped threshold hi + 1 = 2^31 is no int32 value)
+    if (T) memset(T, 0, sizeof *T);
+    const Rng xr = fmt_range(x.f);
+    Rng res = {0, 0};
+    QApproxSeg first;
+    bool uniform = true;
+    int ncmax = 0;
+    for (uint32_t g = 0; g < A.n_seg; ++g) {
+        const qgemul_approx_seg& sg = A.seg[g];
+        const int n = (int)sg.n_coef;
+        QApproxSeg S;
+        memset(&S, 0, sizeof S);
+        S.n_coef = n;
+        Val v;
+        v.f = sg.f[n - 1];
+        v.r = Rng{(I128)sg.a[n - 1], (I128)sg.a[n - 1]};
+        for (int i = n - 2; i >= 0; --i) {
+            QNode nm, na;
+            const Val p = do_mul(c, x, v, sg.f[i], &nm);
+            Val a;
+            a.f = sg.f[i];
+            a.r = Rng{(I128)sg.a[i], (I128)sg.a[i]};
+            v = do_addsub(c, a, p, sg.f[i], false, &na);
+            S.lvl[i].mul = nm.q;
+            S.lvl[i].add = na.q;
+            if (nm.q.d > 62) { c.fail(QG_EUNSUPPORTED, "APPROX stage: rounding shift beyond 62 bits"); return false; }
+            if (nm.q.d > 30) *ok32 = false;
+        }
+        const Val y = do_cvt(c, v, x.f, &S.to_x);
+        if (!S.to_x.identity && S.to_x.d > 62) { c.fail(QG_EUNSUPPORTED, "APPROX stage: rounding shift beyond 62 bits"); return false; }
+        if (!S.to_x.identity && S.to_x.d > 30) *ok32 = false;
+        if (c.out->status != QG_OK) return false;
+        res = g ? Rng{y.r.lo < res.lo ? y.r.lo : res.lo, y.r.hi > res.hi ? y.r.hi : res.hi} : y.r;
+        if (n > ncmax) ncmax = n;
+        // uniform = the formats agree, nothing else: the step records follow from the formats (make_step), except refcmp, which only
+        // the 128-bit kernels read, and WRP::TCPL_SAT's rewrite into a clamp, which every accepted segment gets alike
+        if (!g) first = S;
+        else if (n != first.n_coef) uniform = false;
+        for (int i = 0; g && i < n && uniform; ++i) uniform = same(sg.f[i], A.seg[0].f[i]);
+        if (g && uniform) {
+            QApproxSeg a = S, b = first;
+            a.to_x.refcmp = b.to_x.refcmp = 0;
+            for (int i = 0; i + 1 < n; ++i) a.lvl[i].mul.refcmp = a.lvl[i].add.refcmp = b.lvl[i].mul.refcmp = b.lvl[i].add.refcmp = 0;
+            if (memcmp(&a, &b, sizeof a)) { c.fail(QG_EUNSUPPORTED, "APPROX table: equal formats resolved to different steps (planner invariant)"); return false; }
+        }
+        if (T) {
+            T->seg[g] = S;
+            for (int i = 0; i < n; ++i) T->coef[i][g] = sg.a[i];
+        }
+    }
+    if (T) {
+        T->n_seg = (int)A.n_seg;
+        T->uniform = uniform ? 1 : 0;
+        T->n_coef_max = ncmax;
+        const int64_t lo = (int64_t)xr.lo, hi1 = (int64_t)xr.hi + 1;
+        for (int g = 0; g < QG_MAX_SEG; ++g) {
+            int64_t t = hi1;
+            if (g + 1 < (int)A.n_seg) {
+                // raw / 2^F < bp  <=>  raw < bp * 2^F  <=>  raw < ceil(bp * 2^F): the scaling is exact in double unless it leaves the
+                // double range, and then the result lies far outside [lo, hi + 1] (or, underflowing, inside (0, 1): ceil = 1)
+                const double bp = A.seg[g].breakpoint;
+                double sc = ldexp(bp, (int)x.f.F);
+                if (bp > 0 && sc < 1) sc = 1;
+                else sc = ceil(sc);
+                t = sc <= (double)lo ? lo : (sc >= (double)hi1 ? hi1 : (int64_t)sc);
+            }
+            T->thr[g] = t;
+        }
+    }
+    x.r = res;
+    return true;
+}
+
+} // namespace
+
+int qg_analyze_epx(qfmt cfmt, const qgemul_epilogue* ep, const qgemul_approx* const* ax, QEpTable* out, QApproxTable* axt, int* max_bits, char* reason,
+                   size_t reason_len)
+{
     memset(out, 0, sizeof *out);
+    bool ax32 = true;
     g_fmt_bits_seen = 0;
     QAnalysis* an = new QAnalysis;
     memset(an, 0, sizeof *an);
@@ -340,7 +450,27 @@ int qg_analyze_ep(qfmt cfmt, const qgemul_epilogue* ep, QEpTable* out, int* max_
         bool ok = true;
         for (uint32_t k = 0; k < ep->n_stages && ok; ++k) {
             const qgemul_ew_stage& s = ep->stage[k];
-            if (s.op < QG_EW_ADD || s.op > QG_EW_PASS) { c.fail(QG_EINVAL, "unknown element-wise op"); ok = false; break; }
+            if (s.op < QG_EW_ADD || s.op > (ax ? QG_EW_APPROX : QG_EW_PASS)) { c.fail(QG_EINVAL, "unknown element-wise op"); ok = false; break; }
+            if (ax && (s.op == QG_EW_APPROX) != (ax[k] != nullptr)) {
+                c.fail(QG_EINVAL, s.op == QG_EW_APPROX ? "APPROX stage without its table" : "a table for a stage that is no APPROX stage");
+                ok = false;
+                break;
+            }
+            if (s.op == QG_EW_APPROX) {
+                QEpStage& t = out->st[k];
+                memset(&t, 0, sizeof t);
+                t.op = QG_EW_APPROX;
+                t.scalar = 1;                       // no operand is read
+                t.ebytes = 1;
+                t.node.q.identity = 1;
+                t.cvt.identity = 1;
+                if (!approx_stage(c, s, *ax[k], x, axt ? &axt[k] : nullptr, &ax32)) { ok = false; break; }
+                if (k + 1 < ep->n_stages) {
+                    if (!chain_fmt_ok(s.t)) { ok = false; break; }
+                    x = do_cvt(c, x, s.t, &t.cvt);
+                }
+                continue;
+            }
             if (s.op == QG_EW_PASS) {
                 // the part is carried over in its own format (the imaginary part under a real operand, QuBLAS.h:3654/3670/3701);
                 // only the assignment to the stage's tensor touches it
@@ -377,6 +507,9 @@ int qg_analyze_ep(qfmt cfmt, const qgemul_epilogue* ep, QEpTable* out, int* max_
             }
         }
         if (!ok) break;
+        for (uint32_t k = ep->n_stages; ax && k < QG_MAX_EW; ++k)
+            if (ax[k]) { c.fail(QG_EINVAL, "a table beyond the last stage"); ok = false; }
+        if (!ok) break;
         do_cvt(c, x, ep->d, &out->to_d);
         out->n = (int)ep->n_stages;
         out->dbytes = pow2_bytes(ep->d);
@@ -384,7 +517,7 @@ int qg_analyze_ep(qfmt cfmt, const qgemul_epilogue* ep, QEpTable* out, int* max_
         {
             // 32-bit arithmetic: every intermediate (raw products and aligned operands included) within 32 bits, every
             // format within 32 storage bits, every rounding shift below 31
-            bool ok32 = c.max_bits <= 32 && g_fmt_bits_seen <= 32 && 1 + (int)cfmt.I + (int)cfmt.F <= 32;
+            bool ok32 = ax32 && c.max_bits <= 32 && g_fmt_bits_seen <= 32 && 1 + (int)cfmt.I + (int)cfmt.F <= 32;
             auto shift_ok = [](const QStep& q) { return q.identity || q.d <= 30; };
             for (int k = 0; k < out->n; ++k) ok32 = ok32 && shift_ok(out->st[k].node.q) && shift_ok(out->st[k].cvt) && out->st[k].ebytes <= 4;
             out->bits32 = (ok32 && shift_ok(out->to_d)) ? 1 : 0;

@@ -89,6 +89,24 @@ class qgemul_ep_args(C.Structure):
     _fields_ = [("e_packed", C.c_void_p * QG_MAX_EW), ("e_scalar", C.c_int64 * QG_MAX_EW), ("e_scalar_im", C.c_int64 * QG_MAX_EW)]
 
 
+QG_MAX_SEG, QG_MAX_COEF = 16, 8
+EW_APPROX = 5
+
+
+class qgemul_approx_seg(C.Structure):
+    _fields_ = [("breakpoint", C.c_double), ("n_coef", C.c_uint32), ("reserved", C.c_uint32),
+                ("f", qfmt * QG_MAX_COEF), ("a", C.c_int64 * QG_MAX_COEF)]
+
+
+class qgemul_approx(C.Structure):
+    _fields_ = [("n_seg", C.c_uint32), ("reserved", C.c_uint32), ("seg", qgemul_approx_seg * QG_MAX_SEG)]
+
+
+class qgemul_approx_form(C.Structure):
+    _fields_ = [("bits32", C.c_int32), ("max_bits", C.c_int32), ("uniform", C.c_int32 * QG_MAX_EW),
+                ("threshold", (C.c_int64 * QG_MAX_SEG) * QG_MAX_EW)]
+
+
 class qgemul_info(C.Structure):
     _fields_ = [("cls", C.c_int32), ("supported", C.c_int32), ("max_bits", C.c_int32),
                 ("in_bits", C.c_int32 * 2), ("limbs", C.c_int32 * 2), ("kernel", C.c_int32),
@@ -500,6 +518,63 @@ def lower_epilogue(c: "Qu", stages, d: "Qu") -> qgemul_epilogue:
         ep.stage[k].t = x.c()
     ep.d = d.c()
     return ep
+
+
+# ---- the piecewise-polynomial activation stage (include/qgemul.h, QG_EW_APPROX; the reference's ANUS::Qapprox, QuBLAS.h:4829-4897) ----
+
+@dataclass(frozen=True)
+class Approx:
+    """ANUS::Qapprox<Segment<bp, a0, a1, ...>, ...> applied to the running value x: segments = [(breakpoint, [(raw, Qu), ...]), ...],
+    coefficient 0 first, every coefficient as its RAW integer and its format (a double would go through Qu_s(double), whose
+    RND::CONV path is an artefact for negative inputs).  The result has x's own format; into = as for Ew."""
+    segments: Sequence
+    into: Optional["Qu"] = None
+
+
+def approx_table(st: Approx) -> qgemul_approx:
+    segs = list(st.segments)
+    if not 1 <= len(segs) <= QG_MAX_SEG:
+        raise ValueError("1 .. 16 segments")
+    t = qgemul_approx()
+    t.n_seg = len(segs)
+    for g, (bp, coefs) in enumerate(segs):
+        coefs = list(coefs)
+        if not 1 <= len(coefs) <= QG_MAX_COEF:
+            raise ValueError("1 .. 8 coefficients per segment")
+        t.seg[g].breakpoint = float(bp)
+        t.seg[g].n_coef = len(coefs)
+        for i, (raw, f) in enumerate(coefs):
+            t.seg[g].f[i] = f.c()
+            t.seg[g].a[i] = int(raw)
+    return t
+
+
+def lower_epilogue_x(c: "Qu", stages, d: "Qu"):
+    """lower_epilogue for chains that may hold Approx stages: (qgemul_epilogue, [table or None per stage slot, QG_MAX_EW entries])"""
+    stages = list(stages)
+    if len(stages) > QG_MAX_EW:
+        raise ValueError("too many element-wise stages")
+    ep = qgemul_epilogue()
+    ep.n_stages = len(stages)
+    tables = [None] * QG_MAX_EW
+    x = c
+    for k, st in enumerate(stages):
+        if isinstance(st, Approx):
+            ep.stage[k].op = EW_APPROX
+            ep.stage[k].r = x.c()
+            tables[k] = approx_table(st)
+            r = x
+        else:
+            r = ew_result(x, st)
+            ep.stage[k].op = {"add": EW_ADD, "sub": EW_SUB, "mul": EW_MUL}[st.op]
+            ep.stage[k].x_first = 1 if st.x_first else 0
+            ep.stage[k].e_scalar = 1 if st.scalar else 0
+            ep.stage[k].e = st.e.c()
+            ep.stage[k].r = r.c()
+        x = st.into if (st.into is not None and k + 1 < len(stages)) else r
+        ep.stage[k].t = x.c()
+    ep.d = d.c()
+    return ep, tables
 
 
 # ---- the same after a COMPLEX Qgemul: two part-wise chains (include/qgemul.h, qgemul_epilogue_cplx) ----
