@@ -282,7 +282,7 @@ static int plan_geometry(const qgemul_desc* d, uint32_t flags, QAnalysis* an, qg
         const int L = qg_ring_digits(an->ring_n);
         LA = qg_limbs_for(d->a[0]) < L ? qg_limbs_for(d->a[0]) : L;
         LB = qg_limbs_for(d->b[0]) < L ? qg_limbs_for(d->b[0]) : L;
-        cfg = QMfmaCfg{QG_RING_VARIANT, QG_RING_TM, QG_RING_TN, QG_RING_BK};
+        cfg = QMfmaCfg{QG_MFMA_RING, QG_RING_TM, QG_RING_TN, QG_RING_BK};
         kernel = L == 1 ? QG_KERNEL_MFMA_I8 : QG_KERNEL_MFMA_I8_LIMB;
         const int np = qg_ring_products(LA, LB, L);
         snprintf(info->reason, sizeof info->reason, "linear class: wrapping ring mod 2^%d, %d limb product%s", an->ring_n, np, np == 1 ? "" : "s");
@@ -363,10 +363,10 @@ static int plan_geometry(const qgemul_desc* d, uint32_t flags, QAnalysis* an, qg
         auto ubits = [](qfmt f) { return (int)f.I + (int)f.F + (f.S ? 1 : 0); };
         const int cb = pow2_bytes(sbits(d->c));
         // (what k_mfma_ppl's 3 x 3 body takes: qg_mfma_ppl_applies)
-        ppl33 = kernel == QG_KERNEL_MFMA_I8_LIMB && !comp.on && !d->is_complex && !ep && LA == 3 && LB == 3 && cfg.variant == 10 && (cb == 4 || cb == 8);
+        ppl33 = kernel == QG_KERNEL_MFMA_I8_LIMB && !comp.on && !d->is_complex && !ep && LA == 3 && LB == 3 && cfg.variant == QG_MFMA_PPL && (cb == 4 || cb == 8);
         k6 = ppl33 && !no_kara3 && !(flags & QG_OPT_SCHOOLBOOK_LIMBS) && !centred && !an->band && ubits(d->a[0]) >= 13 && ubits(d->a[0]) <= 18 &&
              ubits(d->b[0]) >= 13 && ubits(d->b[0]) <= 18 && d->K * (int64_t)(126 * 126) < (1ll << 31);
-        if (k6) cfg = QMfmaCfg{QG_K6_VARIANT, QG_K6_TM, QG_K6_TN, QG_K6_BK};
+        if (k6) cfg = QMfmaCfg{QG_MFMA_K6, QG_K6_TM, QG_K6_TN, QG_K6_BK};
     }
     if (kernel != QG_KERNEL_NONE) {
         *pa = QPackedGeom{round_up(d->M, cfg.TM), round_up(d->K, cfg.BK), 1, LA, cfg.TM, cfg.BK};
@@ -459,9 +459,9 @@ static int plan_geometry(const qgemul_desc* d, uint32_t flags, QAnalysis* an, qg
         static const bool no_kara = QG_DIAG_ENV("QG_NO_KARA");   // A/B switch
         auto ubits = [](qfmt f) { return (int)f.I + (int)f.F + (f.S ? 1 : 0); };
         // (problems small enough for the 64x64 tiles are latency-bound: measured 9.5 vs 8.9 us at 1024^3, schoolbook kept there)
-        if (!no_kara && !d->is_complex && LA == 2 && LB == 2 && (kernel == QG_KERNEL_MFMA_I8_LIMB) && (cfg.variant == 3 || cfg.variant == 10) && ubits(d->a[0]) <= 12 &&
+        if (!no_kara && !d->is_complex && LA == 2 && LB == 2 && (kernel == QG_KERNEL_MFMA_I8_LIMB) && (cfg.variant == QG_MFMA_LIMB_128 || cfg.variant == QG_MFMA_PPL) && ubits(d->a[0]) <= 12 &&
             ubits(d->b[0]) <= 12 && d->K * (int64_t)(126 * 126) < (1ll << 31)) {
-            cfg.variant = 3;   // three products on the lock-step Karatsuba kernel (same tiles and k-tiles as variant 10)
+            cfg.variant = QG_MFMA_LIMB_128;   // three products on the lock-step Karatsuba kernel (same tiles and k-tiles as QG_MFMA_PPL)
             for (QPackedGeom* g : {pa, pb}) {
                 const qfmt f = g == pa ? d->a[0] : d->b[0];
                 g->digit6 = 1;
@@ -574,7 +574,7 @@ static int plan_geometry(const qgemul_desc* d, uint32_t flags, QAnalysis* an, qg
 // 64-bit linear pass instead, which keeps the hot kernels' epilogue as it is.
 static bool wide_epilogue(const qgemul_plan* p)
 {
-    if (p->comp.on || p->variant == QG_RING_VARIANT) return false;   // (the combine pass / the ring kernel's epilogue convert in 64-bit arithmetic anyway)
+    if (p->comp.on || p->variant == QG_MFMA_RING) return false;   // (the combine pass / the ring kernel's epilogue convert in 64-bit arithmetic anyway)
     const QStep& q = p->an.lin.to_c[0];
     // ... and a C format beyond 31 value bits does not fit the 32-bit epilogue's clamp bounds at all (second find of the
     // extended fuzz runs: int<7,-2> x int<7,-1> into Qu<24,9>)
@@ -592,6 +592,38 @@ static void centre_args(const qgemul_plan* p, QMfmaArgs& a, const void* packedA,
     a.corr = (int64_t)((uint64_t)p->desc.K * (uint64_t)p->pa.bias * (uint64_t)p->pb.bias);
 }
 
+// plane mask of a packed multi-limb operand (QPackedGeom::trailer); nullptr: all planes
+static const uint32_t* plane_mask(const void* packed, const QPackedGeom& g)
+{
+    return g.trailer ? (const uint32_t*)((const char*)packed + g.trailer) : nullptr;
+}
+
+// what every MFMA launch is given: operands of the geometries ga / gb, the result and its container, the kernel
+static QMfmaArgs mfma_args(const QPackedGeom& ga, const QPackedGeom& gb, int variant, const void* A, const void* B, void* C, int cbytes)
+{
+    QMfmaArgs a;
+    memset(&a, 0, sizeof a);
+    a.A = (const int8_t*)A;
+    a.B = (const int8_t*)B;
+    a.C = C;
+    a.Mp = ga.rows_p;
+    a.Np = gb.rows_p;
+    a.Kp = ga.K_p;
+    a.cbytes = cbytes;
+    a.variant = variant;
+    a.maskA = plane_mask(A, ga);
+    a.maskB = plane_mask(B, gb);
+    return a;
+}
+// ... of a plan's own operands, with the one conversion into C's format and the centres of centred operands
+static QMfmaArgs mfma_args(const qgemul_plan* p, const void* A, const void* B, void* C, int cbytes)
+{
+    QMfmaArgs a = mfma_args(p->pa, p->pb, p->variant, A, B, C, cbytes);
+    a.to_c = p->an.lin.to_c[0];
+    centre_args(p, a, A, B);
+    return a;
+}
+
 #ifdef QG_DIAG
 static uint32_t* g_diag_stamps = nullptr;   // device buffer for in-kernel clock stamps (diagnostic build only)
 extern "C" void qgemul_diag_set_stamps(void* dev) { g_diag_stamps = (uint32_t*)dev; }
@@ -600,7 +632,7 @@ extern "C" void qgemul_diag_set_stamps(void* dev) { g_diag_stamps = (uint32_t*)d
 static bool fuses_epilogue(const qgemul_plan* p)
 {
     if (p->has_ax) return false;   // (an APPROX stage: always the pass of qg_approx.hip)
-    if (wide_epilogue(p) || p->comp.on || p->variant == QG_RING_VARIANT) return false;
+    if (wide_epilogue(p) || p->comp.on || p->variant == QG_MFMA_RING) return false;
     if (p->flags & QG_OPT_UNFUSED_EPILOGUE) return false;
     if (!p->ept.bits32) return false;
     if (p->info.kernel == QG_KERNEL_MFMA_I8_LIMB && p->LA == 3 && p->LB == 3) return true;
@@ -1045,14 +1077,14 @@ int qgemul_execute(qgemul_plan* p, void* packedC, const void* packedA, const voi
     return execute_kernel(p, packedC, packedA, packedB, nullptr);
 }
 
-// the kernels whose epilogue can store the reference layout: k_mfma_pp (variant 9) / k_mfma_ppl (variant 10), real, 4- or 8-byte
+// the kernels whose epilogue can store the reference layout: k_mfma_pp (QG_MFMA_PP) / k_mfma_ppl (QG_MFMA_PPL), real, 4- or 8-byte
 // container equal to the host element, no raw-dot-product detour
 static bool stores_host_c(const qgemul_plan* p)
 {
     if (p->has_ep || p->desc.is_complex || wide_epilogue(p) || p->comp.on) return false;
     if (p->info.kernel != QG_KERNEL_MFMA_I8 && p->info.kernel != QG_KERNEL_MFMA_I8_LIMB) return false;
-    if (p->variant != 9 && p->variant != 10 && p->variant != QG_K6_VARIANT) return false;
-    if (p->variant == 10 && (p->pa.rows_p / p->cfg.TM) * (p->pb.rows_p / p->cfg.TN) < 256) return false;   // (falls back to the lock-step kernel)
+    if (p->variant != QG_MFMA_PP && p->variant != QG_MFMA_PPL && p->variant != QG_MFMA_K6) return false;
+    if (p->variant == QG_MFMA_PPL && (p->pa.rows_p / p->cfg.TM) * (p->pb.rows_p / p->cfg.TN) < 256) return false;   // (falls back to the lock-step kernel)
     return (p->pc.cbytes == 4 || p->pc.cbytes == 8) && p->pc.cbytes == p->hc.size;
 }
 
@@ -1177,23 +1209,10 @@ int qgemul_execute_ep(qgemul_plan* p, void* packedD, const void* packedA, const 
     hipStream_t st = p->ctx->stream;
     if (fuses_epilogue(p)) {
         // fused: the MFMA kernel's epilogue runs the chain on the value it has just converted into C's type
-        QMfmaArgs m;
-        memset(&m, 0, sizeof m);
-        m.A = (const int8_t*)packedA;
-        m.B = (const int8_t*)packedB;
-        m.C = packedD;
-        m.Mp = p->pa.rows_p;
-        m.Np = p->pb.rows_p;
-        m.Kp = p->pa.K_p;
-        m.cbytes = p->pc_c.cbytes;
-        m.variant = p->variant;
-        m.to_c = p->an.lin.to_c[0];
-        m.maskA = p->pa.trailer ? (const uint32_t*)((const char*)packedA + p->pa.trailer) : nullptr;
-        m.maskB = p->pb.trailer ? (const uint32_t*)((const char*)packedB + p->pb.trailer) : nullptr;
+        QMfmaArgs m = mfma_args(p, packedA, packedB, packedD, p->pc_c.cbytes);
         m.has_ep = 1;
         m.ep = p->ept;
         m.epa = a;
-        centre_args(p, m, packedA, packedB);
         QG_HIP(qg_launch_mfma(p->LA, p->LB, m, st));
         return QG_OK;
     }
@@ -1281,19 +1300,8 @@ static int execute_composite(qgemul_plan* p, void* packedC, const void* packedA,
                 const QPackedGeom sa = comp_sub_geom(q, p->pa, 0, p->desc.K, c, i, &offA);
                 const QPackedGeom sb = comp_sub_geom(q, p->pb, 1, p->desc.K, c, j, &offB);
                 char* slab = (char*)p->comp_slabs + (size_t)(i * q.gb + j) * (size_t)n * (size_t)q.slab_bytes;
-                QMfmaArgs a;
-                memset(&a, 0, sizeof a);
-                a.A = (const int8_t*)packedA + offA;
-                a.B = (const int8_t*)packedB + offB;
-                a.C = slab;
-                a.Mp = sa.rows_p;
-                a.Np = sb.rows_p;
-                a.Kp = sa.K_p;
-                a.cbytes = q.slab_bytes;
-                a.variant = q.var[i][j];
+                QMfmaArgs a = mfma_args(sa, sb, q.var[i][j], (const char*)packedA + offA, (const char*)packedB + offB, slab, q.slab_bytes);
                 a.to_c.identity = 1;   // raw dot products
-                a.maskA = sa.trailer ? (const uint32_t*)((const char*)a.A + sa.trailer) : nullptr;
-                a.maskB = sb.trailer ? (const uint32_t*)((const char*)a.B + sb.trailer) : nullptr;
                 QG_HIP(qg_launch_mfma(sa.limbs, sb.limbs, a, st));
                 cb.slab[cb.n_slabs] = slab;
                 cb.sh[cb.n_slabs] = 8 * (sa.limb0 + sb.limb0);
@@ -1330,7 +1338,7 @@ static int execute_kernel(qgemul_plan* p, void* packedC, const void* packedA, co
     switch (p->info.kernel) {
     case QG_KERNEL_MFMA_I8:
     case QG_KERNEL_MFMA_I8_LIMB: {
-        if (p->variant == QG_RING_VARIANT) {
+        if (p->variant == QG_MFMA_RING) {
             QRingArgs r;
             memset(&r, 0, sizeof r);
             r.A = (const int8_t*)packedA;
@@ -1346,23 +1354,10 @@ static int execute_kernel(qgemul_plan* p, void* packedC, const void* packedA, co
             QG_HIP(qg_launch_mfma_ring(p->LA, p->LB, qg_ring_digits(p->an.ring_n), r, st));
             return QG_OK;
         }
-        QMfmaArgs a;
-        memset(&a, 0, sizeof a);
-        a.A = (const int8_t*)packedA;
-        a.B = (const int8_t*)packedB;
-        a.C = packedC;
-        a.Mp = p->pa.rows_p;
-        a.Np = p->pb.rows_p;
-        a.Kp = p->pa.K_p;
-        a.cbytes = pcg.cbytes;
-        a.variant = p->variant;
-        a.to_c = p->an.lin.to_c[0];
-        a.maskA = p->pa.trailer ? (const uint32_t*)((const char*)packedA + p->pa.trailer) : nullptr;
-        a.maskB = p->pb.trailer ? (const uint32_t*)((const char*)packedB + p->pb.trailer) : nullptr;
+        QMfmaArgs a = mfma_args(p, packedA, packedB, packedC, pcg.cbytes);
 #ifdef QG_DIAG
         a.dbg = g_diag_stamps;
 #endif
-        centre_args(p, a, packedA, packedB);
         if (p->pa.digit6) {
             a.kara = 1;
             a.rsA = (const int64_t*)((const char*)packedA + p->pa.rowsum_off);
@@ -1401,19 +1396,9 @@ static int execute_kernel(qgemul_plan* p, void* packedC, const void* packedA, co
         return QG_OK;
     }
     case QG_KERNEL_MFMA_CPLX: {
-        QMfmaArgs a;
-        memset(&a, 0, sizeof a);
-        a.A = (const int8_t*)packedA;
-        a.B = (const int8_t*)packedB;
-        a.C = p->workspace;
-        a.Mp = 2 * p->pa.rows_p;
+        QMfmaArgs a = mfma_args(p->pa, p->pb, p->variant, packedA, packedB, p->workspace, 8);
+        a.Mp = 2 * p->pa.rows_p;   // the parts stacked along the rows: one real GEMM of twice the extents
         a.Np = 2 * p->pb.rows_p;
-        a.Kp = p->pa.K_p;
-        a.cbytes = 8;
-        a.variant = p->variant;
-        a.maskA = p->pa.trailer ? (const uint32_t*)((const char*)packedA + p->pa.trailer) : nullptr;
-        a.maskB = p->pb.trailer ? (const uint32_t*)((const char*)packedB + p->pb.trailer) : nullptr;
-        memset(&a.to_c, 0, sizeof a.to_c);
         a.to_c.identity = 1;  // raw 64-bit dot products
         QG_HIP(qg_launch_mfma(p->LA, p->LB, a, st));
         QCplxCombine g;

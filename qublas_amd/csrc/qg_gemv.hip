@@ -418,12 +418,9 @@ hipError_t launch_gemv_wide(const QGemvArgs& g, hipStream_t st)   // 64-bit valu
     constexpr int IMG = 64 * (CH * 4 + 16);
     const int64_t nseg = g.K / (64 * CH);
     const int lds = IMG * ((nseg == 1 ? 1 : 0) + WAVES);
-    static std::atomic<uint64_t> attr_done{0};
-    if (hipError_t e = qg_lds_attr((const void*)k_gemv<CH, 0, int64_t>, IMG * (1 + WAVES), attr_done); e != hipSuccess) return e;
     int64_t blocks = (g.M + WAVES - 1) / WAVES;
     if (blocks > 256 * 8) blocks = 256 * 8;
-    hipLaunchKernelGGL((k_gemv<CH, 0, int64_t>), dim3((unsigned)blocks), dim3(64 * WAVES), lds, st, g);
-    return hipGetLastError();
+    return qg_launch_lds<k_gemv<CH, 0, int64_t>>((unsigned)blocks, 64 * WAVES, lds, st, g, IMG * (1 + WAVES));
 }
 
 template <int CH, int MODE>
@@ -432,12 +429,9 @@ hipError_t launch_gemv(const QGemvArgs& g, hipStream_t st)
     constexpr int IMG = 64 * (CH * 4 + 16);
     const int64_t nseg = g.K / (64 * CH);
     const int lds = IMG * ((nseg == 1 ? 1 : 0) + WAVES);
-    static std::atomic<uint64_t> attr_done{0};   // one bit per device
-    if (hipError_t e = qg_lds_attr((const void*)k_gemv<CH, MODE>, IMG * (1 + WAVES), attr_done); e != hipSuccess) return e;
     int64_t blocks = (g.M + WAVES - 1) / WAVES;
     if (blocks > 256 * 8) blocks = 256 * 8;   // rows beyond that are walked by the grid-stride loop
-    hipLaunchKernelGGL((k_gemv<CH, MODE>), dim3((unsigned)blocks), dim3(64 * WAVES), lds, st, g);
-    return hipGetLastError();
+    return qg_launch_lds<k_gemv<CH, MODE>>((unsigned)blocks, 64 * WAVES, lds, st, g, IMG * (1 + WAVES));
 }
 
 template <int CH>

@@ -8,6 +8,7 @@
 
 #include "qg_eltwise_args.h"
 #include "qg_plan.h"
+#include "qg_ring.h"
 
 // geometry of one operand in host (reference) layout as seen by pack / fill / unpack kernels
 struct QOperandGeom {
@@ -156,7 +157,7 @@ hipError_t qg_launch_tree_cplx_fast(const QTreeTable* dev_table, int n_levels, Q
 
 // linear class on int8 MFMA with LA x LB limbs
 struct QMfmaCfg {
-    int variant;    // 0 = no kernel for this limb combination
+    int variant;    // QMfmaVariant; 0 = no kernel for this limb combination
     int TM, TN, BK; // output tile and k-tile (bytes) the packed operands are padded to
 };
 QMfmaCfg qg_mfma_pick(int LA, int LB, int64_t M, int64_t N, uint32_t opt_flags = 0);
@@ -199,6 +200,24 @@ enum { QG_K6_VARIANT = 11, QG_K6_TM = 96, QG_K6_TN = 128, QG_K6_BK = 64 };
 bool qg_mfma_k6_applies(const QMfmaArgs& a);
 hipError_t qg_launch_mfma_k6(const QMfmaArgs& a, hipStream_t st);
 
+// QMfmaCfg::variant / QMfmaArgs::variant: which kernel qg_mfma_pick() and plan_geometry (qg_api.hip) chose and qg_launch_mfma
+// starts.  Output tile x k-tile bytes; "limb": any LA x LB other than 1 x 1.
+enum QMfmaVariant {
+    QG_MFMA_NONE = 0,
+    QG_MFMA_128 = 1,         // single limb, k_mfma (32x32x32), 128x128 x 64: more than one workgroup per CU, too few for 256x256
+    QG_MFMA_256 = 2,         // single limb, k_mfma16 (16x16x64), 256x256 x 64, lock-step (QG_OPT_LOCKSTEP_TILES, fused chains)
+    QG_MFMA_LIMB_128 = 3,    // limb, k_mfma16's row-step form (k_mfma where that has no instantiation), 128x128 x 64; Karatsuba 2 x 2
+    QG_MFMA_64 = 5,          // single limb, k_mfma, 64x64 x 64 (diagnostic build: QG_BK64)
+    QG_MFMA_LIMB_64 = 6,     // limb, k_mfma, 64x64 x 64 (small problems; a 5-stage ring at one workgroup per CU)
+    QG_MFMA_64_BK128 = 7,    // single limb, k_mfma, 64x64 x 128 (small problems; two k groups per workgroup for long k)
+    QG_MFMA_128_BK128 = 8,   // single limb, k_mfma, 128x128 x 128 (at most one workgroup per CU)
+    QG_MFMA_PP = 9,          // single limb, k_mfma_pp, 256x256 x 128, two wave groups, persistent (qg_mfma_pp.hip)
+    QG_MFMA_PPL = 10,        // 3 x 3 / 2 x 2 limbs, k_mfma_ppl / k_mfma_ppl22, 128x128 x 64, two wave groups, persistent
+                             // (qg_mfma_ppl.hip); fused chains and narrow C run QG_MFMA_LIMB_128 on the same packed layout
+    QG_MFMA_K6 = QG_K6_VARIANT,       // 11: three base-64 digits, k_mfma_k6, 96x128 x 64 (qg_mfma_k6.hip)
+    QG_MFMA_RING = QG_RING_VARIANT,   // 12: ring plans, k_mfma_ring, 128x128 x 64 (qg_ring.h; launched by qg_launch_mfma_ring)
+};
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is set once per DEVICE (one process may drive several: qgemul_run_sharded);
 // `done` holds one bit per device ordinal of the calling thread's current device
 inline hipError_t qg_lds_attr(const void* fn, int bytes, std::atomic<uint64_t>& done)
@@ -211,6 +230,36 @@ inline hipError_t qg_lds_attr(const void* fn, int bytes, std::atomic<uint64_t>& 
     if (e == hipSuccess && dev >= 0 && dev < 64) done.fetch_or(1ull << dev, std::memory_order_release);
     return e;
 }
+
+// ... and the launch that goes with it, for a kernel with dynamic LDS: one `done` word per kernel instantiation.  lds_max: the
+// attribute's value where launches of one kernel differ in their LDS size (0: lds)
+template <auto Kernel, class Args>
+hipError_t qg_launch_lds(unsigned grid, unsigned block, int lds, hipStream_t st, const Args& a, int lds_max = 0)
+{
+    static std::atomic<uint64_t> attr_done{0};
+    if (hipError_t e = qg_lds_attr((const void*)Kernel, lds_max ? lds_max : lds, attr_done); e != hipSuccess) return e;
+    hipLaunchKernelGGL(Kernel, dim3(grid), dim3(block), lds, st, a);
+    return hipGetLastError();
+}
+
+// grid of a persistent kernel (k_mfma_pp, k_mfma_ppl, k_mfma_k6): one workgroup per CU, a multiple of 8 so that every XCD residue
+// class has the same number (qg_tile_walk.h); fewer tiles than CUs: the tile count rounded up to 8, surplus workgroups find
+// their list empty
+inline hipError_t qg_persistent_grid(int64_t tiles, unsigned* grid)
+{
+    int dev = 0, cus = 0;
+    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
+    if (hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev); e != hipSuccess) return e;
+    int64_t g = cus / 8 * 8;
+    if (g < 8) g = 8;
+    if (g > tiles) g = (tiles + 7) / 8 * 8;
+    *grid = (unsigned)g;
+    return hipSuccess;
+}
+
+// the conversion into C's format that the epilogues specialise at compile time (FAST): truncation (TRN::TCPL, right shift
+// d >= 0) + SAT::TCPL, a shift and a clamp per value
+inline bool qg_step_is_shift_clamp(const QStep& q) { return !q.identity && q.O == QG_SAT_TCPL && q.Q == QG_TRN_TCPL && q.d >= 0; }
 
 // A/B and ablation switches read from the environment exist only in the diagnostic build (libqugemm_diag.so, -DQG_DIAG,
 // used by tools/); the product library ignores the environment altogether.

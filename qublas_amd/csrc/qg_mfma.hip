@@ -17,48 +17,16 @@
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 
-#include <atomic>
 #include <utility>
 
 #include "qg_eltwise.h"
 #include "qg_kernels.h"
+#include "qg_mfma_tile.h"
 #include "qg_step_all.h"
 
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
-
-#define QG_GLOBAL_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define QG_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
-
-// LDS image of one k-tile: rows of BK bytes; chunk c (16 B) of row r is stored at slot c ^ swz(r).
-// swz(r) = (r / rows_per_bank_row) % chunks_per_row makes the 16 lanes of every ds_read_b128 group
-// of a 32x32x32 fragment read (rows l&31, one chunk column) land on 16 distinct 16-byte bank slots.
-template <int BK>
-__device__ __forceinline__ int swz(int r)
-{
-    constexpr int CPR = BK / 16;   // chunks per row
-    constexpr int RPB = 256 / BK;  // rows per 256-byte bank row
-    const int q = (r / RPB) % CPR;
-    // For 64-byte rows q -> {0,2,3,1}[q] keeps the 32x32x32 reads conflict free (any bijection does) AND makes the
-    // 16x16x64 fragment reads (rows l&15, chunk l>>4) conflict free; k_pack applies the same function.
-    return BK == 64 ? ((0x78 >> (2 * q)) & 3) : q;
-}
-
-// Issue-order hint for one basic block that holds NM MFMAs, NDS LDS reads and NVM LDS-DMA issues: the reads and DMA issues
-// are spread evenly between the MFMAs (sched_group_barrier masks: 0x008 MFMA, 0x100 DS read, 0x020 VMEM read) instead of the
-// compiler's default of a burst of reads / a burst of DMA issues and then the MFMAs back to back.  Both waves of a SIMD leave
-// the k-tile barrier together, so bursts collide and the matrix pipe idles while both issue ~100-cycle DMA instructions;
-// interleaved, one wave's MFMAs cover the other's issue slots.  Measured on the 3x3 kernel at 4096^3: 0.432 vs 0.4525 ms.
-template <int NM, int NDS, int NVM, int... M>
-__device__ __forceinline__ void interleave_hint(std::integer_sequence<int, M...>)
-{
-    ((__builtin_amdgcn_sched_group_barrier(0x008, 1, 0),
-      __builtin_amdgcn_sched_group_barrier(0x100, (M + 1) * NDS / NM - M * NDS / NM, 0),
-      __builtin_amdgcn_sched_group_barrier(0x020, (M + 1) * NVM / NM - M * NVM / NM, 0)),
-     ...);
-}
 
 // LA, LB : int8 limbs per A / B element          BK       : k-tile in bytes
 // WGM x WGN waves per workgroup                  TI x TJ  : 32x32 MFMA tiles per wave
@@ -107,21 +75,11 @@ __global__ __launch_bounds__(64 * WGM * WGN * KS) void k_mfma(QMfmaArgs g)
     char* smem = smem_all + kg * (NSTAGE * STAGE);           // the group's own ring
     const int wm = wave / WGN, wn = wave % WGN;
 
-    // XCD-aware tile order: consecutive block ids go to different XCDs, so give each XCD a
-    // contiguous run of tiles, walked in column-major groups of 8 tile-rows for L2 reuse.
+    // XCD-aware tile order (qg_tile_walk.h): a contiguous run of tiles per XCD, walked in column-major groups of 8 tile rows
     const int tiles_m = (int)(g.Mp / TM), tiles_n = (int)(g.Np / TN);
     const int nwg = tiles_m * tiles_n;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg / 8, r = nwg % 8, x = bid % 8;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + bid / 8;
-    }
-    constexpr int GM = 8;
-    const int grp = bid / (GM * tiles_n);
-    const int first_m = grp * GM;
-    const int gsz = (tiles_m - first_m) < GM ? (tiles_m - first_m) : GM;
-    const int tile_m = first_m + (bid % (GM * tiles_n)) % gsz;
-    const int tile_n = (bid % (GM * tiles_n)) / gsz;
+    int tile_m, tile_n;
+    qg_tile_of<8, true>(qg_xcd_block<int>(blockIdx.x, nwg), tiles_m, tiles_n, tile_m, tile_n);
 
     // operands are pre-tiled: block (row tile, k tile) of A is LA*TM*BK contiguous bytes that are
     // already the swizzled LDS image; same for B.  A stage is two linear copies.
@@ -174,13 +132,13 @@ __global__ __launch_bounds__(64 * WGM * WGN * KS) void k_mfma(QMfmaArgs g)
         for (int i = 0; i < TI; ++i) {
             const int ra = (wm * TI + i) * 32 + fr;
 #pragma unroll
-            for (int l = 0; l < LA; ++l) fa[set][l][i] = *(const v4i*)(sA + (l * TM + ra) * BK + ((c ^ swz<BK>(ra)) * 16));
+            for (int l = 0; l < LA; ++l) fa[set][l][i] = *(const v4i*)(sA + (l * TM + ra) * BK + ((c ^ qg_swz<BK>(ra)) * 16));
         }
 #pragma unroll
         for (int j = 0; j < TJ; ++j) {
             const int rb = (wn * TJ + j) * 32 + fr;
 #pragma unroll
-            for (int l = 0; l < LB; ++l) fb[set][l][j] = *(const v4i*)(sB + (l * TN + rb) * BK + ((c ^ swz<BK>(rb)) * 16));
+            for (int l = 0; l < LB; ++l) fb[set][l][j] = *(const v4i*)(sB + (l * TN + rb) * BK + ((c ^ qg_swz<BK>(rb)) * 16));
         }
     };
     // the LA*LB*TI*TJ MFMAs of one k-step, optionally only those with index in [first, last)
@@ -365,7 +323,7 @@ __global__ __launch_bounds__(64 * WGM * WGN * KS) void k_mfma(QMfmaArgs g)
                 qg_ep_apply_runs<int32_t, 4>(v, g.ep, g.epa, base, 8);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) qg_ep_store_run<int32_t>(C, base + 8 * q, g.ep.dbytes, v + 4 * q);
-            } else
+            } else   // (written out, not qg_store_run4 with a run-time container size: as a function it moves this kernel's instruction stream)
             switch (g.cbytes) {
             case 1:
 #pragma unroll
@@ -431,17 +389,8 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_mfma16(QMfmaArgs g)
     const int wm = wave / WGN, wn = wave % WGN;
     const int tiles_m = (int)(g.Mp / TM), tiles_n = (int)(g.Np / TN);
     const int nwg = tiles_m * tiles_n;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg / 8, r = nwg % 8, x = bid % 8;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + bid / 8;
-    }
-    constexpr int GM = 8;
-    const int grp = bid / (GM * tiles_n);
-    const int first_m = grp * GM;
-    const int gsz = (tiles_m - first_m) < GM ? (tiles_m - first_m) : GM;
-    const int tile_m = first_m + (bid % (GM * tiles_n)) % gsz;
-    const int tile_n = (bid % (GM * tiles_n)) / gsz;
+    int tile_m, tile_n;
+    qg_tile_of<8, true>(qg_xcd_block<int>(blockIdx.x, nwg), tiles_m, tiles_n, tile_m, tile_n);
 
     const int nk = (int)(g.Kp / BK);
     constexpr int A_BYTES = LA * TM * BK, B_BYTES = LB * TN * BK, A_PIECES = A_BYTES / 1024;   // copied per stage (the first LA / LB planes)
@@ -490,13 +439,13 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_mfma16(QMfmaArgs g)
         for (int i = 0; i < TI; ++i) {
             const int ra = (wm * TI + i) * 16 + fr;
 #pragma unroll
-            for (int l = 0; l < LA; ++l) fa[set][l][i] = *(const v4i*)(sA + (l * TM + ra) * BK + ((fq ^ swz<BK>(ra)) * 16));
+            for (int l = 0; l < LA; ++l) fa[set][l][i] = *(const v4i*)(sA + (l * TM + ra) * BK + ((fq ^ qg_swz<BK>(ra)) * 16));
         }
 #pragma unroll
         for (int j = 0; j < TJ; ++j) {
             const int rb = (wn * TJ + j) * 16 + fr;
 #pragma unroll
-            for (int l = 0; l < LB; ++l) fb[set][l][j] = *(const v4i*)(sB + (l * TN + rb) * BK + ((fq ^ swz<BK>(rb)) * 16));
+            for (int l = 0; l < LB; ++l) fb[set][l][j] = *(const v4i*)(sB + (l * TN + rb) * BK + ((fq ^ qg_swz<BK>(rb)) * 16));
         }
     };
     auto mfmas = [&](int set) {
@@ -539,7 +488,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_mfma16(QMfmaArgs g)
         auto load_a = [&](int buf, const char* sA, int i) {
             const int ra = (wm * TI + i) * 16 + fr;
 #pragma unroll
-            for (int l = 0; l < LA; ++l) pa[buf][l] = *(const v4i*)(sA + (l * TM + ra) * BK + ((fq ^ swz<BK>(ra)) * 16));
+            for (int l = 0; l < LA; ++l) pa[buf][l] = *(const v4i*)(sA + (l * TM + ra) * BK + ((fq ^ qg_swz<BK>(ra)) * 16));
         };
         auto load_b = [&](int buf, const char* sA) {
             const char* sB = sA + LA * TM * BK;
@@ -547,7 +496,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_mfma16(QMfmaArgs g)
             for (int j = 0; j < TJ; ++j) {
                 const int rb = (wn * TJ + j) * 16 + fr;
 #pragma unroll
-                for (int l = 0; l < LB; ++l) pb[buf][l][j] = *(const v4i*)(sB + (l * TN + rb) * BK + ((fq ^ swz<BK>(rb)) * 16));
+                for (int l = 0; l < LB; ++l) pb[buf][l][j] = *(const v4i*)(sB + (l * TN + rb) * BK + ((fq ^ qg_swz<BK>(rb)) * 16));
             }
         };
         load_b(0, smem);
@@ -712,7 +661,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_mfma16(QMfmaArgs g)
             const int col = (wn * TJ + j) * 16 + fr;
             const int64_t base = tile_base + (int64_t)col * TM + row0;
             const S* q = s + j * 4;
-            switch (g.cbytes) {
+            switch (g.cbytes) {   // (written out: see k_mfma)
             case 1:
                 *(uint32_t*)(C + base) = (uint32_t)(q[0] & 0xff) | ((uint32_t)(q[1] & 0xff) << 8) | ((uint32_t)(q[2] & 0xff) << 16) | ((uint32_t)(q[3] & 0xff) << 24);
                 break;
@@ -736,15 +685,12 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_mfma16(QMfmaArgs g)
 // The partner of a 3 x 3 launch for operands whose third limb planes are empty: 2 x 2 limbs read from the 3-plane storage
 // (each kernel of the pair returns at once unless the plane masks select it).
 template <int BK, int WGM, int WGN, int TI, int TJ, int NSTAGE, bool EP>
-void launch_plane_partner(const QMfmaArgs& a, hipStream_t st, int64_t blocks)
+hipError_t launch_plane_partner(const QMfmaArgs& a, hipStream_t st, int64_t blocks)
 {
     static const bool no_partner = QG_DIAG_ENV("QG_NO_PLANE_MASK");   // A/B switch (tools/measure_masked.py); full-range data only!
-    if (!(a.maskA || a.maskB) || no_partner) return;
+    if (!(a.maskA || a.maskB) || no_partner) return hipSuccess;
     constexpr int TM = WGM * TI * 32, TN = WGN * TJ * 32;
-    constexpr int lds2 = NSTAGE * (2 * TM + 2 * TN) * BK;
-    static std::atomic<uint64_t> attr_done2{0};
-    if (qg_lds_attr((const void*)k_mfma<2, 2, BK, WGM, WGN, TI, TJ, NSTAGE, 0, EP, 3, 3>, lds2, attr_done2) != hipSuccess) return;
-    hipLaunchKernelGGL((k_mfma<2, 2, BK, WGM, WGN, TI, TJ, NSTAGE, 0, EP, 3, 3>), dim3((unsigned)blocks), dim3(64 * WGM * WGN), lds2, st, a);
+    return qg_launch_lds<k_mfma<2, 2, BK, WGM, WGN, TI, TJ, NSTAGE, 0, EP, 3, 3>>((unsigned)blocks, 64 * WGM * WGN, NSTAGE * (2 * TM + 2 * TN) * BK, st, a);
 }
 
 template <int LA, int LB, int WGM, int WGN, int TI, int TJ, bool DBUF, bool EP = false, bool HINT = true, int PV = 1, int SA = LA, int SB = LB, bool KARA = false>
@@ -762,24 +708,18 @@ hipError_t launch16(const QMfmaArgs& a, hipStream_t st)
     if (a.has_ep && (!EP || !a.ep.bits32)) return hipErrorInvalidValue;
     constexpr int TM = WGM * TI * 16, TN = WGN * TJ * 16;
     const int lds = 3 * (LA * TM + LB * TN) * 64;
-    static std::atomic<uint64_t> attr_done{0};   // one bit per device (qg_lds_attr)
-    if (hipError_t e = qg_lds_attr((const void*)k_mfma16<LA, LB, WGM, WGN, TI, TJ, DBUF, EP, HINT, PV, SA, SB, KARA>, lds, attr_done); e != hipSuccess) return e;
     const int64_t blocks = (a.Mp / TM) * (a.Np / TN);
     if (blocks <= 0) return hipSuccess;
     if (blocks > 0x7fffffffll || a.Kp % 64 || a.Mp % TM || a.Np % TN) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((k_mfma16<LA, LB, WGM, WGN, TI, TJ, DBUF, EP, HINT, PV, SA, SB, KARA>), dim3((unsigned)blocks), dim3(64 * WGM * WGN), lds, st, a);
+    const hipError_t e = qg_launch_lds<k_mfma16<LA, LB, WGM, WGN, TI, TJ, DBUF, EP, HINT, PV, SA, SB, KARA>>((unsigned)blocks, 64 * WGM * WGN, lds, st, a);
     if constexpr (LA == 3 && LB == 3 && SA == 3) {
         // the partner for operands whose third limb planes are empty: 2 x 2 limbs read from the 3-plane storage (each kernel
         // of the pair returns at once unless the plane masks select it)
         static const bool no_partner = QG_DIAG_ENV("QG_NO_PLANE_MASK");   // A/B switch (tools/measure_masked.py); full-range data only!
-        if ((a.maskA || a.maskB) && !no_partner) {
-            constexpr int lds2 = 3 * (2 * TM + 2 * TN) * 64;
-            static std::atomic<uint64_t> attr_done2{0};
-            if (hipError_t e = qg_lds_attr((const void*)k_mfma16<2, 2, WGM, WGN, TI, TJ, DBUF, EP, HINT, PV, 3, 3>, lds2, attr_done2); e != hipSuccess) return e;
-            hipLaunchKernelGGL((k_mfma16<2, 2, WGM, WGN, TI, TJ, DBUF, EP, HINT, PV, 3, 3>), dim3((unsigned)blocks), dim3(64 * WGM * WGN), lds2, st, a);
-        }
+        if (e == hipSuccess && (a.maskA || a.maskB) && !no_partner)
+            return qg_launch_lds<k_mfma16<2, 2, WGM, WGN, TI, TJ, DBUF, EP, HINT, PV, 3, 3>>((unsigned)blocks, 64 * WGM * WGN, 3 * (2 * TM + 2 * TN) * 64, st, a);
     }
-    return hipGetLastError();
+    return e;
 }
 
 template <int LA, int LB, int BK, int WGM, int WGN, int TI, int TJ, int NSTAGE, int ABL = 0, bool EP = false>
@@ -792,23 +732,18 @@ hipError_t launch(const QMfmaArgs& a, hipStream_t st)
     constexpr int TM = WGM * TI * 32, TN = WGN * TJ * 32;
     constexpr int STAGE = (LA * TM + LB * TN) * BK;
     const int lds = NSTAGE * STAGE;
-    static std::atomic<uint64_t> attr_done{0};   // one bit per device (qg_lds_attr)
-    if (hipError_t e = qg_lds_attr((const void*)k_mfma<LA, LB, BK, WGM, WGN, TI, TJ, NSTAGE, ABL, EP>, lds, attr_done); e != hipSuccess) return e;
     const int64_t blocks = (a.Mp / TM) * (a.Np / TN);
     if (blocks <= 0) return hipSuccess;
     if (blocks > 0x7fffffffll || a.Kp % BK || a.Mp % TM || a.Np % TN) return hipErrorInvalidValue;
     if constexpr (LA == 2 && LB == 2 && ABL == 0 && !EP) {
-        if (a.kara) {
-            static std::atomic<uint64_t> attr_done_k{0};
-            if (hipError_t e = qg_lds_attr((const void*)k_mfma<2, 2, BK, WGM, WGN, TI, TJ, NSTAGE, 0, false, 2, 2, true>, lds, attr_done_k); e != hipSuccess) return e;
-            hipLaunchKernelGGL((k_mfma<2, 2, BK, WGM, WGN, TI, TJ, NSTAGE, 0, false, 2, 2, true>), dim3((unsigned)blocks), dim3(64 * WGM * WGN), lds, st, a);
-            return hipGetLastError();
-        }
+        if (a.kara) return qg_launch_lds<k_mfma<2, 2, BK, WGM, WGN, TI, TJ, NSTAGE, 0, false, 2, 2, true>>((unsigned)blocks, 64 * WGM * WGN, lds, st, a);
     }
     if (a.kara) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((k_mfma<LA, LB, BK, WGM, WGN, TI, TJ, NSTAGE, ABL, EP>), dim3((unsigned)blocks), dim3(64 * WGM * WGN), lds, st, a);
-    if constexpr (LA == 3 && LB == 3 && ABL == 0) launch_plane_partner<BK, WGM, WGN, TI, TJ, NSTAGE, EP>(a, st, blocks);
-    return hipGetLastError();
+    const hipError_t e = qg_launch_lds<k_mfma<LA, LB, BK, WGM, WGN, TI, TJ, NSTAGE, ABL, EP>>((unsigned)blocks, 64 * WGM * WGN, lds, st, a);
+    if constexpr (LA == 3 && LB == 3 && ABL == 0) {
+        if (e == hipSuccess) return launch_plane_partner<BK, WGM, WGN, TI, TJ, NSTAGE, EP>(a, st, blocks);
+    }
+    return e;
 }
 
 // single limb, KS k groups per workgroup (see k_mfma)
@@ -819,26 +754,23 @@ hipError_t launch_ksplit(const QMfmaArgs& a, hipStream_t st)
     constexpr int STAGE = (TM + TN) * BK;
     constexpr int RED = (KS - 1) * WGM * WGN * TI * TJ * 16 * 64 * 4;
     const int lds = KS * NSTAGE * STAGE > RED ? KS * NSTAGE * STAGE : RED;
-    static std::atomic<uint64_t> attr_done{0};
-    if (hipError_t e = qg_lds_attr((const void*)k_mfma<1, 1, BK, WGM, WGN, TI, TJ, NSTAGE, 0, false, 1, 1, false, KS>, lds, attr_done); e != hipSuccess) return e;
     const int64_t blocks = (a.Mp / TM) * (a.Np / TN);
     if (blocks <= 0) return hipSuccess;
     if (blocks > 0x7fffffffll || a.Kp % (BK * KS) || a.Mp % TM || a.Np % TN || a.has_ep || a.kara) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((k_mfma<1, 1, BK, WGM, WGN, TI, TJ, NSTAGE, 0, false, 1, 1, false, KS>), dim3((unsigned)blocks), dim3(64 * WGM * WGN * KS), lds, st, a);
-    return hipGetLastError();
+    return qg_launch_lds<k_mfma<1, 1, BK, WGM, WGN, TI, TJ, NSTAGE, 0, false, 1, 1, false, KS>>((unsigned)blocks, 64 * WGM * WGN * KS, lds, st, a);
 }
 
 } // namespace
 
 QMfmaCfg qg_mfma_pick(int LA, int LB, int64_t M, int64_t N, uint32_t opt_flags)
 {
-    QMfmaCfg c = {0, 0, 0, 0};
+    QMfmaCfg c = {QG_MFMA_NONE, 0, 0, 0};
     if (LA < 1 || LB < 1 || LA > 3 || LB > 3) return c;
     if (LA == 1 && LB == 1) {
         // 256x256 tiles halve the L2->LDS traffic per MAC; use them once they fill the 256 CUs
         const int64_t big = ((M + 255) / 256) * ((N + 255) / 256);
         // two wave groups alternating on the matrix cores, 128-byte k-tiles (qg_mfma_pp.hip); QG_OPT_LOCKSTEP_TILES keeps k_mfma16
-        if (big >= 256) return (opt_flags & QG_OPT_LOCKSTEP_TILES) ? QMfmaCfg{2, 256, 256, 64} : QMfmaCfg{9, 256, 256, 128};
+        if (big >= 256) return (opt_flags & QG_OPT_LOCKSTEP_TILES) ? QMfmaCfg{QG_MFMA_256, 256, 256, 64} : QMfmaCfg{QG_MFMA_PP, 256, 256, 128};
         // small problems: 64x64 tiles once 128x128 ones would leave more than half of the 256 CUs without a workgroup
         // (1024^2: 64 -> 256 workgroups)
         const int64_t mid = ((M + 127) / 128) * ((N + 127) / 128);
@@ -848,24 +780,24 @@ QMfmaCfg qg_mfma_pick(int LA, int LB, int64_t M, int64_t N, uint32_t opt_flags)
             // one-wave-per-SIMD workgroup (~0.2 us per 64-byte k-tile whatever the ring depth), so half as many k-tiles:
             // 1024^3 5.97 -> 5.35 us, 512^2 x 4096 13.3 -> 10.2 us (profiles/r03n_small_ring.jsonl).  QG_BK64 for A/B.
             static const bool bk64 = QG_DIAG_ENV("QG_BK64");
-            return bk64 ? QMfmaCfg{5, 64, 64, 64} : QMfmaCfg{7, 64, 64, 128};
+            return bk64 ? QMfmaCfg{QG_MFMA_64, 64, 64, 64} : QMfmaCfg{QG_MFMA_64_BK128, 64, 64, 128};
         }
         {   // at most one workgroup per CU: 128-byte k-tiles here as well (2048^2 x 8192 55.3 -> 44.8 us, 1792^2 x 4096 30.8 -> 24.4 us,
             // 2048^3 15.3 -> 15.2 us); with more workgroups the 96 KB LDS image would cost co-residency.  QG_BK64 for A/B.
             static const bool bk64 = QG_DIAG_ENV("QG_BK64");
-            if (!bk64 && mid <= 256) return QMfmaCfg{8, 128, 128, 128};
+            if (!bk64 && mid <= 256) return QMfmaCfg{QG_MFMA_128_BK128, 128, 128, 128};
         }
-        return QMfmaCfg{1, 128, 128, 64};
+        return QMfmaCfg{QG_MFMA_128, 128, 128, 64};
     }
     {   // limb kernels: the same small-problem rule (1024^2 outputs: 64 -> 256 workgroups)
         static const bool no_small = QG_DIAG_ENV("QG_NO_SMALL_TILES");
         const int64_t mid = ((M + 127) / 128) * ((N + 127) / 128);
-        // 3 x 3 limbs with at least a tile per CU: the two-group kernel (qg_mfma_ppl.hip; same packed layout as variant 3)
-        // (2 x 2: unless the operands are Karatsuba-eligible, which plan_geometry decides and then returns to variant 3)
-        if (((LA == 3 && LB == 3) || (LA == 2 && LB == 2)) && mid >= 256 && !(opt_flags & QG_OPT_LOCKSTEP_TILES)) return QMfmaCfg{10, 128, 128, 64};
-        if (!no_small && mid <= 128 && ((M + 63) / 64) * ((N + 63) / 64) > mid) return QMfmaCfg{6, 64, 64, 64};
+        // 3 x 3 limbs with at least a tile per CU: the two-group kernel (qg_mfma_ppl.hip; same packed layout as QG_MFMA_LIMB_128)
+        // (2 x 2: unless the operands are Karatsuba-eligible, which plan_geometry decides and then returns to QG_MFMA_LIMB_128)
+        if (((LA == 3 && LB == 3) || (LA == 2 && LB == 2)) && mid >= 256 && !(opt_flags & QG_OPT_LOCKSTEP_TILES)) return QMfmaCfg{QG_MFMA_PPL, 128, 128, 64};
+        if (!no_small && mid <= 128 && ((M + 63) / 64) * ((N + 63) / 64) > mid) return QMfmaCfg{QG_MFMA_LIMB_64, 64, 64, 64};
     }
-    return QMfmaCfg{3, 128, 128, 64};
+    return QMfmaCfg{QG_MFMA_LIMB_128, 128, 128, 64};
 }
 
 // QG_ABLATE=1..5 selects diagnostic variants of the two benchmarked kernels (results are WRONG by construction; used only
@@ -884,14 +816,14 @@ static constexpr int ablation() { return 0; }
 
 hipError_t qg_launch_mfma(int LA, int LB, const QMfmaArgs& a_in, hipStream_t st)
 {
-    if (a_in.variant == QG_K6_VARIANT) return qg_launch_mfma_k6(a_in, st);
-    if (a_in.variant == 10 && qg_mfma_ppl_applies(LA, LB, a_in)) return qg_launch_mfma_ppl(LA, a_in, st);
+    if (a_in.variant == QG_MFMA_K6) return qg_launch_mfma_k6(a_in, st);
+    if (a_in.variant == QG_MFMA_PPL && qg_mfma_ppl_applies(LA, LB, a_in)) return qg_launch_mfma_ppl(LA, a_in, st);
     QMfmaArgs a_v3;
-    if (a_in.variant == 10) { a_v3 = a_in; a_v3.variant = 3; }   // (fused chain, narrow C: the lock-step kernel on the same packed layout)
-    const QMfmaArgs& a = a_in.variant == 10 ? a_v3 : a_in;
+    if (a_in.variant == QG_MFMA_PPL) { a_v3 = a_in; a_v3.variant = QG_MFMA_LIMB_128; }   // (fused chain, narrow C: the lock-step kernel on the same packed layout)
+    const QMfmaArgs& a = a_in.variant == QG_MFMA_PPL ? a_v3 : a_in;
 #ifdef QG_DIAG
     if (const int abl = ablation(); abl > 0 && abl < 16) {
-        if (LA == 3 && LB == 3 && a.variant == 3) {   // (the diagnostic variants exist for the 128x128-tile geometry only)
+        if (LA == 3 && LB == 3 && a.variant == QG_MFMA_LIMB_128) {   // (the diagnostic variants exist for the 128x128-tile geometry only)
             switch (abl) {
             case 1: return launch<3, 3, 64, 2, 4, 2, 1, 3, 1>(a, st);
             case 2: return launch<3, 3, 64, 2, 4, 2, 1, 3, 2>(a, st);
@@ -902,7 +834,7 @@ hipError_t qg_launch_mfma(int LA, int LB, const QMfmaArgs& a_in, hipStream_t st)
             default: return launch<3, 3, 64, 2, 4, 2, 1, 3, 5>(a, st);
             }
         }
-        if (LA == 1 && LB == 1 && a.variant == 2) {
+        if (LA == 1 && LB == 1 && a.variant == QG_MFMA_256) {
             switch (abl) {
             case 1: return launch<1, 1, 64, 2, 4, 4, 2, 3, 1>(a, st);
             case 2: return launch<1, 1, 64, 2, 4, 4, 2, 3, 2>(a, st);
@@ -917,9 +849,9 @@ hipError_t qg_launch_mfma(int LA, int LB, const QMfmaArgs& a_in, hipStream_t st)
     if (LA == 1 && LB == 1) {
         // single limb: v_mfma_i32_16x16x64_i8 measured 8 % faster than 32x32x32 at the same tiles
         // (0.283 vs 0.308 ms at 8192x8192x4096, profiles/r01n_ablation_mfma_shape.log); QG_ABLATE=32 keeps the other
-        if (a.variant == 9) return a.has_ep ? hipErrorInvalidValue : qg_launch_mfma_pp(a, st);
-        if (a.variant == 5) return launch<1, 1, 64, 2, 2, 1, 1, 3>(a, st);   // 64x64 tiles, one 32x32 MFMA tile per wave
-        if (a.variant == 7) {   // the same on 128-byte k-tiles
+        if (a.variant == QG_MFMA_PP) return a.has_ep ? hipErrorInvalidValue : qg_launch_mfma_pp(a, st);
+        if (a.variant == QG_MFMA_64) return launch<1, 1, 64, 2, 2, 1, 1, 3>(a, st);   // 64x64 tiles, one 32x32 MFMA tile per wave
+        if (a.variant == QG_MFMA_64_BK128) {   // the same on 128-byte k-tiles
             // ... with two k groups per workgroup for long-k problems of at most one workgroup per CU (diag: QG_NO_KSPLIT for A/B).
             // Measured (us, split / not split): 512^2 x 4096 9.30 / 10.20, 256^2 x 4096 9.16 / 10.03 — but 1024^3 (8 k-tiles)
             // 5.50 / 5.30, and with more than 256 workgroups the 8-wave, 96 KB workgroups no longer share a CU: 1536 x 1024^2
@@ -929,18 +861,18 @@ hipError_t qg_launch_mfma(int LA, int LB, const QMfmaArgs& a_in, hipStream_t st)
                 return launch_ksplit<128, 2, 2, 1, 1, 3, 2>(a, st);
             return launch<1, 1, 128, 2, 2, 1, 1, 3>(a, st);
         }
-        if (a.variant == 8) return launch<1, 1, 128, 2, 2, 2, 2, 3>(a, st);   // 128x128 tiles on 128-byte k-tiles
+        if (a.variant == QG_MFMA_128_BK128) return launch<1, 1, 128, 2, 2, 2, 2, 3>(a, st);   // 128x128 tiles on 128-byte k-tiles
 #ifdef QG_DIAG
-        if (ablation() == 32) return a.variant == 2 ? launch<1, 1, 64, 2, 4, 4, 2, 3>(a, st) : launch<1, 1, 64, 2, 2, 2, 2, 3>(a, st);
+        if (ablation() == 32) return a.variant == QG_MFMA_256 ? launch<1, 1, 64, 2, 4, 4, 2, 3>(a, st) : launch<1, 1, 64, 2, 2, 2, 2, 3>(a, st);
 #endif
-        if (a.variant == 2) {
+        if (a.variant == QG_MFMA_256) {
             static const bool shallow = QG_DIAG_ENV("QG_NO_DEEP");   // A/B: one k-tile in flight instead of two
             if (shallow && !a.has_ep) return launch16<1, 1, 2, 4, 8, 4, true, false, true, 0>(a, st);
             return launch16<1, 1, 2, 4, 8, 4, true>(a, st);
         }
         return launch<1, 1, 64, 2, 2, 2, 2, 3>(a, st);  // 128x128 tiles (small problems): the 32x32x32 kernel is the faster one there
     }
-    if (a.variant == 6 && !a.has_ep && !a.kara && (a.Mp / 64) * (a.Np / 64) <= 256) {
+    if (a.variant == QG_MFMA_LIMB_64 && !a.has_ep && !a.kara && (a.Mp / 64) * (a.Np / 64) <= 256) {
         // At most one workgroup per CU anyway: a 5-stage LDS ring (4 k-tiles in flight; a k-tile of these kernels is a few hundred
         // cycles, less than one trip to L2).  512^2 x 4096 int<8,8>: 39.8 -> 27.9 us; with more workgroups than CUs the ring's LDS
         // would cost co-residency (1536 x 1024 x 1024: 21.2 -> 24.4 us), and the single-limb 64x64 kernel gained nothing from it
@@ -954,7 +886,7 @@ hipError_t qg_launch_mfma(int LA, int LB, const QMfmaArgs& a_in, hipStream_t st)
             default: break;
             }
     }
-    if (a.variant == 6) {   // 64x64 tiles, 4 waves, one 32x32 MFMA tile per wave
+    if (a.variant == QG_MFMA_LIMB_64) {   // 64x64 tiles, 4 waves, one 32x32 MFMA tile per wave
         switch (LA * 10 + LB) {
         case 12: return launch<1, 2, 64, 2, 2, 1, 1, 3>(a, st);
         case 21: return launch<2, 1, 64, 2, 2, 1, 1, 3>(a, st);
@@ -967,11 +899,11 @@ hipError_t qg_launch_mfma(int LA, int LB, const QMfmaArgs& a_in, hipStream_t st)
         default: return hipErrorInvalidValue;
         }
     }
-    if (a.variant == 3 && a.kara && LA == 2 && LB == 2 && !a.has_ep) {
+    if (a.variant == QG_MFMA_LIMB_128 && a.kara && LA == 2 && LB == 2 && !a.has_ep) {
         static const bool kara32 = QG_DIAG_ENV("QG_KARA32");   // A/B: the Karatsuba kernel on 32x32x32
         if (!kara32) return launch16<2, 2, 2, 4, 4, 2, false, false, true, 1, 2, 2, true>(a, st);
     }
-    if (a.variant == 3 && !a.kara) {
+    if (a.variant == QG_MFMA_LIMB_128 && !a.kara) {
         // 128x128 limb tiles: v_mfma_i32_16x16x64_i8 with the row-step fragment pipeline (k_mfma16, DBUF = false) against
         // 32x32x32 (k_mfma) at 4096^3, same box, ms: 3x3 0.388 / 0.427, 2x3 0.290 / 0.329, 3x2 0.295 / 0.332, 2x2 0.221 / 0.232,
         // 1x3 0.194 / 0.199, 3x1 0.200 / 0.206, 1x2 0.128 / 0.176, 2x1 0.130 / 0.178 (the chip holds a higher clock on the

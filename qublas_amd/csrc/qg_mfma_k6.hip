@@ -35,34 +35,18 @@
 // the DMA ring runs across tile boundaries; both groups run a tile's epilogue at the same time.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <type_traits>
 
 #include "qg_kernels.h"
+#include "qg_mfma_tile.h"
 #include "qg_step_all.h"
 
 namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-
-#define QG_GLOBAL_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define QG_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 
 constexpr int TM = 96, TN = 128, BK = 64;
 constexpr int PLANE_A = TM * BK, PLANE_B = TN * BK;   // 6 and 8 pieces of 1 KiB
 constexpr int BUF = 3 * PLANE_A + 3 * PLANE_B;        // one k-tile: A's planes, then B's
 constexpr int NBUF = 3;
-
-__device__ __forceinline__ void tile_of(int w, int tiles_m, int tiles_n, int& tile_m, int& tile_n)
-{
-    constexpr int GM = 8;
-    const int grp = w / (GM * tiles_n);
-    const int first_m = grp * GM;
-    const int gsz = (tiles_m - first_m) < GM ? (tiles_m - first_m) : GM;
-    const int rem = w - grp * (GM * tiles_n);
-    tile_m = first_m + rem % gsz;
-    tile_n = rem / gsz;
-}
 
 // base + S00 + 2^6 c1 + 2^12 c2 + 2^18 c3 + 2^24 S22 (mod 2^64) from five unsigned 32-bit pieces: one 64-bit add and four
 // v_mad_u64_u32.  The weights pass through an empty asm so that they stay run-time scalars: written as constants hipcc turns each
@@ -91,15 +75,8 @@ __global__ __launch_bounds__(512) void k_mfma_k6(QMfmaArgs g)
 
     const int tiles_m = (int)(g.Mp / TM), tiles_n = (int)(g.Np / TN);
     const int nwg = tiles_m * tiles_n;
-    int w_first, w_step, n_my;
-    {
-        const int q = nwg / 8, r = nwg % 8, x = blockIdx.x % 8;
-        const int start = x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-        const int cnt = q + (x < r ? 1 : 0), j = blockIdx.x / 8, P = gridDim.x / 8;
-        w_first = start + j;
-        w_step = P;
-        n_my = j < cnt ? (cnt - j + P - 1) / P : 0;
-    }
+    const QTileList my = qg_tile_list(nwg, blockIdx, gridDim);   // this workgroup's tiles (qg_tile_walk.h)
+    const int n_my = my.count;
     if (n_my == 0) return;
 
     const int nk = (int)(g.Kp / BK);
@@ -111,7 +88,7 @@ __global__ __launch_bounds__(512) void k_mfma_k6(QMfmaArgs g)
     struct Cursor { const int8_t* a; const int8_t* b; int kt, ti; };
     auto cursor_at_tile = [&](int ti) {
         int tm, tn;
-        tile_of(w_first + ti * w_step, tiles_m, tiles_n, tm, tn);
+        qg_tile_of<8>(my.first + ti * my.step, tiles_m, tiles_n, tm, tn);
         return Cursor{g.A + tm * panel_a, g.B + tn * panel_b, 0, ti};
     };
     auto advance = [&](Cursor c) {
@@ -137,10 +114,9 @@ __global__ __launch_bounds__(512) void k_mfma_k6(QMfmaArgs g)
     enum { S00, S11, P01, S22, P12, P02, NACC };
     v4i acc[NACC][3][2];
     // fragment of v_mfma_i32_16x16x64_i8: lane l holds row (l & 15), bytes [16 (l >> 4), +16) of the 64-byte k-step; LDS image:
-    // 64-byte rows, chunk c of row r at slot c ^ {0,2,3,1}[(r / 4) % 4] (swz<64>, qg_mfma.hip); 48 wm + 16 i is a multiple of 16,
-    // so the slot is a lane constant
+    // 64-byte rows, chunk c of row r at slot c ^ qg_swz<64>(r); 48 wm + 16 i is a multiple of 16, so the slot is a lane constant
     const int fr = lane & 15, fq = lane >> 4;
-    const int chunk = (fq ^ ((0x78 >> (2 * (fr >> 2))) & 3)) * 16;
+    const int chunk = (fq ^ qg_swz<64>(fr)) * 16;
     const int a_lane = (wm * 48 + fr) * BK + chunk;
     const int b_lane = 3 * PLANE_A + (wn * 32 + fr) * BK + chunk;
     v4i fa[3][3], fb[3][2];   // [register set][tile]
@@ -234,7 +210,7 @@ __global__ __launch_bounds__(512) void k_mfma_k6(QMfmaArgs g)
         // epilogue: recombine the six sums into 64 bits, take the biases out with the row sums, one round + overflow, stores of 4
         // consecutive rows.  C/D of the 16x16 MFMA: col = lane & 15, rows 4 (lane >> 4) + e; packed C is column-major inside the tile
         int tile_m, tile_n;
-        tile_of(w_first + ti * w_step, tiles_m, tiles_n, tile_m, tile_n);
+        qg_tile_of<8>(my.first + ti * my.step, tiles_m, tiles_n, tile_m, tile_n);
         const QStep st = g.to_c;
         char* C = (char*)g.C;
         // packed C keeps the 128 x 128 tiling of every other limb plan (QCGeom), whatever A's row-tile pitch: a run of 4 rows lies in
@@ -280,7 +256,8 @@ __global__ __launch_bounds__(512) void k_mfma_k6(QMfmaArgs g)
             for (int j = 0; j < 2; ++j) {
                 const int col = wn * 32 + j * 16 + fr;
                 const int64_t* q = s + j * 4;
-                if (g.c_host) {   // the reference layout itself (wave-uniform choice): element (r, c) at r + c * ld
+                if (g.c_host) {   // the reference layout itself (wave-uniform choice): element (r, c) at r + c * ld.  (Written out in each of
+                    // k_mfma_pp, k_mfma_ppl and k_mfma_k6: as a shared function it moves every one of their instruction streams)
                     const int64_t gr = (int64_t)tile_m * TM + row0, gc = (int64_t)tile_n * TN + col;
                     if (gc < g.c_N) {
                         using E = std::conditional_t<CB == 4, int32_t, int64_t>;
@@ -299,13 +276,7 @@ __global__ __launch_bounds__(512) void k_mfma_k6(QMfmaArgs g)
                 const int64_t gr = (int64_t)tile_m * TM + row0;
                 if (gr >= g.Mc) continue;
                 const int64_t base = (((gr / CT) * tiles_n + tile_n) * CT + col) * CT + gr % CT;
-                if constexpr (CB == 4) {
-                    *(int4*)(C + base * 4) = make_int4((int)q[0], (int)q[1], (int)q[2], (int)q[3]);
-                } else {
-                    int64_t* p = (int64_t*)(C + base * 8);
-                    *(longlong2*)p = make_longlong2(q[0], q[1]);
-                    *(longlong2*)(p + 2) = make_longlong2(q[2], q[3]);
-                }
+                qg_store_run4<CB>(C, base, q);
             }
         }
     }
@@ -317,18 +288,14 @@ __global__ __launch_bounds__(512) void k_mfma_k6(QMfmaArgs g)
 template <bool FAST, int CB>
 hipError_t launch_k6(const QMfmaArgs& a, unsigned grid, hipStream_t st)
 {
-    constexpr int lds = NBUF * BUF;
-    static std::atomic<uint64_t> attr_done{0};   // one bit per device (qg_lds_attr)
-    if (hipError_t e = qg_lds_attr((const void*)k_mfma_k6<FAST, CB>, lds, attr_done); e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_mfma_k6<FAST, CB>), dim3(grid), dim3(512), lds, st, a);
-    return hipGetLastError();
+    return qg_launch_lds<k_mfma_k6<FAST, CB>>(grid, 512, NBUF * BUF, st, a);
 }
 
 } // namespace
 
 bool qg_mfma_k6_applies(const QMfmaArgs& a)
 {
-    if (a.has_ep || !a.kara || a.variant != 11 || !a.rsA || !a.rsB) return false;
+    if (a.has_ep || !a.kara || a.variant != QG_MFMA_K6 || !a.rsA || !a.rsB) return false;
     if (a.cbytes != 4 && a.cbytes != 8) return false;
     return a.Kp > 0 && a.Kp % BK == 0 && a.Mp % TM == 0 && a.Np % TN == 0 && a.Mc > 0 && a.Mc % 128 == 0 && a.Mc <= a.Mp + 127;
 }
@@ -339,14 +306,9 @@ hipError_t qg_launch_mfma_k6(const QMfmaArgs& a, hipStream_t st)
     const int64_t blocks = (a.Mp / TM) * (a.Np / TN);
     if (blocks <= 0) return hipSuccess;
     if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
-    int dev = 0, cus = 0;
-    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-    if (hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev); e != hipSuccess) return e;
-    int64_t grid = cus / 8 * 8;
-    if (grid < 8) grid = 8;
-    if (grid > blocks) grid = (blocks + 7) / 8 * 8;
-    const QStep& q = a.to_c;
-    const bool fast = !q.identity && q.O == QG_SAT_TCPL && q.Q == QG_TRN_TCPL && q.d >= 0;
+    unsigned grid = 0;
+    if (hipError_t e = qg_persistent_grid(blocks, &grid); e != hipSuccess) return e;
+    const bool fast = qg_step_is_shift_clamp(a.to_c);
     if (a.cbytes == 4) return fast ? launch_k6<true, 4>(a, grid, st) : launch_k6<false, 4>(a, grid, st);
     return fast ? launch_k6<true, 8>(a, grid, st) : launch_k6<false, 8>(a, grid, st);
 }

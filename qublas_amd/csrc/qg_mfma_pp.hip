@@ -28,18 +28,13 @@
 // a slot read in phase p is provably idle two intervals later, when group 0 refills it.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <type_traits>
 
 #include "qg_kernels.h"
+#include "qg_mfma_tile.h"
 #include "qg_step_all.h"
 
 namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-
-#define QG_GLOBAL_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define QG_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 
 constexpr int TM = 256, TN = 256, BK = 128;
 constexpr int HALF = 128 * BK;     // one half-tile: 128 rows of 128 bytes
@@ -47,18 +42,6 @@ constexpr int BUF = 4 * HALF;      // A[0] A[1] B[0] B[1]
 constexpr int TILE_BYTES = TM * BK;   // a (row tile, k tile) block of a packed operand
 constexpr int PP_DMA_SPLIT = 1;       // PH2: LDS-DMA pieces per wave in phase A / phase B: 0 = 4 / 4, 1 = 2 / 6 (shipped), 2 = 0 / 8
 constexpr bool PP_TWO_PHASES = true;  // k_mfma_pp's default phase structure (PH2): measured 2-6 % faster than four phases
-
-// the walk over the output tiles (as k_mfma16): groups of 8 tile rows, column by column inside a group
-__device__ __forceinline__ void tile_of(int w, int tiles_m, int tiles_n, int& tile_m, int& tile_n)
-{
-    constexpr int GM = 8;
-    const int grp = w / (GM * tiles_n);
-    const int first_m = grp * GM;
-    const int gsz = (tiles_m - first_m) < GM ? (tiles_m - first_m) : GM;
-    const int rem = w - grp * (GM * tiles_n);
-    tile_m = first_m + rem % gsz;
-    tile_n = rem / gsz;
-}
 
 // PERSIST: one workgroup per CU walks a list of tiles, and the LDS-DMA pipeline runs straight across tile boundaries — the
 // refills issued during a tile's last two k-tiles fetch the NEXT tile's first k-tiles, so there is no prologue latency, no
@@ -95,26 +78,14 @@ __global__ __launch_bounds__(512) void k_mfma_pp(QMfmaArgs g)
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wr = wave >> 2, wc = wave & 3;
 
-    // XCD-aware tile order: block ids b and b + 8 share an XCD (observed dispatch; speed only), so each of the 8 residue
-    // classes gets a contiguous run of the walk.  PERSIST: the P = gridDim.x / 8 workgroups of a class take the run's tiles
-    // round-robin, i.e. in every round a class works on P consecutive tiles of the walk (8 tile rows x P / 8 columns).
+    // XCD-aware tile order (qg_tile_walk.h).  PERSIST: this workgroup's list — in every round an XCD residue class works on
+    // gridDim.x / 8 consecutive tiles of the walk (8 tile rows x gridDim.x / 64 columns); otherwise the one tile of this block
     const int tiles_m = (int)(g.Mp / TM), tiles_n = (int)(g.Np / TN);
     const int nwg = tiles_m * tiles_n;
-    int w_first, w_step, n_my;
-    {
-        const int q = nwg / 8, r = nwg % 8, x = blockIdx.x % 8;
-        const int start = x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-        if constexpr (PERSIST) {
-            const int cnt = q + (x < r ? 1 : 0), j = blockIdx.x / 8, P = gridDim.x / 8;
-            w_first = start + j;
-            w_step = P;
-            n_my = j < cnt ? (cnt - j + P - 1) / P : 0;
-        } else {
-            w_first = start + blockIdx.x / 8;
-            w_step = 0;
-            n_my = 1;
-        }
-    }
+    QTileList my;
+    if constexpr (PERSIST) my = qg_tile_list(nwg, blockIdx, gridDim);
+    else my = QTileList{qg_xcd_block<int>((int)blockIdx.x, nwg), 0, 1};
+    const int n_my = my.count;
     if (n_my == 0) return;   // (the whole workgroup, before any barrier)
 
     const int nk = (int)(g.Kp / BK);
@@ -127,7 +98,7 @@ __global__ __launch_bounds__(512) void k_mfma_pp(QMfmaArgs g)
     struct Cursor { const int8_t* a; const int8_t* b; int kt, ti; };
     auto cursor_at_tile = [&](int ti) {
         int tm, tn;
-        tile_of(w_first + ti * w_step, tiles_m, tiles_n, tm, tn);
+        qg_tile_of<8>(my.first + ti * my.step, tiles_m, tiles_n, tm, tn);
         return Cursor{g.A + tm * panel, g.B + tn * panel, 0, ti};
     };
     auto advance = [&](Cursor c) {
@@ -156,8 +127,10 @@ __global__ __launch_bounds__(512) void k_mfma_pp(QMfmaArgs g)
     if constexpr (STAMP) stamps[threadIdx.x & 63] = 0;
 
     // fragment of v_mfma_i32_16x16x64_i8: lane l holds row (l & 15), bytes [16 (l >> 4), +16) of the 64-byte k-step.
-    // LDS image: 128-byte rows, 16-byte chunk c of row r at slot c ^ ((r >> 1) & 7) (swz<128>, qg_mfma.hip; the pack kernels
-    // write it); every row this lane reads is (a multiple of 16) + fr, so its swizzle term is a lane constant.
+    // LDS image: 128-byte rows, 16-byte chunk c of row r at slot c ^ qg_swz<128>(r); every row this lane reads is (a multiple
+    // of 16) + fr, so its swizzle term is a lane constant.  (qg_swz<128>(fr) with its mask folded into the & 7: the call itself
+    // moves two instructions of this kernel)
+    static_assert(qg_swz<128>(13) == 13 >> 1 && qg_swz<128>(255) == 7, "the lane constant below is qg_swz<128>");
     const int fr = lane & 15, fq = lane >> 4;
     const int c0 = ((fq ^ (fr >> 1)) & 7) * 16;   // k-step 0: chunk fq; k-step 1 (chunk 4 + fq): c0 ^ 64
     const int a_lane = (wr * 64 + fr) * BK + c0;
@@ -326,7 +299,7 @@ __global__ __launch_bounds__(512) void k_mfma_pp(QMfmaArgs g)
         // epilogue: one round + overflow, stored as runs of 4 rows (packed C is column-major inside the tile)
         // C/D of the 16x16 MFMA: col = lane & 15, rows 4 (lane >> 4) + e
         int tile_m, tile_n;
-        tile_of(w_first + ti * w_step, tiles_m, tiles_n, tile_m, tile_n);
+        qg_tile_of<8>(my.first + ti * my.step, tiles_m, tiles_n, tile_m, tile_n);
         const QStep st = g.to_c;
         [[maybe_unused]] const int sh = st.d;
         [[maybe_unused]] const int32_t clo = (int32_t)st.lo, chi = (int32_t)st.hi;
@@ -436,7 +409,8 @@ __global__ __launch_bounds__(512) void k_mfma_pp(QMfmaArgs g)
                         for (int u = 0; u < 2; ++u) {
                             const int col = qj * 128 + wc * 32 + u * 16 + fr;
                             const int32_t* q = s + (qj * 2 + u) * 4;
-                            if (g.c_host) {   // the reference layout itself (wave-uniform choice): element (r, c) at r + c * ld
+                            if (g.c_host) {   // the reference layout itself (wave-uniform choice): element (r, c) at r + c * ld.  (Written out in each of
+                                // k_mfma_pp, k_mfma_ppl and k_mfma_k6: as a shared function it moves every one of their instruction streams)
                                 const int64_t gr = (int64_t)tile_m * TM + row0, gc = (int64_t)tile_n * TN + col;
                                 if (gc < g.c_N) {
                                     using E = std::conditional_t<CB == 4, int32_t, int64_t>;
@@ -453,13 +427,7 @@ __global__ __launch_bounds__(512) void k_mfma_pp(QMfmaArgs g)
                                 continue;
                             }
                             const int64_t base = tile_base + (int64_t)col * TM + row0;
-                            if constexpr (CB == 4) {
-                                *(int4*)(C + base * 4) = make_int4(q[0], q[1], q[2], q[3]);
-                            } else {
-                                int64_t* p = (int64_t*)(C + base * 8);
-                                *(longlong2*)p = make_longlong2((int64_t)q[0], (int64_t)q[1]);
-                                *(longlong2*)(p + 2) = make_longlong2((int64_t)q[2], (int64_t)q[3]);
-                            }
+                            qg_store_run4<CB>(C, base, q);
                         }
                 }
         }
@@ -479,16 +447,12 @@ namespace {
 template <bool PERSIST, bool FAST, int CB, bool STAMP = false>
 hipError_t launch_pp(const QMfmaArgs& a, unsigned grid, int lds, hipStream_t st)
 {
-    static std::atomic<uint64_t> attr_done{0};   // one bit per device (qg_lds_attr)
-    if (hipError_t e = qg_lds_attr((const void*)k_mfma_pp<PERSIST, FAST, CB, STAMP>, lds, attr_done); e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_mfma_pp<PERSIST, FAST, CB, STAMP>), dim3(grid), dim3(512), lds, st, a);
-    return hipGetLastError();
+    return qg_launch_lds<k_mfma_pp<PERSIST, FAST, CB, STAMP>>(grid, 512, lds, st, a);
 }
 template <bool PERSIST, bool STAMP = false>
 hipError_t launch_pp_modes(const QMfmaArgs& a, unsigned grid, int lds, hipStream_t st)
 {
-    const QStep& q = a.to_c;
-    const bool fast = !q.identity && q.O == QG_SAT_TCPL && q.Q == QG_TRN_TCPL && q.d >= 0;
+    const bool fast = qg_step_is_shift_clamp(a.to_c);
     switch (a.cbytes) {
     case 1: return fast ? launch_pp<PERSIST, true, 1, STAMP>(a, grid, lds, st) : launch_pp<PERSIST, false, 1, STAMP>(a, grid, lds, st);
     case 2: return fast ? launch_pp<PERSIST, true, 2, STAMP>(a, grid, lds, st) : launch_pp<PERSIST, false, 2, STAMP>(a, grid, lds, st);
@@ -510,50 +474,22 @@ hipError_t qg_launch_mfma_pp(const QMfmaArgs& a, hipStream_t st)
 #ifdef QG_DIAG
     if (QG_DIAG_ENV("QG_PP_LAUNCH_PER_TILE")) return launch_pp_modes<false>(b, (unsigned)blocks, lds, st);   // A/B: one workgroup per tile
 #endif
-    // one workgroup per CU (128 KB of LDS each), a multiple of 8 so that every XCD residue class has the same number
-    int dev = 0, cus = 0;
-    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-    if (hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev); e != hipSuccess) return e;
-    int64_t grid = cus / 8 * 8;
-    if (grid < 8) grid = 8;
-    if (grid > blocks) grid = (blocks + 7) / 8 * 8;   // (fewer tiles than CUs: surplus workgroups find their list empty)
+    unsigned grid = 0;   // one workgroup per CU (128 KB of LDS each)
+    if (hipError_t e = qg_persistent_grid(blocks, &grid); e != hipSuccess) return e;
 #ifdef QG_DIAG
-    if (a.dbg) return launch_pp_modes<true, true>(b, (unsigned)grid, lds + 4096, st);
-    if (const char* dm = getenv("QG_PP_DMA")) {   // A/B: DMA pieces per phase (fast 1-byte variant only)
-        const QStep& q = a.to_c;
-        if (a.cbytes == 1 && !q.identity && q.O == QG_SAT_TCPL && q.Q == QG_TRN_TCPL && q.d >= 0) {
-            static std::atomic<uint64_t> d0{0}, d1{0}, d2{0};
+    if (a.dbg) return launch_pp_modes<true, true>(b, grid, lds + 4096, st);
+    if (a.cbytes == 1 && qg_step_is_shift_clamp(a.to_c)) {   // A/B switches of the fast 1-byte variant
+        if (const char* dm = getenv("QG_PP_DMA")) {          // DMA pieces per phase
             switch (atoi(dm)) {
-            case 0:
-                if (hipError_t er = qg_lds_attr((const void*)k_mfma_pp<true, true, 1, false, true, 0>, lds, d0); er != hipSuccess) return er;
-                hipLaunchKernelGGL((k_mfma_pp<true, true, 1, false, true, 0>), dim3((unsigned)grid), dim3(512), lds, st, b);
-                return hipGetLastError();
-            case 1:
-                if (hipError_t er = qg_lds_attr((const void*)k_mfma_pp<true, true, 1, false, true, 1>, lds, d1); er != hipSuccess) return er;
-                hipLaunchKernelGGL((k_mfma_pp<true, true, 1, false, true, 1>), dim3((unsigned)grid), dim3(512), lds, st, b);
-                return hipGetLastError();
-            case 2:
-                if (hipError_t er = qg_lds_attr((const void*)k_mfma_pp<true, true, 1, false, true, 2>, lds, d2); er != hipSuccess) return er;
-                hipLaunchKernelGGL((k_mfma_pp<true, true, 1, false, true, 2>), dim3((unsigned)grid), dim3(512), lds, st, b);
-                return hipGetLastError();
+            case 0: return qg_launch_lds<k_mfma_pp<true, true, 1, false, true, 0>>(grid, 512, lds, st, b);
+            case 1: return qg_launch_lds<k_mfma_pp<true, true, 1, false, true, 1>>(grid, 512, lds, st, b);
+            case 2: return qg_launch_lds<k_mfma_pp<true, true, 1, false, true, 2>>(grid, 512, lds, st, b);
             default: break;
             }
         }
-    }
-    if (QG_DIAG_ENV("QG_PP_PH2") || QG_DIAG_ENV("QG_PP_PH4")) {   // A/B of the phase structure (fast 1-byte variant only)
-        const QStep& q = a.to_c;
-        if (a.cbytes == 1 && !q.identity && q.O == QG_SAT_TCPL && q.Q == QG_TRN_TCPL && q.d >= 0) {
-            static std::atomic<uint64_t> d2{0}, d4{0};
-            if (QG_DIAG_ENV("QG_PP_PH2")) {
-                if (hipError_t er = qg_lds_attr((const void*)k_mfma_pp<true, true, 1, false, true>, lds, d2); er != hipSuccess) return er;
-                hipLaunchKernelGGL((k_mfma_pp<true, true, 1, false, true>), dim3((unsigned)grid), dim3(512), lds, st, b);
-            } else {
-                if (hipError_t er = qg_lds_attr((const void*)k_mfma_pp<true, true, 1, false, false>, lds, d4); er != hipSuccess) return er;
-                hipLaunchKernelGGL((k_mfma_pp<true, true, 1, false, false>), dim3((unsigned)grid), dim3(512), lds, st, b);
-            }
-            return hipGetLastError();
-        }
+        if (QG_DIAG_ENV("QG_PP_PH2")) return qg_launch_lds<k_mfma_pp<true, true, 1, false, true>>(grid, 512, lds, st, b);    // the phase structure
+        if (QG_DIAG_ENV("QG_PP_PH4")) return qg_launch_lds<k_mfma_pp<true, true, 1, false, false>>(grid, 512, lds, st, b);
     }
 #endif
-    return launch_pp_modes<true>(b, (unsigned)grid, lds, st);
+    return launch_pp_modes<true>(b, grid, lds, st);
 }

@@ -28,32 +28,16 @@
 // across tile boundaries; both groups run a tile's epilogue at the same time.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <type_traits>
 
 #include "qg_kernels.h"
+#include "qg_mfma_tile.h"
 #include "qg_step_all.h"
 
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-
-#define QG_GLOBAL_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define QG_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
-
 constexpr int TM = 128, TN = 128, BK = 64;
 constexpr int PLANE = TM * BK;   // one limb plane of a (row tile, k tile) block: 128 rows x 64 bytes = 8 pieces of 1 KiB
-
-__device__ __forceinline__ void tile_of(int w, int tiles_m, int tiles_n, int& tile_m, int& tile_n)
-{
-    constexpr int GM = 8;
-    const int grp = w / (GM * tiles_n);
-    const int first_m = grp * GM;
-    const int gsz = (tiles_m - first_m) < GM ? (tiles_m - first_m) : GM;
-    const int rem = w - grp * (GM * tiles_n);
-    tile_m = first_m + rem % gsz;
-    tile_n = rem / gsz;
-}
 
 // LA x LB limbs computed, SA x SB planes stored per operand (3 x 3 storage with empty third planes runs as 2 x 2: plane masks,
 // k_mfma_ppl below).  FAST: truncation (TRN::TCPL, right shift d >= 0) + SAT::TCPL as a 64-bit shift and a clamp; otherwise the
@@ -71,15 +55,12 @@ __device__ __forceinline__ void ppl_body(const QMfmaArgs& g)
 
     const int tiles_m = (int)(g.Mp / TM), tiles_n = (int)(g.Np / TN);
     const int nwg = tiles_m * tiles_n;
-    int w_first, w_step, n_my;
-    {
-        const int q = nwg / 8, r = nwg % 8, x = blockIdx.x % 8;
-        const int start = x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-        const int cnt = q + (x < r ? 1 : 0), j = blockIdx.x / 8, P = gridDim.x / 8;
-        w_first = start + j;
-        w_step = P;
-        n_my = j < cnt ? (cnt - j + P - 1) / P : 0;
-    }
+    // this workgroup's tiles: qg_tile_list(nwg, blockIdx, gridDim) written out (the call moves k_mfma_ppl's instruction stream)
+    const int q = nwg / 8, r = nwg % 8, x = blockIdx.x % 8;
+    const int start = qg_xcd_run_start<int>(nwg, x);
+    const int cnt = q + (x < r ? 1 : 0), j = blockIdx.x / 8, P = gridDim.x / 8;
+    const QTileList my{start + j, P, j < cnt ? (cnt - j + P - 1) / P : 0};
+    const int n_my = my.count;
     if (n_my == 0) return;
 
     const int nk = (int)(g.Kp / BK);
@@ -89,7 +70,7 @@ __device__ __forceinline__ void ppl_body(const QMfmaArgs& g)
     struct Cursor { const int8_t* a; const int8_t* b; int kt, ti; };
     auto cursor_at_tile = [&](int ti) {
         int tm, tn;
-        tile_of(w_first + ti * w_step, tiles_m, tiles_n, tm, tn);
+        qg_tile_of<8>(my.first + ti * my.step, tiles_m, tiles_n, tm, tn);
         return Cursor{g.A + tm * panel_a, g.B + tn * panel_b, 0, ti};
     };
     auto advance = [&](Cursor c) {
@@ -106,9 +87,9 @@ __device__ __forceinline__ void ppl_body(const QMfmaArgs& g)
 
     v4i acc[NW][4][2];
     // fragment of v_mfma_i32_16x16x64_i8: lane l holds row (l & 15), bytes [16 (l >> 4), +16) of the 64-byte k-step; LDS image:
-    // 64-byte rows, chunk c of row r at slot c ^ {0,2,3,1}[(r / 4) % 4] (swz<64>, qg_mfma.hip) — a lane constant here
+    // 64-byte rows, chunk c of row r at slot c ^ qg_swz<64>(r) — a lane constant here (every row read is a multiple of 16 + fr)
     const int fr = lane & 15, fq = lane >> 4;
-    const int chunk = (fq ^ ((0x78 >> (2 * (fr >> 2))) & 3)) * 16;
+    const int chunk = (fq ^ qg_swz<64>(fr)) * 16;
     const int a_lane = (wm * 64 + fr) * BK + chunk;
     const int b_lane = LA * PLANE + (wn * 32 + fr) * BK + chunk;
     v4i fa[4], fb[LB][2];
@@ -227,7 +208,7 @@ __device__ __forceinline__ void ppl_body(const QMfmaArgs& g)
         // epilogue: recombine the limb weights in 64 bits, one round + overflow, stores of 4 consecutive rows
         // C/D of the 16x16 MFMA: col = lane & 15, rows 4 (lane >> 4) + e; packed C is column-major inside the tile
         int tile_m, tile_n;
-        tile_of(w_first + ti * w_step, tiles_m, tiles_n, tile_m, tile_n);
+        qg_tile_of<8>(my.first + ti * my.step, tiles_m, tiles_n, tile_m, tile_n);
         const QStep st = g.to_c;
         char* C = (char*)g.C;
         const int64_t tile_base = ((int64_t)tile_m * tiles_n + tile_n) * TM * TN;
@@ -261,7 +242,8 @@ __device__ __forceinline__ void ppl_body(const QMfmaArgs& g)
             for (int j = 0; j < 2; ++j) {
                 const int col = wn * 32 + j * 16 + fr;
                 const int64_t* q = s + j * 4;
-                if (g.c_host) {   // the reference layout itself (wave-uniform choice): element (r, c) at r + c * ld
+                if (g.c_host) {   // the reference layout itself (wave-uniform choice): element (r, c) at r + c * ld.  (Written out in each of
+                    // k_mfma_pp, k_mfma_ppl and k_mfma_k6: as a shared function it moves every one of their instruction streams)
                     const int64_t gr = (int64_t)tile_m * TM + row0, gc = (int64_t)tile_n * TN + col;
                     if (gc < g.c_N) {
                         using E = std::conditional_t<CB == 4, int32_t, int64_t>;
@@ -278,13 +260,7 @@ __device__ __forceinline__ void ppl_body(const QMfmaArgs& g)
                     continue;
                 }
                 const int64_t base = tile_base + (int64_t)col * TM + row0;
-                if constexpr (CB == 4) {
-                    *(int4*)(C + base * 4) = make_int4((int)q[0], (int)q[1], (int)q[2], (int)q[3]);
-                } else {
-                    int64_t* p = (int64_t*)(C + base * 8);
-                    *(longlong2*)p = make_longlong2(q[0], q[1]);
-                    *(longlong2*)(p + 2) = make_longlong2(q[2], q[3]);
-                }
+                qg_store_run4<CB>(C, base, q);
             }
         }
     }
@@ -316,27 +292,18 @@ __global__ __launch_bounds__(512) void k_mfma_ppl22(QMfmaArgs g)
 template <bool FAST, int CB>
 hipError_t launch_ppl22(const QMfmaArgs& a, unsigned grid, hipStream_t st)
 {
-    constexpr int lds = 2 * 4 * PLANE;
-    static std::atomic<uint64_t> attr_done{0};   // one bit per device (qg_lds_attr)
-    if (hipError_t e = qg_lds_attr((const void*)k_mfma_ppl22<FAST, CB>, lds, attr_done); e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_mfma_ppl22<FAST, CB>), dim3(grid), dim3(512), lds, st, a);
-    return hipGetLastError();
+    return qg_launch_lds<k_mfma_ppl22<FAST, CB>>(grid, 512, 2 * 4 * PLANE, st, a);
 }
 
 template <bool FAST, int CB>
 hipError_t launch_ppl(const QMfmaArgs& a, unsigned grid, hipStream_t st)
 {
-    constexpr int lds = 2 * 6 * PLANE;   // the 3 x 3 path's two buffers
-    static std::atomic<uint64_t> attr_done{0};   // one bit per device (qg_lds_attr)
-    if (hipError_t e = qg_lds_attr((const void*)k_mfma_ppl<FAST, CB>, lds, attr_done); e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_mfma_ppl<FAST, CB>), dim3(grid), dim3(512), lds, st, a);
-    return hipGetLastError();
+    return qg_launch_lds<k_mfma_ppl<FAST, CB>>(grid, 512, 2 * 6 * PLANE, st, a);   // the 3 x 3 path's two buffers
 }
 
 hipError_t launch_ppl_modes(int limbs, const QMfmaArgs& a, unsigned grid, hipStream_t st)
 {
-    const QStep& q = a.to_c;
-    const bool fast = !q.identity && q.O == QG_SAT_TCPL && q.Q == QG_TRN_TCPL && q.d >= 0;
+    const bool fast = qg_step_is_shift_clamp(a.to_c);
     if (limbs == 2) {
         if (a.cbytes == 4) return fast ? launch_ppl22<true, 4>(a, grid, st) : launch_ppl22<false, 4>(a, grid, st);
         if (a.cbytes == 8) return fast ? launch_ppl22<true, 8>(a, grid, st) : launch_ppl22<false, 8>(a, grid, st);
@@ -351,7 +318,7 @@ hipError_t launch_ppl_modes(int limbs, const QMfmaArgs& a, unsigned grid, hipStr
 
 bool qg_mfma_ppl_applies(int LA, int LB, const QMfmaArgs& a)
 {
-    if (!((LA == 3 && LB == 3) || (LA == 2 && LB == 2)) || a.has_ep || a.kara || a.variant != 10) return false;
+    if (!((LA == 3 && LB == 3) || (LA == 2 && LB == 2)) || a.has_ep || a.kara || a.variant != QG_MFMA_PPL) return false;
     if (a.cbytes != 4 && a.cbytes != 8) return false;
     return (a.Mp / TM) * (a.Np / TN) >= 256;   // persistent: one workgroup per CU with at least a tile each
 }
@@ -361,11 +328,7 @@ hipError_t qg_launch_mfma_ppl(int limbs, const QMfmaArgs& a, hipStream_t st)
     const int64_t blocks = (a.Mp / TM) * (a.Np / TN);
     if (blocks <= 0) return hipSuccess;
     if (blocks > 0x7fffffffll || a.Kp % BK || a.Mp % TM || a.Np % TN) return hipErrorInvalidValue;
-    int dev = 0, cus = 0;
-    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-    if (hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev); e != hipSuccess) return e;
-    int64_t grid = cus / 8 * 8;
-    if (grid < 8) grid = 8;
-    if (grid > blocks) grid = (blocks + 7) / 8 * 8;
-    return launch_ppl_modes(limbs, a, (unsigned)grid, st);
+    unsigned grid = 0;
+    if (hipError_t e = qg_persistent_grid(blocks, &grid); e != hipSuccess) return e;
+    return launch_ppl_modes(limbs, a, grid, st);
 }

@@ -26,19 +26,14 @@
 // three stages — taken wherever they fit, LA + LB <= 6 — keep two in flight with a counted wait.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <utility>
 
 #include "qg_kernels.h"
+#include "qg_mfma_tile.h"
 #include "qg_ring.h"
 #include "qg_step_all.h"
 
 namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-
-#define QG_GLOBAL_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define QG_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 
 constexpr int BK = QG_RING_BK, TM = QG_RING_TM, TN = QG_RING_TN;
 constexpr int WGM = 2, WGN = 4, TI = 4, TJ = 2, NWAVES = WGM * WGN;
@@ -53,17 +48,6 @@ constexpr int ring_np(int LA, int LB, int L)
     return c;
 }
 constexpr int ring_stages(int LA, int LB) { return 3 * (LA * TM + LB * TN) * BK <= LDS_MAX ? 3 : 2; }
-
-// chunk c (16 B) of row r of a 64-byte-row LDS image sits at slot c ^ swz64(r) (qg_mfma.hip: swz<64>; k_pack applies the same)
-__device__ __forceinline__ int swz64(int r) { return (0x78 >> (2 * ((r >> 2) & 3))) & 3; }
-
-// one MFMA, then its share of NVM LDS-DMA issues (sched_group_barrier masks: 0x008 MFMA, 0x020 VMEM read): the issues are spread
-// between the MFMAs of the basic block instead of a burst in front of them (qg_mfma.hip: interleave_hint)
-template <int NM, int NVM, int... M>
-__device__ __forceinline__ void spread_dma(std::integer_sequence<int, M...>)
-{
-    ((__builtin_amdgcn_sched_group_barrier(0x008, 1, 0), __builtin_amdgcn_sched_group_barrier(0x020, (M + 1) * NVM / NM - M * NVM / NM, 0)), ...);
-}
 
 // LA, LB: limb planes of A, B;  L: weights kept (digits of the ring, at most LA + LB - 1: beyond that no product exists)
 template <int LA, int LB, int L>
@@ -80,20 +64,11 @@ __global__ __launch_bounds__(64 * NWAVES) void k_mfma_ring(QRingArgs g)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wm = wave / WGN, wn = wave % WGN;
-    // XCD-aware tile order (k_mfma16): a contiguous run of tiles per XCD, walked in column-major groups of 8 tile rows
+    // XCD-aware tile order (qg_tile_walk.h): a contiguous run of tiles per XCD, walked in column-major groups of 8 tile rows
     const int tiles_m = (int)(g.Mp / TM), tiles_n = (int)(g.Np / TN);
     const int nwg = tiles_m * tiles_n;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg / 8, r = nwg % 8, x = bid % 8;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + bid / 8;
-    }
-    constexpr int GM = 8;
-    const int grp = bid / (GM * tiles_n);
-    const int first_m = grp * GM;
-    const int gsz = (tiles_m - first_m) < GM ? (tiles_m - first_m) : GM;
-    const int tile_m = first_m + (bid % (GM * tiles_n)) % gsz;
-    const int tile_n = (bid % (GM * tiles_n)) / gsz;
+    int tile_m, tile_n;
+    qg_tile_of<8, true>(qg_xcd_block<int>(blockIdx.x, nwg), tiles_m, tiles_n, tile_m, tile_n);
 
     const int nk = (int)(g.Kp / BK);
     const int8_t* Ag = g.A + (int64_t)tile_m * nk * A_BYTES + lane * 16;
@@ -123,13 +98,14 @@ __global__ __launch_bounds__(64 * NWAVES) void k_mfma_ring(QRingArgs g)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) acc[w][i][j][e] = 0;
 
-    // fragment of v_mfma_i32_16x16x64_i8: lane l holds row (l & 15), bytes [16 (l >> 4), +16) of the 64-byte k-step
+    // fragment of v_mfma_i32_16x16x64_i8: lane l holds row (l & 15), bytes [16 (l >> 4), +16) of the 64-byte k-step; chunk c of
+    // row r sits at slot c ^ qg_swz<BK>(r), and every row read is (a multiple of 16) + fr: the swizzle of fr
     const int fr = lane & 15, fq = lane >> 4;
     v4i pa[2][LA], pb[2][LB][TJ];
     auto load_a = [&](int buf, const char* sA, int i) {
         const int ra = (wm * TI + i) * 16 + fr;
 #pragma unroll
-        for (int l = 0; l < LA; ++l) pa[buf][l] = *(const v4i*)(sA + (l * TM + ra) * BK + ((fq ^ swz64(ra)) * 16));
+        for (int l = 0; l < LA; ++l) pa[buf][l] = *(const v4i*)(sA + (l * TM + ra) * BK + ((fq ^ qg_swz<BK>(fr)) * 16));
     };
     auto load_b = [&](int buf, const char* sA) {
         const char* sB = sA + A_BYTES;
@@ -137,7 +113,7 @@ __global__ __launch_bounds__(64 * NWAVES) void k_mfma_ring(QRingArgs g)
         for (int j = 0; j < TJ; ++j) {
             const int rb = (wn * TJ + j) * 16 + fr;
 #pragma unroll
-            for (int l = 0; l < LB; ++l) pb[buf][l][j] = *(const v4i*)(sB + (l * TN + rb) * BK + ((fq ^ swz64(rb)) * 16));
+            for (int l = 0; l < LB; ++l) pb[buf][l][j] = *(const v4i*)(sB + (l * TN + rb) * BK + ((fq ^ qg_swz<BK>(fr)) * 16));
         }
     };
     constexpr int NM = ring_np(LA, LB, L) * TJ;   // MFMAs of one row step
@@ -189,7 +165,7 @@ __global__ __launch_bounds__(64 * NWAVES) void k_mfma_ring(QRingArgs g)
                         __builtin_amdgcn_sched_barrier(0);
                         issue(cur, k + NSTAGE);           // the stage of tile k itself: nobody reads it again
                         mfmas(i, h);
-                        spread_dma<NM, PPW>(std::make_integer_sequence<int, NM>{});
+                        interleave_hint<NM, 0, PPW>(std::make_integer_sequence<int, NM>{});
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 }
@@ -226,7 +202,7 @@ __global__ __launch_bounds__(64 * NWAVES) void k_mfma_ring(QRingArgs g)
             const int col = (wn * TJ + j) * 16 + fr;
             const int64_t base = tile_base + (int64_t)col * TM + row0;
             const int64_t* q = s + j * 4;
-            switch (g.cbytes) {
+            switch (g.cbytes) {   // (written out, not qg_store_run4 with a run-time container size: as a function it moves this kernel's instruction stream)
             case 1:
                 *(uint32_t*)(C + base) = (uint32_t)(q[0] & 0xff) | ((uint32_t)(q[1] & 0xff) << 8) | ((uint32_t)(q[2] & 0xff) << 16) | ((uint32_t)(q[3] & 0xff) << 24);
                 break;
@@ -251,11 +227,8 @@ template <int LA, int LB, int L>
 hipError_t launch_ring(const QRingArgs& a, hipStream_t st)
 {
     constexpr int lds = ring_stages(LA, LB) * (LA * TM + LB * TN) * BK;
-    static std::atomic<uint64_t> attr_done{0};   // one bit per device (qg_lds_attr)
-    if (hipError_t e = qg_lds_attr((const void*)k_mfma_ring<LA, LB, L>, lds, attr_done); e != hipSuccess) return e;
     const int64_t blocks = (a.Mp / TM) * (a.Np / TN);
-    hipLaunchKernelGGL((k_mfma_ring<LA, LB, L>), dim3((unsigned)blocks), dim3(64 * NWAVES), lds, st, a);
-    return hipGetLastError();
+    return qg_launch_lds<k_mfma_ring<LA, LB, L>>((unsigned)blocks, 64 * NWAVES, lds, st, a);
 }
 
 } // namespace

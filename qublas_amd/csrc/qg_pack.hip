@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "qg_kernels.h"
+#include "qg_tile_walk.h"
 
 namespace {
 
@@ -79,9 +80,7 @@ __device__ __forceinline__ unsigned put_packed(const QPackedGeom& p, char* dst, 
         r += (int64_t)part * p.rows_p;
         const int64_t nk = p.K_p / p.bk;
         const int rl = (int)(r % p.tr), kl = (int)(k % p.bk);
-        const int cpr = p.bk / 16, rpb = 256 / p.bk;
-        int sw = (rl / rpb) % cpr;
-        if (p.bk == 64) sw = (0x78 >> (2 * sw)) & 3;  // the kernels' swz<64>(): {0,2,3,1}
+        const int sw = qg_swz(p.bk, rl);
         const int slot = (kl / 16) ^ sw;
         const int64_t blk = ((r / p.tr) * nk + k / p.bk) * p.limbs;
         if (p.digit6) {   // Karatsuba layout: unsigned base-64 digits of the (already biased, non-negative) value
@@ -187,7 +186,7 @@ __global__ __launch_bounds__(256) void k_pack_limb32(QOperandGeom g, QPackedGeom
         }
     }
     const int rl = (int)(r % p.tr);
-    // the kernels' swz<BK>(): 64-byte rows {0,2,3,1}[(row / 4) % 4], 128-byte rows (row / 2) % 8
+    // qg_swz<64>(rl) : qg_swz<128>(rl) spelled with shifts (rl >= 0): the calls divide a signed row, which moves this kernel's code
     const int sw = p.bk == 64 ? (0x78 >> (2 * ((rl >> 2) & 3))) & 3 : (rl >> 1) & 7;
     const int c = p.bk == 64 ? kc : (tk & 1) * 4 + kc;   // 16-byte chunk of this thread inside its k-tile
     const int64_t blk = ((r / p.tr) * (p.K_p / p.bk) + (p.bk == 64 ? tk : tk >> 1)) * p.limbs;

@@ -23,6 +23,7 @@
 #include "qg_forms.h"
 #include "qg_kernels.h"
 #include "qg_step_all.h"
+#include "qg_tile_walk.h"
 
 namespace {
 
@@ -203,18 +204,12 @@ __global__ __launch_bounds__(256, ((cplx_dense_waves<MODE, TF>) ? (MAXL == 12 ? 
     const QTreeTable* __restrict__ tab = g.tab;
     const int tid = threadIdx.x;
     const int tx = tid & 15, ty = tid >> 4;
-    // XCD-aware block order (blocks b and b+8 share an XCD and its L2): every XCD gets a contiguous run of
-    // tiles, walked column-major in groups of 16 tile rows, so neighbouring blocks re-use A rows and B columns in L2
+    // XCD-aware block order (qg_tile_walk.h): every XCD gets a contiguous run of tiles, walked column-major in groups of 16
+    // tile rows, so neighbouring blocks re-use A rows and B columns in L2
     const int64_t tiles_n = (g.N + TNB - 1) / TNB, tiles_m = (g.M + TMB - 1) / TMB;
-    int64_t bid = blockIdx.x;
-    {
-        const int64_t nwg = tiles_m * tiles_n, q = nwg / 8, r = nwg % 8, x = bid % 8;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + bid / 8;
-    }
-    constexpr int64_t GMT = 16;
-    const int64_t grp = bid / (GMT * tiles_n), first_m = grp * GMT;
-    const int64_t gsz = (tiles_m - first_m) < GMT ? (tiles_m - first_m) : GMT;
-    const int64_t m0 = (first_m + (bid % (GMT * tiles_n)) % gsz) * TMB, n0 = ((bid % (GMT * tiles_n)) / gsz) * TNB;
+    int64_t tile_m, tile_n;
+    qg_tile_of<16, true>(qg_xcd_block<int64_t>(blockIdx.x, tiles_m * tiles_n), tiles_m, tiles_n, tile_m, tile_n);
+    const int64_t m0 = tile_m * TMB, n0 = tile_n * TNB;
     const int nl = tab->n_levels_k;   // (a tree shorter than 5 levels is continued with identity levels: qg_plan.h)
     // QCF_UNIFORM ("one clamp for the whole loop", qg_plan.cpp): ONE range for every value of the k loop and no shift / rounding at the
     // sums and the tree nodes: the bounds and the products' (addend, shift) live in registers for the whole launch; the products'
@@ -554,15 +549,9 @@ __global__ __launch_bounds__(256, 3) void k_tree_cplx_pk16(QTreeCplxArgs g)
     const int tid = threadIdx.x;
     const int tx = tid & 15, ty = tid >> 4;
     const int64_t tiles_n = (g.N + TNB - 1) / TNB, tiles_m = (g.M + TM16 - 1) / TM16;
-    int64_t bid = blockIdx.x;
-    {   // XCD-aware block order, as k_tree_cplx
-        const int64_t nwg = tiles_m * tiles_n, q = nwg / 8, r = nwg % 8, x = bid % 8;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + bid / 8;
-    }
-    constexpr int64_t GMT = 16;
-    const int64_t grp = bid / (GMT * tiles_n), first_m = grp * GMT;
-    const int64_t gsz = (tiles_m - first_m) < GMT ? (tiles_m - first_m) : GMT;
-    const int64_t m0 = (first_m + (bid % (GMT * tiles_n)) % gsz) * TM16, n0 = ((bid % (GMT * tiles_n)) / gsz) * TNB;
+    int64_t tile_m, tile_n;   // XCD-aware block order (qg_tile_walk.h), as k_tree_cplx
+    qg_tile_of<16, true>(qg_xcd_block<int64_t>(blockIdx.x, tiles_m * tiles_n), tiles_m, tiles_n, tile_m, tile_n);
+    const int64_t m0 = tile_m * TM16, n0 = tile_n * TNB;
     const int nl = tab->n_levels_k;
     const int s16 = tab->lj16.s;
     const int m1 = (0xffff << s16) & 0xffff, mask2 = m1 | (m1 << 16);

@@ -20,6 +20,7 @@
 #include "qg_fix.h"
 #include "qg_forms.h"
 #include "qg_kernels.h"
+#include "qg_tile_walk.h"
 
 namespace {
 
@@ -225,14 +226,11 @@ __global__ __launch_bounds__(256) void k_tree_fast(QTreeFastArgs g)
     const QTreeTable* __restrict__ tab = g.tab;
     const int tid = threadIdx.x;
     const int tx = tid & 15, ty = tid >> 4;
-    // XCD-aware block order (blocks b and b+8 share an XCD and its L2): every XCD gets a contiguous run of
-    // tiles, walked column-major in groups of 16 tile rows, so neighbouring blocks re-use A rows and B columns in L2
+    // XCD-aware block order (qg_tile_walk.h): every XCD gets a contiguous run of tiles, walked column-major in groups of 16
+    // tile rows, so neighbouring blocks re-use A rows and B columns in L2
     const int64_t tiles_n = (g.N + TNB - 1) / TNB, tiles_m = (g.M + TMB - 1) / TMB;
-    int64_t bid = blockIdx.x;
-    {
-        const int64_t nwg = tiles_m * tiles_n, q = nwg / 8, r = nwg % 8, x = bid % 8;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + bid / 8;
-    }
+    // (the group walk is qg_tile_of<16, true> written out: the call moves the instruction stream of two instantiations)
+    const int64_t bid = qg_xcd_block<int64_t>(blockIdx.x, tiles_m * tiles_n);
     constexpr int64_t GMT = 16;
     const int64_t grp = bid / (GMT * tiles_n), first_m = grp * GMT;
     const int64_t gsz = (tiles_m - first_m) < GMT ? (tiles_m - first_m) : GMT;
@@ -565,15 +563,9 @@ __global__ __launch_bounds__(256) void k_tree_pk16(QTreeFastArgs g)
     const int tid = threadIdx.x;
     const int tx = tid & 15, ty = tid >> 4;
     const int64_t tiles_n = (g.N + TNB - 1) / TNB, tiles_m = (g.M + TMB - 1) / TMB;
-    int64_t bid = blockIdx.x;
-    {   // XCD-aware block order, as k_tree_fast
-        const int64_t nwg = tiles_m * tiles_n, q = nwg / 8, r = nwg % 8, x = bid % 8;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + bid / 8;
-    }
-    constexpr int64_t GMT = 16;
-    const int64_t grp = bid / (GMT * tiles_n), first_m = grp * GMT;
-    const int64_t gsz = (tiles_m - first_m) < GMT ? (tiles_m - first_m) : GMT;
-    const int64_t m0 = (first_m + (bid % (GMT * tiles_n)) % gsz) * TMB, n0 = ((bid % (GMT * tiles_n)) / gsz) * TNB;
+    int64_t tile_m, tile_n;   // XCD-aware block order (qg_tile_walk.h), as k_tree_fast
+    qg_tile_of<16, true>(qg_xcd_block<int64_t>(blockIdx.x, tiles_m * tiles_n), tiles_m, tiles_n, tile_m, tile_n);
+    const int64_t m0 = tile_m * TMB, n0 = tile_n * TNB;
     const int nl = tab->n_levels_k;
     const int s16 = HYB ? tab->lj.s - 16 : tab->lj16.s, ea = HYB ? tab->lj.e[0] : tab->lj16.e[0], eb = HYB ? tab->lj.e[1] : tab->lj16.e[1];
     const int m1 = (0xffff << s16) & 0xffff, mask2 = m1 | (m1 << 16);
