@@ -14,9 +14,15 @@
 // 6 sets x 6 tiles x 4 = 144 accumulator registers.  All three digit planes of a k-tile are held in registers (3 x (12 + 8) = 60)
 // and the three sums are formed IN PLACE, so a k-tile is ONE phase:
 //     LOAD : 15 ds_read_b128 (d0, e0, d1, e1, d2, e2); 6 LDS-DMA issues; vmcnt(6); lgkmcnt(0); s_barrier
+//            No vector ALU instruction: the two LDS read addresses are carried in registers, and a DMA address is a scalar base
+//            (cursor + piece) beside the lane's 32-bit offset.  The partner on the SIMD is in its MFMA interval at priority 1,
+//            and a vector instruction beside it waits for an issue slot.
 //     MFMA : S00, S11, S22 (18 MFMAs on the plain digits), and beside them on the vector pipe
-//            d1 += d2 -> P12;   d1 += d0 - d2 (= d0 + d1; at most 189 in a byte on the way, still no carry) -> P01;   d0 += d2 -> P02;
-//            36 MFMAs and 80 v_add / v_sub per wave;                                                     s_barrier
+//            d1 += d2 -> P12;   d1 += d0 - d2 (= d0 + d1; hipcc forms the pairwise sum directly) -> P01;   d0 += d2 -> P02;
+//            36 MFMAs, 60 v_add_u32 and the two adds that move the LDS read addresses on to the next k-tile, in a FIXED issue
+//            order (paced_valu_hint, qg_mfma_tile.h): 31 x (one MFMA, two adds), then 5 MFMAs.  The interval opens with an MFMA,
+//            no run of adds outlasts the issue slots a 16-cycle MFMA leaves free, and every sum is formed at least one MFMA
+//            ahead of the MFMA that reads it (no s_nop).                                                      s_barrier
 // and waves 4-7 run one barrier interval behind waves 0-3: on every SIMD one wave feeds the matrix pipe while its partner reads
 // LDS and issues DMA.  (The first version walked a k-tile in two phases of 18 MFMAs with the sums formed in the LOAD intervals
 // and A's 18 pieces rounded up to 24 issues: 0.364 ms at 4096^3, no faster than the nine products; a LOAD interval — reads, their
@@ -81,7 +87,8 @@ __global__ __launch_bounds__(512) void k_mfma_k6(QMfmaArgs g)
 
     const int nk = (int)(g.Kp / BK);
     const int64_t panel_a = (int64_t)nk * 3 * PLANE_A, panel_b = (int64_t)nk * 3 * PLANE_B;
-    const uint32_t lane16 = (uint32_t)(lane * 16);
+    // lane offsets of the DMA sources: 32-bit, in one register each, beside a scalar base (c.a + piece): global_load_lds v, s[..]
+    uint32_t lane16 = (uint32_t)(lane * 16), lane4 = (uint32_t)(lane * 4);
     // this wave's pieces (byte offsets inside a k-tile block of A / of B; the LDS image has the same order)
     const int pa0 = wave * 1024, pa1 = (8 + wave) * 1024, pa2 = 16 * 1024 + wave * 256;   // (pa2: a quarter piece, 4 bytes per lane)
     const int pb0 = wave * 1024, pb1 = (8 + wave) * 1024, pb2 = (16 + wave) * 1024;
@@ -108,7 +115,7 @@ __global__ __launch_bounds__(512) void k_mfma_k6(QMfmaArgs g)
         issue_b(buf_off, pb1, c);
         issue_a(buf_off, pa1, c);
         issue_b(buf_off, pb2, c);
-        __builtin_amdgcn_global_load_lds(QG_GLOBAL_PTR(c.a + pa2 + lane * 4), QG_LDS_PTR(smem + buf_off + pa2), 4, 0, 0);
+        __builtin_amdgcn_global_load_lds(QG_GLOBAL_PTR(c.a + pa2 + lane4), QG_LDS_PTR(smem + buf_off + pa2), 4, 0, 0);
     };
 
     enum { S00, S11, P01, S22, P12, P02, NACC };
@@ -120,11 +127,16 @@ __global__ __launch_bounds__(512) void k_mfma_k6(QMfmaArgs g)
     const int a_lane = (wm * 48 + fr) * BK + chunk;
     const int b_lane = 3 * PLANE_A + (wn * 32 + fr) * BK + chunk;
     v4i fa[3][3], fb[3][2];   // [register set][tile]
-    auto read_ab = [&](int buf_off, int plane, int set) {
+    // the two LDS read addresses of the k-tile to come (buffer + a_lane, buffer + b_lane) are carried in registers: a wave moves
+    // them on at the end of its MFMA interval, so that its LOAD interval holds no vector ALU instruction
+    typedef const __attribute__((address_space(3))) v4i* LdsFrag;
+    const uint32_t lds0 = (uint32_t)(uintptr_t)QG_LDS_PTR(smem);
+    uint32_t rd_a = lds0 + a_lane, rd_b = lds0 + b_lane;
+    auto read_ab = [&](int plane, int set) {
 #pragma unroll
-        for (int i = 0; i < 3; ++i) fa[set][i] = *(const v4i*)(smem + buf_off + plane * PLANE_A + i * (16 * BK) + a_lane);
+        for (int i = 0; i < 3; ++i) fa[set][i] = *(LdsFrag)(uintptr_t)(rd_a + plane * PLANE_A + i * (16 * BK));
 #pragma unroll
-        for (int j = 0; j < 2; ++j) fb[set][j] = *(const v4i*)(smem + buf_off + plane * PLANE_B + j * (16 * BK) + b_lane);
+        for (int j = 0; j < 2; ++j) fb[set][j] = *(LdsFrag)(uintptr_t)(rd_b + plane * PLANE_B + j * (16 * BK));
     };
     auto product = [&](int s, int set) {
 #pragma unroll
@@ -172,9 +184,10 @@ __global__ __launch_bounds__(512) void k_mfma_k6(QMfmaArgs g)
         __builtin_amdgcn_sched_barrier(0);
 
         for (int kt = 0; kt < nk; ++kt) {
-            read_ab(cur, 0, 0);
-            read_ab(cur, 1, 1);
-            read_ab(cur, 2, 2);
+            asm volatile("" : "+v"(lane16), "+v"(lane4));   // (no instruction: keeps the zero-extension of the offsets in this block)
+            read_ab(0, 0);
+            read_ab(1, 1);
+            read_ab(2, 2);
             issue_tile(fill, nxt);
             QG_LOAD_DONE(asm volatile("s_waitcnt vmcnt(6)" ::: "memory"));   // this wave's share of k-tile kt+1 is in
             __builtin_amdgcn_s_setprio(1);
@@ -198,11 +211,15 @@ __global__ __launch_bounds__(512) void k_mfma_k6(QMfmaArgs g)
 #pragma unroll
             for (int j = 0; j < 2; ++j) fb[0][j] += fb[2][j];
             product(P02, 0);
+            const int t = cur, step = cur + BUF == NBUF * BUF ? -(NBUF - 1) * BUF : BUF;
+            cur += step;
+            fill = t;
+            rd_a += step;
+            rd_b += step;
+            asm volatile("" : "+v"(rd_a), "+v"(rd_b));   // formed here, beside the last MFMAs, and nowhere else
+            paced_valu_hint<31, 2, 5>();
             QG_MFMA_DONE();
             nxt = advance(nxt);
-            const int t = cur;
-            cur = cur + BUF == NBUF * BUF ? 0 : cur + BUF;
-            fill = t;
         }
         if (wm == 0) __builtin_amdgcn_s_barrier();   // pairs with group 1's last barrier: both groups are level again
         __builtin_amdgcn_sched_barrier(0);
@@ -223,16 +240,26 @@ __global__ __launch_bounds__(512) void k_mfma_k6(QMfmaArgs g)
         // <= 2 K 63^2, and 3 K 63^2 = 3/4 K 126^2 < 2^31 — so wrapping 32-bit subtraction gives them exactly and they zero-extend.
         // What depends on the column alone (corr - biasA rsB[col]) is formed once per column of the lane, what depends on the row
         // alone (biasB rsA[row]) once per row; the 64-bit sums are modulo 2^64, as they were.
-        uint64_t colt[2];
+        // Every row sum the lane needs — 2 of B, 12 of A — is loaded here as one batch (the fragment registers are dead) and turned
+        // into its term ahead of the first store of C: one round trip per tile, and no later wait that a store has to satisfy.
+        // The wait itself is vmcnt(0), not a counted one: vector memory operations return in order and these loads are the youngest,
+        // so it also drains the 12 DMA pieces already issued for the next tile.  That is once per tile, where it was three times.
+        uint64_t colt[2], rowt[3][4];
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
-            colt[j] = (uint64_t)g.corr - (uint64_t)g.biasA * (uint64_t)g.rsB[(int64_t)tile_n * TN + wn * 32 + j * 16 + fr];
+        for (int j = 0; j < 2; ++j) colt[j] = (uint64_t)g.rsB[(int64_t)tile_n * TN + wn * 32 + j * 16 + fr];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) rowt[i][e] = (uint64_t)g.rsA[(int64_t)tile_m * TM + wm * 48 + i * 16 + 4 * fq + e];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) colt[j] = (uint64_t)g.corr - (uint64_t)g.biasA * colt[j];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) rowt[i][e] = (uint64_t)g.biasB * rowt[i][e];
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             int64_t s[8];
-            uint64_t rowt[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) rowt[e] = (uint64_t)g.biasB * (uint64_t)g.rsA[(int64_t)tile_m * TM + wm * 48 + i * 16 + 4 * fq + e];
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -240,7 +267,7 @@ __global__ __launch_bounds__(512) void k_mfma_k6(QMfmaArgs g)
                     const uint32_t s00 = (uint32_t)acc[S00][i][j][e], s11 = (uint32_t)acc[S11][i][j][e], s22 = (uint32_t)acc[S22][i][j][e];
                     const uint32_t c1 = (uint32_t)acc[P01][i][j][e] - s00 - s11, c3 = (uint32_t)acc[P12][i][j][e] - s11 - s22,
                                    c2 = (uint32_t)acc[P02][i][j][e] - s00 - s22 + s11;
-                    s[j * 4 + e] = (int64_t)k6_recombine(s00, c1, c2, c3, s22, colt[j] - rowt[e]);
+                    s[j * 4 + e] = (int64_t)k6_recombine(s00, c1, c2, c3, s22, colt[j] - rowt[i][e]);
                 }
             if constexpr (FAST) {
 #pragma unroll

@@ -27,6 +27,22 @@ __device__ __forceinline__ void interleave_hint(std::integer_sequence<int, M...>
      ...);
 }
 
+// Issue-order hint for one basic block that holds NP + NT MFMAs and NP * NV vector ALU instructions beside them (operand sums of a
+// Karatsuba form, address updates): NP times (one MFMA, NV vector instructions), then the last NT MFMAs back to back.  The block
+// opens with an MFMA, and an in-order wave never holds an MFMA back behind a run of vector instructions longer than the issue
+// slots a 16-cycle MFMA leaves free; a value formed NV instructions or more ahead of its MFMA needs no s_nop in front of it.
+template <int NV, int... P>
+__device__ __forceinline__ void paced_valu_pairs(std::integer_sequence<int, P...>)
+{
+    (((void)P, __builtin_amdgcn_sched_group_barrier(0x008, 1, 0), __builtin_amdgcn_sched_group_barrier(0x002, NV, 0)), ...);
+}
+template <int NP, int NV, int NT>
+__device__ __forceinline__ void paced_valu_hint()
+{
+    paced_valu_pairs<NV>(std::make_integer_sequence<int, NP>{});
+    __builtin_amdgcn_sched_group_barrier(0x008, NT, 0);
+}
+
 // Packed C is tiled [tile_m][tile_n][col][row] (column-major inside the tile, the order of the host tensor), and every lane of an
 // MFMA's C/D layout owns runs of 4 consecutive rows of one column: a run is ONE store of 4 / 8 / 16 / 32 bytes.  base: element
 // index of the run's first row; q: its four values (int32 or int64), stored in containers of CB bytes (4 or 8: the kernels that
