@@ -355,11 +355,12 @@ template <class EA, class EB, typename... Tags>
 struct slots_of<EA, EB, TypeList<Tags...>> {
     static constexpr Slots value = [] { Slots s; s.m[0] = merge_mul(EA::fmt, EB::fmt, parse<Tags...>::value); s.prod[0] = s.prod[1] = s.m[0]; return s; }();
 };
-template <class EA, class EB, typename... Args>
-    requires(EA::is_complex)
-struct slots_of<EA, EB, TypeList<BasicComplexMul<Args...>>> {
-    static constexpr Slots value = [] {
-        constexpr Fmt a = re_fmt<EA>(), b = im_fmt<EA>(), c = re_fmt<EB>(), d = im_fmt<EB>();
+// the complex multiplier a tag list names, on part formats: f1 = a + bi the first argument, f2 = c + di the second
+template <class MulList> struct cmul_of;
+template <typename... Args>
+struct cmul_of<TypeList<BasicComplexMul<Args...>>> {
+    static constexpr Slots slots(Fmt a, Fmt b, Fmt c, Fmt d)
+    {
         Slots s; s.cmul = QG_CMUL_BASIC;
         s.m[QG_B_AC] = merge_mul(a, c, sub_tags<acT, Args...>::value);
         s.m[QG_B_BD] = merge_mul(b, d, sub_tags<bdT, Args...>::value);
@@ -369,16 +370,13 @@ struct slots_of<EA, EB, TypeList<BasicComplexMul<Args...>>> {
         s.m[QG_B_IM] = merge_add(s.m[QG_B_AD], s.m[QG_B_BC], sub_tags<adbcT, Args...>::value);
         s.prod[0] = s.m[QG_B_RE]; s.prod[1] = s.m[QG_B_IM];
         return s;
-    }();
+    }
 };
-template <class EA, class EB>
-    requires(EA::is_complex)
-struct slots_of<EA, EB, TypeList<>> : slots_of<EA, EB, TypeList<BasicComplexMul<>>> {};  // QuBLAS.h:3422-3424
-template <class EA, class EB, typename... Args>
-    requires(EA::is_complex)
-struct slots_of<EA, EB, TypeList<TFComplexMul<Args...>>> {
-    static constexpr Slots value = [] {
-        constexpr Fmt a = re_fmt<EA>(), b = im_fmt<EA>(), c = re_fmt<EB>(), d = im_fmt<EB>();
+template <> struct cmul_of<TypeList<>> : cmul_of<TypeList<BasicComplexMul<>>> {};  // QuBLAS.h:3422-3424
+template <typename... Args>
+struct cmul_of<TypeList<TFComplexMul<Args...>>> {
+    static constexpr Slots slots(Fmt a, Fmt b, Fmt c, Fmt d)
+    {
         Slots s; s.cmul = QG_CMUL_TF;
         s.m[QG_T_AB] = merge_add(a, b, sub_tags<abT, Args...>::value);
         s.m[QG_T_CD] = merge_add(c, d, sub_tags<cdT, Args...>::value);
@@ -390,7 +388,12 @@ struct slots_of<EA, EB, TypeList<TFComplexMul<Args...>>> {
         s.m[QG_T_IM] = merge_add(s.m[QG_T_B], s.m[QG_T_C], sub_tags<BCT, Args...>::value);
         s.prod[0] = s.m[QG_T_RE]; s.prod[1] = s.m[QG_T_IM];
         return s;
-    }();
+    }
+};
+template <class EA, class EB, class MulList>
+    requires(EA::is_complex)
+struct slots_of<EA, EB, MulList> {
+    static constexpr Slots value = cmul_of<MulList>::slots(re_fmt<EA>(), im_fmt<EA>(), re_fmt<EB>(), im_fmt<EB>());
 };
 
 // level list -> array of (re, im) formats
@@ -516,7 +519,9 @@ void Qgemul(TC& C, const TA& A, const TB& B)
 // is Qop<tags…>(x, e) with x the running value; ThenRsub is Qsub<tags…>(e, x).  Into = the element type of the tensor
 // the operator's result is assigned to before the next operator (void: the operator's own result type); the last
 // operator's result is assigned to D.  e is a tensor of D's shape or a scalar.  After a complex Qgemul: complex operands
-// for ThenAdd / ThenSub / ThenRsub (realT<…> / imagT<…> tags), real operands for all four; no complex x complex ThenMul.
+// for ThenAdd / ThenSub / ThenRsub (realT<…> / imagT<…> tags), real operands for all four, and
+// ThenMul<Into, BasicComplexMul<…> | TFComplexMul<…> | nothing>(E) with a complex tensor or scalar E: the reference's
+// complex x complex Qmul (QuBLAS.h:3421-3534; include/qgemul.h, QG_EW_CMUL).  Qmul<M>(E, x), the operand first, is ThenRmul.
 template <class CT> struct QgemulResult {};
 
 // ------------------------------------------------------------------ piecewise-polynomial activation (the reference's ANUS helpers, QuBLAS.h:4829-4897)
@@ -548,6 +553,7 @@ struct ApproxStage {
     static constexpr bool approx = true;
     static constexpr bool scalar = true;      // no tensor operand
     static constexpr bool e_complex = false;
+    static constexpr bool cmul = false;
     static constexpr Fmt into(Fmt r) { if constexpr (std::is_void_v<Into>) return r; else return Into::fmt; }
     static constexpr qgemul_approx table()
     {
@@ -594,6 +600,23 @@ struct EwStage {
     {
         if constexpr (std::is_void_v<Into>) return r; else return P == 0 ? re_fmt<Into>() : im_fmt<Into>();
     }
+    // ---- complex x complex multiplication on the running value (xr, xi): every sub-operation's format, first argument first
+    static constexpr bool cmul = e_complex && OP == QG_EW_MUL;
+    static constexpr Slots cmul_slots(Fmt xr, Fmt xi)
+    {
+        const Fmt er = efmt_part<0>(), ei = efmt_part<1>();
+        return XFIRST ? cmul_of<TypeList<Tags...>>::slots(xr, xi, er, ei) : cmul_of<TypeList<Tags...>>::slots(er, ei, xr, xi);
+    }
+};
+// the qgemul_cmul records of a chain, in stage order (on[k]: stage k is a complex x complex multiplication)
+struct CmulRecords {
+    qgemul_cmul rec[QG_MAX_EW]{};
+    bool on[QG_MAX_EW]{};
+    constexpr void pointers(const qgemul_cmul* (&p)[QG_MAX_EW]) const { for (int k = 0; k < QG_MAX_EW; ++k) p[k] = on[k] ? &rec[k] : nullptr; }
+};
+struct CplxChain {
+    qgemul_epilogue_cplx ep{};
+    CmulRecords cx{};
 };
 template <class... Tags> struct pick_result { using type = void; };
 template <class CT, class... Rest> struct pick_result<QgemulResult<CT>, Rest...> { using type = CT; };
@@ -628,21 +651,28 @@ constexpr qgemul_epilogue lower_chain(Fmt c, Fmt d)
 }
 
 template <class... Stages>
-constexpr qgemul_epilogue_cplx lower_chain_cplx(Fmt cre, Fmt cim, Fmt dre, Fmt dim_)
+constexpr CplxChain lower_chain_cplx(Fmt cre, Fmt cim, Fmt dre, Fmt dim_)
 {
     static_assert(sizeof...(Stages) <= QG_MAX_EW, "at most QG_MAX_EW element-wise operators");
     static_assert((!Stages::approx && ...), "Qapprox is defined on real values only (QuBLAS.h:4868: toDouble() of a complex value)");
-    static_assert((!(Stages::e_complex && Stages::op == QG_EW_MUL) && ...), "complex x complex multiplication mixes the parts: not an element-wise stage");
-    qgemul_epilogue_cplx ep{};
+    CplxChain out{};
+    qgemul_epilogue_cplx& ep = out.ep;
     ep.part[0].n_stages = ep.part[1].n_stages = sizeof...(Stages);
     Fmt x[2] = {cre, cim};
     uint32_t k = 0;
     ([&] {
         ep.e_complex[k] = Stages::e_complex;
+        Slots m{};
+        if constexpr (Stages::cmul) {   // both parts carry op 6; r = the RE / IM slot
+            m = Stages::cmul_slots(x[0], x[1]);
+            out.cx.on[k] = true;
+            out.cx.rec[k].cmul = uint8_t(m.cmul);
+            for (int i = 0; i < (m.cmul == QG_CMUL_TF ? 8 : 6); ++i) out.cx.rec[k].mul[i] = m.m[i].c();   // (Basic: slots 6, 7 stay zero)
+        }
         auto one = [&]<int P>() {
             qgemul_ew_stage& s = ep.part[P].stage[k];
-            const Fmt r = Stages::template result_part<P>(x[P]);
-            s.op = uint8_t(Stages::template op_part<P>());
+            const Fmt r = Stages::cmul ? m.prod[P] : Stages::template result_part<P>(x[P]);
+            s.op = Stages::cmul ? uint8_t(QG_EW_CMUL) : uint8_t(Stages::template op_part<P>());
             s.x_first = Stages::x_first;
             s.e_scalar = Stages::template scalar_part<P>();
             s.e = Stages::template efmt_part<P>().c();
@@ -656,7 +686,7 @@ constexpr qgemul_epilogue_cplx lower_chain_cplx(Fmt cre, Fmt cim, Fmt dre, Fmt d
     }(), ...);
     ep.part[0].d = dre.c();
     ep.part[1].d = dim_.c();
-    return ep;
+    return out;
 }
 } // namespace detail
 
@@ -664,6 +694,7 @@ template <class Into = void, typename... Tags, class Operand> auto ThenMul(const
 template <class Into = void, typename... Tags, class Operand> auto ThenAdd(const Operand& e) { return detail::EwStage<QG_EW_ADD, true, Into, Operand, Tags...>{e}; }
 template <class Into = void, typename... Tags, class Operand> auto ThenSub(const Operand& e) { return detail::EwStage<QG_EW_SUB, true, Into, Operand, Tags...>{e}; }
 template <class Into = void, typename... Tags, class Operand> auto ThenRsub(const Operand& e) { return detail::EwStage<QG_EW_SUB, false, Into, Operand, Tags...>{e}; }
+template <class Into = void, typename... Tags, class Operand> auto ThenRmul(const Operand& e) { return detail::EwStage<QG_EW_MUL, false, Into, Operand, Tags...>{e}; }
 template <class Into, class... Segments> auto ThenApprox() { return detail::ApproxStage<Into, Segments...>{}; }
 // the tables of a chain, in stage order: the stage's qgemul_approx, nullptr for a stage that is no ThenApprox
 template <class... Stages>
@@ -693,7 +724,15 @@ constexpr qgemul_epilogue_cplx Qgemul_lower_epilogue_cplx(const TD&, const Stage
     static_assert(!std::is_void_v<CT>, "Qgemul with element-wise operators needs QgemulResult<CT>: the element type of the Qgemul result");
     static_assert(CT::is_complex && TD::elem_t::is_complex, "a complex chain runs from a complex Qgemul result into a complex tensor");
     using DT = typename TD::elem_t;
-    return detail::lower_chain_cplx<Stages...>(CT::realType::fmt, CT::imagType::fmt, DT::realType::fmt, DT::imagType::fmt);
+    return detail::lower_chain_cplx<Stages...>(CT::realType::fmt, CT::imagType::fmt, DT::realType::fmt, DT::imagType::fmt).ep;
+}
+// the qgemul_cmul record of every complex x complex ThenMul / ThenRmul of the chain, for the _epcx entry points
+template <typename... Tags, class TD, class... Stages>
+constexpr detail::CmulRecords Qgemul_lower_cmul(const TD&, const Stages&...)
+{
+    using CT = typename detail::pick_result<Tags...>::type;
+    using DT = typename TD::elem_t;
+    return detail::lower_chain_cplx<Stages...>(CT::realType::fmt, CT::imagType::fmt, DT::realType::fmt, DT::imagType::fmt).cx;
 }
 
 // D = the element-wise chain applied to A' * B
@@ -716,7 +755,14 @@ void Qgemul(TD& D, const TA& A, const TB& B, const S0& s0, const Stages&... st)
     int rc;
     if constexpr (CT::is_complex) {
         const qgemul_epilogue_cplx ep = Qgemul_lower_epilogue_cplx<Tags...>(D, s0, st...);
-        rc = qgemul_run_epc(&d, &ep, D.data.data(), A.data.data(), B.data.data(), E, nullptr);
+        if constexpr (S0::cmul || (Stages::cmul || ...)) {
+            const detail::CmulRecords cx = Qgemul_lower_cmul<Tags...>(D, s0, st...);
+            const qgemul_cmul* pcx[QG_MAX_EW];
+            cx.pointers(pcx);
+            rc = qgemul_run_epcx(&d, &ep, pcx, D.data.data(), A.data.data(), B.data.data(), E, nullptr);
+        } else {
+            rc = qgemul_run_epc(&d, &ep, D.data.data(), A.data.data(), B.data.data(), E, nullptr);
+        }
     } else {
         const qgemul_epilogue ep = Qgemul_lower_epilogue<Tags...>(D, s0, st...);
         if constexpr (S0::approx || (Stages::approx || ...)) {

@@ -386,8 +386,9 @@ int qgemul_run_ep(const qgemul_desc* d, const qgemul_epilogue* ep, void* D, cons
  *                              format, :3670 / :3654 / :3701)
  *   real - complex             real part: SUB (e, x); imaginary part: SUB (e, x) with a scalar operand of the real
  *                              operand's format whose value is 0 (:3686: Qsub<tags>(Qu_s<realArgs1...>(), f2.imag))
- * complex x complex multiplication (BasicComplexMul / TFComplexMul, :3426-3534) mixes the parts and is not an epilogue
- * stage (the headers refuse to lower it).  The chain always runs as its own pass after the complex kernel.
+ * complex x complex multiplication (BasicComplexMul / TFComplexMul, :3426-3534) mixes the parts: it is the QG_EW_CMUL
+ * stage below, served by the _epcx entry points; these _epc entry points refuse it.  The chain always runs as its own pass
+ * after the complex kernel.
  * Operands: stage k's tensor operand is ONE packed buffer; e_complex[k] = 1: a complex tensor packed like the plan's
  * packed C ([2][M][N], both parts in the container of the wider one), part p reads its half; 0: a real tensor, which
  * either part may read.  Scalars: e_scalar[k] for part[0], e_scalar_im[k] for part[1]. */
@@ -463,9 +464,51 @@ typedef struct qgemul_approx_form {
     int64_t threshold[QG_MAX_EW][QG_MAX_SEG];
 } qgemul_approx_form;
 int qgemul_approx_plan_form(const qgemul_desc* d, const qgemul_epilogue* ep, const qgemul_approx* const ax[QG_MAX_EW], qgemul_approx_form* out);
+/* ---- complex x complex multiplication as a stage of a complex chain (Qmul on two complex values, QuBLAS.h:3421-3534; per
+ *      element of the lazy tensor operator, :3780-3799) ----
+ * Stage k replaces the running complex value x by  Qmul<M>(x, e)  (x_first = 1) or  Qmul<M>(e, x)  (x_first = 0), e a complex
+ * tensor of D's shape or a complex scalar, M = BasicComplexMul<...> / TFComplexMul<...> / nothing (= BasicComplexMul<>, :3421-3424).
+ * With f1 = a + bi the first argument and f2 = c + di the second:
+ *   Basic   re = Qsub<acbdT>(Qmul<acT>(a, c), Qmul<bdT>(b, d)),   im = Qadd<adbcT>(Qmul<adT>(a, d), Qmul<bcT>(b, c))
+ *   TF      A = Qmul<abcT>(Qadd<abT>(a, b), c),  B = Qmul<badT>(Qadd<cdT>(c, d), b),  C = Qmul<cdbT>(Qsub(b, a), d),
+ *           re = Qsub<ABT>(A, B),  im = Qsub<BCT>(B, C)       (the reference's two quirks, as for qgemul_desc.mul[])
+ * The roles of the two arguments differ (formats, and TF altogether), so the order matters.  The result is assigned part by
+ * part to the stage's tensor type t, like every stage.
+ * In a qgemul_epilogue_cplx the stage carries op = QG_EW_CMUL in BOTH parts, with the same x_first and e_scalar; e is that
+ * part's format of the operand, r the RE / IM slot of qgemul_cmul.mul[] (checked), t as usual, e_complex[k] = 1; a scalar
+ * operand comes from e_scalar[k] / e_scalar_im[k].  qgemul_cmul.mul[] holds the resolved result format of every
+ * sub-operation in the slot order of qgemul_desc.mul[] (QG_B_* / QG_T_*), the quirks applied by the lowering.
+ * The _epcx entry points are the _epc ones plus  cx[QG_MAX_EW]:  cx[k] is non-null exactly for the CMUL stages; the plan
+ * copies the records.  qgemul_execute_ep, qgemul_time_execute_ep, qgemul_apply_epilogue, qgemul_time_apply_epilogue,
+ * qgemul_pack_c, qgemul_pack_e, qgemul_packed_e_bytes, qgemul_unpack_c and qgemul_export_bitstream serve such plans unchanged.
+ * A chain with a CMUL stage runs as ONE pass over packed C whose lanes own both halves of their elements
+ * (qgemul_plan_fuses_epilogue = 0); a chain without one runs exactly as under _epc.  The _ep / _epc / _epx entry points keep
+ * refusing op 6, and so does a real GEMM.
+ * QG_EINVAL: op 6 in one part only, x_first / e_scalar differing between the parts, e_complex[k] = 0, a missing or surplus
+ * cx[k], cmul neither Basic nor TF, r unequal to the RE / IM slot in any of the five fields.  QG_EUNSUPPORTED: a sub-operation
+ * or a format beyond 62 bits, and whatever the chain refuses anywhere (WRP::TCPL_SAT that can act, the 32- / 64-bit shift
+ * artefacts, unsigned WRP::TCPL with exactly 32 value bits). */
+#define QG_EW_CMUL 6
+typedef struct qgemul_cmul {
+    uint8_t cmul;       /* QG_CMUL_BASIC | QG_CMUL_TF */
+    uint8_t reserved[7];
+    qfmt mul[8];
+} qgemul_cmul;
+int qgemul_classify_epcx(const qgemul_desc* d, const qgemul_epilogue_cplx* ep, const qgemul_cmul* const cx[QG_MAX_EW], uint32_t opt_flags,
+                         qgemul_info* out);
+int qgemul_plan_create_epcx(qgemul_ctx* c, const qgemul_desc* d, const qgemul_epilogue_cplx* ep, const qgemul_cmul* const cx[QG_MAX_EW],
+                            uint32_t opt_flags, qgemul_plan** out);
+int qgemul_run_epcx(const qgemul_desc* d, const qgemul_epilogue_cplx* ep, const qgemul_cmul* const cx[QG_MAX_EW], void* D, const void* A,
+                    const void* B, const void* const* E, const qgemul_opts* o);
+/* what the planner made of a complex chain (pure host code): has_cmul = it holds a CMUL stage (the one-pass kernel runs),
+ * bits32 = that pass runs in 32-bit arithmetic (both part chains and every CMUL node), max_bits = the widest intermediate */
+typedef struct qgemul_cmul_form {
+    int32_t has_cmul, bits32, max_bits, reserved;
+} qgemul_cmul_form;
+int qgemul_cmul_plan_form(const qgemul_desc* d, const qgemul_epilogue_cplx* ep, const qgemul_cmul* const cx[QG_MAX_EW], qgemul_cmul_form* out);
 /* sizeof of an ABI struct as THIS library was compiled (language bindings check their mirrors against it); 0: unknown id */
 enum { QG_SIZEOF_QFMT = 0, QG_SIZEOF_DESC = 1, QG_SIZEOF_OPTS = 2, QG_SIZEOF_INFO = 3, QG_SIZEOF_EW_STAGE = 4, QG_SIZEOF_EPILOGUE = 5,
-       QG_SIZEOF_EP_ARGS = 6, QG_SIZEOF_EPILOGUE_CPLX = 7, QG_SIZEOF_APPROX_SEG = 8, QG_SIZEOF_APPROX = 9 };
+       QG_SIZEOF_EP_ARGS = 6, QG_SIZEOF_EPILOGUE_CPLX = 7, QG_SIZEOF_APPROX_SEG = 8, QG_SIZEOF_APPROX = 9, QG_SIZEOF_CMUL = 10 };
 size_t qgemul_sizeof(int which);
 
 /* ---- several GPUs in one process ----

@@ -80,11 +80,12 @@ struct slots<EA, EB, TypeList<BasicComplexMul<Args...>>> {
     using im_t = decltype(Qadd<typename S::addADBCType>(std::declval<ad_t>(), std::declval<bc_t>()));
     using prod_t = Qcomplex<re_t, im_t>;
     static constexpr int cmul = QG_CMUL_BASIC;
-    static void fill(qgemul_desc& d)
+    static void fill(qfmt (&m)[8])
     {
-        d.mul[QG_B_AC] = fmt_of<ac_t>(); d.mul[QG_B_BD] = fmt_of<bd_t>(); d.mul[QG_B_AD] = fmt_of<ad_t>();
-        d.mul[QG_B_BC] = fmt_of<bc_t>(); d.mul[QG_B_RE] = fmt_of<re_t>(); d.mul[QG_B_IM] = fmt_of<im_t>();
+        m[QG_B_AC] = fmt_of<ac_t>(); m[QG_B_BD] = fmt_of<bd_t>(); m[QG_B_AD] = fmt_of<ad_t>();
+        m[QG_B_BC] = fmt_of<bc_t>(); m[QG_B_RE] = fmt_of<re_t>(); m[QG_B_IM] = fmt_of<im_t>();
     }
+    static void fill(qgemul_desc& d) { fill(d.mul); }
 };
 template <class EA, class EB>
     requires(EA::is_complex)
@@ -105,12 +106,13 @@ struct slots<EA, EB, TypeList<TFComplexMul<Args...>>> {
     using im_t = decltype(Qsub<typename S::subBCType>(std::declval<B_t>(), std::declval<C_t>()));
     using prod_t = Qcomplex<re_t, im_t>;
     static constexpr int cmul = QG_CMUL_TF;
-    static void fill(qgemul_desc& d)
+    static void fill(qfmt (&m)[8])
     {
-        d.mul[QG_T_AB] = fmt_of<ab_t>(); d.mul[QG_T_CD] = fmt_of<cd_t>(); d.mul[QG_T_BA] = fmt_of<ba_t>();
-        d.mul[QG_T_A] = fmt_of<A_t>(); d.mul[QG_T_B] = fmt_of<B_t>(); d.mul[QG_T_C] = fmt_of<C_t>();
-        d.mul[QG_T_RE] = fmt_of<re_t>(); d.mul[QG_T_IM] = fmt_of<im_t>();
+        m[QG_T_AB] = fmt_of<ab_t>(); m[QG_T_CD] = fmt_of<cd_t>(); m[QG_T_BA] = fmt_of<ba_t>();
+        m[QG_T_A] = fmt_of<A_t>(); m[QG_T_B] = fmt_of<B_t>(); m[QG_T_C] = fmt_of<C_t>();
+        m[QG_T_RE] = fmt_of<re_t>(); m[QG_T_IM] = fmt_of<im_t>();
     }
+    static void fill(qgemul_desc& d) { fill(d.mul); }
 };
 
 // ---- tree levels: type of level l as Reducer selects it, formats of the add and of the buffer.
@@ -218,7 +220,10 @@ void Qgemul(TC& C, const TA& A, const TB& B)
 // type and the operand's element type, so the chain resolves exactly as the three statements above do.
 // After a COMPLEX Qgemul the same spelling takes complex operands for ThenAdd / ThenSub / ThenRsub (realT<…> / imagT<…>
 // tags, QuBLAS.h:3549-3589) and real operands for all four (:3604-3707); the chain is lowered to the two part-wise
-// chains of qgemul_epilogue_cplx.  complex x complex ThenMul does not compile (it mixes the parts).
+// chains of qgemul_epilogue_cplx.  ThenMul<Into, BasicComplexMul<…> | TFComplexMul<…> | nothing>(E) with a complex tensor or
+// scalar E is the header's complex x complex Qmul (QuBLAS.h:3421-3534): a QG_EW_CMUL stage whose sub-operation formats are
+// resolved by decltype on the header's own Qmul / Qadd / Qsub, as the GEMM's multiplier slots are; a chain that holds one
+// goes through qgemul_run_epcx.  Qmul<M>(E, x), the operand first, is ThenRmul.
 template <class CT> struct QgemulResult {};
 
 namespace qgemul_detail {
@@ -239,6 +244,8 @@ struct EwStage {
     }
     template <class X> using r_t = decltype(apply(std::declval<X>(), std::declval<e_t>()));
     template <class X> using next_t = std::conditional_t<std::is_void_v<Into>, r_t<X>, Into>;
+    // complex x complex Qmul on the running element type X: the multiplier's sub-operation formats, first argument first
+    template <class X> using cmul_slots = std::conditional_t<XFIRST, slots<X, e_t, TypeList<Tags...>>, slots<e_t, X, TypeList<Tags...>>>;
 };
 template <class... Tags> struct pick_result { using type = void; };
 template <class CT, class... Rest> struct pick_result<QgemulResult<CT>, Rest...> { using type = CT; };
@@ -283,20 +290,36 @@ struct ApproxStage {
 template <class S> constexpr bool is_approx = requires { requires S::approx; };
 
 // complex chains: stage k of the chain of part P (0 = real parts, 1 = imaginary parts) — include/qgemul.h's table
-template <class X> void fill_chain_cplx(qgemul_epilogue_cplx&, uint32_t) {}
+template <class X, class S> constexpr bool is_cmul = requires { requires S::e_t::is_complex && S::op == QG_EW_MUL && X::is_complex; };
+// the qgemul_cmul records of a chain, in stage order (on[k]: stage k is a complex x complex multiplication)
+struct CmulRecords {
+    qgemul_cmul rec[QG_MAX_EW];
+    bool on[QG_MAX_EW];
+    void pointers(const qgemul_cmul* (&p)[QG_MAX_EW]) const { for (int k = 0; k < QG_MAX_EW; ++k) p[k] = on[k] ? &rec[k] : nullptr; }
+};
+template <class X> void fill_chain_cplx(qgemul_epilogue_cplx&, uint32_t, CmulRecords*) {}
 template <class X, class S0, class... Ss>
-void fill_chain_cplx(qgemul_epilogue_cplx& ep, uint32_t k)
+void fill_chain_cplx(qgemul_epilogue_cplx& ep, uint32_t k, CmulRecords* cx)
 {
     static_assert(!is_approx<S0>, "Qapprox is defined on real values only (QuBLAS.h:4868)");
     using e_t = typename S0::e_t;
     using r_t = typename S0::template r_t<X>;
     using n_t = typename S0::template next_t<X>;
     static_assert(X::is_complex && r_t::is_complex && n_t::is_complex, "a complex chain runs on complex tensors");
-    static_assert(!(e_t::is_complex && S0::op == QG_EW_MUL), "complex x complex multiplication mixes the parts: not an element-wise stage");
     ep.e_complex[k] = e_t::is_complex;
     qgemul_ew_stage& re = ep.part[0].stage[k];
     qgemul_ew_stage& im = ep.part[1].stage[k];
     re.op = im.op = uint8_t(S0::op);
+    if constexpr (is_cmul<X, S0>) {   // r_t is the header's own Qmul result: the RE / IM slots by construction
+        using M = typename S0::template cmul_slots<X>;
+        static_assert(std::is_same_v<typename M::prod_t, r_t>);
+        re.op = im.op = uint8_t(QG_EW_CMUL);
+        if (cx) {
+            cx->rec[k].cmul = uint8_t(M::cmul);
+            M::fill(cx->rec[k].mul);
+            cx->on[k] = true;
+        }
+    }
     re.x_first = im.x_first = S0::x_first;
     re.e_scalar = im.e_scalar = S0::scalar;
     re.e = fmt_of<typename parts<e_t>::re>();
@@ -309,7 +332,13 @@ void fill_chain_cplx(qgemul_epilogue_cplx& ep, uint32_t k)
         if constexpr (S0::op == QG_EW_ADD || S0::x_first) im.op = QG_EW_PASS;   // the imaginary part is carried over (QuBLAS.h:3654, :3670, :3701)
         im.e_scalar = 1;                                                        // real - complex: the zero of the operand's type (:3686)
     }
-    fill_chain_cplx<n_t, Ss...>(ep, k + 1);
+    fill_chain_cplx<n_t, Ss...>(ep, k + 1, cx);
+}
+template <class X> constexpr bool chain_has_cmul() { return false; }
+template <class X, class S0, class... Ss> constexpr bool chain_has_cmul()
+{
+    if constexpr (is_approx<S0>) return false;
+    else return is_cmul<X, S0> || chain_has_cmul<typename S0::template next_t<X>, Ss...>();
 }
 
 template <class X> void fill_chain(qgemul_epilogue&, uint32_t) {}
@@ -334,6 +363,7 @@ template <class Into = void, typename... Tags, class Operand> auto ThenMul(const
 template <class Into = void, typename... Tags, class Operand> auto ThenAdd(const Operand& e) { return qgemul_detail::EwStage<QG_EW_ADD, true, Into, Operand, Tags...>{e}; }
 template <class Into = void, typename... Tags, class Operand> auto ThenSub(const Operand& e) { return qgemul_detail::EwStage<QG_EW_SUB, true, Into, Operand, Tags...>{e}; }
 template <class Into = void, typename... Tags, class Operand> auto ThenRsub(const Operand& e) { return qgemul_detail::EwStage<QG_EW_SUB, false, Into, Operand, Tags...>{e}; }
+template <class Into = void, typename... Tags, class Operand> auto ThenRmul(const Operand& e) { return qgemul_detail::EwStage<QG_EW_MUL, false, Into, Operand, Tags...>{e}; }
 template <class Into, class... Segments> auto ThenApprox() { return qgemul_detail::ApproxStage<Into, Segments...>{}; }
 // the tables of a chain, in stage order: the stage's qgemul_approx, nullptr for a stage that is no ThenApprox
 template <class... Stages>
@@ -343,6 +373,22 @@ std::array<const qgemul_approx*, QG_MAX_EW> Qgemul_lower_approx(const Stages&...
     uint32_t k = 0;
     ([&] { if constexpr (qgemul_detail::is_approx<Stages>) t[k] = Stages::table(); ++k; }(), ...);
     return t;
+}
+
+template <typename... Tags, class TD, class... Stages>
+qgemul_epilogue_cplx Qgemul_lower_epilogue_cplx_x(qgemul_detail::CmulRecords* cx, std::type_identity<TD>, std::type_identity<Stages>...)
+{
+    using CT = typename qgemul_detail::pick_result<Tags...>::type;
+    static_assert(!std::is_void_v<CT>, "Qgemul with element-wise operators needs QgemulResult<CT>: the element type of the Qgemul result");
+    static_assert(sizeof...(Stages) <= QG_MAX_EW, "at most QG_MAX_EW element-wise operators");
+    static_assert(CT::is_complex && TD::elem_t::is_complex, "a complex chain runs from a complex Qgemul result into a complex tensor");
+    qgemul_epilogue_cplx ep{};
+    ep.part[0].n_stages = ep.part[1].n_stages = sizeof...(Stages);
+    if (cx) *cx = qgemul_detail::CmulRecords{};
+    qgemul_detail::fill_chain_cplx<CT, Stages...>(ep, 0, cx);
+    ep.part[0].d = qgemul_detail::fmt_of<typename TD::elem_t::realType>();
+    ep.part[1].d = qgemul_detail::fmt_of<typename TD::elem_t::imagType>();
+    return ep;
 }
 
 template <typename... Tags, class TD, class... Stages>
@@ -362,16 +408,15 @@ qgemul_epilogue Qgemul_lower_epilogue(const TD&, const Stages&...)
 template <typename... Tags, class TD, class... Stages>
 qgemul_epilogue_cplx Qgemul_lower_epilogue_cplx(const TD&, const Stages&...)
 {
-    using CT = typename qgemul_detail::pick_result<Tags...>::type;
-    static_assert(!std::is_void_v<CT>, "Qgemul with element-wise operators needs QgemulResult<CT>: the element type of the Qgemul result");
-    static_assert(sizeof...(Stages) <= QG_MAX_EW, "at most QG_MAX_EW element-wise operators");
-    static_assert(CT::is_complex && TD::elem_t::is_complex, "a complex chain runs from a complex Qgemul result into a complex tensor");
-    qgemul_epilogue_cplx ep{};
-    ep.part[0].n_stages = ep.part[1].n_stages = sizeof...(Stages);
-    qgemul_detail::fill_chain_cplx<CT, Stages...>(ep, 0);
-    ep.part[0].d = qgemul_detail::fmt_of<typename TD::elem_t::realType>();
-    ep.part[1].d = qgemul_detail::fmt_of<typename TD::elem_t::imagType>();
-    return ep;
+    return Qgemul_lower_epilogue_cplx_x<Tags...>(static_cast<qgemul_detail::CmulRecords*>(nullptr), std::type_identity<TD>{}, std::type_identity<Stages>{}...);
+}
+// the qgemul_cmul record of every complex x complex ThenMul / ThenRmul of the chain, for the _epcx entry points
+template <typename... Tags, class TD, class... Stages>
+qgemul_detail::CmulRecords Qgemul_lower_cmul(const TD&, const Stages&...)
+{
+    qgemul_detail::CmulRecords cx;
+    Qgemul_lower_epilogue_cplx_x<Tags...>(&cx, std::type_identity<TD>{}, std::type_identity<Stages>{}...);
+    return cx;
 }
 
 template <typename... Tags, class TD, class TA, class TB, class S0, class... Stages>
@@ -390,8 +435,14 @@ void Qgemul(TD& D, const TA& A, const TB& B, const S0& s0, const Stages&... st)
     const void* E[QG_MAX_EW] = {ptr(s0), ptr(st)...};
     int rc;
     if constexpr (CT::is_complex) {
-        const qgemul_epilogue_cplx ep = Qgemul_lower_epilogue_cplx<Tags...>(D, s0, st...);
-        rc = qgemul_run_epc(&d, &ep, D.data.data(), A.data.data(), B.data.data(), E, nullptr);
+        qgemul_detail::CmulRecords cx;
+        const qgemul_epilogue_cplx ep = Qgemul_lower_epilogue_cplx_x<Tags...>(&cx, std::type_identity<TD>{}, std::type_identity<S0>{}, std::type_identity<Stages>{}...);
+        if constexpr (qgemul_detail::chain_has_cmul<CT, S0, Stages...>()) {
+            const qgemul_cmul* pcx[QG_MAX_EW];
+            cx.pointers(pcx);
+            rc = qgemul_run_epcx(&d, &ep, pcx, D.data.data(), A.data.data(), B.data.data(), E, nullptr);
+        } else
+            rc = qgemul_run_epc(&d, &ep, D.data.data(), A.data.data(), B.data.data(), E, nullptr);
     } else {
         const qgemul_epilogue ep = Qgemul_lower_epilogue<Tags...>(D, s0, st...);
         if constexpr (qgemul_detail::is_approx<S0> || (qgemul_detail::is_approx<Stages> || ...)) {

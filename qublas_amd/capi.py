@@ -13,7 +13,7 @@ from typing import Optional
 
 import numpy as np
 
-from .desc import (QG_MAX_EW, Qcomplex, Qu, host_layout, qfmt, qgemul_approx, qgemul_approx_form, qgemul_approx_seg, qgemul_desc, qgemul_ep_args, qgemul_epilogue,
+from .desc import (QG_MAX_EW, Qcomplex, Qu, host_layout, qfmt, qgemul_approx, qgemul_approx_form, qgemul_approx_seg, qgemul_cmul, qgemul_cmul_form, qgemul_desc, qgemul_ep_args, qgemul_epilogue,
                    qgemul_epilogue_cplx, qgemul_ew_stage, qgemul_info, qgemul_opts)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -43,10 +43,11 @@ EXPORTS = [
     "qgemul_comm_unique_id", "qgemul_comm_create", "qgemul_comm_destroy", "qgemul_comm_info", "qgemul_gather_packed_c", "qgemul_comm_fence",
     "qgemul_comm_sync", "qgemul_comm_barrier", "qgemul_comm_max_f64", "qgemul_last_rccl_error", "qgemul_ctx_device",
     "qgemul_classify_epx", "qgemul_plan_create_epx", "qgemul_run_epx", "qgemul_plan_approx_uniform", "qgemul_sizeof", "qgemul_approx_plan_form", "qgemul_apply_epilogue", "qgemul_time_apply_epilogue", "qgemul_packed_c_bytes", "qgemul_pack_c",
+    "qgemul_classify_epcx", "qgemul_plan_create_epcx", "qgemul_run_epcx", "qgemul_cmul_plan_form",
 ]
 # qgemul_sizeof ids (include/qgemul.h) and the ctypes mirror each one must match
 SIZEOF_MIRRORS = {0: qfmt, 1: qgemul_desc, 2: qgemul_opts, 3: qgemul_info, 4: qgemul_ew_stage, 5: qgemul_epilogue, 6: qgemul_ep_args,
-                  7: qgemul_epilogue_cplx, 8: qgemul_approx_seg, 9: qgemul_approx}
+                  7: qgemul_epilogue_cplx, 8: qgemul_approx_seg, 9: qgemul_approx, 10: qgemul_cmul}
 
 _lib = None
 
@@ -139,6 +140,11 @@ def lib() -> C.CDLL:
         L.qgemul_pack_c.argtypes = [vp, vp, i64, vp]
         L.qgemul_apply_epilogue.argtypes = [vp, vp, vp, pa]
         L.qgemul_time_apply_epilogue.argtypes = [vp, vp, vp, pa, C.c_int, C.c_int, C.POINTER(C.c_float)]
+        pcx = C.POINTER(C.POINTER(qgemul_cmul))
+        L.qgemul_classify_epcx.argtypes = [pd, pec, pcx, u32, C.POINTER(qgemul_info)]
+        L.qgemul_plan_create_epcx.argtypes = [vp, pd, pec, pcx, u32, C.POINTER(vp)]
+        L.qgemul_run_epcx.argtypes = [pd, pec, pcx, vp, vp, vp, C.POINTER(vp), C.POINTER(qgemul_opts)]
+        L.qgemul_cmul_plan_form.argtypes = [pd, pec, pcx, C.POINTER(qgemul_cmul_form)]
         L.qgemul_sizeof.argtypes = [C.c_int]
         L.qgemul_sizeof.restype = C.c_size_t
         _lib = L
@@ -213,6 +219,39 @@ def approx_plan_form(desc: qgemul_desc, ep: qgemul_epilogue, approx) -> qgemul_a
     out = qgemul_approx_form()
     _chk(lib().qgemul_approx_plan_form(C.byref(desc), C.byref(ep), _tables(approx), C.byref(out)), "qgemul_approx_plan_form")
     return out
+
+
+def _cmuls(cmul):
+    """QG_MAX_EW pointers: the stage's qgemul_cmul, or null for a stage that is no CMUL stage"""
+    cmul = list(cmul) + [None] * (QG_MAX_EW - len(cmul))
+    return (C.POINTER(qgemul_cmul) * QG_MAX_EW)(*[C.pointer(t) if t is not None else None for t in cmul[:QG_MAX_EW]])
+
+
+def classify_epcx(desc: qgemul_desc, ep: qgemul_epilogue_cplx, cmul, flags: int = 0):
+    """qgemul_classify_epcx: (status, info); cmul[k] = stage k's qgemul_cmul or None (desc.lower_epilogue_cplx_x)"""
+    info = qgemul_info()
+    st = lib().qgemul_classify_epcx(C.byref(desc), C.byref(ep), _cmuls(cmul), flags, C.byref(info))
+    return st, info
+
+
+def cmul_plan_form(desc: qgemul_desc, ep: qgemul_epilogue_cplx, cmul):
+    """qgemul_cmul_plan_form: (status, form)"""
+    out = qgemul_cmul_form()
+    st = lib().qgemul_cmul_plan_form(C.byref(desc), C.byref(ep), _cmuls(cmul), C.byref(out))
+    return st, out
+
+
+def run_epcx(desc: qgemul_desc, ep: qgemul_epilogue_cplx, cmul, D_out: np.ndarray, A: np.ndarray, B: np.ndarray, E, *, lda: int = 0,
+             ldb: int = 0, ldc: int = 0, device: int = -1, flags: int = 0) -> np.ndarray:
+    """qgemul_run_epcx: as run_ep on a complex chain that may hold CMUL stages"""
+    A = np.ascontiguousarray(A)
+    B = np.ascontiguousarray(B)
+    E = [np.ascontiguousarray(e) for e in E]
+    ptrs = (C.c_void_p * max(1, len(E)))(*[e.ctypes.data for e in E])
+    o = qgemul_opts(lda, ldb, ldc, device, flags)
+    _chk(lib().qgemul_run_epcx(C.byref(desc), C.byref(ep), _cmuls(cmul), D_out.ctypes.data_as(C.c_void_p), A.ctypes.data_as(C.c_void_p),
+                               B.ctypes.data_as(C.c_void_p), ptrs, C.byref(o)), "qgemul_run_epcx")
+    return D_out
 
 
 def sizeof(which: int) -> int:
@@ -348,12 +387,14 @@ def _chk_rccl(st: int, what: str):
 
 
 class Plan:
-    def __init__(self, ctx: Context, desc: qgemul_desc, flags: int = 0, epilogue=None, approx=None):
+    def __init__(self, ctx: Context, desc: qgemul_desc, flags: int = 0, epilogue=None, approx=None, cmul=None):
         self.ctx = ctx
         self.desc = desc
         self.epilogue = epilogue
         self.h = C.c_void_p()
-        if approx is not None and any(t is not None for t in approx):
+        if cmul is not None:
+            _chk(lib().qgemul_plan_create_epcx(ctx.h, C.byref(desc), C.byref(epilogue), _cmuls(cmul), flags, C.byref(self.h)), "qgemul_plan_create_epcx")
+        elif approx is not None and any(t is not None for t in approx):
             _chk(lib().qgemul_plan_create_epx(ctx.h, C.byref(desc), C.byref(epilogue), _tables(approx), flags, C.byref(self.h)), "qgemul_plan_create_epx")
         elif epilogue is None:
             _chk(lib().qgemul_plan_create(ctx.h, C.byref(desc), flags, C.byref(self.h)), "qgemul_plan_create")

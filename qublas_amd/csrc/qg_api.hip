@@ -15,6 +15,7 @@
 #include "qg_ring.h"
 #include "qg_plan.h"
 #include "qg_approx.h"
+#include "qg_cmul.h"
 
 static thread_local int g_last_hip = 0;
 
@@ -106,6 +107,11 @@ struct qgemul_plan {
     // table on the device, ax_uniform = every table has the uniform form
     int has_ax, ax_uniform;
     QApproxTable* ax_dev[QG_MAX_EW];
+    // CMUL stages (qg_cmul.h): has_cmul = the complex chain holds one (it then runs as the one pass of qg_eltwise_cplx.hip, never as
+    // two k_eltwise launches); cx = the plan's copy of the caller's records, cm_dev = QG_MAX_EW pre-resolved records on the device
+    int has_cmul;
+    qgemul_cmul cx[QG_MAX_EW];
+    QCmulStage* cm_dev;
     QCGeom pc_c;
     void* cwork;
     int32_t* wide_ws;     // single-limb MFMA with a left-shifting epilogue that leaves 32 bits: raw int32 dot products
@@ -117,7 +123,16 @@ struct qgemul_plan {
 
 struct HostC { void* C; int64_t ld; };
 // an element-wise chain as the planner sees it: a real chain (im == nullptr) or the two part chains of a complex one
-struct EpView { const qgemul_epilogue* re; const qgemul_epilogue* im; const uint8_t* e_cplx; const qgemul_approx* const* ax; };   // execute_kernel: store the reference layout directly (kernels that can)
+struct EpView { const qgemul_epilogue* re; const qgemul_epilogue* im; const uint8_t* e_cplx; const qgemul_approx* const* ax; const qgemul_epilogue_cplx* epc; const qgemul_cmul* const* cx; };
+// a chain that came in through an _epcx entry point and holds a CMUL stage in either part (such a chain is planned in lock step)
+static bool view_has_cmul(const EpView* ev)
+{
+    if (!ev || !ev->cx || !ev->im) return false;
+    for (int p = 0; p < 2; ++p)
+        for (uint32_t k = 0; k < ev->epc->part[p].n_stages && k < QG_MAX_EW; ++k)
+            if (ev->epc->part[p].stage[k].op == QG_EW_CMUL) return true;
+    return false;
+}   // execute_kernel: store the reference layout directly (kernels that can)
 
 static int pow2_bytes(int storage_bits)
 {
@@ -229,7 +244,7 @@ static hipError_t comp_zero_rowsums(const qgemul_plan* p, int operand, void* pac
 static int plan_geometry(const qgemul_desc* d, uint32_t flags, QAnalysis* an, qgemul_info* info, int* pLA, int* pLB, QMfmaCfg* pVar,
                          QPackedGeom* pa, QPackedGeom* pb, QCGeom* pc, QHostElem* ha, QHostElem* hb, QHostElem* hc,
                          const EpView* ev = nullptr, QEpTable* ept = nullptr, QCGeom* pc_c = nullptr, QEpTable* ept_im = nullptr,
-                         QComposite* pcomp = nullptr, QApproxTable* axt = nullptr)
+                         QComposite* pcomp = nullptr, QApproxTable* axt = nullptr, QCmulStage* cmt = nullptr)
 {
     QComposite comp_local;
     QComposite& comp = pcomp ? *pcomp : comp_local;
@@ -505,11 +520,29 @@ static int plan_geometry(const qgemul_desc* d, uint32_t flags, QAnalysis* an, qg
         QEpTable local[2];
         QEpTable* t[2] = {ept ? ept : &local[0], ept_im ? ept_im : &local[1]};
         qfmt df[2] = {ep->d, ep->d};
+        const bool lockstep = view_has_cmul(ev);   // a CMUL stage needs both running values: the part chains are planned together
+        if (ev->cx && !lockstep)
+            for (int k = 0; k < QG_MAX_EW; ++k)
+                if (ev->cx[k]) {
+                    info->supported = 0;
+                    snprintf(info->reason, sizeof info->reason, "a CMUL record for a stage that is no CMUL stage");
+                    return QG_EINVAL;
+                }
+        QEpTable both[2];
         for (int part = 0; part < parts; ++part) {
             const qgemul_epilogue* e = part ? ev->im : ep;
             int ep_bits = 0;
             char why[96];
-            const int st = qg_analyze_epx(d->c[part], e, part ? nullptr : ev->ax, t[part], part ? nullptr : axt, &ep_bits, why, sizeof why);
+            int st = QG_OK;
+            if (lockstep) {
+                if (part == 0) {
+                    st = qg_analyze_epcx(d->c, ev->epc, ev->cx, both, cmt, &ep_bits, why, sizeof why);
+                    *t[0] = both[0];
+                    *t[1] = both[1];
+                }
+            } else {
+                st = qg_analyze_epx(d->c[part], e, part ? nullptr : ev->ax, t[part], part ? nullptr : axt, &ep_bits, why, sizeof why);
+            }
             if (st != QG_OK) {
                 info->supported = 0;
                 snprintf(info->reason, sizeof info->reason, "%s", why);
@@ -632,6 +665,7 @@ extern "C" void qgemul_diag_set_stamps(void* dev) { g_diag_stamps = (uint32_t*)d
 static bool fuses_epilogue(const qgemul_plan* p)
 {
     if (p->has_ax) return false;   // (an APPROX stage: always the pass of qg_approx.hip)
+    if (p->has_cmul) return false; // (a CMUL stage: always the pass of qg_eltwise_cplx.hip)
     if (wide_epilogue(p) || p->comp.on || p->variant == QG_MFMA_RING) return false;
     if (p->flags & QG_OPT_UNFUSED_EPILOGUE) return false;
     if (!p->ept.bits32) return false;
@@ -724,6 +758,7 @@ size_t qgemul_sizeof(int which)
     case QG_SIZEOF_EPILOGUE_CPLX: return sizeof(qgemul_epilogue_cplx);
     case QG_SIZEOF_APPROX_SEG: return sizeof(qgemul_approx_seg);
     case QG_SIZEOF_APPROX: return sizeof(qgemul_approx);
+    case QG_SIZEOF_CMUL: return sizeof(qgemul_cmul);
     default: return 0;
     }
 }
@@ -733,6 +768,35 @@ int qgemul_classify_epc(const qgemul_desc* d, const qgemul_epilogue_cplx* ep, ui
     if (!ep) return QG_EINVAL;
     const EpView v = {&ep->part[0], &ep->part[1], ep->e_complex};
     return classify_view(d, &v, opt_flags, out);
+}
+
+int qgemul_classify_epcx(const qgemul_desc* d, const qgemul_epilogue_cplx* ep, const qgemul_cmul* const cx[QG_MAX_EW], uint32_t opt_flags, qgemul_info* out)
+{
+    if (!ep || !cx) return QG_EINVAL;
+    const EpView v = {&ep->part[0], &ep->part[1], ep->e_complex, nullptr, ep, cx};
+    return classify_view(d, &v, opt_flags, out);
+}
+
+int qgemul_cmul_plan_form(const qgemul_desc* d, const qgemul_epilogue_cplx* ep, const qgemul_cmul* const cx[QG_MAX_EW], qgemul_cmul_form* out)
+{
+    if (!d || !ep || !cx || !out) return QG_EINVAL;
+    memset(out, 0, sizeof *out);
+    if (!d->is_complex) return QG_EINVAL;
+    const EpView v = {&ep->part[0], &ep->part[1], ep->e_complex, nullptr, ep, cx};
+    if (!view_has_cmul(&v)) {
+        for (int k = 0; k < QG_MAX_EW; ++k)
+            if (cx[k]) return QG_EINVAL;
+        return QG_OK;
+    }
+    QEpTable t[2];
+    int bits = 0;
+    const int st = qg_analyze_epcx(d->c, ep, cx, t, nullptr, &bits, nullptr, 0);
+    if (st == QG_OK) {
+        out->has_cmul = 1;
+        out->bits32 = t[0].bits32;
+        out->max_bits = bits;
+    }
+    return st;
 }
 
 int qgemul_ctx_create(int device, qgemul_ctx** out)
@@ -842,6 +906,14 @@ int qgemul_plan_create_epc(qgemul_ctx* c, const qgemul_desc* d, const qgemul_epi
     return plan_create_view(c, d, &v, opt_flags, out);
 }
 
+int qgemul_plan_create_epcx(qgemul_ctx* c, const qgemul_desc* d, const qgemul_epilogue_cplx* ep, const qgemul_cmul* const cx[QG_MAX_EW],
+                            uint32_t opt_flags, qgemul_plan** out)
+{
+    if (!ep || !cx) return QG_EINVAL;
+    const EpView v = {&ep->part[0], &ep->part[1], ep->e_complex, nullptr, ep, cx};
+    return plan_create_view(c, d, &v, opt_flags, out);
+}
+
 static int plan_create_view(qgemul_ctx* c, const qgemul_desc* d, const EpView* ev, uint32_t opt_flags, qgemul_plan** out)
 {
     if (!c || !d || !out) return QG_EINVAL;
@@ -860,12 +932,16 @@ static int plan_create_view(qgemul_ctx* c, const qgemul_desc* d, const EpView* e
             memcpy(p->e_cplx, ev->e_cplx, sizeof p->e_cplx);
         }
         for (int k = 0; ev->ax && k < QG_MAX_EW; ++k) p->has_ax |= ev->ax[k] != nullptr;
+        p->has_cmul = view_has_cmul(ev) ? 1 : 0;
+        for (int k = 0; p->has_cmul && k < QG_MAX_EW; ++k)
+            if (ev->cx[k]) p->cx[k] = *ev->cx[k];
     }
+    QCmulStage cmt[QG_MAX_EW];
     QApproxTable* axt = p->has_ax ? new (std::nothrow) QApproxTable[QG_MAX_EW] : nullptr;
     if (p->has_ax && !axt) { delete p; return QG_EINVAL; }
     struct AxtGuard { QApproxTable* t; ~AxtGuard() { delete[] t; } } axt_guard = {axt};
     int st = plan_geometry(d, opt_flags, &p->an, &p->info, &p->LA, &p->LB, &p->cfg, &p->pa, &p->pb, &p->pc, &p->ha, &p->hb, &p->hc,
-                           ev, &p->ept, &p->pc_c, &p->ept_im, &p->comp, axt);
+                           ev, &p->ept, &p->pc_c, &p->ept_im, &p->comp, axt, p->has_cmul ? cmt : nullptr);
     if (st != QG_OK) { delete p; return st; }
     p->variant = p->cfg.variant;
     p->tc = qg_tree_choice(&p->an, d, opt_flags, true);
@@ -933,6 +1009,14 @@ static int plan_create_view(qgemul_ctx* c, const qgemul_desc* d, const EpView* e
             return QG_EHIP;
         }
     }
+    if (p->has_cmul) {
+        // the pre-resolved records of the CMUL stages: one device buffer (host temporaries: copied before they go)
+        if (hipMalloc((void**)&p->cm_dev, sizeof cmt) != hipSuccess ||
+            hipMemcpyAsync(p->cm_dev, cmt, sizeof cmt, hipMemcpyHostToDevice, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
+            qgemul_plan_destroy(p);
+            return QG_EHIP;
+        }
+    }
     *out = p;
     return QG_OK;
 }
@@ -950,6 +1034,7 @@ void qgemul_plan_destroy(qgemul_plan* p)
     hipFree(p->comp_slabs);
     hipFree(p->comp_acc);
     for (int k = 0; k < QG_MAX_EW; ++k) hipFree(p->ax_dev[k]);
+    hipFree(p->cm_dev);
     delete p;
 }
 
@@ -1136,6 +1221,23 @@ static int run_chain_pass(qgemul_plan* p, const void* packedC, void* packedD, co
         for (int k = 0; k < QG_MAX_EW; ++k) x.ax[k] = p->ax_dev[k];
         x.force_general = (p->flags & QG_OPT_APPROX_GENERAL) ? 1 : 0;   // result-identical form choice (include/qgemul.h)
         QG_HIP(qg_launch_approx(x, st));
+        return QG_OK;
+    }
+    if (p->has_cmul) {
+        // a CMUL stage needs both parts of an element in one thread: ONE pass whose lanes own both halves
+        QCplxPassArgs x;
+        memset(&x, 0, sizeof x);
+        x.C = g.C;
+        x.D = g.D;
+        x.n = g.n;
+        x.cbytes = g.cbytes;
+        x.t[0] = p->ept;
+        x.t[1] = p->ept_im;
+        x.a = a;
+        for (int k = 0; k < p->ept.n; ++k) x.scalar_im[k] = args->e_scalar_im[k];
+        memcpy(x.e_cplx, p->e_cplx, sizeof x.e_cplx);
+        x.cm = p->cm_dev;
+        QG_HIP(qg_launch_eltwise_cplx(x, st));
         return QG_OK;
     }
     QG_HIP(qg_launch_eltwise(g, st));
@@ -1586,6 +1688,8 @@ struct RunCache {
     bool has_pe = false, pe_cplx = false;
     qgemul_approx* pax = nullptr;     // QG_MAX_EW tables of the cached plan's APPROX stages (allocated at the first such plan)
     uint8_t pax_on[QG_MAX_EW] = {};
+    qgemul_cmul pcx[QG_MAX_EW];       // the cached plan's CMUL records (pcx_on[k]: the caller passed cx[k])
+    uint8_t pcx_on[QG_MAX_EW] = {};
     uint32_t pflags = 0;
     enum { NBUF = 6 + 16 };   // 0-5: host-layout A, B, C and packed A, B, C; behind them: the epilogue operands (2 per stage) or, on the
                               // root of a sharded call, the landing buffers of the other bands
@@ -1666,6 +1770,19 @@ bool same_tables(const RunCache& c, const qgemul_approx* const* ax)
     return true;
 }
 
+bool same_cmul(const RunCache& c, const qgemul_cmul* const* cx)
+{
+    for (int k = 0; k < QG_MAX_EW; ++k) {
+        const qgemul_cmul* t = cx ? cx[k] : nullptr;
+        if ((t != nullptr) != (c.pcx_on[k] != 0)) return false;
+        if (!t) continue;
+        if (t->cmul != c.pcx[k].cmul) return false;
+        for (int i = 0; i < 8; ++i)
+            if (!same_fmt(t->mul[i], c.pcx[k].mul[i])) return false;
+    }
+    return true;
+}
+
 int cache_buffer(RunCache& c, int i, size_t bytes, void** out)   // (the caller has made the cache's device current)
 {
     if (bytes > c.cap[i]) {
@@ -1700,6 +1817,7 @@ static void release_cache(RunCache& c)
     delete[] c.pax;
     c.pax = nullptr;
     memset(c.pax_on, 0, sizeof c.pax_on);
+    memset(c.pcx_on, 0, sizeof c.pcx_on);
 }
 
 namespace {
@@ -1750,6 +1868,14 @@ int qgemul_run_epc(const qgemul_desc* d, const qgemul_epilogue_cplx* ep, void* C
     return run_view(d, &v, C, A, B, E, o);
 }
 
+int qgemul_run_epcx(const qgemul_desc* d, const qgemul_epilogue_cplx* ep, const qgemul_cmul* const cx[QG_MAX_EW], void* C, const void* A,
+                    const void* B, const void* const* E, const qgemul_opts* o)
+{
+    if (!ep || !cx) return QG_EINVAL;
+    const EpView v = {&ep->part[0], &ep->part[1], ep->e_complex, nullptr, ep, cx};
+    return run_view(d, &v, C, A, B, E, o);
+}
+
 static int run_view(const qgemul_desc* d, const EpView* ev, void* C, const void* A, const void* B, const void* const* E, const qgemul_opts* o)
 {
     if (!d || !C || !A || !B) return QG_EINVAL;
@@ -1778,7 +1904,7 @@ static int run_view(const qgemul_desc* d, const EpView* ev, void* C, const void*
     const bool same_plan = c.plan && c.pflags == opts.flags && same_desc(c.pd, *d) && c.has_pe == (ep != nullptr) &&
                            (!ep || (same_epilogue(c.pe.part[0], *ep) && c.pe_cplx == (ev->im != nullptr) &&
                                     (!ev->im || (same_epilogue(c.pe.part[1], *ev->im) && !memcmp(c.pe.e_complex, ev->e_cplx, ep->n_stages))) &&
-                                    same_tables(c, ev->ax))) &&
+                                    same_tables(c, ev->ax) && same_cmul(c, ev->cx))) &&
                            (opts.device < 0 || opts.device == c.device);
     if (!same_plan) {
         // validate before touching the device so that descriptor errors are reported without a GPU
@@ -1815,6 +1941,12 @@ static int run_view(const qgemul_desc* d, const EpView* ev, void* C, const void*
             if (!c.pax) c.pax = new qgemul_approx[QG_MAX_EW];
             c.pax[k] = *ev->ax[k];
             c.pax_on[k] = 1;
+        }
+        memset(c.pcx_on, 0, sizeof c.pcx_on);
+        for (int k = 0; ev && ev->cx && k < QG_MAX_EW; ++k) {
+            if (!ev->cx[k]) continue;
+            c.pcx[k] = *ev->cx[k];
+            c.pcx_on[k] = 1;
         }
         c.pflags = opts.flags;
     }

@@ -1,6 +1,7 @@
 // qg_plan.cpp — descriptor analysis (host only).  See qg_plan.h.
 #include "qg_plan.h"
 #include "qg_approx.h"
+#include "qg_cmul.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -419,6 +420,66 @@ bool approx_stage(Ctx& c, const qgemul_ew_stage& s, const qgemul_approx& A, Val&
 
 } // namespace
 
+namespace {
+
+int ep_pow2_bytes(qfmt f)
+{
+    int b = (1 + (int)f.I + (int)f.F + 7) / 8, r = 1;
+    while (r < b) r *= 2;
+    return r;
+}
+
+// the chain kernels are 64-bit only: make_step gives a step bounds only up to 62 value bits
+bool chain_fmt_ok(Ctx& c, qfmt f)
+{
+    if (!fmt_ok(c, f)) return false;
+    if ((int)f.I + (int)f.F > 62) { c.fail(QG_EUNSUPPORTED, "element-wise chain format wider than 62 value bits"); return false; }
+    return true;
+}
+
+// One ADD / SUB / MUL / PASS stage: x, the running value, is replaced by the stage's result as assigned to the stage's tensor
+// (`last`: the last stage's result goes into D instead, by the caller's to_d).
+bool plain_stage(Ctx& c, const qgemul_ew_stage& s, bool last, Val& x, QEpStage& t)
+{
+    if (s.op == QG_EW_PASS) {
+        // the part is carried over in its own format (the imaginary part under a real operand, QuBLAS.h:3654/3670/3701);
+        // only the assignment to the stage's tensor touches it
+        memset(&t, 0, sizeof t);
+        t.op = QG_EW_PASS;
+        t.scalar = 1;                       // no operand is read
+        t.ebytes = 1;
+        t.node.q.identity = 1;
+        t.cvt.identity = 1;
+        if (!last) {
+            if (!chain_fmt_ok(c, s.t)) return false;
+            x = do_cvt(c, x, s.t, &t.cvt);
+        }
+        return true;
+    }
+    if (!chain_fmt_ok(c, s.e) || !chain_fmt_ok(c, s.r)) return false;
+    Val e;
+    e.f = s.e;
+    e.r = fmt_range(s.e);
+    t.op = s.op;
+    t.x_first = s.x_first ? 1 : 0;
+    t.scalar = s.e_scalar ? 1 : 0;
+    t.ebytes = ep_pow2_bytes(s.e);
+    const Val& first = t.x_first ? x : e;
+    const Val& second = t.x_first ? e : x;
+    x = s.op == QG_EW_MUL ? do_mul(c, first, second, s.r, &t.node) : do_addsub(c, first, second, s.r, s.op == QG_EW_SUB, &t.node);
+    memset(&t.cvt, 0, sizeof t.cvt);
+    t.cvt.identity = 1;
+    if (!last) {
+        if (!chain_fmt_ok(c, s.t)) return false;
+        x = do_cvt(c, x, s.t, &t.cvt);
+    }
+    return true;
+}
+
+bool shift32_ok(const QStep& q) { return q.identity || q.d <= 30; }
+
+} // namespace
+
 int qg_analyze_epx(qfmt cfmt, const qgemul_epilogue* ep, const qgemul_approx* const* ax, QEpTable* out, QApproxTable* axt, int* max_bits, char* reason,
                    size_t reason_len)
 {
@@ -430,20 +491,9 @@ int qg_analyze_epx(qfmt cfmt, const qgemul_epilogue* ep, const qgemul_approx* co
     an->status = QG_OK;
     Ctx c;
     c.out = an;
-    auto pow2_bytes = [](qfmt f) {
-        int b = (1 + (int)f.I + (int)f.F + 7) / 8, r = 1;
-        while (r < b) r *= 2;
-        return r;
-    };
-    // the chain kernels are 64-bit only: make_step gives a step bounds only up to 62 value bits
-    auto chain_fmt_ok = [&c](qfmt f) {
-        if (!fmt_ok(c, f)) return false;
-        if ((int)f.I + (int)f.F > 62) { c.fail(QG_EUNSUPPORTED, "element-wise chain format wider than 62 value bits"); return false; }
-        return true;
-    };
     do {
         if (!ep || ep->n_stages > QG_MAX_EW) { c.fail(QG_EINVAL, "null epilogue or too many stages"); break; }
-        if (!chain_fmt_ok(cfmt) || !chain_fmt_ok(ep->d)) break;
+        if (!chain_fmt_ok(c, cfmt) || !chain_fmt_ok(c, ep->d)) break;
         Val x;
         x.f = cfmt;
         x.r = fmt_range(cfmt);
@@ -466,45 +516,12 @@ int qg_analyze_epx(qfmt cfmt, const qgemul_epilogue* ep, const qgemul_approx* co
                 t.cvt.identity = 1;
                 if (!approx_stage(c, s, *ax[k], x, axt ? &axt[k] : nullptr, &ax32)) { ok = false; break; }
                 if (k + 1 < ep->n_stages) {
-                    if (!chain_fmt_ok(s.t)) { ok = false; break; }
+                    if (!chain_fmt_ok(c, s.t)) { ok = false; break; }
                     x = do_cvt(c, x, s.t, &t.cvt);
                 }
                 continue;
             }
-            if (s.op == QG_EW_PASS) {
-                // the part is carried over in its own format (the imaginary part under a real operand, QuBLAS.h:3654/3670/3701);
-                // only the assignment to the stage's tensor touches it
-                QEpStage& t = out->st[k];
-                memset(&t, 0, sizeof t);
-                t.op = QG_EW_PASS;
-                t.scalar = 1;                       // no operand is read
-                t.ebytes = 1;
-                t.node.q.identity = 1;
-                t.cvt.identity = 1;
-                if (k + 1 < ep->n_stages) {
-                    if (!chain_fmt_ok(s.t)) { ok = false; break; }
-                    x = do_cvt(c, x, s.t, &t.cvt);
-                }
-                continue;
-            }
-            if (!chain_fmt_ok(s.e) || !chain_fmt_ok(s.r)) { ok = false; break; }
-            Val e;
-            e.f = s.e;
-            e.r = fmt_range(s.e);
-            QEpStage& t = out->st[k];
-            t.op = s.op;
-            t.x_first = s.x_first ? 1 : 0;
-            t.scalar = s.e_scalar ? 1 : 0;
-            t.ebytes = pow2_bytes(s.e);
-            const Val& first = t.x_first ? x : e;
-            const Val& second = t.x_first ? e : x;
-            x = s.op == QG_EW_MUL ? do_mul(c, first, second, s.r, &t.node) : do_addsub(c, first, second, s.r, s.op == QG_EW_SUB, &t.node);
-            memset(&t.cvt, 0, sizeof t.cvt);
-            t.cvt.identity = 1;
-            if (k + 1 < ep->n_stages) {
-                if (!chain_fmt_ok(s.t)) { ok = false; break; }
-                x = do_cvt(c, x, s.t, &t.cvt);
-            }
+            ok = plain_stage(c, s, k + 1 == ep->n_stages, x, out->st[k]);
         }
         if (!ok) break;
         for (uint32_t k = ep->n_stages; ax && k < QG_MAX_EW; ++k)
@@ -512,15 +529,150 @@ int qg_analyze_epx(qfmt cfmt, const qgemul_epilogue* ep, const qgemul_approx* co
         if (!ok) break;
         do_cvt(c, x, ep->d, &out->to_d);
         out->n = (int)ep->n_stages;
-        out->dbytes = pow2_bytes(ep->d);
+        out->dbytes = ep_pow2_bytes(ep->d);
         out->max_bits = c.max_bits;
         {
             // 32-bit arithmetic: every intermediate (raw products and aligned operands included) within 32 bits, every
             // format within 32 storage bits, every rounding shift below 31
             bool ok32 = ax32 && c.max_bits <= 32 && g_fmt_bits_seen <= 32 && 1 + (int)cfmt.I + (int)cfmt.F <= 32;
-            auto shift_ok = [](const QStep& q) { return q.identity || q.d <= 30; };
-            for (int k = 0; k < out->n; ++k) ok32 = ok32 && shift_ok(out->st[k].node.q) && shift_ok(out->st[k].cvt) && out->st[k].ebytes <= 4;
-            out->bits32 = (ok32 && shift_ok(out->to_d)) ? 1 : 0;
+            for (int k = 0; k < out->n; ++k) ok32 = ok32 && shift32_ok(out->st[k].node.q) && shift32_ok(out->st[k].cvt) && out->st[k].ebytes <= 4;
+            out->bits32 = (ok32 && shift32_ok(out->to_d)) ? 1 : 0;
+        }
+        if (c.max_bits > 62) c.fail(QG_EUNSUPPORTED, "epilogue intermediate wider than 62 bits");
+    } while (0);
+    const int st = an->status;
+    if (reason && reason_len) snprintf(reason, reason_len, "%s", an->reason);
+    if (max_bits) *max_bits = c.max_bits;
+    delete an;
+    return st;
+}
+
+// A complex chain with CMUL stages (qg_cmul.h): the two part chains in lock step, since a CMUL stage needs both running values.
+// Every sub-operation goes through do_mul / do_addsub / do_cvt on the parts' whole ranges, so max_bits, bits32 and every refusal
+// of a plain chain hold here with no rule of their own.
+int qg_analyze_epcx(const qfmt cf[2], const qgemul_epilogue_cplx* ep, const qgemul_cmul* const* cx, QEpTable t[2], QCmulStage* cmt, int* max_bits,
+                    char* reason, size_t reason_len)
+{
+    memset(t, 0, 2 * sizeof *t);
+    if (cmt) memset(cmt, 0, QG_MAX_EW * sizeof *cmt);
+    g_fmt_bits_seen = 0;
+    QAnalysis* an = new QAnalysis;
+    memset(an, 0, sizeof *an);
+    an->status = QG_OK;
+    Ctx c;
+    c.out = an;
+    do {
+        if (!ep || !cx || ep->part[0].n_stages > QG_MAX_EW) { c.fail(QG_EINVAL, "null epilogue or too many stages"); break; }
+        if (ep->part[1].n_stages != ep->part[0].n_stages) { c.fail(QG_EINVAL, "complex chain: the part chains differ in length"); break; }
+        const uint32_t n = ep->part[0].n_stages;
+        bool ok = true;
+        Val x[2];
+        for (int p = 0; p < 2 && ok; ++p) {
+            ok = chain_fmt_ok(c, cf[p]) && chain_fmt_ok(c, ep->part[p].d);
+            if (!ok) break;
+            x[p].f = cf[p];
+            x[p].r = fmt_range(cf[p]);
+        }
+        bool cm32 = true;
+        for (uint32_t k = 0; k < n && ok; ++k) {
+            const qgemul_ew_stage* s[2] = {&ep->part[0].stage[k], &ep->part[1].stage[k]};
+            const bool last = k + 1 == n;
+            for (int p = 0; p < 2 && ok; ++p)
+                if (s[p]->op < QG_EW_ADD || s[p]->op > QG_EW_CMUL || s[p]->op == QG_EW_APPROX) { c.fail(QG_EINVAL, "unknown element-wise op"); ok = false; }
+            if (!ok) break;
+            const bool cm = s[0]->op == QG_EW_CMUL;
+            if (cm != (s[1]->op == QG_EW_CMUL)) { c.fail(QG_EINVAL, "CMUL stage: op 6 in one part only"); ok = false; break; }
+            if (cm != (cx[k] != nullptr)) {
+                c.fail(QG_EINVAL, cm ? "CMUL stage without its record" : "a CMUL record for a stage that is no CMUL stage");
+                ok = false;
+                break;
+            }
+            if (!cm) {
+                for (int p = 0; p < 2 && ok; ++p) ok = plain_stage(c, *s[p], last, x[p], t[p].st[k]);
+                continue;
+            }
+            const qgemul_cmul& M = *cx[k];
+            if ((s[0]->x_first != 0) != (s[1]->x_first != 0) || (s[0]->e_scalar != 0) != (s[1]->e_scalar != 0)) {
+                c.fail(QG_EINVAL, "CMUL stage: x_first / e_scalar differ between the parts");
+                ok = false;
+                break;
+            }
+            if (!ep->e_complex[k]) { c.fail(QG_EINVAL, "CMUL stage: the operand is complex (e_complex = 1)"); ok = false; break; }
+            if (M.cmul != QG_CMUL_BASIC && M.cmul != QG_CMUL_TF) { c.fail(QG_EINVAL, "CMUL stage: cmul is neither Basic nor TF"); ok = false; break; }
+            const bool tf = M.cmul == QG_CMUL_TF;
+            const int n_nodes = tf ? 8 : 6, RE = tf ? QG_T_RE : QG_B_RE, IM = tf ? QG_T_IM : QG_B_IM;
+            if (!same(s[0]->r, M.mul[RE]) || !same(s[1]->r, M.mul[IM])) { c.fail(QG_EINVAL, "CMUL stage: r is not the RE / IM slot of mul[]"); ok = false; break; }
+            for (int i = 0; i < n_nodes && ok; ++i) ok = chain_fmt_ok(c, M.mul[i]);
+            for (int p = 0; p < 2 && ok; ++p) ok = chain_fmt_ok(c, s[p]->e);
+            if (!ok) break;
+            Val e[2];
+            for (int p = 0; p < 2; ++p) {
+                e[p].f = s[p]->e;
+                e[p].r = fmt_range(s[p]->e);
+            }
+            const bool xf = s[0]->x_first != 0;
+            const Val &a = xf ? x[0] : e[0], &b = xf ? x[1] : e[1], &cc = xf ? e[0] : x[0], &d = xf ? e[1] : x[1];
+            QNode nd[8];
+            memset(nd, 0, sizeof nd);
+            Val re, im;
+            if (!tf) {
+                const Val ac = do_mul(c, a, cc, M.mul[QG_B_AC], &nd[QG_B_AC]), bd = do_mul(c, b, d, M.mul[QG_B_BD], &nd[QG_B_BD]);
+                const Val ad = do_mul(c, a, d, M.mul[QG_B_AD], &nd[QG_B_AD]), bc = do_mul(c, b, cc, M.mul[QG_B_BC], &nd[QG_B_BC]);
+                re = do_addsub(c, ac, bd, M.mul[QG_B_RE], true, &nd[QG_B_RE]);
+                im = do_addsub(c, ad, bc, M.mul[QG_B_IM], false, &nd[QG_B_IM]);
+            } else {
+                const Val ab = do_addsub(c, a, b, M.mul[QG_T_AB], false, &nd[QG_T_AB]), cd = do_addsub(c, cc, d, M.mul[QG_T_CD], false, &nd[QG_T_CD]);
+                const Val ba = do_addsub(c, b, a, M.mul[QG_T_BA], true, &nd[QG_T_BA]);
+                const Val A = do_mul(c, ab, cc, M.mul[QG_T_A], &nd[QG_T_A]), B = do_mul(c, cd, b, M.mul[QG_T_B], &nd[QG_T_B]);
+                const Val C = do_mul(c, ba, d, M.mul[QG_T_C], &nd[QG_T_C]);
+                re = do_addsub(c, A, B, M.mul[QG_T_RE], true, &nd[QG_T_RE]);
+                im = do_addsub(c, B, C, M.mul[QG_T_IM], true, &nd[QG_T_IM]);
+            }
+            for (int i = 0; i < n_nodes; ++i) cm32 = cm32 && shift32_ok(nd[i].q);
+            const int eb = ep_pow2_bytes(s[0]->e) > ep_pow2_bytes(s[1]->e) ? ep_pow2_bytes(s[0]->e) : ep_pow2_bytes(s[1]->e);
+            x[0] = re;
+            x[1] = im;
+            for (int p = 0; p < 2 && ok; ++p) {
+                QEpStage& q = t[p].st[k];
+                memset(&q, 0, sizeof q);
+                q.op = QG_EW_CMUL;
+                q.x_first = xf ? 1 : 0;
+                q.scalar = s[0]->e_scalar ? 1 : 0;
+                q.ebytes = eb;
+                q.node = nd[p ? IM : RE];
+                q.cvt.identity = 1;
+                if (!last) {
+                    ok = chain_fmt_ok(c, s[p]->t);
+                    if (ok) x[p] = do_cvt(c, x[p], s[p]->t, &q.cvt);
+                }
+            }
+            if (cmt) {
+                QCmulStage& q = cmt[k];
+                q.cmul = M.cmul;
+                q.x_first = xf ? 1 : 0;
+                q.scalar = s[0]->e_scalar ? 1 : 0;
+                q.ebytes = eb;
+                memcpy(q.n, nd, sizeof nd);
+            }
+        }
+        if (!ok) break;
+        for (uint32_t k = n; k < QG_MAX_EW; ++k)
+            if (cx[k]) { c.fail(QG_EINVAL, "a CMUL record beyond the last stage"); ok = false; }
+        if (!ok) break;
+        for (int p = 0; p < 2; ++p) {
+            do_cvt(c, x[p], ep->part[p].d, &t[p].to_d);
+            t[p].n = (int)n;
+            t[p].dbytes = ep_pow2_bytes(ep->part[p].d);
+        }
+        // the one pass runs in 32-bit arithmetic when that holds for both chains and every CMUL node
+        bool ok32 = cm32 && c.max_bits <= 32 && g_fmt_bits_seen <= 32 && sbits(cf[0]) <= 32 && sbits(cf[1]) <= 32;
+        for (int p = 0; p < 2; ++p) {
+            for (uint32_t k = 0; k < n; ++k) ok32 = ok32 && shift32_ok(t[p].st[k].node.q) && shift32_ok(t[p].st[k].cvt) && t[p].st[k].ebytes <= 4;
+            ok32 = ok32 && shift32_ok(t[p].to_d);
+        }
+        for (int p = 0; p < 2; ++p) {
+            t[p].bits32 = ok32 ? 1 : 0;
+            t[p].max_bits = c.max_bits;
         }
         if (c.max_bits > 62) c.fail(QG_EUNSUPPORTED, "epilogue intermediate wider than 62 bits");
     } while (0);

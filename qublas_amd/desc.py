@@ -107,6 +107,17 @@ class qgemul_approx_form(C.Structure):
                 ("threshold", (C.c_int64 * QG_MAX_SEG) * QG_MAX_EW)]
 
 
+EW_CMUL = 6
+
+
+class qgemul_cmul(C.Structure):
+    _fields_ = [("cmul", C.c_uint8), ("reserved", C.c_uint8 * 7), ("mul", qfmt * 8)]
+
+
+class qgemul_cmul_form(C.Structure):
+    _fields_ = [("has_cmul", C.c_int32), ("bits32", C.c_int32), ("max_bits", C.c_int32), ("reserved", C.c_int32)]
+
+
 class qgemul_info(C.Structure):
     _fields_ = [("cls", C.c_int32), ("supported", C.c_int32), ("max_bits", C.c_int32),
                 ("in_bits", C.c_int32 * 2), ("limbs", C.c_int32 * 2), ("kernel", C.c_int32),
@@ -596,48 +607,98 @@ class EwC:
     into: Optional["Qcomplex"] = None
 
 
+def _lower_stage_cplx(epc: qgemul_epilogue_cplx, k: int, st: "EwC", x, last: bool):
+    """stage k of a part-wise chain on the running part formats x = [real, imag]; returns the part formats after the stage"""
+    opc = {"add": EW_ADD, "sub": EW_SUB, "mul": EW_MUL}
+    cplx = isinstance(st.e, Qcomplex)
+    if cplx and st.op == "mul":
+        raise ValueError("complex x complex multiplication mixes the parts: not an element-wise epilogue stage")
+    epc.e_complex[k] = 1 if cplx else 0
+    r = [None, None]
+    for p in range(2):
+        sg = epc.part[p].stage[k]
+        e = (st.e.real, st.e.imag)[p] if cplx else st.e
+        own = st.real_tags if p == 0 else st.imag_tags
+        sg.x_first = 1 if st.x_first else 0
+        sg.e_scalar = 1 if st.scalar else 0
+        sg.e = e.c()
+        if cplx or st.op == "mul":
+            t = _pick(own, st.tags)
+        else:
+            t = _tags(st.tags)
+            if p == 1 and (st.op == "add" or st.x_first):
+                sg.op = EW_PASS                 # the imaginary part is carried over
+                sg.e_scalar = 1
+                r[p] = x[p]
+                sg.r = r[p].c()
+                continue
+            if p == 1:
+                sg.e_scalar = 1                 # real - complex: Qsub(zero of the operand's type, x.imag)
+        first, second = (x[p], e) if st.x_first else (e, x[p])
+        r[p] = mul_merge(first, second, t) if st.op == "mul" else add_merge(first, second, t)
+        sg.op = opc[st.op]
+        sg.r = r[p].c()
+    x = [((st.into.real, st.into.imag)[p] if (st.into is not None and not last) else r[p]) for p in range(2)]
+    for p in range(2):
+        epc.part[p].stage[k].t = x[p].c()
+    return x
+
+
 def lower_epilogue_cplx(c: "Qcomplex", stages, d: "Qcomplex") -> qgemul_epilogue_cplx:
     stages = list(stages)
     if len(stages) > QG_MAX_EW:
         raise ValueError("too many element-wise stages")
     epc = qgemul_epilogue_cplx()
     x = [c.real, c.imag]
-    opc = {"add": EW_ADD, "sub": EW_SUB, "mul": EW_MUL}
     for p in range(2):
         epc.part[p].n_stages = len(stages)
     for k, st in enumerate(stages):
-        cplx = isinstance(st.e, Qcomplex)
-        if cplx and st.op == "mul":
-            raise ValueError("complex x complex multiplication mixes the parts: not an element-wise epilogue stage")
-        epc.e_complex[k] = 1 if cplx else 0
-        r = [None, None]
-        for p in range(2):
-            sg = epc.part[p].stage[k]
-            e = (st.e.real, st.e.imag)[p] if cplx else st.e
-            own = st.real_tags if p == 0 else st.imag_tags
-            sg.x_first = 1 if st.x_first else 0
-            sg.e_scalar = 1 if st.scalar else 0
-            sg.e = e.c()
-            if cplx or st.op == "mul":
-                t = _pick(own, st.tags)
-            else:
-                t = _tags(st.tags)
-                if p == 1 and (st.op == "add" or st.x_first):
-                    sg.op = EW_PASS                 # the imaginary part is carried over
-                    sg.e_scalar = 1
-                    r[p] = x[p]
-                    sg.r = r[p].c()
-                    continue
-                if p == 1:
-                    sg.e_scalar = 1                 # real - complex: Qsub(zero of the operand's type, x.imag)
-            first, second = (x[p], e) if st.x_first else (e, x[p])
-            r[p] = mul_merge(first, second, t) if st.op == "mul" else add_merge(first, second, t)
-            sg.op = opc[st.op]
-            sg.r = r[p].c()
-        for p in range(2):
-            x[p] = ((st.into.real, st.into.imag)[p] if (st.into is not None and k + 1 < len(stages)) else r[p])
-            epc.part[p].stage[k].t = x[p].c()
+        x = _lower_stage_cplx(epc, k, st, x, k + 1 == len(stages))
     epc.part[0].d = d.real.c()
     epc.part[1].d = d.imag.c()
     return epc
 
+
+# ---- ... with complex x complex multiplication as a stage (include/qgemul.h, QG_EW_CMUL; BasicComplexMul / TFComplexMul, QuBLAS.h:3421-3534) ----
+
+def cmul_record(first: "Qcomplex", second: "Qcomplex", m: MulArgs):
+    """(qgemul_cmul, result Qcomplex) of Qmul<m>(first, second): every sub-operation's result format, quirks applied"""
+    cmul, slots = complex_mul_slots(first, second, m)
+    rec = qgemul_cmul()
+    rec.cmul = cmul
+    for i, q in enumerate(slots):
+        rec.mul[i] = q.c()
+    re, im = (slots[6], slots[7]) if cmul == CMUL_TF else (slots[4], slots[5])
+    return rec, Qcomplex(re, im)
+
+
+def lower_epilogue_cplx_x(c: "Qcomplex", stages, d: "Qcomplex"):
+    """lower_epilogue_cplx for chains that may hold EwC("mul", e=Qcomplex, tags=BasicComplexMul(...) | TFComplexMul(...) | None)
+    stages: (qgemul_epilogue_cplx, [qgemul_cmul or None per stage slot, QG_MAX_EW entries]).  Every other stage lowers as in
+    lower_epilogue_cplx (the same per-stage code)."""
+    stages = list(stages)
+    if len(stages) > QG_MAX_EW:
+        raise ValueError("too many element-wise stages")
+    epc = qgemul_epilogue_cplx()
+    records = [None] * QG_MAX_EW
+    x = c
+    for p in range(2):
+        epc.part[p].n_stages = len(stages)
+    for k, st in enumerate(stages):
+        last = k + 1 == len(stages)
+        if isinstance(st.e, Qcomplex) and st.op == "mul":
+            first, second = (x, st.e) if st.x_first else (st.e, x)
+            records[k], r = cmul_record(first, second, st.tags)
+            epc.e_complex[k] = 1
+            x = st.into if (st.into is not None and not last) else r
+            for p, (ep_, rp, xp) in enumerate(((st.e.real, r.real, x.real), (st.e.imag, r.imag, x.imag))):
+                sg = epc.part[p].stage[k]
+                sg.op = EW_CMUL
+                sg.x_first = 1 if st.x_first else 0
+                sg.e_scalar = 1 if st.scalar else 0
+                sg.e, sg.r, sg.t = ep_.c(), rp.c(), xp.c()
+            continue
+        x = Qcomplex(*_lower_stage_cplx(epc, k, st, [x.real, x.imag], last))
+    epc.part[0].d = d.real.c()
+    epc.part[1].d = d.imag.c()
+    return epc, records
