@@ -509,6 +509,42 @@ void Qgemul(TC& C, const TA& A, const TB& B)
     if (st != QG_OK) throw std::runtime_error(std::string("Qgemul: ") + qgemul_strerror(st));
 }
 
+// ---- batched Qgemul: `Bt` independent GEMMs of one descriptor on 3-d tensors ----
+//     Qu<dim<M, N, Bt>, EC> C;  Qu<dim<M, K, Bt>, EA> A;  Qu<dim<K, N, Bt>, EB> B;     (A: dim<K, M, Bt> under QgemulTransposedA<true>)
+//     QgemulBatched<tags...>(C, A, B);      // member b:  Qgemul<tags...>(C[:, :, b], A[:, :, b], B[:, :, b])
+// The column-major index makes the members contiguous at stride rows * cols.  Same tags and same lowering as Qgemul: the
+// descriptor is the one Qgemul lowers for ONE member (qgemul_run_batched, qgemul.h); small linear-class members run as one launch.
+template <typename... Tags, size_t CM, size_t CN, size_t CB, size_t AR, size_t AC, size_t AB, size_t BR, size_t BN, size_t BB, class EC, class EA, class EB>
+qgemul_desc QgemulBatched_lower_types(std::type_identity<Qu_s<dim<CM, CN, CB>, EC>>, std::type_identity<Qu_s<dim<AR, AC, AB>, EA>>,
+                                      std::type_identity<Qu_s<dim<BR, BN, BB>, EB>>, int64_t* batch, int64_t* strides)
+{
+    static_assert(CB == AB && CB == BB && CB >= 1, "QgemulBatched: C, A and B hold the same number of members (their last extent)");
+    *batch = int64_t(CB);
+    strides[0] = int64_t(CM * CN);
+    strides[1] = int64_t(AR * AC);
+    strides[2] = int64_t(BR * BN);
+    return Qgemul_lower_types<Tags...>(std::type_identity<Qu_s<dim<CM, CN>, EC>>{}, std::type_identity<Qu_s<dim<AR, AC>, EA>>{},
+                                       std::type_identity<Qu_s<dim<BR, BN>, EB>>{});
+}
+// the member descriptor, the member count and the strides of C, A, B in elements
+template <typename... Tags, class TC, class TA, class TB>
+qgemul_desc QgemulBatched_lower(const TC&, const TA&, const TB&, int64_t* batch, int64_t* strides)
+{
+    return QgemulBatched_lower_types<Tags...>(std::type_identity<TC>{}, std::type_identity<TA>{}, std::type_identity<TB>{}, batch, strides);
+}
+template <typename... Tags, class TC, class TA, class TB>
+void QgemulBatched(TC& C, const TA& A, const TB& B)
+{
+    int64_t batch = 0, strides[3] = {0, 0, 0};
+    qgemul_desc d = QgemulBatched_lower<Tags...>(C, A, B, &batch, strides);
+    d.flags |= QgemulDescFlags();
+    qgemul_opts opts{};
+    opts.device = -1;
+    opts.flags = QgemulRunFlags();
+    const int st = qgemul_run_batched(&d, batch, C.data.data(), A.data.data(), B.data.data(), strides[0], strides[1], strides[2], &opts);
+    if (st != QG_OK) throw std::runtime_error(std::string("QgemulBatched: ") + qgemul_strerror(st));
+}
+
 // ------------------------------------------------------------------ element-wise operators after the GEMM (SURVEY.md §8-f "next" #2)
 // The reference's lazy tensor operators Qmul / Qadd / Qsub<tags…>(tensor, tensor | scalar) (QuBLAS.h:3780-3877,
 // front-ends :4079-4100) applied to a Qgemul result:

@@ -297,6 +297,43 @@ int qgemul_fill_packed(qgemul_plan* p, int operand, uint64_t seed, int dist, voi
 int qgemul_time_execute(qgemul_plan* p, void* packedC, const void* packedA, const void* packedB,
                         int warmup, int iters, float* avg_ms);
 
+/* ---- batched Qgemul: `batch` independent GEMMs of ONE descriptor (same M, N, K, formats and tags) ----
+ * Member b is exactly  Qgemul<...>(C_b, A_b, B_b);  its operands start member_stride host elements after those of member b - 1
+ * (a stride in elements of that operand, at least the member's extent (cols - 1) * ld + rows, never 0).  A SHARED operand (one B
+ * for every A_b, or one A) needs no batch: it is a plain Qgemul on the stacked A (or B).
+ * Linear-class members on the lock-step MFMA kernels run as ONE launch: the members' packed operands are stacked by row
+ * tiles — the stack is itself a packed A and a packed B, with one plane mask and one row-sum array for all members — and the
+ * workgroups walk the block diagonal of the big product.  Everything else (tree class, complex, ring and
+ * composite plans, members large enough for the two-group kernels, conversions that take the raw-dot-product pass) runs member
+ * by member on the existing path through the same entry points, so every supported descriptor is served.
+ * The packed layouts belong to the batched plan (they may differ from the plain plan of the same descriptor); packed C is the
+ * members' packed Cs back to back.  qgemul_info.packed_bytes[] of a batched classify / plan are for the whole batch, ops too.
+ * A batched plan is destroyed with qgemul_plan_destroy and answers qgemul_plan_info and qgemul_plan_packed_layout (in the one-
+ * launch form: the stack's trailer, row sums and rows); every other plain entry point refuses it (QG_EINVAL), and the batched
+ * entry points refuse a plain plan.  Epilogue chains on batched plans do not exist yet.
+ * QG_EINVAL: batch < 1, a stride below the member's extent (0 included), more than 2^31 - 1 output tiles in the batch.
+ *   qgemul_classify_batched            pure host code
+ *   qgemul_classify_batched_launches   pure host code: what qgemul_plan_batched_launches will answer (< 0: a status)
+ *   qgemul_plan_batched_launches       kernel launches per qgemul_execute_batched: 1 in the block-diagonal form (a 3 x 3-limb
+ *                                      launch is a pair whose partner returns at once, as in qgemul_execute; it counts once),
+ *                                      else batch times what one member's qgemul_execute issues
+ *   qgemul_pack_batched                operand A or B of every member -> the batch's packed operand (ld as in qgemul_pack)
+ *   qgemul_unpack_c_batched            the batch's packed C -> the members' C tensors; bytes between them are not written
+ *   qgemul_execute_batched             the hot path, asynchronous on the ctx stream
+ *   qgemul_run_batched                 one-shot, host pointers, synchronous; strides in host elements; lda / ldb / ldc from
+ *                                      opts; the plan lives in the calling thread's cache like qgemul_run's (a changed batch
+ *                                      count re-plans); QG_OPT_ALL_DEVICES: QG_EUNSUPPORTED */
+int qgemul_classify_batched(const qgemul_desc* d, int64_t batch, uint32_t opt_flags, qgemul_info* out);
+int qgemul_classify_batched_launches(const qgemul_desc* d, int64_t batch, uint32_t opt_flags);
+int qgemul_plan_create_batched(qgemul_ctx* c, const qgemul_desc* d, int64_t batch, uint32_t opt_flags, qgemul_plan** out);
+int qgemul_plan_batched_launches(const qgemul_plan* p);
+int qgemul_pack_batched(qgemul_plan* p, int operand, const void* src_dev, int64_t ld, int64_t member_stride, void* packed_dev);
+int qgemul_unpack_c_batched(qgemul_plan* p, const void* packed_dev, void* dst_dev, int64_t ld, int64_t member_stride);
+int qgemul_execute_batched(qgemul_plan* p, void* packedC, const void* packedA, const void* packedB);
+int qgemul_time_execute_batched(qgemul_plan* p, void* packedC, const void* packedA, const void* packedB, int warmup, int iters, float* avg_ms);
+int qgemul_run_batched(const qgemul_desc* d, int64_t batch, void* C, const void* A, const void* B, int64_t strideC, int64_t strideA, int64_t strideB,
+                       const qgemul_opts* o);
+
 /* ---- fused element-wise epilogue ----
  * The reference's lazy tensor operators (Qmul/Qadd/Qsub on tensors, QuBLAS.h:3780-3877, front-ends
  * :4079-4100) evaluate  Qop<tags...>(x[i], e[i])  per element on operator[] (:3795-3798, :3828-3831,

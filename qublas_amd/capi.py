@@ -44,6 +44,8 @@ EXPORTS = [
     "qgemul_comm_sync", "qgemul_comm_barrier", "qgemul_comm_max_f64", "qgemul_last_rccl_error", "qgemul_ctx_device",
     "qgemul_classify_epx", "qgemul_plan_create_epx", "qgemul_run_epx", "qgemul_plan_approx_uniform", "qgemul_sizeof", "qgemul_approx_plan_form", "qgemul_apply_epilogue", "qgemul_time_apply_epilogue", "qgemul_packed_c_bytes", "qgemul_pack_c",
     "qgemul_classify_epcx", "qgemul_plan_create_epcx", "qgemul_run_epcx", "qgemul_cmul_plan_form",
+    "qgemul_classify_batched", "qgemul_classify_batched_launches", "qgemul_plan_create_batched", "qgemul_plan_batched_launches", "qgemul_pack_batched",
+    "qgemul_unpack_c_batched", "qgemul_execute_batched", "qgemul_time_execute_batched", "qgemul_run_batched",
 ]
 # qgemul_sizeof ids (include/qgemul.h) and the ctypes mirror each one must match
 SIZEOF_MIRRORS = {0: qfmt, 1: qgemul_desc, 2: qgemul_opts, 3: qgemul_info, 4: qgemul_ew_stage, 5: qgemul_epilogue, 6: qgemul_ep_args,
@@ -145,6 +147,15 @@ def lib() -> C.CDLL:
         L.qgemul_plan_create_epcx.argtypes = [vp, pd, pec, pcx, u32, C.POINTER(vp)]
         L.qgemul_run_epcx.argtypes = [pd, pec, pcx, vp, vp, vp, C.POINTER(vp), C.POINTER(qgemul_opts)]
         L.qgemul_cmul_plan_form.argtypes = [pd, pec, pcx, C.POINTER(qgemul_cmul_form)]
+        L.qgemul_classify_batched.argtypes = [pd, i64, u32, C.POINTER(qgemul_info)]
+        L.qgemul_classify_batched_launches.argtypes = [pd, i64, u32]
+        L.qgemul_plan_create_batched.argtypes = [vp, pd, i64, u32, C.POINTER(vp)]
+        L.qgemul_plan_batched_launches.argtypes = [vp]
+        L.qgemul_pack_batched.argtypes = [vp, C.c_int, vp, i64, i64, vp]
+        L.qgemul_unpack_c_batched.argtypes = [vp, vp, vp, i64, i64]
+        L.qgemul_execute_batched.argtypes = [vp, vp, vp, vp]
+        L.qgemul_time_execute_batched.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(C.c_float)]
+        L.qgemul_run_batched.argtypes = [pd, i64, vp, vp, vp, i64, i64, i64, C.POINTER(qgemul_opts)]
         L.qgemul_sizeof.argtypes = [C.c_int]
         L.qgemul_sizeof.restype = C.c_size_t
         _lib = L
@@ -273,6 +284,34 @@ def run(desc: qgemul_desc, C_out: np.ndarray, A: np.ndarray, B: np.ndarray, *, l
     o = qgemul_opts(lda, ldb, ldc, device, flags)
     _chk(lib().qgemul_run(C.byref(desc), C_out.ctypes.data_as(C.c_void_p), A.ctypes.data_as(C.c_void_p),
                           B.ctypes.data_as(C.c_void_p), C.byref(o)), "qgemul_run")
+    return C_out
+
+
+def classify_batched_status(desc: qgemul_desc, batch: int, flags: int = 0):
+    """qgemul_classify_batched: (status, info); info.packed_bytes are for the whole batch"""
+    info = qgemul_info()
+    st = lib().qgemul_classify_batched(C.byref(desc), batch, flags, C.byref(info))
+    return st, info
+
+
+def classify_batched_launches(desc: qgemul_desc, batch: int, flags: int = 0) -> int:
+    """kernel launches per execute of the batched plan (1: the block-diagonal form); a negative value is a status"""
+    return int(lib().qgemul_classify_batched_launches(C.byref(desc), batch, flags))
+
+
+def run_batched_status(desc: qgemul_desc, batch: int, C_out: np.ndarray, A: np.ndarray, B: np.ndarray, strideC: int, strideA: int, strideB: int, *,
+                       lda: int = 0, ldb: int = 0, ldc: int = 0, device: int = -1, flags: int = 0) -> int:
+    """qgemul_run_batched on host-layout numpy buffers (strides in host elements); returns the status"""
+    A = np.ascontiguousarray(A)
+    B = np.ascontiguousarray(B)
+    assert C_out.flags["C_CONTIGUOUS"]
+    o = qgemul_opts(lda, ldb, ldc, device, flags)
+    return int(lib().qgemul_run_batched(C.byref(desc), batch, C_out.ctypes.data_as(C.c_void_p), A.ctypes.data_as(C.c_void_p), B.ctypes.data_as(C.c_void_p),
+                                        strideC, strideA, strideB, C.byref(o)))
+
+
+def run_batched(desc: qgemul_desc, batch: int, C_out: np.ndarray, A: np.ndarray, B: np.ndarray, strideC: int, strideA: int, strideB: int, **kw) -> np.ndarray:
+    _chk(run_batched_status(desc, batch, C_out, A, B, strideC, strideA, strideB, **kw), "qgemul_run_batched")
     return C_out
 
 
@@ -504,4 +543,45 @@ class Plan:
         ms = C.c_float()
         _chk(lib().qgemul_time_execute(self.h, C.c_void_p(pC), C.c_void_p(pA), C.c_void_p(pB), warmup, iters,
                                        C.byref(ms)), "qgemul_time_execute")
+        return ms.value
+
+
+class BatchedPlan:
+    """A batched plan (include/qgemul.h, qgemul_*_batched): `batch` GEMMs of one descriptor at constant strides."""
+
+    def __init__(self, ctx: Context, desc: qgemul_desc, batch: int, flags: int = 0):
+        self.ctx = ctx
+        self.desc = desc
+        self.batch = batch
+        self.h = C.c_void_p()
+        _chk(lib().qgemul_plan_create_batched(ctx.h, C.byref(desc), batch, flags, C.byref(self.h)), "qgemul_plan_create_batched")
+        self.info = qgemul_info()
+        _chk(lib().qgemul_plan_info(self.h, C.byref(self.info)), "qgemul_plan_info")
+
+    def close(self):
+        if self.h:
+            lib().qgemul_plan_destroy(self.h)
+            self.h = C.c_void_p()
+
+    @property
+    def launches(self) -> int:
+        return int(lib().qgemul_plan_batched_launches(self.h))
+
+    def packed_layout(self, operand):
+        out = (C.c_int64 * 4)()
+        _chk(lib().qgemul_plan_packed_layout(self.h, operand, out), "qgemul_plan_packed_layout")
+        return tuple(int(x) for x in out)
+
+    def pack(self, operand: int, src_dev: int, packed_dev: int, member_stride: int, ld: int = 0):
+        _chk(lib().qgemul_pack_batched(self.h, operand, C.c_void_p(src_dev), ld, member_stride, C.c_void_p(packed_dev)), "qgemul_pack_batched")
+
+    def execute(self, pC: int, pA: int, pB: int):
+        _chk(lib().qgemul_execute_batched(self.h, C.c_void_p(pC), C.c_void_p(pA), C.c_void_p(pB)), "qgemul_execute_batched")
+
+    def unpack_c(self, pC: int, dst_dev: int, member_stride: int, ld: int = 0):
+        _chk(lib().qgemul_unpack_c_batched(self.h, C.c_void_p(pC), C.c_void_p(dst_dev), ld, member_stride), "qgemul_unpack_c_batched")
+
+    def time_execute(self, pC: int, pA: int, pB: int, warmup: int, iters: int) -> float:
+        ms = C.c_float()
+        _chk(lib().qgemul_time_execute_batched(self.h, C.c_void_p(pC), C.c_void_p(pA), C.c_void_p(pB), warmup, iters, C.byref(ms)), "qgemul_time_execute_batched")
         return ms.value

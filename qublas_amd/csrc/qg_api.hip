@@ -119,6 +119,15 @@ struct qgemul_plan {
     QComposite comp;      // composite linear plan (comp.on): limb groups x k-chunks of sub-GEMMs + an exact combine pass
     void* comp_slabs;     // comp.ga * comp.gb slabs of raw dot products, one common packed-C layout
     void* comp_acc;       // running exact sums between k-chunks (comp.nc > 1)
+    // batched plan (qgemul_plan_create_batched; batch > 0): `batch` GEMMs of desc at constant strides.  `member` is the plain plan of
+    // ONE member and owns every device resource; this object holds what belongs to the batch: info (packed_bytes of the whole
+    // batch), the packed operands' stride from member to member (mstride) and, in the block-diagonal form (bd: one launch of
+    // k_mfma's BD form over the stacked operands), the STACK's packed geometries in pa / pb — member's with batch times the
+    // rows, one plane-mask trailer and one row-sum array behind the planes of all members.  bd == 0: member by member on `member`
+    int64_t batch;
+    int bd, member_launches;
+    qgemul_plan* member;
+    int64_t mstride[3];
 };
 
 struct HostC { void* C; int64_t ld; };
@@ -244,8 +253,14 @@ static hipError_t comp_zero_rowsums(const qgemul_plan* p, int operand, void* pac
 static int plan_geometry(const qgemul_desc* d, uint32_t flags, QAnalysis* an, qgemul_info* info, int* pLA, int* pLB, QMfmaCfg* pVar,
                          QPackedGeom* pa, QPackedGeom* pb, QCGeom* pc, QHostElem* ha, QHostElem* hb, QHostElem* hc,
                          const EpView* ev = nullptr, QEpTable* ept = nullptr, QCGeom* pc_c = nullptr, QEpTable* ept_im = nullptr,
-                         QComposite* pcomp = nullptr, QApproxTable* axt = nullptr, QCmulStage* cmt = nullptr)
+                         QComposite* pcomp = nullptr, QApproxTable* axt = nullptr, QCmulStage* cmt = nullptr, int64_t batch = 0, int* pbd = nullptr)
 {
+    // batch > 0: the member of a batched plan.  Where k_mfma has a block-diagonal form for it, the tile geometry comes from
+    // qg_mfma_pick_batched (the batch's total tile count, the member's padding waste) and *pbd = 1: the packed layouts then belong
+    // to the batched plan and may differ from the plain plan of the same descriptor
+    if (pbd) *pbd = 0;
+    bool bd = false;
+    QMfmaCfg plain_cfg = {0, 0, 0, 0};   // what qg_mfma_pick chose for the member alone
     QComposite comp_local;
     QComposite& comp = pcomp ? *pcomp : comp_local;
     memset(&comp, 0, sizeof comp);
@@ -335,6 +350,10 @@ static int plan_geometry(const qgemul_desc* d, uint32_t flags, QAnalysis* an, qg
         }
         const int mn = LA < LB ? LA : LB;
         cfg = qg_mfma_pick(LA, LB, d->M * parts, d->N * parts, (ep ? QG_OPT_LOCKSTEP_TILES : 0u) | flags);   // (the fused / unfused element-wise chain keeps the kernel it was measured on)
+        if (batch > 0 && !d->is_complex && !ep) {
+            const QMfmaCfg bc = qg_mfma_pick_batched(LA, LB, batch, cfg);
+            if (bc.variant) { plain_cfg = cfg; cfg = bc; bd = true; }
+        }
         // (wide plans: the kernels' own epilogues are 64-bit; the composite plan's combine pass is not.  Centred single-limb pairs: the
         //  single-limb kernels' epilogue is 32-bit, sum a b of two uint8 operands is not: raw int32 slab + combine pass)
         // (... except where its image in C fits 31 bits and no element-wise chain follows: the single-limb kernels' epilogues then restore
@@ -356,6 +375,16 @@ static int plan_geometry(const qgemul_desc* d, uint32_t flags, QAnalysis* an, qg
             LA = LB = 0;
             centred = false;
             snprintf(info->reason, sizeof info->reason, "linear class, but limbs/K outside the MFMA kernels' range: tree kernel");
+        }
+        if (bd) {
+            // the block-diagonal form takes what ONE launch of a lock-step kernel with its own conversion serves: no composite plan, no
+            // raw-dot-product detour (wide_epilogue below).  A member without it runs on the plain plan's own geometry
+            const QStep& q = an->lin.to_c[0];
+            const bool raw_pass = kernel == QG_KERNEL_MFMA_I8 && !q.identity && (q.W > 30 || (q.d < 0 && an->dot_bits - q.d > 31));
+            if (comp.on || raw_pass || (kernel != QG_KERNEL_MFMA_I8 && kernel != QG_KERNEL_MFMA_I8_LIMB)) {
+                bd = false;
+                if (!comp.on) cfg = plain_cfg;
+            }
         }
     }
     pc->M = d->M;
@@ -432,6 +461,7 @@ static int plan_geometry(const qgemul_desc* d, uint32_t flags, QAnalysis* an, qg
         pc->Np = d->N;
         pc->tm = pc->tn = 0;
     }
+    if (pbd) *pbd = bd ? 1 : 0;
     info->kernel = kernel;
     info->limbs[0] = LA;
     info->limbs[1] = LB;
@@ -881,7 +911,7 @@ int qgemul_plan_create(qgemul_ctx* c, const qgemul_desc* d, uint32_t opt_flags, 
     return qgemul_plan_create_ep(c, d, nullptr, opt_flags, out);
 }
 
-static int plan_create_view(qgemul_ctx* c, const qgemul_desc* d, const EpView* ev, uint32_t opt_flags, qgemul_plan** out);
+static int plan_create_view(qgemul_ctx* c, const qgemul_desc* d, const EpView* ev, uint32_t opt_flags, qgemul_plan** out, int64_t batch = 0);
 
 int qgemul_plan_create_ep(qgemul_ctx* c, const qgemul_desc* d, const qgemul_epilogue* ep, uint32_t opt_flags, qgemul_plan** out)
 {
@@ -914,7 +944,7 @@ int qgemul_plan_create_epcx(qgemul_ctx* c, const qgemul_desc* d, const qgemul_ep
     return plan_create_view(c, d, &v, opt_flags, out);
 }
 
-static int plan_create_view(qgemul_ctx* c, const qgemul_desc* d, const EpView* ev, uint32_t opt_flags, qgemul_plan** out)
+static int plan_create_view(qgemul_ctx* c, const qgemul_desc* d, const EpView* ev, uint32_t opt_flags, qgemul_plan** out, int64_t batch)   // batch > 0: the member of a batched plan
 {
     if (!c || !d || !out) return QG_EINVAL;
     qgemul_plan* p = new (std::nothrow) qgemul_plan;
@@ -941,7 +971,7 @@ static int plan_create_view(qgemul_ctx* c, const qgemul_desc* d, const EpView* e
     if (p->has_ax && !axt) { delete p; return QG_EINVAL; }
     struct AxtGuard { QApproxTable* t; ~AxtGuard() { delete[] t; } } axt_guard = {axt};
     int st = plan_geometry(d, opt_flags, &p->an, &p->info, &p->LA, &p->LB, &p->cfg, &p->pa, &p->pb, &p->pc, &p->ha, &p->hb, &p->hc,
-                           ev, &p->ept, &p->pc_c, &p->ept_im, &p->comp, axt, p->has_cmul ? cmt : nullptr);
+                           ev, &p->ept, &p->pc_c, &p->ept_im, &p->comp, axt, p->has_cmul ? cmt : nullptr, batch);
     if (st != QG_OK) { delete p; return st; }
     p->variant = p->cfg.variant;
     p->tc = qg_tree_choice(&p->an, d, opt_flags, true);
@@ -1024,6 +1054,7 @@ static int plan_create_view(qgemul_ctx* c, const qgemul_desc* d, const EpView* e
 void qgemul_plan_destroy(qgemul_plan* p)
 {
     if (!p) return;
+    if (p->member) qgemul_plan_destroy(p->member);   // (a batched plan: its member owns the device resources)
     DeviceScope scope(p->ctx->device);
     hipStreamSynchronize(p->ctx->stream);
     hipFree(p->dev_table);
@@ -1079,6 +1110,7 @@ static QOperandGeom operand_geom(const qgemul_plan* p, int operand, int64_t ld)
 int qgemul_pack(qgemul_plan* p, int operand, const void* src_dev, int64_t ld, void* packed_dev)
 {
     if (!p || !src_dev || !packed_dev || (operand != QG_OPERAND_A && operand != QG_OPERAND_B)) return QG_EINVAL;
+    if (p->batch) return QG_EINVAL;   // a batched plan runs through the _batched entry points
     QG_ON_DEVICE(p->ctx);
     QOperandGeom g = operand_geom(p, operand, ld);
     const QPackedGeom& pg = operand == QG_OPERAND_A ? p->pa : p->pb;
@@ -1103,6 +1135,7 @@ int qgemul_pack(qgemul_plan* p, int operand, const void* src_dev, int64_t ld, vo
 int qgemul_pack_f64(qgemul_plan* p, int operand, const double* src_dev, int64_t ld, void* packed_dev)
 {
     if (!p || !src_dev || !packed_dev || (operand != QG_OPERAND_A && operand != QG_OPERAND_B)) return QG_EINVAL;
+    if (p->batch) return QG_EINVAL;   // a batched plan runs through the _batched entry points
     if (!(p->flags & QG_OPT_ARITHMETIC_CONV)) {
         // Qu_s(double) with QuMode<RND::CONV>: the reference's result is an artefact of its multi-word CONV branch
         // (QuBLAS.h:2137-2156 on ArbiInt<2400>); silently returning the arithmetic answer would break bit-exactness
@@ -1127,6 +1160,7 @@ int qgemul_pack_f64(qgemul_plan* p, int operand, const double* src_dev, int64_t 
 int qgemul_fill_packed(qgemul_plan* p, int operand, uint64_t seed, int dist, void* packed_dev)
 {
     if (!p || !packed_dev || (operand != QG_OPERAND_A && operand != QG_OPERAND_B)) return QG_EINVAL;
+    if (p->batch) return QG_EINVAL;   // a batched plan runs through the _batched entry points
     QG_ON_DEVICE(p->ctx);
     QOperandGeom g = operand_geom(p, operand, 0);
     const QPackedGeom& pg = operand == QG_OPERAND_A ? p->pa : p->pb;
@@ -1144,6 +1178,7 @@ int qgemul_fill_packed(qgemul_plan* p, int operand, uint64_t seed, int dist, voi
 int qgemul_unpack_c(qgemul_plan* p, const void* packed_dev, void* dst_dev, int64_t ld)
 {
     if (!p || !packed_dev || !dst_dev) return QG_EINVAL;
+    if (p->batch) return QG_EINVAL;   // a batched plan runs through the _batched entry points
     QG_ON_DEVICE(p->ctx);
     QCGeom c = p->pc;
     c.ldc = ld ? ld : p->desc.M;
@@ -1156,6 +1191,7 @@ static int execute_kernel(qgemul_plan* p, void* packedC, const void* packedA, co
 int qgemul_execute(qgemul_plan* p, void* packedC, const void* packedA, const void* packedB)
 {
     if (!p || !packedC || !packedA || !packedB) return QG_EINVAL;
+    if (p->batch) return QG_EINVAL;   // a batched plan runs through the _batched entry points
     if (p->has_ep) return QG_EINVAL;  // a plan with an epilogue runs through qgemul_execute_ep
     if (p->desc.M == 0 || p->desc.N == 0) return QG_OK;
     QG_ON_DEVICE(p->ctx);
@@ -1178,6 +1214,7 @@ int qgemul_plan_stores_host_c(const qgemul_plan* p) { return p && stores_host_c(
 int qgemul_execute_host_c(qgemul_plan* p, void* C_dev, int64_t ldc, const void* packedA, const void* packedB)
 {
     if (!p || !C_dev || !packedA || !packedB || p->has_ep) return QG_EINVAL;
+    if (p->batch) return QG_EINVAL;   // a batched plan runs through the _batched entry points
     if (ldc && ldc < p->desc.M) return QG_EINVAL;
     if (p->desc.M == 0 || p->desc.N == 0) return QG_OK;
     QG_ON_DEVICE(p->ctx);
@@ -1564,7 +1601,7 @@ static int result_width(const qgemul_plan* p, int part = 0)
 
 int64_t qgemul_bitstream_bytes(const qgemul_plan* p, int format)
 {
-    if (!p) return 0;
+    if (!p || p->batch) return 0;
     const int64_t n = p->desc.M * p->desc.N;
     // complex: "(re-bits, im-bits)" per element as characters; packed: the binary characters only
     const int64_t bits = p->desc.is_complex ? n * (result_width(p, 0) + result_width(p, 1) + (format == QG_BITS_PACKED ? 0 : 4)) : n * (int64_t)result_width(p);
@@ -1575,6 +1612,7 @@ int64_t qgemul_bitstream_bytes(const qgemul_plan* p, int format)
 int qgemul_export_bitstream(qgemul_plan* p, const void* packedC, int tensor_chunk, int elem_chunk, int format, void* out_dev)
 {
     if (!p || !packedC || !out_dev || (format != QG_BITS_ASCII && format != QG_BITS_PACKED)) return QG_EINVAL;
+    if (p->batch) return QG_EINVAL;   // a batched plan runs through the _batched entry points
     const int w = p->desc.is_complex ? result_width(p, 0) + result_width(p, 1) + 4 : result_width(p);
     const int64_t n = p->desc.M * p->desc.N;
     if (w <= 0 || tensor_chunk < 0 || elem_chunk < 0) return QG_EINVAL;
@@ -1627,12 +1665,15 @@ int qgemul_export_bitstream(qgemul_plan* p, const void* packedC, int tensor_chun
 }
 
 static int time_execute(qgemul_plan* p, void* packedC, const void* packedA, const void* packedB, const qgemul_ep_args* args,
-                        int warmup, int iters, float* avg_ms)
+                        int warmup, int iters, float* avg_ms, bool batched = false)
 {
-    if (!p || !avg_ms || iters < 1) return QG_EINVAL;
+    if (!p || !avg_ms || iters < 1 || (p->batch != 0) != batched) return QG_EINVAL;
     QG_ON_DEVICE(p->ctx);
     hipStream_t st = p->ctx->stream;
-    auto once = [&]() { return p->has_ep ? qgemul_execute_ep(p, packedC, packedA, packedB, args) : qgemul_execute(p, packedC, packedA, packedB); };
+    auto once = [&]() {
+        if (batched) return qgemul_execute_batched(p, packedC, packedA, packedB);
+        return p->has_ep ? qgemul_execute_ep(p, packedC, packedA, packedB, args) : qgemul_execute(p, packedC, packedA, packedB);
+    };
     for (int i = 0; i < warmup; ++i) {
         int s = once();
         if (s) return s;
@@ -1691,6 +1732,7 @@ struct RunCache {
     qgemul_cmul pcx[QG_MAX_EW];       // the cached plan's CMUL records (pcx_on[k]: the caller passed cx[k])
     uint8_t pcx_on[QG_MAX_EW] = {};
     uint32_t pflags = 0;
+    int64_t pbatch = 0;       // > 0: the cached plan is a batched plan of that many members (qgemul_run_batched)
     enum { NBUF = 6 + 16 };   // 0-5: host-layout A, B, C and packed A, B, C; behind them: the epilogue operands (2 per stage) or, on the
                               // root of a sharded call, the landing buffers of the other bands
     void* buf[NBUF] = {};
@@ -1901,7 +1943,7 @@ static int run_view(const qgemul_desc* d, const EpView* ev, void* C, const void*
         opts.flags &= ~(uint32_t)QG_OPT_ALL_DEVICES;
         return qgemul_run_sharded(d, C, A, B, &opts, list, n);
     }
-    const bool same_plan = c.plan && c.pflags == opts.flags && same_desc(c.pd, *d) && c.has_pe == (ep != nullptr) &&
+    const bool same_plan = c.plan && c.pbatch == 0 && c.pflags == opts.flags && same_desc(c.pd, *d) && c.has_pe == (ep != nullptr) &&
                            (!ep || (same_epilogue(c.pe.part[0], *ep) && c.pe_cplx == (ev->im != nullptr) &&
                                     (!ev->im || (same_epilogue(c.pe.part[1], *ev->im) && !memcmp(c.pe.e_complex, ev->e_cplx, ep->n_stages))) &&
                                     same_tables(c, ev->ax) && same_cmul(c, ev->cx))) &&
@@ -1949,6 +1991,7 @@ static int run_view(const qgemul_desc* d, const EpView* ev, void* C, const void*
             c.pcx_on[k] = 1;
         }
         c.pflags = opts.flags;
+        c.pbatch = 0;
     }
     qgemul_plan* p = c.plan;
     void *dA, *dB, *dC, *pA, *pB, *pC;
@@ -2168,6 +2211,285 @@ int qgemul_run_sharded(const qgemul_desc* d, void* C, const void* A, const void*
         const hipError_t e = hipStreamSynchronize(g_shard[i].ctx->stream);
         if (st == QG_OK && e != hipSuccess) { g_last_hip = (int)e; st = QG_EHIP; }
     }
+    return st;
+}
+
+// ---- batched Qgemul: `batch` GEMMs of one descriptor at constant strides (include/qgemul.h) ----
+// kernel launches of one qgemul_execute on a plain plan (a 3 x 3 launch pair counts once: its partner returns in its first instructions)
+static int plan_launches(const qgemul_plan* p)
+{
+    if (p->comp.on) return p->comp.nc * (p->comp.ga * p->comp.gb + 1);
+    switch (p->info.kernel) {
+    case QG_KERNEL_MFMA_I8:
+    case QG_KERNEL_MFMA_I8_LIMB: return p->variant != QG_MFMA_RING && wide_epilogue(p) ? 2 : 1;
+    case QG_KERNEL_MFMA_CPLX: return 2;
+    default: return 1;
+    }
+}
+
+// host elements one member of operand `operand` spans at leading dimension ld (0: tight); 0: ld is too small
+static int64_t member_extent(const qgemul_desc& d, int operand, int64_t ld)
+{
+    const int64_t rows = operand == QG_OPERAND_A ? (d.transA ? d.K : d.M) : operand == QG_OPERAND_B ? d.K : d.M;
+    const int64_t cols = operand == QG_OPERAND_A ? (d.transA ? d.M : d.K) : d.N;
+    if (!ld) ld = rows;
+    if (ld < rows) return 0;
+    return cols > 0 && rows > 0 ? (cols - 1) * ld + rows : 1;
+}
+
+// the geometry of a batched plan, pure host code: m (zeroed) receives the member's, b (zeroed) the batch's
+static int batched_geometry(const qgemul_desc* d, int64_t batch, uint32_t flags, qgemul_plan* m, qgemul_plan* b)
+{
+    if (!d || batch < 1) return QG_EINVAL;
+    int bd = 0;
+    m->desc = *d;
+    m->flags = flags;
+    const int st = plan_geometry(d, flags, &m->an, &m->info, &m->LA, &m->LB, &m->cfg, &m->pa, &m->pb, &m->pc, &m->ha, &m->hb, &m->hc, nullptr, &m->ept, &m->pc_c,
+                                 &m->ept_im, &m->comp, nullptr, nullptr, batch, &bd);
+    b->info = m->info;
+    if (st != QG_OK) return st;
+    m->variant = m->cfg.variant;
+    b->desc = *d;
+    b->flags = flags;
+    b->batch = batch;
+    b->bd = bd;
+    b->LA = m->LA;
+    b->LB = m->LB;
+    b->cfg = m->cfg;
+    b->variant = m->variant;
+    b->ha = m->ha;
+    b->hb = m->hb;
+    b->hc = m->hc;
+    b->pc = m->pc;
+    b->member_launches = plan_launches(m);
+    int64_t total[3];
+    bool over = false;
+    if (bd) {
+        int64_t tiles = 0;
+        over |= __builtin_mul_overflow((m->pa.rows_p / m->cfg.TM) * (m->pb.rows_p / m->cfg.TN), batch, &tiles) || tiles > 0x7fffffffll;
+        QPackedGeom* sg[2] = {&b->pa, &b->pb};
+        const QPackedGeom* mg[2] = {&m->pa, &m->pb};
+        for (int w = 0; w < 2 && !over; ++w) {
+            QPackedGeom& s = *sg[w];
+            s = *mg[w];
+            int64_t planes = 0;
+            over |= __builtin_mul_overflow(s.rows_p, batch, &s.rows_p) || __builtin_mul_overflow((int64_t)s.limbs * s.K_p, s.rows_p, &planes) || planes > (1ll << 60);
+            b->mstride[w] = (int64_t)mg[w]->limbs * mg[w]->rows_p * mg[w]->K_p;
+            int64_t bytes = planes;
+            s.trailer = 0;
+            if (s.limbs > 1) { s.trailer = bytes; bytes += QG_TRAILER_BYTES; }   // ONE plane mask: the OR over every member
+            if (s.offs) {                                                         // ONE row-sum array behind the planes of all members
+                s.rowsum_off = round_up(bytes, 256);
+                bytes = s.rowsum_off + s.rows_p * 8;
+            }
+            total[w] = bytes;
+        }
+        b->mstride[2] = m->info.packed_bytes[2];
+        over |= __builtin_mul_overflow(b->mstride[2], batch, &total[2]);
+        snprintf(b->info.reason, sizeof b->info.reason, "linear class: %lld members in one block-diagonal launch, %dx%d tiles", (long long)batch, m->cfg.TM, m->cfg.TN);
+    } else {
+        for (int w = 0; w < 3; ++w) {
+            b->mstride[w] = round_up(m->info.packed_bytes[w], 256);
+            over |= __builtin_mul_overflow(b->mstride[w], batch, &total[w]) || total[w] > (1ll << 60);
+        }
+        b->pa = m->pa;
+        b->pb = m->pb;
+    }
+    if (over) {
+        b->info.supported = 0;
+        snprintf(b->info.reason, sizeof b->info.reason, "batched plan: more than 2^31 - 1 tiles / packed operands beyond the address range");
+        return QG_EINVAL;
+    }
+    for (int w = 0; w < 3; ++w) b->info.packed_bytes[w] = total[w];
+    b->info.ops = m->info.ops * (double)batch;
+    return QG_OK;
+}
+
+int qgemul_classify_batched(const qgemul_desc* d, int64_t batch, uint32_t opt_flags, qgemul_info* out)
+{
+    if (!d || !out) return QG_EINVAL;
+    qgemul_plan* two = new (std::nothrow) qgemul_plan[2];
+    if (!two) return QG_EINVAL;
+    memset(two, 0, 2 * sizeof *two);
+    const int st = batched_geometry(d, batch, opt_flags, &two[0], &two[1]);
+    if (batch >= 1) *out = two[1].info;
+    delete[] two;
+    return st;
+}
+
+int qgemul_classify_batched_launches(const qgemul_desc* d, int64_t batch, uint32_t opt_flags)
+{
+    if (!d) return QG_EINVAL;
+    qgemul_plan* two = new (std::nothrow) qgemul_plan[2];
+    if (!two) return QG_EINVAL;
+    memset(two, 0, 2 * sizeof *two);
+    int st = batched_geometry(d, batch, opt_flags, &two[0], &two[1]);
+    if (st == QG_OK) st = qgemul_plan_batched_launches(&two[1]);
+    delete[] two;
+    return st;
+}
+
+int qgemul_plan_create_batched(qgemul_ctx* c, const qgemul_desc* d, int64_t batch, uint32_t opt_flags, qgemul_plan** out)
+{
+    if (!c || !d || !out) return QG_EINVAL;
+    qgemul_plan* two = new (std::nothrow) qgemul_plan[2];
+    qgemul_plan* b = new (std::nothrow) qgemul_plan;
+    if (!two || !b) { delete[] two; delete b; return QG_EINVAL; }
+    memset(two, 0, 2 * sizeof *two);
+    int st = batched_geometry(d, batch, opt_flags, &two[0], &two[1]);
+    *b = two[1];
+    delete[] two;
+    if (st == QG_OK) st = plan_create_view(c, d, nullptr, opt_flags, &b->member, batch);
+    if (st != QG_OK) { delete b; return st; }
+    b->ctx = c;
+    *out = b;
+    return QG_OK;
+}
+
+int qgemul_plan_batched_launches(const qgemul_plan* p)
+{
+    if (!p || !p->batch) return QG_EINVAL;
+    if (p->bd) return 1;
+    const int64_t n = p->batch * p->member_launches;
+    return n > 0x7fffffffll ? 0x7fffffff : (int)n;
+}
+
+int qgemul_pack_batched(qgemul_plan* p, int operand, const void* src_dev, int64_t ld, int64_t member_stride, void* packed_dev)
+{
+    if (!p || !p->batch || !src_dev || !packed_dev || (operand != QG_OPERAND_A && operand != QG_OPERAND_B)) return QG_EINVAL;
+    const int64_t ext = member_extent(p->desc, operand, ld);
+    if (ext < 1 || member_stride < ext) return QG_EINVAL;
+    qgemul_plan* m = p->member;
+    const int64_t eb = operand == QG_OPERAND_A ? p->ha.size : p->hb.size;
+    if (!p->bd) {
+        for (int64_t b = 0; b < p->batch; ++b)
+            if (const int st = qgemul_pack(m, operand, (const char*)src_dev + b * member_stride * eb, ld, (char*)packed_dev + b * p->mstride[operand]); st != QG_OK) return st;
+        return QG_OK;
+    }
+    QG_ON_DEVICE(p->ctx);
+    const QOperandGeom g = operand_geom(m, operand, ld);
+    const int check = (p->flags & QG_OPT_CHECK_RANGE) ? 1 : 0;
+    if (check) QG_HIP(hipMemsetAsync(p->ctx->flag_dev, 0, 4, p->ctx->stream));
+    QG_HIP(qg_launch_pack_stack(g, operand == QG_OPERAND_A ? m->pa : m->pb, operand == QG_OPERAND_A ? p->pa : p->pb, p->batch, src_dev, member_stride * eb,
+                                packed_dev, check, p->ctx->flag_dev, p->ctx->stream, (p->flags & QG_OPT_GENERIC_LAYOUT) ? 1 : 0));
+    if (check) {
+        int flag = 0;
+        QG_HIP(hipMemcpyAsync(&flag, p->ctx->flag_dev, 4, hipMemcpyDeviceToHost, p->ctx->stream));
+        QG_HIP(hipStreamSynchronize(p->ctx->stream));
+        if (flag) return QG_ERANGE;
+    }
+    return QG_OK;
+}
+
+int qgemul_unpack_c_batched(qgemul_plan* p, const void* packed_dev, void* dst_dev, int64_t ld, int64_t member_stride)
+{
+    if (!p || !p->batch || !packed_dev || !dst_dev) return QG_EINVAL;
+    const int64_t ext = member_extent(p->desc, QG_OPERAND_C, ld);
+    if (ext < 1 || member_stride < ext) return QG_EINVAL;
+    for (int64_t b = 0; b < p->batch; ++b)   // (a layout step: one launch per member, the members' packed Cs back to back)
+        if (const int st = qgemul_unpack_c(p->member, (const char*)packed_dev + b * p->mstride[2], (char*)dst_dev + b * member_stride * p->hc.size, ld); st != QG_OK) return st;
+    return QG_OK;
+}
+
+int qgemul_execute_batched(qgemul_plan* p, void* packedC, const void* packedA, const void* packedB)
+{
+    if (!p || !p->batch || !packedC || !packedA || !packedB) return QG_EINVAL;
+    if (p->desc.M == 0 || p->desc.N == 0) return QG_OK;
+    qgemul_plan* m = p->member;
+    if (!p->bd) {
+        for (int64_t b = 0; b < p->batch; ++b)
+            if (const int st = qgemul_execute(m, (char*)packedC + b * p->mstride[2], (const char*)packedA + b * p->mstride[0], (const char*)packedB + b * p->mstride[1]); st != QG_OK)
+                return st;
+        return QG_OK;
+    }
+    QG_ON_DEVICE(p->ctx);
+    // the stack is a packed A and a packed B: its own plane masks and row sums, the member's conversion into C
+    QMfmaArgs a = mfma_args(p->pa, p->pb, p->variant, packedA, packedB, packedC, p->pc.cbytes);
+    a.to_c = m->an.lin.to_c[0];
+    if (p->pa.offs) {   // centred operands: one centre per operand for the whole stack (centre_args)
+        a.rsA = (const int64_t*)((const char*)packedA + p->pa.rowsum_off);
+        a.rsB = (const int64_t*)((const char*)packedB + p->pb.rowsum_off);
+        a.biasA = p->pa.bias;
+        a.biasB = p->pb.bias;
+        a.corr = (int64_t)((uint64_t)p->desc.K * (uint64_t)p->pa.bias * (uint64_t)p->pb.bias);
+    }
+    a.bd_tm = (int32_t)(m->pa.rows_p / p->cfg.TM);
+    a.bd_tn = (int32_t)(m->pb.rows_p / p->cfg.TN);
+    QG_HIP(qg_launch_mfma_bd(p->LA, p->LB, a, p->batch, p->ctx->stream));
+    return QG_OK;
+}
+
+int qgemul_time_execute_batched(qgemul_plan* p, void* packedC, const void* packedA, const void* packedB, int warmup, int iters, float* avg_ms)
+{
+    return time_execute(p, packedC, packedA, packedB, nullptr, warmup, iters, avg_ms, true);
+}
+
+int qgemul_run_batched(const qgemul_desc* d, int64_t batch, void* C, const void* A, const void* B, int64_t strideC, int64_t strideA, int64_t strideB,
+                       const qgemul_opts* o)
+{
+    if (!d || !C || !A || !B || batch < 1) return QG_EINVAL;
+    qgemul_opts opts;
+    memset(&opts, 0, sizeof opts);
+    opts.device = -1;
+    if (o) opts = *o;
+    if (opts.flags & QG_OPT_ALL_DEVICES) return QG_EUNSUPPORTED;   // (the sharded entry has no batched form)
+    const int64_t extA = member_extent(*d, QG_OPERAND_A, opts.lda), extB = member_extent(*d, QG_OPERAND_B, opts.ldb), extC = member_extent(*d, QG_OPERAND_C, opts.ldc);
+    if (extA < 1 || extB < 1 || extC < 1 || strideA < extA || strideB < extB || strideC < extC) return QG_EINVAL;
+    g_reaper.armed = true;
+    static ShutdownHook hook;
+    RunCache& c = g_run;
+    if (opts.device < 0 && c.ctx) {
+        int cur = c.device;
+        if (hipGetDevice(&cur) == hipSuccess) opts.device = cur;
+    }
+    const bool same_plan = c.plan && c.pbatch == batch && c.pflags == opts.flags && same_desc(c.pd, *d) && !c.has_pe && (opts.device < 0 || opts.device == c.device);
+    if (!same_plan) {   // validate before touching the device
+        qgemul_info info;
+        if (const int st = qgemul_classify_batched(d, batch, opts.flags, &info); st != QG_OK) return st;
+    }
+    if (d->M == 0 || d->N == 0) return QG_OK;
+    int st = QG_OK;
+    if (!c.ctx || (opts.device >= 0 && opts.device != c.device)) {
+        release_cache(c);
+        st = qgemul_ctx_create(opts.device, &c.ctx);
+        if (st != QG_OK) { c.ctx = nullptr; return st; }
+        c.device = c.ctx->device;
+    } else {
+        QG_HIP(hipSetDevice(c.device));
+    }
+    if (!same_plan) {
+        if (c.plan) { qgemul_plan_destroy(c.plan); c.plan = nullptr; }
+        st = qgemul_plan_create_batched(c.ctx, d, batch, opts.flags, &c.plan);
+        if (st != QG_OK) { c.plan = nullptr; return st; }
+        c.pd = *d;
+        c.has_pe = false;
+        c.pe_cplx = false;
+        memset(c.pax_on, 0, sizeof c.pax_on);
+        memset(c.pcx_on, 0, sizeof c.pcx_on);
+        c.pflags = opts.flags;
+        c.pbatch = batch;
+    }
+    qgemul_plan* p = c.plan;
+    void *dA, *dB, *dC, *pA, *pB, *pC;
+    do {
+        const size_t bytesA = (size_t)((batch - 1) * strideA + extA) * p->ha.size;
+        const size_t bytesB = (size_t)((batch - 1) * strideB + extB) * p->hb.size;
+        const size_t bytesC = (size_t)((batch - 1) * strideC + extC) * p->hc.size;
+        if ((st = cache_buffer(c, 0, bytesA, &dA)) || (st = cache_buffer(c, 1, bytesB, &dB)) || (st = cache_buffer(c, 2, bytesC, &dC)) ||
+            (st = cache_buffer(c, 3, (size_t)p->info.packed_bytes[0], &pA)) || (st = cache_buffer(c, 4, (size_t)p->info.packed_bytes[1], &pB)) ||
+            (st = cache_buffer(c, 5, (size_t)p->info.packed_bytes[2], &pC)))
+            break;
+        hipStream_t s = c.ctx->stream;
+        if (hipMemcpyAsync(dA, A, bytesA, hipMemcpyHostToDevice, s) != hipSuccess || hipMemcpyAsync(dB, B, bytesB, hipMemcpyHostToDevice, s) != hipSuccess) { st = QG_EHIP; break; }
+        // the caller's C may have gaps between columns and between members: those bytes stay as they are
+        if ((strideC != d->M * d->N || (opts.ldc && opts.ldc != d->M)) && hipMemcpyAsync(dC, C, bytesC, hipMemcpyHostToDevice, s) != hipSuccess) { st = QG_EHIP; break; }
+        if ((st = qgemul_pack_batched(p, QG_OPERAND_A, dA, opts.lda, strideA, pA)) || (st = qgemul_pack_batched(p, QG_OPERAND_B, dB, opts.ldb, strideB, pB))) break;
+        if ((st = qgemul_execute_batched(p, pC, pA, pB))) break;
+        if ((st = qgemul_unpack_c_batched(p, pC, dC, opts.ldc, strideC))) break;
+        if (hipMemcpyAsync(C, dC, bytesC, hipMemcpyDeviceToHost, s) != hipSuccess) { st = QG_EHIP; break; }
+    } while (0);
+    const hipError_t e = hipStreamSynchronize(c.ctx->stream);
+    if (st == QG_OK && e != hipSuccess) { g_last_hip = (int)e; st = QG_EHIP; }
     return st;
 }
 

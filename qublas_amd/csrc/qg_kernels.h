@@ -1,6 +1,7 @@
 // qg_kernels.h — launch interface between the C-ABI layer (qg_api.cpp) and the gfx950 kernels.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdlib.h>
 
@@ -95,6 +96,12 @@ hipError_t qg_launch_pack(const QOperandGeom& g, const QPackedGeom& p, const voi
 hipError_t qg_launch_pack_f64(const QOperandGeom& g, const QPackedGeom& p, const void* src, void* dst, hipStream_t st, int generic = 0);
 hipError_t qg_launch_fill(const QOperandGeom& g, const QPackedGeom& p, uint64_t seed, int dist, void* dst, hipStream_t st);
 hipError_t qg_launch_unpack_c(const QCGeom& c, const void* packed, void* dst, hipStream_t st, int generic = 0);
+// batched plans, block-diagonal form: `batch` members of geometry g / member (ONE member's packed geometry; limb layout) at
+// src + b * stride_bytes are packed into the row tiles [b * member.rows_p / tr, ...) of the stack `stack` (member with batch times
+// the rows).  What belongs to the STACK is set up once, not per member: the plane-mask trailer (the OR over every member) and
+// the row sums of centred operands, which sit behind the planes of all members.
+hipError_t qg_launch_pack_stack(const QOperandGeom& g, const QPackedGeom& member, const QPackedGeom& stack, int64_t batch, const void* src,
+                                int64_t stride_bytes, void* dst, int check_range, int* range_flag, hipStream_t st, int generic = 0);
 
 // complex linear class: combine the four raw dot-product blocks of D (tiled int64) into packed complex C [2][M][N]
 struct QCplxCombine {
@@ -173,11 +180,15 @@ struct QMfmaArgs {
     const int64_t* rsA;
     const int64_t* rsB;
     int64_t biasA, biasB, corr;
-    int32_t kara, pad3_;
+    // bd_tm, bd_tn (below): the block-diagonal form (batched Qgemul, qg_launch_mfma_bd; 0: one GEMM).  A and B are the members'
+    // packed operands stacked by row tiles (Mp, Np: the stack's rows), bd_tm x bd_tn the tiles of ONE member; workgroup w of
+    // batch * bd_tm * bd_tn works on qg_bd_tile_of(w) and stores into the members' packed Cs back to back.  (The two fields sit
+    // where the struct had padding: its size and every other field's offset are what they were, so no kernel's code moves.)
+    int32_t kara, bd_tm;
     int64_t Mc;             // k_mfma_k6: padded rows of packed C (128-row tiles), which differ from Mp (A on 96-row tiles)
     const uint32_t* maskA;  // plane masks of the packed operands (QPackedGeom::trailer); nullptr: all planes
     const uint32_t* maskB;
-    int32_t has_ep, pad_;   // fused element-wise epilogue: C below is then packed D (ep.dbytes containers)
+    int32_t has_ep, bd_tn;  // fused element-wise epilogue: C below is then packed D (ep.dbytes containers)
     uint32_t* dbg;          // diagnostic build: in-kernel clock stamps (qg_mfma_pp.hip); nullptr otherwise
     // c_host != 0 (k_mfma_pp / k_mfma_ppl, 4- and 8-byte containers): C is the REFERENCE layout on the device — element (i, j)
     // at i + j * c_ld, c_M x c_N logical — and the epilogue's runs of 4 rows land there directly: no packed C, no unpack pass.
@@ -187,7 +198,17 @@ struct QMfmaArgs {
     QEpTable ep;
     QEpArgs epa;
 };
+// bd_tm / bd_tn took the place of two padding words: the struct's size and every other field's offset are the parent's
+static_assert(offsetof(QMfmaArgs, bd_tm) == offsetof(QMfmaArgs, kara) + 4 && offsetof(QMfmaArgs, Mc) == offsetof(QMfmaArgs, kara) + 8 &&
+              offsetof(QMfmaArgs, bd_tn) == offsetof(QMfmaArgs, has_ep) + 4 && offsetof(QMfmaArgs, dbg) == offsetof(QMfmaArgs, has_ep) + 8,
+              "QMfmaArgs: the block-diagonal fields sit in former padding; no field may move");
 hipError_t qg_launch_mfma(int LA, int LB, const QMfmaArgs& a, hipStream_t st);
+// `batch` GEMMs of one member shape in ONE launch of k_mfma's block-diagonal form (qg_mfma.hip): the variants qg_mfma_pick_batched
+// returns, no element-wise chain, no Karatsuba digits; anything else is hipErrorInvalidValue
+hipError_t qg_launch_mfma_bd(int LA, int LB, const QMfmaArgs& a, int64_t batch, hipStream_t st);
+// tile geometry of a batched plan; variant 0: no block-diagonal form for this member (it runs member by member on `plain`, the
+// member's own qg_mfma_pick)
+QMfmaCfg qg_mfma_pick_batched(int LA, int LB, int64_t batch, const QMfmaCfg& plain);
 // single limb, 256x256 tiles, 128-byte k-tiles, two wave groups alternating on the matrix cores (qg_mfma_pp.hip; variant 9)
 hipError_t qg_launch_mfma_pp(const QMfmaArgs& a, hipStream_t st);
 // 3 x 3 and 2 x 2 limbs, 128x128 tiles, the two-group scheme with one A limb plane per phase (qg_mfma_ppl.hip; variant 10)

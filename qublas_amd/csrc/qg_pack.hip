@@ -576,13 +576,15 @@ static hipError_t zero_trailer(const QPackedGeom& p, void* dst, hipStream_t st)
     return hipMemsetAsync((char*)dst + p.trailer, 0, bytes, st);
 }
 
-hipError_t qg_launch_pack(const QOperandGeom& g, const QPackedGeom& p, const void* src, void* dst, int check_range,
-                          int* range_flag, hipStream_t st, int generic)
+// zero: clear the trailer and the row sums the packed operand owns (qg_launch_pack_stack has cleared the stack's once)
+static hipError_t launch_pack(const QOperandGeom& g, const QPackedGeom& p, const void* src, void* dst, int check_range,
+                              int* range_flag, hipStream_t st, int generic, bool zero)
 {
     int64_t blocks = ((p.K_p + 63) / 64) * ((p.rows_p + 63) / 64) * g.parts;
     if (blocks <= 0) return hipSuccess;
     if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
-    if (hipError_t e = zero_trailer(p, dst, st); e != hipSuccess) return e;
+    if (zero)
+        if (hipError_t e = zero_trailer(p, dst, st); e != hipSuccess) return e;
     const bool no_fast = generic != 0;   // QG_OPT_GENERIC_LAYOUT: the any-format kernel (byte-identical; the equivalence test)
     const bool centred_fast = !p.offs || (g.W[0] <= 24 && p.bias > -(1ll << 24) && p.bias < (1ll << 24));   // (x - centre within int32)
     if (!no_fast && g.parts == 1 && g.elem_bytes == 4 && g.sb[0] == 4 && g.off[0] == 0 && p.limbs >= 1 && p.limbs <= 4 && (!p.digit6 || p.limbs == 3) && centred_fast && (p.bk == 64 || p.bk == 128) &&
@@ -598,6 +600,38 @@ hipError_t qg_launch_pack(const QOperandGeom& g, const QPackedGeom& p, const voi
     hipLaunchKernelGGL(k_pack, dim3((unsigned)blocks), dim3(256), 0, st, g, p, (const char*)src, (char*)dst, check_range,
                        range_flag, 0, 0ull, 0);
     return hipGetLastError();
+}
+
+hipError_t qg_launch_pack(const QOperandGeom& g, const QPackedGeom& p, const void* src, void* dst, int check_range,
+                          int* range_flag, hipStream_t st, int generic)
+{
+    return launch_pack(g, p, src, dst, check_range, range_flag, st, generic, true);
+}
+
+hipError_t qg_launch_pack_stack(const QOperandGeom& g, const QPackedGeom& member, const QPackedGeom& stack, int64_t batch, const void* src,
+                                int64_t stride_bytes, void* dst, int check_range, int* range_flag, hipStream_t st, int generic)
+{
+    if (batch < 1 || member.limbs < 1 || member.digit6 || g.parts != 1 || stack.rows_p != member.rows_p * batch) return hipErrorInvalidValue;
+    // the stack's own trailer and row sums: cleared ONCE; every member then ORs / adds into them
+    if (stack.trailer)
+        if (hipError_t e = hipMemsetAsync((char*)dst + stack.trailer, 0, QG_TRAILER_BYTES, st); e != hipSuccess) return e;
+    if (stack.offs)
+        if (hipError_t e = hipMemsetAsync((char*)dst + stack.rowsum_off, 0, (size_t)stack.rows_p * 8, st); e != hipSuccess) return e;
+    // member b owns the row tiles [b * rows_p / tr, (b + 1) * rows_p / tr): `planes` contiguous bytes of the stack; the trailer and
+    // its row sums are addressed relative to that start (both stay positive: they lie behind the planes of ALL members)
+    const int64_t planes = (int64_t)member.limbs * member.rows_p * member.K_p;
+    for (int64_t b = 0; b < batch; ++b) {
+        QPackedGeom m = member;
+        m.trailer = stack.trailer ? stack.trailer - b * planes : 0;
+        if (stack.offs) {
+            m.offs = 2;   // adds to row sums its caller has zeroed
+            m.bias = stack.bias;
+            m.rowsum_off = stack.rowsum_off + b * member.rows_p * 8 - b * planes;
+        }
+        if (hipError_t e = launch_pack(g, m, (const char*)src + b * stride_bytes, (char*)dst + b * planes, check_range, range_flag, st, generic, false); e != hipSuccess)
+            return e;
+    }
+    return hipSuccess;
 }
 
 hipError_t qg_launch_pack_f64(const QOperandGeom& g, const QPackedGeom& p, const void* src, void* dst, hipStream_t st, int generic)

@@ -67,6 +67,18 @@ QG_HD void qg_tile_of(I w, I tiles_m, I tiles_n, I& tile_m, I& tile_n)
     tile_n = rem / gsz;
 }
 
+// Block-diagonal walk (batched Qgemul: `batch` members of tmM x tnN tiles each, operands stacked): tile number w of the batch's
+// batch * tmM * tnN tiles -> (member, tile_m, tile_n), the tile indices local to the member.  A member's tiles are consecutive
+// tile numbers, walked inside the member as qg_tile_of<8, true> walks one GEMM, so that with qg_xcd_block over the batch's total a
+// member's tiles fall into one XCD residue class's run (or two neighbouring ones) and share that L2.
+template <class I>
+QG_HD void qg_bd_tile_of(I w, I tmM, I tnN, I& member, I& tile_m, I& tile_n)
+{
+    const I per = tmM * tnN;
+    member = w / per;
+    qg_tile_of<8, true>(w % per, tmM, tnN, tile_m, tile_n);
+}
+
 // Persistent kernels (grid workgroups, a multiple of 8, each walking a list of tiles): the grid / 8 workgroups of a residue
 // class take the tiles of the class's run round-robin, i.e. in every round a class works on grid / 8 consecutive tiles of the
 // walk.  Workgroup block.x of grid.x owns the tile numbers first + i * step, i < count (count == 0: nothing to do).  A kernel
