@@ -8,8 +8,10 @@
 int main()
 {
     const int batches[] = {1, 2, 7, 8, 9, 300};
-    for (int tmM = 1; tmM <= 3; ++tmM)
-        for (int tnN = 1; tnN <= 3; ++tnN)
+    const int rows[] = {1, 2, 3, 8, 9, 10, 17};   // tile rows of a member: below, on and beyond the walk's groups of 8, ragged last groups
+    const int cols[] = {1, 2, 3, 5};
+    for (int tmM : rows)
+        for (int tnN : cols)
             for (int batch : batches) {
                 const int nwg = batch * tmM * tnN;
                 printf("bd %d %d %d :", tmM, tnN, batch);

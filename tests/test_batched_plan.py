@@ -77,6 +77,76 @@ def test_one_launch_for_small_linear_members_and_the_loop_for_everything_else():
     assert list(capi.classify_batched_status(big, 2)[1].packed_bytes) == [2 * b for b in capi.classify(big).packed_bytes]
 
 
+# ---- what tests/test_gpu_batched_edges.py runs on the GPU, as the planner answers it
+E77 = Qu(7, 7)
+LIMBS = {E43: 1, E77: 2, E88: 3}
+
+
+def tags(ea, eb, grow=13):
+    """the exact product and an accumulator of `grow` - 1 more bits: the linear class for K < 2^(grow - 1)"""
+    return dict(mul_args=Tags(ea.intBits + eb.intBits + 1, ea.fracBits + eb.fracBits), add_args=[Qu(ea.intBits + eb.intBits + grow, ea.fracBits + eb.fracBits)])
+
+
+def roomy(ea, eb, grow=13):
+    """a C that holds every dot product of tags(ea, eb, grow), at the coarser operand's resolution"""
+    return Qu(ea.intBits + eb.intBits + grow - 1, max(ea.fracBits, eb.fracBits))
+
+
+# name -> (A element, B element, the largest K with min(LA, LB) * K <= 2^17 - 1)
+BOUND = {"1x1": (E43, E43, 131071), "2x2": (E77, E77, 65535), "3x3": (E88, E88, 43690), "3x1": (E88, E43, 131071)}
+
+
+def bound_case(name, over=0):
+    """descriptor and C of a member of (3, 2, Kmax + over).  The accumulator and C hold Kmax * a * b exactly.  The single-limb
+    pair's 32-bit epilogue takes a C of at most 30 value bits: Qu<26,0>, six fraction bits below the product's — a floor that is
+    exact where one factor is the format's minimum, -2^7."""
+    ea, eb, K = BOUND[name]
+    kw = tags(ea, eb, 18)
+    ec = Qu(26, 0) if name == "1x1" else kw["add_args"][0]
+    return ea, eb, ec, K, lower(ea, eb, ec, 3, 2, K + over, **kw)
+
+
+def test_the_one_launch_form_ends_at_the_exactness_bound():
+    batch = 2
+    for name in BOUND:
+        ea, eb, _, K, d = bound_case(name)
+        assert min(LIMBS[ea], LIMBS[eb]) * K <= 2 ** 17 - 1 < min(LIMBS[ea], LIMBS[eb]) * (K + 1)
+        st, info = capi.classify_batched_status(d, batch)
+        assert st == capi.QG_OK and list(info.limbs) == [LIMBS[ea], LIMBS[eb]] and capi.classify_batched_launches(d, batch) == 1, (name, info.reason)
+        assert b"one block-diagonal launch" in bytes(info.reason)
+        over = bound_case(name, 1)[4]
+        st, info = capi.classify_batched_status(over, batch)
+        assert st == capi.QG_OK and capi.classify_batched_launches(over, batch) > batch and b"k-chunk" in bytes(info.reason), (name, info.reason)
+
+
+def test_all_nine_limb_pairs_take_one_launch():
+    seen = set()
+    for ea in (E43, E77, E88):
+        for eb in (E43, E77, E88):
+            for ta in (False, True):
+                d = lower(ea, eb, roomy(ea, eb), 65, 33, 193, transposed_a=ta, **tags(ea, eb))
+                for batch in (2, 9):
+                    st, info = capi.classify_batched_status(d, batch)
+                    assert st == capi.QG_OK and list(info.limbs) == [LIMBS[ea], LIMBS[eb]], info.reason
+                    assert capi.classify_batched_launches(d, batch) == 1 and b"64x64" in bytes(info.reason), info.reason
+                seen.add(tuple(info.limbs))
+    assert len(seen) == 9
+
+
+def test_a_member_of_eighteen_tile_rows_stays_in_one_launch():
+    M, N, K, batch = 1089, 65, 65, 2
+    d = lower(E43, E43, roomy(E43, E43), M, N, K, **tags(E43, E43))
+    st, info = capi.classify_batched_status(d, batch)
+    assert st == capi.QG_OK and capi.classify_batched_launches(d, batch) == 1 and b"64x64" in bytes(info.reason)
+    # single limb: 18 x 2 tiles of 64x64 per member on one 128-byte k-tile; C in a 4-byte container (Qu<20,3>: 24 bits)
+    assert list(info.packed_bytes) == [batch * 18 * 64 * 128, batch * 2 * 64 * 128, batch * 18 * 2 * 64 * 64 * 4]
+    d = lower(E88, E88, roomy(E88, E88), M, N, K, **tags(E88, E88))
+    st, info = capi.classify_batched_status(d, batch)
+    assert st == capi.QG_OK and capi.classify_batched_launches(d, batch) == 1 and b"64x64" in bytes(info.reason)
+    # three limbs: two 64-byte k-tiles, three planes per member and ONE trailer; C in an 8-byte container (Qu<28,8>: 37 bits)
+    assert list(info.packed_bytes) == [batch * 3 * 18 * 64 * 128 + 256, batch * 3 * 2 * 64 * 128 + 256, batch * 18 * 2 * 64 * 64 * 8]
+
+
 def test_every_einval():
     d = lower(E43, E43, W16, 64, 64, 64, **L43)
     for batch in (0, -1):

@@ -9,6 +9,8 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BATCHES = (1, 2, 7, 8, 9, 300)
+TILE_ROWS = (1, 2, 3, 8, 9, 10, 17)      # qg_tile_of<8, true> walks a member in groups of 8 tile rows: one group, exactly one, a ragged second and third
+TILE_COLS = (1, 2, 3, 5)
 
 
 @pytest.fixture(scope="module")
@@ -50,8 +52,8 @@ def bd_tile_of(w, tmM, tnN):
 
 def test_every_workgroup_of_every_batch(printed):
     n = 0
-    for tmM in (1, 2, 3):
-        for tnN in (1, 2, 3):
+    for tmM in TILE_ROWS:
+        for tnN in TILE_COLS:
             for batch in BATCHES:
                 nwg = batch * tmM * tnN
                 got = printed[(tmM, tnN, batch)]
@@ -65,4 +67,4 @@ def test_every_workgroup_of_every_batch(printed):
                 assert sorted(by_w) == list(range(nwg))
                 assert [by_w[w][0] for w in range(nwg)] == [w // (tmM * tnN) for w in range(nwg)], (tmM, tnN, batch)
                 n += 1
-    assert n == 9 * len(BATCHES)
+    assert n == len(TILE_ROWS) * len(TILE_COLS) * len(BATCHES)
