@@ -811,6 +811,54 @@ void Qgemul(TD& D, const TA& A, const TB& B, const S0& s0, const Stages&... st)
     if (rc != QG_OK) throw std::runtime_error(std::string("Qgemul: ") + qgemul_strerror(rc));
 }
 
+// ---- the same on a batch: member b of D is the chain applied to Qgemul<…>(C[:, :, b], A[:, :, b], B[:, :, b]) ----
+//     Qu<dim<M, N, Bt>, DT> D;   Qu<dim<M, N>, BT> Bias;   Qu<dim<M, N, Bt>, RT> Res;
+//     QgemulBatched<…, QgemulResult<CT>>(D, A, B, ThenMul<…>(s), ThenAdd<…>(Bias), ThenSub<…>(Res), ThenApprox<…>());
+// A tensor operand of dim<M, N, Bt> holds one M x N tensor per member; one of dim<M, N> is SHARED by all members (a bias); a scalar
+// is one value for all members.  Real chains (qgemul_run_batched_epx, qgemul.h): small linear-class members run as one
+// block-diagonal launch and one pass over the whole stack, everything else member by member.
+namespace detail {
+template <class Dim> struct member_dim;
+template <size_t M, size_t N, size_t Bt> struct member_dim<dim<M, N, Bt>> { using type = dim<M, N>; };
+} // namespace detail
+template <typename... Tags, class TD, class TA, class TB, class S0, class... Stages>
+void QgemulBatched(TD& D, const TA& A, const TB& B, const S0& s0, const Stages&... st)
+{
+    using CT = typename detail::pick_result<Tags...>::type;
+    static_assert(!std::is_void_v<CT>, "QgemulBatched with element-wise operators needs QgemulResult<CT>");
+    static_assert(!CT::is_complex && !TD::elem_t::is_complex, "QgemulBatched: element-wise chains on a batch are real chains");
+    using member = typename detail::member_dim<typename TD::size>::type;
+    int64_t batch = 0, strides[3] = {0, 0, 0};
+    qgemul_desc d = QgemulBatched_lower_types<Tags...>(std::type_identity<Qu_s<typename TD::size, CT>>{}, std::type_identity<TA>{}, std::type_identity<TB>{}, &batch, strides);
+    d.flags |= QgemulDescFlags();
+    const void* E[QG_MAX_EW] = {};
+    int64_t strideE[QG_MAX_EW] = {};
+    uint32_t k = 0;
+    auto one = [&](const auto& stage) {
+        using S = std::remove_cvref_t<decltype(stage)>;
+        if constexpr (S::approx) {
+            E[k] = nullptr;                                   // reads no operand
+        } else if constexpr (S::scalar) {
+            E[k] = &stage.e;                                  // one element as the tensors store them
+        } else {
+            using esize = typename std::remove_cvref_t<decltype(stage.e)>::size;
+            static_assert(std::is_same_v<esize, typename TD::size> || std::is_same_v<esize, member>, "a tensor operand has D's shape (one per member) or one member's (shared)");
+            E[k] = stage.e.data.data();
+            strideE[k] = std::is_same_v<esize, member> ? 0 : strides[0];
+        }
+        ++k;
+    };
+    one(s0);
+    (one(st), ...);
+    const qgemul_epilogue ep = detail::lower_chain<S0, Stages...>(CT::fmt, TD::elem_t::fmt);
+    const auto ax = Qgemul_lower_approx(s0, st...);
+    qgemul_opts opts{};
+    opts.device = -1;
+    opts.flags = QgemulRunFlags();
+    const int rc = qgemul_run_batched_epx(&d, batch, &ep, ax.data(), D.data.data(), A.data.data(), B.data.data(), E, strides[0], strides[1], strides[2], strideE, &opts);
+    if (rc != QG_OK) throw std::runtime_error(std::string("QgemulBatched: ") + qgemul_strerror(rc));
+}
+
 // ------------------------------------------------------------------ Qreduce (SURVEY.md §8-f "next" #1)
 // The reference's tree reduction of a tensor, Qreduce<L…>(v) (QuBLAS.h:4960-4990, :5014-5018), on the
 // same engine path: C[1 x 1] = A[1 x len] * ones[len x 1] with the product format equal to the element

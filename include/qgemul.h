@@ -310,7 +310,7 @@ int qgemul_time_execute(qgemul_plan* p, void* packedC, const void* packedA, cons
  * members' packed Cs back to back.  qgemul_info.packed_bytes[] of a batched classify / plan are for the whole batch, ops too.
  * A batched plan is destroyed with qgemul_plan_destroy and answers qgemul_plan_info and qgemul_plan_packed_layout (in the one-
  * launch form: the stack's trailer, row sums and rows); every other plain entry point refuses it (QG_EINVAL), and the batched
- * entry points refuse a plain plan.  Epilogue chains on batched plans do not exist yet.
+ * entry points refuse a plain plan.  Element-wise chains on batched plans: the _batched_ep entry points further down.
  * QG_EINVAL: batch < 1, a stride below the member's extent (0 included), more than 2^31 - 1 output tiles in the batch.
  *   qgemul_classify_batched            pure host code
  *   qgemul_classify_batched_launches   pure host code: what qgemul_plan_batched_launches will answer (< 0: a status)
@@ -543,6 +543,53 @@ typedef struct qgemul_cmul_form {
     int32_t has_cmul, bits32, max_bits, reserved;
 } qgemul_cmul_form;
 int qgemul_cmul_plan_form(const qgemul_desc* d, const qgemul_epilogue_cplx* ep, const qgemul_cmul* const cx[QG_MAX_EW], qgemul_cmul_form* out);
+/* ---- element-wise chains on batched plans ----
+ * Member b of the batch is exactly  Qgemul<...>(C_b, A_b, B_b)  followed by the chain qgemul_execute_ep runs on a plain plan
+ * (qgemul_epilogue, APPROX stages included): scale, bias and activation after each of many small fixed-point layers, without the host
+ * loop over members.  ep is a real chain of 0 .. QG_MAX_EW stages; ax is as in qgemul_plan_create_epx (NULL: no APPROX stage).  A
+ * tensor operand of stage k is either ONE M x N tensor for every member (SHARED, e_shared[k] = 1: a bias) or one tensor per member
+ * (0); bep == NULL: no stage is shared.  Scalars are those of qgemul_ep_args, one per stage for all members.
+ * Status: whatever qgemul_classify_epx answers for the member descriptor (a complex descriptor is refused exactly as there);
+ * batch < 1 and the size checks of the batched plan — D and the stacked tensor operands included — are QG_EINVAL.
+ * Three forms; qgemul_info.reason names the one that runs and qgemul_plan_batched_launches counts its launches:
+ *   fused  (1)  members with the block-diagonal form, chain bounded by 32-bit arithmetic, no APPROX stage: the chain runs in the
+ *               epilogue of the ONE block-diagonal launch (k_mfma_ep_bd).  On request only: QG_OPT_FUSED_EPILOGUE
+ *   pass   (2)  the same members with any other supported chain, QG_OPT_UNFUSED_EPILOGUE, and the default: the block-diagonal
+ *               launch into a packed C of the plan for the whole stack, then ONE pass over the stack (k_eltwise_bd / k_approx_bd)
+ *   member by member   everything else (tree class, ring and composite plans, two-group-sized members, the raw-dot-product
+ *               pass): batch times what one member's qgemul_execute_ep issues, through the same entry points
+ * A shared operand is packed once and read at the member-local index: it is not replicated.
+ *   qgemul_pack_e_batched     member_stride in host elements of the operand: at least the member's extent (N - 1) * ld + M for a
+ *                             per-member stage, exactly 0 for a shared one; QG_EINVAL for anything else, for a stride that
+ *                             disagrees with the plan's e_shared and for a scalar or APPROX stage
+ *   qgemul_packed_e_bytes     on such a plan: one member's bytes for a shared stage, the stack's for a per-member one
+ *   qgemul_unpack_c_batched   unpacks D; qgemul_plan_info, qgemul_plan_fuses_epilogue, qgemul_plan_batched_launches and
+ *                             qgemul_plan_destroy answer for the plan; the plain entry points refuse it (QG_EINVAL);
+ *                             qgemul_execute_batched treats it as qgemul_execute treats a plain plan with an epilogue (QG_EINVAL);
+ *                             the _batched_ep entries refuse a batched plan without a chain and a plain plan
+ *   qgemul_run_batched_epx    one-shot, host pointers, synchronous.  Strides in host elements; strideE[k] == 0 marks stage k as
+ *                             shared; E[k] of a scalar stage points to one element; stage tensors are tight (ld = M); lda / ldb /
+ *                             ldc from opts.  The plan lives in the calling thread's cache like qgemul_run_batched's: a changed
+ *                             batch count, chain or shared pattern re-plans.  QG_OPT_ALL_DEVICES: QG_EUNSUPPORTED
+ * Not served: complex chains, per-member scalars, per-member shapes, a sharded form, BitStream export of a batched D. */
+typedef struct qgemul_batched_ep {
+    uint8_t e_shared[QG_MAX_EW];   /* tensor stage k: 1 = ONE M x N operand for every member, 0 = one operand per member;
+                                      ignored for scalar and APPROX stages */
+    uint8_t reserved[4];
+} qgemul_batched_ep;
+int qgemul_classify_batched_epx(const qgemul_desc* d, int64_t batch, const qgemul_epilogue* ep, const qgemul_approx* const ax[QG_MAX_EW],
+                                const qgemul_batched_ep* bep, uint32_t opt_flags, qgemul_info* out);
+int qgemul_classify_batched_epx_launches(const qgemul_desc* d, int64_t batch, const qgemul_epilogue* ep, const qgemul_approx* const ax[QG_MAX_EW],
+                                         const qgemul_batched_ep* bep, uint32_t opt_flags);
+int qgemul_plan_create_batched_epx(qgemul_ctx* c, const qgemul_desc* d, int64_t batch, const qgemul_epilogue* ep, const qgemul_approx* const ax[QG_MAX_EW],
+                                   const qgemul_batched_ep* bep, uint32_t opt_flags, qgemul_plan** out);
+int qgemul_pack_e_batched(qgemul_plan* p, int stage, const void* src_dev, int64_t ld, int64_t member_stride, void* packed_dev);
+int qgemul_execute_batched_ep(qgemul_plan* p, void* packedD, const void* packedA, const void* packedB, const qgemul_ep_args* args);
+int qgemul_time_execute_batched_ep(qgemul_plan* p, void* packedD, const void* packedA, const void* packedB, const qgemul_ep_args* args, int warmup, int iters,
+                                   float* avg_ms);
+int qgemul_run_batched_epx(const qgemul_desc* d, int64_t batch, const qgemul_epilogue* ep, const qgemul_approx* const ax[QG_MAX_EW], void* D, const void* A,
+                           const void* B, const void* const* E, int64_t strideD, int64_t strideA, int64_t strideB, const int64_t strideE[QG_MAX_EW],
+                           const qgemul_opts* o);
 /* sizeof of an ABI struct as THIS library was compiled (language bindings check their mirrors against it); 0: unknown id */
 enum { QG_SIZEOF_QFMT = 0, QG_SIZEOF_DESC = 1, QG_SIZEOF_OPTS = 2, QG_SIZEOF_INFO = 3, QG_SIZEOF_EW_STAGE = 4, QG_SIZEOF_EPILOGUE = 5,
        QG_SIZEOF_EP_ARGS = 6, QG_SIZEOF_EPILOGUE_CPLX = 7, QG_SIZEOF_APPROX_SEG = 8, QG_SIZEOF_APPROX = 9, QG_SIZEOF_CMUL = 10 };

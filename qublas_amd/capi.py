@@ -13,7 +13,7 @@ from typing import Optional
 
 import numpy as np
 
-from .desc import (QG_MAX_EW, Qcomplex, Qu, host_layout, qfmt, qgemul_approx, qgemul_approx_form, qgemul_approx_seg, qgemul_cmul, qgemul_cmul_form, qgemul_desc, qgemul_ep_args, qgemul_epilogue,
+from .desc import (QG_MAX_EW, Qcomplex, Qu, host_layout, qfmt, qgemul_approx, qgemul_approx_form, qgemul_approx_seg, qgemul_batched_ep, batched_ep, qgemul_cmul, qgemul_cmul_form, qgemul_desc, qgemul_ep_args, qgemul_epilogue,
                    qgemul_epilogue_cplx, qgemul_ew_stage, qgemul_info, qgemul_opts)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -46,6 +46,8 @@ EXPORTS = [
     "qgemul_classify_epcx", "qgemul_plan_create_epcx", "qgemul_run_epcx", "qgemul_cmul_plan_form",
     "qgemul_classify_batched", "qgemul_classify_batched_launches", "qgemul_plan_create_batched", "qgemul_plan_batched_launches", "qgemul_pack_batched",
     "qgemul_unpack_c_batched", "qgemul_execute_batched", "qgemul_time_execute_batched", "qgemul_run_batched",
+    "qgemul_classify_batched_epx", "qgemul_classify_batched_epx_launches", "qgemul_plan_create_batched_epx", "qgemul_pack_e_batched", "qgemul_execute_batched_ep",
+    "qgemul_time_execute_batched_ep", "qgemul_run_batched_epx",
 ]
 # qgemul_sizeof ids (include/qgemul.h) and the ctypes mirror each one must match
 SIZEOF_MIRRORS = {0: qfmt, 1: qgemul_desc, 2: qgemul_opts, 3: qgemul_info, 4: qgemul_ew_stage, 5: qgemul_epilogue, 6: qgemul_ep_args,
@@ -156,6 +158,14 @@ def lib() -> C.CDLL:
         L.qgemul_execute_batched.argtypes = [vp, vp, vp, vp]
         L.qgemul_time_execute_batched.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(C.c_float)]
         L.qgemul_run_batched.argtypes = [pd, i64, vp, vp, vp, i64, i64, i64, C.POINTER(qgemul_opts)]
+        pbe = C.POINTER(qgemul_batched_ep)
+        L.qgemul_classify_batched_epx.argtypes = [pd, i64, pe, pax, pbe, u32, C.POINTER(qgemul_info)]
+        L.qgemul_classify_batched_epx_launches.argtypes = [pd, i64, pe, pax, pbe, u32]
+        L.qgemul_plan_create_batched_epx.argtypes = [vp, pd, i64, pe, pax, pbe, u32, C.POINTER(vp)]
+        L.qgemul_pack_e_batched.argtypes = [vp, C.c_int, vp, i64, i64, vp]
+        L.qgemul_execute_batched_ep.argtypes = [vp, vp, vp, vp, pa]
+        L.qgemul_time_execute_batched_ep.argtypes = [vp, vp, vp, vp, pa, C.c_int, C.c_int, C.POINTER(C.c_float)]
+        L.qgemul_run_batched_epx.argtypes = [pd, i64, pe, pax, vp, vp, vp, C.POINTER(vp), i64, i64, i64, C.POINTER(i64), C.POINTER(qgemul_opts)]
         L.qgemul_sizeof.argtypes = [C.c_int]
         L.qgemul_sizeof.restype = C.c_size_t
         _lib = L
@@ -313,6 +323,43 @@ def run_batched_status(desc: qgemul_desc, batch: int, C_out: np.ndarray, A: np.n
 def run_batched(desc: qgemul_desc, batch: int, C_out: np.ndarray, A: np.ndarray, B: np.ndarray, strideC: int, strideA: int, strideB: int, **kw) -> np.ndarray:
     _chk(run_batched_status(desc, batch, C_out, A, B, strideC, strideA, strideB, **kw), "qgemul_run_batched")
     return C_out
+
+
+def _shared(shared):
+    """a qgemul_batched_ep from a sequence of flags (None: no stage is shared)"""
+    return C.byref(batched_ep(shared)) if shared is not None else None
+
+
+def classify_batched_epx_status(desc: qgemul_desc, batch: int, ep: qgemul_epilogue, approx=None, shared=None, flags: int = 0):
+    """qgemul_classify_batched_epx: (status, info); approx[k] = stage k's qgemul_approx or None, shared[k] = stage k's operand is shared"""
+    info = qgemul_info()
+    st = lib().qgemul_classify_batched_epx(C.byref(desc), batch, C.byref(ep), _tables(approx) if approx is not None else None, _shared(shared), flags, C.byref(info))
+    return st, info
+
+
+def classify_batched_epx_launches(desc: qgemul_desc, batch: int, ep: qgemul_epilogue, approx=None, shared=None, flags: int = 0) -> int:
+    """kernel launches per execute_ep of the batched plan (1 fused, 2 pass form, else batch x the member's); negative: a status"""
+    return int(lib().qgemul_classify_batched_epx_launches(C.byref(desc), batch, C.byref(ep), _tables(approx) if approx is not None else None, _shared(shared), flags))
+
+
+def run_batched_epx_status(desc: qgemul_desc, batch: int, ep: qgemul_epilogue, approx, D_out: np.ndarray, A: np.ndarray, B: np.ndarray, E, strideD: int, strideA: int,
+                           strideB: int, strideE, *, lda: int = 0, ldb: int = 0, ldc: int = 0, device: int = -1, flags: int = 0) -> int:
+    """qgemul_run_batched_epx on host-layout numpy buffers; E[k]: stage k's tensor(s), its one scalar element, or None (APPROX);
+    strideE[k] = 0 marks stage k as shared.  Returns the status."""
+    A = np.ascontiguousarray(A)
+    B = np.ascontiguousarray(B)
+    assert D_out.flags["C_CONTIGUOUS"]
+    E = [None if e is None else np.ascontiguousarray(e) for e in E]
+    ptrs = (C.c_void_p * QG_MAX_EW)(*[None if e is None else e.ctypes.data for e in E])
+    se = (C.c_int64 * QG_MAX_EW)(*[int(x) for x in strideE])
+    o = qgemul_opts(lda, ldb, ldc, device, flags)
+    return int(lib().qgemul_run_batched_epx(C.byref(desc), batch, C.byref(ep), _tables(approx) if approx is not None else None, D_out.ctypes.data_as(C.c_void_p),
+                                            A.ctypes.data_as(C.c_void_p), B.ctypes.data_as(C.c_void_p), ptrs, strideD, strideA, strideB, se, C.byref(o)))
+
+
+def run_batched_epx(desc, batch, ep, approx, D_out, A, B, E, strideD, strideA, strideB, strideE, **kw) -> np.ndarray:
+    _chk(run_batched_epx_status(desc, batch, ep, approx, D_out, A, B, E, strideD, strideA, strideB, strideE, **kw), "qgemul_run_batched_epx")
+    return D_out
 
 
 def run_sharded(desc: qgemul_desc, C_out: np.ndarray, A: np.ndarray, B: np.ndarray, devices, *, lda: int = 0, ldb: int = 0,
@@ -549,12 +596,19 @@ class Plan:
 class BatchedPlan:
     """A batched plan (include/qgemul.h, qgemul_*_batched): `batch` GEMMs of one descriptor at constant strides."""
 
-    def __init__(self, ctx: Context, desc: qgemul_desc, batch: int, flags: int = 0):
+    def __init__(self, ctx: Context, desc: qgemul_desc, batch: int, flags: int = 0, ep=None, approx=None, shared=None):
+        """ep: an element-wise chain after every member's GEMM (qgemul_plan_create_batched_epx); approx[k]: stage k's table or
+        None; shared[k]: stage k's tensor operand is ONE tensor for every member"""
         self.ctx = ctx
         self.desc = desc
         self.batch = batch
+        self.epilogue = ep
         self.h = C.c_void_p()
-        _chk(lib().qgemul_plan_create_batched(ctx.h, C.byref(desc), batch, flags, C.byref(self.h)), "qgemul_plan_create_batched")
+        if ep is None:
+            _chk(lib().qgemul_plan_create_batched(ctx.h, C.byref(desc), batch, flags, C.byref(self.h)), "qgemul_plan_create_batched")
+        else:
+            _chk(lib().qgemul_plan_create_batched_epx(ctx.h, C.byref(desc), batch, C.byref(ep), _tables(approx) if approx is not None else None, _shared(shared), flags,
+                                                      C.byref(self.h)), "qgemul_plan_create_batched_epx")
         self.info = qgemul_info()
         _chk(lib().qgemul_plan_info(self.h, C.byref(self.info)), "qgemul_plan_info")
 
@@ -584,4 +638,26 @@ class BatchedPlan:
     def time_execute(self, pC: int, pA: int, pB: int, warmup: int, iters: int) -> float:
         ms = C.c_float()
         _chk(lib().qgemul_time_execute_batched(self.h, C.c_void_p(pC), C.c_void_p(pA), C.c_void_p(pB), warmup, iters, C.byref(ms)), "qgemul_time_execute_batched")
+        return ms.value
+
+    # ---- plans with an element-wise chain (ep is not None) ----
+    @property
+    def fuses(self) -> int:
+        """1: the chain runs inside the GEMM launch(es), 0: as its own pass"""
+        return int(lib().qgemul_plan_fuses_epilogue(self.h))
+
+    def packed_e_bytes(self, stage: int) -> int:
+        """one member's bytes for a shared stage, the stack's for a per-member one, 0 for a scalar or APPROX stage"""
+        return int(lib().qgemul_packed_e_bytes(self.h, stage))
+
+    def pack_e(self, stage: int, src_dev: int, packed_dev: int, member_stride: int, ld: int = 0):
+        _chk(lib().qgemul_pack_e_batched(self.h, stage, C.c_void_p(src_dev), ld, member_stride, C.c_void_p(packed_dev)), "qgemul_pack_e_batched")
+
+    def execute_ep(self, pD: int, pA: int, pB: int, args: qgemul_ep_args):
+        _chk(lib().qgemul_execute_batched_ep(self.h, C.c_void_p(pD), C.c_void_p(pA), C.c_void_p(pB), C.byref(args)), "qgemul_execute_batched_ep")
+
+    def time_execute_ep(self, pD: int, pA: int, pB: int, args: qgemul_ep_args, warmup: int, iters: int) -> float:
+        ms = C.c_float()
+        _chk(lib().qgemul_time_execute_batched_ep(self.h, C.c_void_p(pD), C.c_void_p(pA), C.c_void_p(pB), C.byref(args), warmup, iters, C.byref(ms)),
+             "qgemul_time_execute_batched_ep")
         return ms.value

@@ -16,6 +16,7 @@
 #include "qg_plan.h"
 #include "qg_approx.h"
 #include "qg_cmul.h"
+#include "qg_bd_ep.h"
 
 static thread_local int g_last_hip = 0;
 
@@ -128,6 +129,14 @@ struct qgemul_plan {
     int bd, member_launches;
     qgemul_plan* member;
     int64_t mstride[3];
+    // element-wise chain on a batched plan (qgemul_plan_create_batched_epx: batch > 0 with has_ep).  ep / ept / pc (D) / pc_c (C) are
+    // the member's.  e_shared[k]: stage k's tensor operand is ONE M x N tensor for every member; estride[k]: bytes of one member's
+    // packed operand of stage k (0: no tensor operand) = the step from member to member of a per-member one.  With bd the chain runs
+    // inside the block-diagonal launch (bd_fused: k_mfma_ep_bd) or as one block-diagonal pass over the stack's packed C, which is
+    // this plan's cwork; without bd member by member through qgemul_execute_ep on `member`
+    uint8_t e_shared[QG_MAX_EW];
+    int bd_fused;
+    int64_t estride[QG_MAX_EW];
 };
 
 struct HostC { void* C; int64_t ld; };
@@ -350,7 +359,7 @@ static int plan_geometry(const qgemul_desc* d, uint32_t flags, QAnalysis* an, qg
         }
         const int mn = LA < LB ? LA : LB;
         cfg = qg_mfma_pick(LA, LB, d->M * parts, d->N * parts, (ep ? QG_OPT_LOCKSTEP_TILES : 0u) | flags);   // (the fused / unfused element-wise chain keeps the kernel it was measured on)
-        if (batch > 0 && !d->is_complex && !ep) {
+        if (batch > 0 && !d->is_complex && (!ep || !ev->im)) {   // (with a real chain: qgemul_plan_create_batched_epx)
             const QMfmaCfg bc = qg_mfma_pick_batched(LA, LB, batch, cfg);
             if (bc.variant) { plain_cfg = cfg; cfg = bc; bd = true; }
         }
@@ -1306,6 +1315,7 @@ static QEpArgs ep_device_args(const qgemul_plan* p, const qgemul_ep_args* args)
 int qgemul_apply_epilogue(qgemul_plan* p, void* packedD, const void* packedC, const qgemul_ep_args* args)
 {
     if (!p || !packedD || !packedC || !p->has_ep) return QG_EINVAL;
+    if (p->batch) return QG_EINVAL;   // a batched plan runs through the _batched entry points
     if (int s = ep_args_ok(p, args)) return s;
     if (p->desc.M == 0 || p->desc.N == 0) return QG_OK;
     QG_ON_DEVICE(p->ctx);
@@ -1340,6 +1350,7 @@ int qgemul_time_apply_epilogue(qgemul_plan* p, void* packedD, const void* packed
 int qgemul_execute_ep(qgemul_plan* p, void* packedD, const void* packedA, const void* packedB, const qgemul_ep_args* args)
 {
     if (!p || !packedD || !packedA || !packedB) return QG_EINVAL;
+    if (p->batch) return QG_EINVAL;   // a batched plan runs through the _batched entry points
     if (!p->has_ep) return args ? QG_EINVAL : qgemul_execute(p, packedD, packedA, packedB);
     if (int s = ep_args_ok(p, args)) return s;
     if (p->desc.M == 0 || p->desc.N == 0) return QG_OK;
@@ -1361,7 +1372,11 @@ int qgemul_execute_ep(qgemul_plan* p, void* packedD, const void* packedA, const 
     return run_chain_pass(p, p->cwork, packedD, a, args);
 }
 
-int qgemul_plan_fuses_epilogue(const qgemul_plan* p) { return p && p->has_ep && fuses_epilogue(p) ? 1 : 0; }
+int qgemul_plan_fuses_epilogue(const qgemul_plan* p)
+{
+    if (p && p->batch) return p->has_ep && (p->bd ? p->bd_fused : fuses_epilogue(p->member)) ? 1 : 0;
+    return p && p->has_ep && fuses_epilogue(p) ? 1 : 0;
+}
 
 int qgemul_plan_packed_layout(const qgemul_plan* p, int operand, int64_t out[4])
 {
@@ -1384,13 +1399,14 @@ static const QEpStage* stage_tensor(const qgemul_plan* p, int k)
 
 int64_t qgemul_packed_c_bytes(const qgemul_plan* p)
 {
-    return p && p->has_ep ? (int64_t)p->pc_c.parts * p->pc_c.Mp * p->pc_c.Np * p->pc_c.cbytes : 0;
+    return p && p->has_ep && !p->batch ? (int64_t)p->pc_c.parts * p->pc_c.Mp * p->pc_c.Np * p->pc_c.cbytes : 0;
 }
 
 // a tensor of the GEMM result's own element type -> the packed C the chain's pass reads (qgemul_apply_epilogue)
 int qgemul_pack_c(qgemul_plan* p, const void* src_dev, int64_t ld, void* packed_dev)
 {
     if (!p || !src_dev || !packed_dev || !p->has_ep) return QG_EINVAL;
+    if (p->batch) return QG_EINVAL;   // a batched plan runs through the _batched entry points
     if (ld && ld < p->desc.M) return QG_EINVAL;
     QG_ON_DEVICE(p->ctx);
     const QHostElem h = qg_host_elem(p->desc.c, p->desc.is_complex);
@@ -1402,6 +1418,7 @@ int qgemul_pack_c(qgemul_plan* p, const void* src_dev, int64_t ld, void* packed_
 int64_t qgemul_packed_e_bytes(const qgemul_plan* p, int stage)
 {
     if (!p || !p->has_ep || stage < 0 || stage >= p->ept.n) return 0;
+    if (p->batch) return p->e_shared[stage] ? p->estride[stage] : p->batch * p->estride[stage];   // (one member's / the stack's)
     const QEpStage* t = stage_tensor(p, stage);
     if (!t) return 0;
     return (p->ep_cplx && p->e_cplx[stage] ? 2 : 1) * p->pc.Mp * p->pc.Np * (int64_t)t->ebytes;
@@ -1410,6 +1427,7 @@ int64_t qgemul_packed_e_bytes(const qgemul_plan* p, int stage)
 int qgemul_pack_e(qgemul_plan* p, int stage, const void* src_dev, int64_t ld, void* packed_dev)
 {
     if (!p || !src_dev || !packed_dev || !p->has_ep || stage < 0 || stage >= p->ept.n) return QG_EINVAL;
+    if (p->batch) return QG_EINVAL;   // a batched plan runs through the _batched entry points
     const QEpStage* t = stage_tensor(p, stage);
     if (!t) return QG_EINVAL;
     if (ld && ld < p->desc.M) return QG_EINVAL;
@@ -1671,7 +1689,7 @@ static int time_execute(qgemul_plan* p, void* packedC, const void* packedA, cons
     QG_ON_DEVICE(p->ctx);
     hipStream_t st = p->ctx->stream;
     auto once = [&]() {
-        if (batched) return qgemul_execute_batched(p, packedC, packedA, packedB);
+        if (batched) return p->has_ep ? qgemul_execute_batched_ep(p, packedC, packedA, packedB, args) : qgemul_execute_batched(p, packedC, packedA, packedB);
         return p->has_ep ? qgemul_execute_ep(p, packedC, packedA, packedB, args) : qgemul_execute(p, packedC, packedA, packedB);
     };
     for (int i = 0; i < warmup; ++i) {
@@ -1733,6 +1751,7 @@ struct RunCache {
     uint8_t pcx_on[QG_MAX_EW] = {};
     uint32_t pflags = 0;
     int64_t pbatch = 0;       // > 0: the cached plan is a batched plan of that many members (qgemul_run_batched)
+    uint8_t pshared[QG_MAX_EW] = {};   // ... with a chain (qgemul_run_batched_epx): which stages' operands are shared
     enum { NBUF = 6 + 16 };   // 0-5: host-layout A, B, C and packed A, B, C; behind them: the epilogue operands (2 per stage) or, on the
                               // root of a sharded call, the landing buffers of the other bands
     void* buf[NBUF] = {};
@@ -2238,13 +2257,19 @@ static int64_t member_extent(const qgemul_desc& d, int operand, int64_t ld)
 }
 
 // the geometry of a batched plan, pure host code: m (zeroed) receives the member's, b (zeroed) the batch's
-static int batched_geometry(const qgemul_desc* d, int64_t batch, uint32_t flags, qgemul_plan* m, qgemul_plan* b)
+// ev: the chain of a batched plan with one (qgemul_plan_create_batched_epx), bep: which of its tensor operands are shared
+static int batched_geometry(const qgemul_desc* d, int64_t batch, uint32_t flags, qgemul_plan* m, qgemul_plan* b, const EpView* ev = nullptr,
+                            const qgemul_batched_ep* bep = nullptr)
 {
     if (!d || batch < 1) return QG_EINVAL;
     int bd = 0;
     m->desc = *d;
     m->flags = flags;
-    const int st = plan_geometry(d, flags, &m->an, &m->info, &m->LA, &m->LB, &m->cfg, &m->pa, &m->pb, &m->pc, &m->ha, &m->hb, &m->hc, nullptr, &m->ept, &m->pc_c,
+    if (ev) {
+        m->has_ep = 1;
+        for (int k = 0; ev->ax && k < QG_MAX_EW; ++k) m->has_ax |= ev->ax[k] != nullptr;
+    }
+    const int st = plan_geometry(d, flags, &m->an, &m->info, &m->LA, &m->LB, &m->cfg, &m->pa, &m->pb, &m->pc, &m->ha, &m->hb, &m->hc, ev, &m->ept, &m->pc_c,
                                  &m->ept_im, &m->comp, nullptr, nullptr, batch, &bd);
     b->info = m->info;
     if (st != QG_OK) return st;
@@ -2264,6 +2289,29 @@ static int batched_geometry(const qgemul_desc* d, int64_t batch, uint32_t flags,
     b->member_launches = plan_launches(m);
     int64_t total[3];
     bool over = false;
+    if (ev) {
+        // the chain is the member's; what one member's qgemul_execute_ep issues: its kernel and, unless fused, the chain's pass
+        b->has_ep = 1;
+        b->has_ax = m->has_ax;
+        b->ep = *ev->re;
+        b->ept = m->ept;
+        b->pc_c = m->pc_c;
+        if (!fuses_epilogue(m)) b->member_launches += 1;
+        // fused form: what fuses_epilogue accepts on arithmetic grounds, on request (the default between the two block-diagonal
+        // forms is the pass until tools/measure_batched_ep.py has decided otherwise: DESIGN.md section 9)
+        b->bd_fused = bd && m->ept.bits32 && !m->has_ax && (flags & QG_OPT_FUSED_EPILOGUE) && !(flags & QG_OPT_UNFUSED_EPILOGUE);
+        for (int k = 0; k < m->ept.n; ++k) {
+            const QEpStage& s = m->ept.st[k];
+            if (s.scalar || s.op == QG_EW_APPROX) continue;
+            b->e_shared[k] = bep && bep->e_shared[k] ? 1 : 0;
+            // (member by member: 256-byte steps like the other packed operands', so that every member's operand keeps the alignment the
+            // pass's 16-byte loads have on a plain plan)
+            int64_t stack = 0;
+            over |= __builtin_mul_overflow(m->pc.Mp * m->pc.Np, (int64_t)s.ebytes, &b->estride[k]);
+            if (!bd) b->estride[k] = round_up(b->estride[k], 256);
+            over |= __builtin_mul_overflow(b->estride[k], batch, &stack) || stack > (1ll << 60);
+        }
+    }
     if (bd) {
         int64_t tiles = 0;
         over |= __builtin_mul_overflow((m->pa.rows_p / m->cfg.TM) * (m->pb.rows_p / m->cfg.TN), batch, &tiles) || tiles > 0x7fffffffll;
@@ -2287,6 +2335,9 @@ static int batched_geometry(const qgemul_desc* d, int64_t batch, uint32_t flags,
         b->mstride[2] = m->info.packed_bytes[2];
         over |= __builtin_mul_overflow(b->mstride[2], batch, &total[2]);
         snprintf(b->info.reason, sizeof b->info.reason, "linear class: %lld members in one block-diagonal launch, %dx%d tiles", (long long)batch, m->cfg.TM, m->cfg.TN);
+        if (ev)
+            snprintf(b->info.reason, sizeof b->info.reason, b->bd_fused ? "linear class: %lld members, chain fused into one block-diagonal launch" : "linear class: %lld members, block-diagonal launch + one chain pass over the stack",
+                     (long long)batch);
     } else {
         for (int w = 0; w < 3; ++w) {
             b->mstride[w] = round_up(m->info.packed_bytes[w], 256);
@@ -2294,6 +2345,11 @@ static int batched_geometry(const qgemul_desc* d, int64_t batch, uint32_t flags,
         }
         b->pa = m->pa;
         b->pb = m->pb;
+        if (ev) {
+            char why[sizeof m->info.reason];
+            memcpy(why, m->info.reason, sizeof why);
+            snprintf(b->info.reason, sizeof b->info.reason, "chain member by member: %.70s", why);
+        }
     }
     if (over) {
         b->info.supported = 0;
@@ -2349,7 +2405,7 @@ int qgemul_plan_create_batched(qgemul_ctx* c, const qgemul_desc* d, int64_t batc
 int qgemul_plan_batched_launches(const qgemul_plan* p)
 {
     if (!p || !p->batch) return QG_EINVAL;
-    if (p->bd) return 1;
+    if (p->bd) return p->has_ep && !p->bd_fused ? 2 : 1;
     const int64_t n = p->batch * p->member_launches;
     return n > 0x7fffffffll ? 0x7fffffff : (int)n;
 }
@@ -2391,20 +2447,12 @@ int qgemul_unpack_c_batched(qgemul_plan* p, const void* packed_dev, void* dst_de
     return QG_OK;
 }
 
-int qgemul_execute_batched(qgemul_plan* p, void* packedC, const void* packedA, const void* packedB)
+// the block-diagonal launch of a batched plan: the stack is a packed A and a packed B, with its own plane masks and row sums, and the
+// member's conversion into C
+static QMfmaArgs bd_mfma_args(const qgemul_plan* p, void* packedC, const void* packedA, const void* packedB, int cbytes)
 {
-    if (!p || !p->batch || !packedC || !packedA || !packedB) return QG_EINVAL;
-    if (p->desc.M == 0 || p->desc.N == 0) return QG_OK;
-    qgemul_plan* m = p->member;
-    if (!p->bd) {
-        for (int64_t b = 0; b < p->batch; ++b)
-            if (const int st = qgemul_execute(m, (char*)packedC + b * p->mstride[2], (const char*)packedA + b * p->mstride[0], (const char*)packedB + b * p->mstride[1]); st != QG_OK)
-                return st;
-        return QG_OK;
-    }
-    QG_ON_DEVICE(p->ctx);
-    // the stack is a packed A and a packed B: its own plane masks and row sums, the member's conversion into C
-    QMfmaArgs a = mfma_args(p->pa, p->pb, p->variant, packedA, packedB, packedC, p->pc.cbytes);
+    const qgemul_plan* m = p->member;
+    QMfmaArgs a = mfma_args(p->pa, p->pb, p->variant, packedA, packedB, packedC, cbytes);
     a.to_c = m->an.lin.to_c[0];
     if (p->pa.offs) {   // centred operands: one centre per operand for the whole stack (centre_args)
         a.rsA = (const int64_t*)((const char*)packedA + p->pa.rowsum_off);
@@ -2415,12 +2463,30 @@ int qgemul_execute_batched(qgemul_plan* p, void* packedC, const void* packedA, c
     }
     a.bd_tm = (int32_t)(m->pa.rows_p / p->cfg.TM);
     a.bd_tn = (int32_t)(m->pb.rows_p / p->cfg.TN);
+    return a;
+}
+
+int qgemul_execute_batched(qgemul_plan* p, void* packedC, const void* packedA, const void* packedB)
+{
+    if (!p || !p->batch || !packedC || !packedA || !packedB) return QG_EINVAL;
+    if (p->has_ep) return QG_EINVAL;  // a batched plan with a chain runs through qgemul_execute_batched_ep
+    if (p->desc.M == 0 || p->desc.N == 0) return QG_OK;
+    qgemul_plan* m = p->member;
+    if (!p->bd) {
+        for (int64_t b = 0; b < p->batch; ++b)
+            if (const int st = qgemul_execute(m, (char*)packedC + b * p->mstride[2], (const char*)packedA + b * p->mstride[0], (const char*)packedB + b * p->mstride[1]); st != QG_OK)
+                return st;
+        return QG_OK;
+    }
+    QG_ON_DEVICE(p->ctx);
+    const QMfmaArgs a = bd_mfma_args(p, packedC, packedA, packedB, p->pc.cbytes);
     QG_HIP(qg_launch_mfma_bd(p->LA, p->LB, a, p->batch, p->ctx->stream));
     return QG_OK;
 }
 
 int qgemul_time_execute_batched(qgemul_plan* p, void* packedC, const void* packedA, const void* packedB, int warmup, int iters, float* avg_ms)
 {
+    if (p && p->has_ep) return QG_EINVAL;
     return time_execute(p, packedC, packedA, packedB, nullptr, warmup, iters, avg_ms, true);
 }
 
@@ -2487,6 +2553,265 @@ int qgemul_run_batched(const qgemul_desc* d, int64_t batch, void* C, const void*
         if ((st = qgemul_execute_batched(p, pC, pA, pB))) break;
         if ((st = qgemul_unpack_c_batched(p, pC, dC, opts.ldc, strideC))) break;
         if (hipMemcpyAsync(C, dC, bytesC, hipMemcpyDeviceToHost, s) != hipSuccess) { st = QG_EHIP; break; }
+    } while (0);
+    const hipError_t e = hipStreamSynchronize(c.ctx->stream);
+    if (st == QG_OK && e != hipSuccess) { g_last_hip = (int)e; st = QG_EHIP; }
+    return st;
+}
+
+// ---- element-wise chains on batched plans (include/qgemul.h): member b is Qgemul<...>(C_b, A_b, B_b) followed by the chain ----
+static int classify_batched_epx(const qgemul_desc* d, int64_t batch, const qgemul_epilogue* ep, const qgemul_approx* const* ax, const qgemul_batched_ep* bep,
+                                uint32_t opt_flags, qgemul_info* out, int* launches)
+{
+    if (!d || !ep) return QG_EINVAL;
+    static const qgemul_approx* const no_ax[QG_MAX_EW] = {};
+    const EpView v = {ep, nullptr, nullptr, ax ? ax : no_ax};
+    qgemul_plan* two = new (std::nothrow) qgemul_plan[2];
+    if (!two) return QG_EINVAL;
+    memset(two, 0, 2 * sizeof *two);
+    int st = batched_geometry(d, batch, opt_flags, &two[0], &two[1], &v, bep);
+    if (out && batch >= 1) *out = two[1].info;
+    if (launches && st == QG_OK) *launches = qgemul_plan_batched_launches(&two[1]);
+    delete[] two;
+    return st;
+}
+
+int qgemul_classify_batched_epx(const qgemul_desc* d, int64_t batch, const qgemul_epilogue* ep, const qgemul_approx* const ax[QG_MAX_EW],
+                                const qgemul_batched_ep* bep, uint32_t opt_flags, qgemul_info* out)
+{
+    if (!out) return QG_EINVAL;
+    return classify_batched_epx(d, batch, ep, ax, bep, opt_flags, out, nullptr);
+}
+
+int qgemul_classify_batched_epx_launches(const qgemul_desc* d, int64_t batch, const qgemul_epilogue* ep, const qgemul_approx* const ax[QG_MAX_EW],
+                                         const qgemul_batched_ep* bep, uint32_t opt_flags)
+{
+    int n = 0;
+    const int st = classify_batched_epx(d, batch, ep, ax, bep, opt_flags, nullptr, &n);
+    return st == QG_OK ? n : st;
+}
+
+int qgemul_plan_create_batched_epx(qgemul_ctx* c, const qgemul_desc* d, int64_t batch, const qgemul_epilogue* ep, const qgemul_approx* const ax[QG_MAX_EW],
+                                   const qgemul_batched_ep* bep, uint32_t opt_flags, qgemul_plan** out)
+{
+    if (!c || !d || !ep || !out) return QG_EINVAL;
+    static const qgemul_approx* const no_ax[QG_MAX_EW] = {};
+    const EpView v = {ep, nullptr, nullptr, ax ? ax : no_ax};
+    qgemul_plan* two = new (std::nothrow) qgemul_plan[2];
+    qgemul_plan* b = new (std::nothrow) qgemul_plan;
+    if (!two || !b) { delete[] two; delete b; return QG_EINVAL; }
+    memset(two, 0, 2 * sizeof *two);
+    int st = batched_geometry(d, batch, opt_flags, &two[0], &two[1], &v, bep);
+    *b = two[1];
+    delete[] two;
+    b->ctx = c;
+    // the member owns the chain's device tables (APPROX) and, member by member, everything else
+    if (st == QG_OK) st = plan_create_view(c, d, &v, opt_flags, &b->member, batch);
+    if (st != QG_OK) { delete b; return st; }
+    if (b->bd && !b->bd_fused) {   // the pass form: the stack's packed C between the two launches
+        DeviceScope scope(c->device);
+        const size_t cb = (size_t)batch * (size_t)(b->pc_c.Mp * b->pc_c.Np) * (size_t)b->pc_c.cbytes;
+        if (scope.err != hipSuccess || hipMalloc(&b->cwork, cb ? cb : 16) != hipSuccess) {
+            qgemul_plan_destroy(b);
+            return QG_EHIP;
+        }
+    }
+    *out = b;
+    return QG_OK;
+}
+
+int qgemul_pack_e_batched(qgemul_plan* p, int stage, const void* src_dev, int64_t ld, int64_t member_stride, void* packed_dev)
+{
+    if (!p || !p->batch || !p->has_ep || !src_dev || !packed_dev || stage < 0 || stage >= p->ept.n) return QG_EINVAL;
+    if (!p->estride[stage]) return QG_EINVAL;   // a scalar or APPROX stage has no tensor operand
+    const int64_t ext = member_extent(p->desc, QG_OPERAND_C, ld);
+    if (ext < 1) return QG_EINVAL;
+    if (p->e_shared[stage] ? member_stride != 0 : member_stride < ext) return QG_EINVAL;
+    const qfmt f[2] = {p->ep.stage[stage].e, p->ep.stage[stage].e};
+    const int64_t eb = qg_host_elem(f, 0).size;
+    const int64_t n = p->e_shared[stage] ? 1 : p->batch;
+    for (int64_t b = 0; b < n; ++b)   // (a layout step like qgemul_unpack_c_batched: one launch per member)
+        if (const int st = qgemul_pack_e(p->member, stage, (const char*)src_dev + b * member_stride * eb, ld, (char*)packed_dev + b * p->estride[stage]); st != QG_OK) return st;
+    return QG_OK;
+}
+
+int qgemul_execute_batched_ep(qgemul_plan* p, void* packedD, const void* packedA, const void* packedB, const qgemul_ep_args* args)
+{
+    if (!p || !p->batch || !p->has_ep || !packedD || !packedA || !packedB) return QG_EINVAL;
+    if (int s = ep_args_ok(p, args)) return s;
+    if (p->desc.M == 0 || p->desc.N == 0) return QG_OK;
+    qgemul_plan* m = p->member;
+    if (!p->bd) {
+        for (int64_t b = 0; b < p->batch; ++b) {
+            qgemul_ep_args ma;
+            memset(&ma, 0, sizeof ma);
+            for (int k = 0; k < p->ept.n; ++k) {
+                ma.e_scalar[k] = args->e_scalar[k];
+                if (p->estride[k]) ma.e_packed[k] = (const char*)args->e_packed[k] + (p->e_shared[k] ? 0 : b * p->estride[k]);
+            }
+            if (const int st = qgemul_execute_ep(m, (char*)packedD + b * p->mstride[2], (const char*)packedA + b * p->mstride[0], (const char*)packedB + b * p->mstride[1], &ma); st != QG_OK)
+                return st;
+        }
+        return QG_OK;
+    }
+    QG_ON_DEVICE(p->ctx);
+    hipStream_t st = p->ctx->stream;
+    QBdEp be;
+    memset(&be, 0, sizeof be);
+    be.msize = p->pc_c.Mp * p->pc_c.Np;
+    for (int k = 0; k < p->ept.n; ++k)
+        if (p->estride[k] && p->e_shared[k]) be.shared |= 1u << k;
+    const QEpArgs ea = ep_device_args(p, args);
+    if (p->bd_fused) {
+        // ONE launch: the block-diagonal kernel's epilogue runs the chain on the value it has just converted into C's type
+        QMfmaEpBdArgs a;
+        memset(&a, 0, sizeof a);
+        (QMfmaArgs&)a = bd_mfma_args(p, packedD, packedA, packedB, p->pc_c.cbytes);
+        a.has_ep = 1;
+        a.ep = p->ept;
+        a.epa = ea;
+        a.bd = be;
+        QG_HIP(qg_launch_mfma_ep_bd(p->LA, p->LB, a, p->batch, st));
+        return QG_OK;
+    }
+    // TWO launches: the block-diagonal kernel as it is into the plan's packed C of the whole stack, then ONE pass over the stack
+    const QMfmaArgs a = bd_mfma_args(p, p->cwork, packedA, packedB, p->pc_c.cbytes);
+    QG_HIP(qg_launch_mfma_bd(p->LA, p->LB, a, p->batch, st));
+    QEltwiseArgs g;
+    memset(&g, 0, sizeof g);
+    g.C = (const char*)p->cwork;
+    g.D = (char*)packedD;
+    g.n = p->batch * be.msize;
+    g.cbytes = p->pc_c.cbytes;
+    g.t = p->ept;
+    g.a = ea;
+    if (p->has_ax) {
+        QApproxBdArgs x;
+        memset(&x, 0, sizeof x);
+        x.x.g = g;
+        for (int k = 0; k < QG_MAX_EW; ++k) x.x.ax[k] = m->ax_dev[k];
+        x.x.force_general = (p->flags & QG_OPT_APPROX_GENERAL) ? 1 : 0;
+        x.bd = be;
+        QG_HIP(qg_launch_approx_bd(x, st));
+        return QG_OK;
+    }
+    QEltwiseBdArgs e;
+    memset(&e, 0, sizeof e);
+    e.g = g;
+    e.bd = be;
+    QG_HIP(qg_launch_eltwise_bd(e, st));
+    return QG_OK;
+}
+
+int qgemul_time_execute_batched_ep(qgemul_plan* p, void* packedD, const void* packedA, const void* packedB, const qgemul_ep_args* args, int warmup, int iters,
+                                   float* avg_ms)
+{
+    if (!p || !p->has_ep) return QG_EINVAL;
+    return time_execute(p, packedD, packedA, packedB, args, warmup, iters, avg_ms, true);
+}
+
+int qgemul_run_batched_epx(const qgemul_desc* d, int64_t batch, const qgemul_epilogue* ep, const qgemul_approx* const ax[QG_MAX_EW], void* D, const void* A,
+                           const void* B, const void* const* E, int64_t strideD, int64_t strideA, int64_t strideB, const int64_t strideE[QG_MAX_EW],
+                           const qgemul_opts* o)
+{
+    if (!d || !ep || !D || !A || !B || batch < 1 || ep->n_stages > QG_MAX_EW) return QG_EINVAL;
+    qgemul_opts opts;
+    memset(&opts, 0, sizeof opts);
+    opts.device = -1;
+    if (o) opts = *o;
+    if (opts.flags & QG_OPT_ALL_DEVICES) return QG_EUNSUPPORTED;   // (the sharded entry has no batched form)
+    const int64_t extA = member_extent(*d, QG_OPERAND_A, opts.lda), extB = member_extent(*d, QG_OPERAND_B, opts.ldb), extD = member_extent(*d, QG_OPERAND_C, opts.ldc);
+    if (extA < 1 || extB < 1 || extD < 1 || strideA < extA || strideB < extB || strideD < extD) return QG_EINVAL;
+    const int64_t extE = member_extent(*d, QG_OPERAND_C, 0);   // (stage operands are tight)
+    qgemul_batched_ep bep;
+    memset(&bep, 0, sizeof bep);
+    for (uint32_t k = 0; k < ep->n_stages; ++k) {
+        const qgemul_ew_stage& s = ep->stage[k];
+        if (s.op == QG_EW_APPROX) continue;
+        if (!E || !E[k]) return QG_EINVAL;
+        if (s.e_scalar) continue;
+        if (!strideE || (strideE[k] != 0 && strideE[k] < extE)) return QG_EINVAL;
+        bep.e_shared[k] = strideE[k] == 0;
+    }
+    g_reaper.armed = true;
+    static ShutdownHook hook;
+    RunCache& c = g_run;
+    if (opts.device < 0 && c.ctx) {
+        int cur = c.device;
+        if (hipGetDevice(&cur) == hipSuccess) opts.device = cur;
+    }
+    const bool same_plan = c.plan && c.pbatch == batch && c.pflags == opts.flags && same_desc(c.pd, *d) && c.has_pe && !c.pe_cplx && same_epilogue(c.pe.part[0], *ep) &&
+                           same_tables(c, ax) && !memcmp(c.pshared, bep.e_shared, sizeof c.pshared) && (opts.device < 0 || opts.device == c.device);
+    if (!same_plan) {   // validate before touching the device
+        qgemul_info info;
+        if (const int st = qgemul_classify_batched_epx(d, batch, ep, ax, &bep, opts.flags, &info); st != QG_OK) return st;
+    }
+    if (d->M == 0 || d->N == 0) return QG_OK;
+    int st = QG_OK;
+    if (!c.ctx || (opts.device >= 0 && opts.device != c.device)) {
+        release_cache(c);
+        st = qgemul_ctx_create(opts.device, &c.ctx);
+        if (st != QG_OK) { c.ctx = nullptr; return st; }
+        c.device = c.ctx->device;
+    } else {
+        QG_HIP(hipSetDevice(c.device));
+    }
+    if (!same_plan) {
+        if (c.plan) { qgemul_plan_destroy(c.plan); c.plan = nullptr; }
+        st = qgemul_plan_create_batched_epx(c.ctx, d, batch, ep, ax, &bep, opts.flags, &c.plan);
+        if (st != QG_OK) { c.plan = nullptr; return st; }
+        c.pd = *d;
+        c.has_pe = true;
+        c.pe_cplx = false;
+        c.pe.part[0] = *ep;
+        memset(c.pax_on, 0, sizeof c.pax_on);
+        for (int k = 0; ax && k < QG_MAX_EW; ++k) {
+            if (!ax[k]) continue;
+            if (!c.pax) c.pax = new qgemul_approx[QG_MAX_EW];
+            c.pax[k] = *ax[k];
+            c.pax_on[k] = 1;
+        }
+        memset(c.pcx_on, 0, sizeof c.pcx_on);
+        memcpy(c.pshared, bep.e_shared, sizeof c.pshared);
+        c.pflags = opts.flags;
+        c.pbatch = batch;
+    }
+    qgemul_plan* p = c.plan;
+    void *dA, *dB, *dD, *pA, *pB, *pD;
+    do {
+        const size_t bytesA = (size_t)((batch - 1) * strideA + extA) * p->ha.size;
+        const size_t bytesB = (size_t)((batch - 1) * strideB + extB) * p->hb.size;
+        const size_t bytesD = (size_t)((batch - 1) * strideD + extD) * p->hc.size;
+        if ((st = cache_buffer(c, 0, bytesA, &dA)) || (st = cache_buffer(c, 1, bytesB, &dB)) || (st = cache_buffer(c, 2, bytesD, &dD)) ||
+            (st = cache_buffer(c, 3, (size_t)p->info.packed_bytes[0], &pA)) || (st = cache_buffer(c, 4, (size_t)p->info.packed_bytes[1], &pB)) ||
+            (st = cache_buffer(c, 5, (size_t)p->info.packed_bytes[2], &pD)))
+            break;
+        hipStream_t s = c.ctx->stream;
+        if (hipMemcpyAsync(dA, A, bytesA, hipMemcpyHostToDevice, s) != hipSuccess || hipMemcpyAsync(dB, B, bytesB, hipMemcpyHostToDevice, s) != hipSuccess) { st = QG_EHIP; break; }
+        // the caller's D may have gaps between columns and between members: those bytes stay as they are
+        if ((strideD != d->M * d->N || (opts.ldc && opts.ldc != d->M)) && hipMemcpyAsync(dD, D, bytesD, hipMemcpyHostToDevice, s) != hipSuccess) { st = QG_EHIP; break; }
+        if ((st = qgemul_pack_batched(p, QG_OPERAND_A, dA, opts.lda, strideA, pA)) || (st = qgemul_pack_batched(p, QG_OPERAND_B, dB, opts.ldb, strideB, pB))) break;
+        qgemul_ep_args ea;
+        memset(&ea, 0, sizeof ea);
+        for (uint32_t k = 0; k < ep->n_stages && !st; ++k) {
+            const qgemul_ew_stage& sr = ep->stage[k];
+            if (sr.op == QG_EW_APPROX) continue;
+            if (sr.e_scalar) {
+                ea.e_scalar[k] = (1 + (int)sr.e.I + (int)sr.e.F) <= 32 ? (int64_t) * (const int32_t*)E[k] : *(const int64_t*)E[k];
+                continue;
+            }
+            const qfmt f[2] = {sr.e, sr.e};
+            const size_t bytesE = (size_t)((bep.e_shared[k] ? 0 : (batch - 1) * strideE[k]) + extE) * (size_t)qg_host_elem(f, 0).size;
+            void *dE, *pE;
+            if ((st = cache_buffer(c, 6 + 2 * (int)k, bytesE, &dE)) || (st = cache_buffer(c, 7 + 2 * (int)k, (size_t)qgemul_packed_e_bytes(p, (int)k), &pE))) break;
+            if (hipMemcpyAsync(dE, E[k], bytesE, hipMemcpyHostToDevice, s) != hipSuccess) { st = QG_EHIP; break; }
+            if ((st = qgemul_pack_e_batched(p, (int)k, dE, 0, strideE[k], pE))) break;
+            ea.e_packed[k] = pE;
+        }
+        if (st) break;
+        if ((st = qgemul_execute_batched_ep(p, pD, pA, pB, &ea))) break;
+        if ((st = qgemul_unpack_c_batched(p, pD, dD, opts.ldc, strideD))) break;
+        if (hipMemcpyAsync(D, dD, bytesD, hipMemcpyDeviceToHost, s) != hipSuccess) { st = QG_EHIP; break; }
     } while (0);
     const hipError_t e = hipStreamSynchronize(c.ctx->stream);
     if (st == QG_OK && e != hipSuccess) { g_last_hip = (int)e; st = QG_EHIP; }

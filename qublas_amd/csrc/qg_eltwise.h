@@ -99,6 +99,26 @@ __device__ __forceinline__ void qg_ep_apply_runs(T (&v)[4 * NR], const QEpTable&
     qg_step_all<T, 4 * NR>(v, t.to_d);
 }
 
+// ... in the block-diagonal forms of a batched plan (QBdEp, qg_kernels.h): idx0 runs over the whole stack; stage k's tensor operand
+// is read there too unless bit k of `shared` is set: a shared operand is one member's tensor, read `member_off` elements lower
+template <class T, int NR>
+__device__ __forceinline__ void qg_ep_apply_runs_bd(T (&v)[4 * NR], const QEpTable& t, const QEpArgs& a, int64_t idx0, int64_t stride, int64_t member_off, uint32_t shared)
+{
+    for (int k = 0; k < t.n; ++k) {
+        T e[4 * NR];
+        if (t.st[k].scalar) {
+#pragma unroll
+            for (int o = 0; o < 4 * NR; ++o) e[o] = (T)a.scalar[k];
+        } else {
+            const int64_t i0 = ((shared >> k) & 1u) ? idx0 - member_off : idx0;
+#pragma unroll
+            for (int q = 0; q < NR; ++q) qg_ep_load_run<4, T>(a.e[k], i0 + q * stride, t.st[k].ebytes, e + 4 * q);
+        }
+        qg_ep_stage<T, 4 * NR>(v, e, t.st[k]);
+    }
+    qg_step_all<T, 4 * NR>(v, t.to_d);
+}
+
 // RUN consecutive packed elements of `bytes` each, starting at element index idx
 template <class T>
 __device__ __forceinline__ void qg_ep_store_run(char* D, int64_t idx, int bytes, const T* v)

@@ -203,6 +203,26 @@ static_assert(offsetof(QMfmaArgs, bd_tm) == offsetof(QMfmaArgs, kara) + 4 && off
               offsetof(QMfmaArgs, bd_tn) == offsetof(QMfmaArgs, has_ep) + 4 && offsetof(QMfmaArgs, dbg) == offsetof(QMfmaArgs, has_ep) + 8,
               "QMfmaArgs: the block-diagonal fields sit in former padding; no field may move");
 hipError_t qg_launch_mfma(int LA, int LB, const QMfmaArgs& a, hipStream_t st);
+// An element-wise chain on a batched plan (qgemul_plan_create_batched_epx) in its block-diagonal forms: C, D and every per-member
+// tensor operand are the members' packed tensors back to back (one index space over the whole stack); a SHARED operand is ONE
+// member's packed tensor, read at the member-local index  i - member * msize.  msize = elements of one member's packed C (a
+// whole number of 64 x 64 tiles), shared bit k = stage k's tensor operand is shared.  The new kernels carry this in argument
+// structs of their own: QMfmaArgs, QEpArgs and QEltwiseArgs are what they were, so no existing kernel's code moves.
+struct QBdEp {
+    int64_t msize;
+    uint32_t shared, pad_;
+};
+struct QMfmaEpBdArgs : QMfmaArgs {
+    QBdEp bd;
+};
+// the QBdEp of a kernel's argument struct (kernels whose arguments have none never evaluate the result)
+template <class G>
+QG_HD auto qg_bd_ep_of(const G& g, int) -> decltype(g.bd) { return g.bd; }
+template <class G>
+QG_HD QBdEp qg_bd_ep_of(const G&, long) { return QBdEp{0, 0, 0}; }
+// the block-diagonal launch with the chain in the kernel's epilogue (qg_mfma_ep_bd.hip: k_mfma_ep_bd, the body of k_mfma with BD and
+// EP together): the geometries of qg_launch_mfma_bd, chains the planner has bounded by 32-bit arithmetic
+hipError_t qg_launch_mfma_ep_bd(int LA, int LB, const QMfmaEpBdArgs& a, int64_t batch, hipStream_t st);
 // `batch` GEMMs of one member shape in ONE launch of k_mfma's block-diagonal form (qg_mfma.hip): the variants qg_mfma_pick_batched
 // returns, no element-wise chain, no Karatsuba digits; anything else is hipErrorInvalidValue
 hipError_t qg_launch_mfma_bd(int LA, int LB, const QMfmaArgs& a, int64_t batch, hipStream_t st);

@@ -1,6 +1,7 @@
-// qg_mfma_body.h — the body of k_mfma and k_mfma_bd (qg_mfma.hip), included INSIDE both kernels: no include guard, nothing at
-// namespace scope.  In scope where it is included: the kernel argument `QMfmaArgs g` and the compile-time constants LA, LB, BK,
-// WGM, WGN, TI, TJ, NSTAGE, ABL, EP, SA, SB, KARA, KS, BD (their meaning: the comment in front of k_mfma).
+// qg_mfma_body.h — the body of k_mfma and k_mfma_bd (qg_mfma.hip) and of k_mfma_ep_bd (qg_mfma_ep_bd.hip), included INSIDE the
+// kernels: no include guard, nothing at namespace scope.  In scope where it is included: the kernel argument `QMfmaArgs g` (BD with
+// EP: a QMfmaEpBdArgs) and the compile-time constants LA, LB, BK, WGM, WGN, TI, TJ, NSTAGE, ABL, EP, SA, SB, KARA, KS, BD (their
+// meaning: the comment in front of k_mfma).
     if constexpr (SA == 3 && SB == 3 && ABL == 0) {
         const unsigned ma = qg_plane_mask(g.maskA);
         const unsigned mb = qg_plane_mask(g.maskB);
@@ -31,14 +32,16 @@
     const int nwg = tiles_m * tiles_n;
     int tile_m, tile_n;
     int64_t bd_c_tile = 0;   // BD: this workgroup's tile of the batch's packed C
+    int bd_member = 0;       // BD: the member that tile belongs to (wave-uniform)
     if constexpr (BD) {
         // tiles_m, tiles_n count the STACK's row tiles; the batch has gridDim.x = batch * bd_tm * bd_tn tiles on its diagonal
-        static_assert(!BD || (KS == 1 && !KARA && !EP && ABL == 0), "block-diagonal form: the plain lock-step body");
+        static_assert(!BD || (KS == 1 && !KARA && ABL == 0), "block-diagonal form: the plain lock-step body");
         int member, lm, ln;
         qg_bd_tile_of<int>(qg_xcd_block<int>(blockIdx.x, (int)gridDim.x), g.bd_tm, g.bd_tn, member, lm, ln);
         tile_m = member * g.bd_tm + lm;
         tile_n = member * g.bd_tn + ln;
         bd_c_tile = ((int64_t)member * g.bd_tm + lm) * g.bd_tn + ln;
+        bd_member = member;
     } else
     qg_tile_of<8, true>(qg_xcd_block<int>(blockIdx.x, nwg), tiles_m, tiles_n, tile_m, tile_n);
 
@@ -281,6 +284,10 @@
                 int32_t v[16];
 #pragma unroll
                 for (int e = 0; e < 16; ++e) v[e] = (int32_t)s[e];
+                if constexpr (BD) {   // D and per-member operands at the stack-wide index, a shared operand at the member-local one
+                    const QBdEp be = qg_bd_ep_of(g, 0);
+                    qg_ep_apply_runs_bd<int32_t, 4>(v, g.ep, g.epa, base, 8, (int64_t)bd_member * be.msize, be.shared);
+                } else
                 qg_ep_apply_runs<int32_t, 4>(v, g.ep, g.epa, base, 8);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) qg_ep_store_run<int32_t>(C, base + 8 * q, g.ep.dbytes, v + 4 * q);

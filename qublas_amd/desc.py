@@ -114,6 +114,18 @@ class qgemul_cmul(C.Structure):
     _fields_ = [("cmul", C.c_uint8), ("reserved", C.c_uint8 * 7), ("mul", qfmt * 8)]
 
 
+class qgemul_batched_ep(C.Structure):
+    """which tensor operands of a batched plan's chain are SHARED (one M x N tensor for every member); include/qgemul.h"""
+    _fields_ = [("e_shared", C.c_uint8 * QG_MAX_EW), ("reserved", C.c_uint8 * 4)]
+
+
+def batched_ep(shared=()) -> "qgemul_batched_ep":
+    b = qgemul_batched_ep()
+    for k, v in enumerate(shared):
+        b.e_shared[k] = 1 if v else 0
+    return b
+
+
 class qgemul_cmul_form(C.Structure):
     _fields_ = [("has_cmul", C.c_int32), ("bits32", C.c_int32), ("max_bits", C.c_int32), ("reserved", C.c_int32)]
 
