@@ -1,147 +1,16 @@
-// qg_api.hip — the C-ABI of include/qgemul.h: contexts, plans, packing, execution.
+// qg_api.hip — the C-ABI of include/qgemul.h: contexts, classification, plans, packing, execution (the one-shot calls: qg_run.hip).
 //
 // There is deliberately no CPU arithmetic path in this library: without a gfx950 device every
 // compute entry point returns QG_ENOGPU.  (The CPU restatement lives in oracle/ and is test
 // infrastructure only.)
-#include <hip/hip_runtime.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <new>
-
-#include "../../include/qgemul.h"
-#include "qg_kernels.h"
-#include "qg_ring.h"
-#include "qg_plan.h"
-#include "qg_approx.h"
-#include "qg_cmul.h"
-#include "qg_bd_ep.h"
+#include "qg_api_int.h"
 
 static thread_local int g_last_hip = 0;
-
-#define QG_HIP(expr)                         \
-    do {                                     \
-        hipError_t e_ = (expr);              \
-        if (e_ != hipSuccess) {              \
-            g_last_hip = (int)e_;            \
-            return QG_EHIP;                  \
-        }                                    \
-    } while (0)
-
-struct qgemul_ctx {
-    int device;
-    hipStream_t stream;
-    int* flag_dev;
-};
-
-// Every entry point that launches, allocates or frees runs on ITS context's device, whatever device the calling thread has
-// current, and leaves the caller's current device as it found it (one process may drive several GPUs: qgemul_run_sharded).
-struct DeviceScope {
-    int prev = -1;
-    bool changed = false;
-    hipError_t err = hipSuccess;
-    explicit DeviceScope(int dev)
-    {
-        err = hipGetDevice(&prev);
-        if (err == hipSuccess && prev != dev) {
-            err = hipSetDevice(dev);
-            changed = err == hipSuccess;
-        }
-    }
-    ~DeviceScope() { if (changed) hipSetDevice(prev); }
-    DeviceScope(const DeviceScope&) = delete;
-    DeviceScope& operator=(const DeviceScope&) = delete;
-};
-#define QG_ON_DEVICE(ctxp)                 \
-    DeviceScope dev_scope_((ctxp)->device); \
-    QG_HIP(dev_scope_.err)
-
-// Composite linear plan.  The MFMA kernels take operands of at most 3 int8 limbs and keep exact int32 accumulators only while
-// K * min(LA, LB) < 2^17.  Beyond either bound the linear class used to fall to the 64-bit VALU tree kernel (40-300x slower); the
-// reference has no such boundary (Reducer, QuBLAS.h:4960-4990; ArbiInt elements up to 64 bits, :347-564).  Now:
-//   * an operand of L > 3 limbs is stored as limb GROUPS of 2-3 limbs (x = sum_g x_g * 256^limb0[g], every x_g a balanced
-//     base-256 number of its own), each group a complete packed operand of the existing layout;
-//   * K is cut into chunks of at most kc reduction indices (a multiple of 256), each chunk a complete packed operand as well;
-//   * every (chunk, A group, B group) is ONE launch of an existing MFMA kernel that stores raw dot products (identity
-//     epilogue) into a slab, and k_lin_combine (qg_pack.hip) adds the slabs by weight into an exact running sum and, after the
-//     last chunk, rounds + overflow-handles it once into C — the linear class's whole epilogue (QuBLAS.h:2398-2411).
-// Packed operand = the sub-operands back to back, chunk-major, each 256-byte aligned.
-struct QComposite {
-    int on;
-    int ga, gb;            // limb groups of A, B (1..3)
-    int la[3], lb[3];      // limbs per group
-    int la0[3], lb0[3];    // first limb of each group
-    int var[3][3];         // MFMA variant of the pair (A group, B group); one tile geometry for all pairs
-    int nc;                // k-chunks
-    int64_t kc;            // reduction indices per chunk (the last chunk: K - (nc - 1) * kc)
-    int slab_bytes;        // 4: single-limb pairs (raw int32), 8 otherwise
-    int wide;              // 128-bit sums
-    int64_t chunk_bytes[2];   // bytes of one FULL chunk of packed A / B (all groups)
-};
-
-struct qgemul_plan {
-    qgemul_ctx* ctx;
-    qgemul_desc desc;
-    uint32_t flags;
-    QAnalysis an;
-    qgemul_info info;
-    int LA, LB, variant;
-    QPackedGeom pa, pb;
-    QCGeom pc;
-    QHostElem ha, hb, hc;
-    QTreeTable* dev_table;
-    QTreeChoice tc;       // the tree kernels' step form that launches (qg_tree_choice: the diagnostic library's A/B switches applied)
-    int64_t* workspace;   // complex linear class: raw dot products [2Mh x 2Nh] int64
-    QMfmaCfg cfg;
-    // element-wise epilogue (qgemul_epilogue): pc then describes packed D; pc_c is the kernel's own packed C, which
-    // only exists in memory (cwork) for the kernels that do not fuse the chain
-    int has_ep;
-    qgemul_epilogue ep;
-    QEpTable ept;
-    // complex chain (qgemul_epilogue_cplx): ep / ept are the chain of the real parts, ep_im / ept_im of the imaginary parts
-    int ep_cplx;
-    qgemul_epilogue ep_im;
-    QEpTable ept_im;
-    uint8_t e_cplx[QG_MAX_EW];
-    // APPROX stages (qg_approx.h): has_ax = the chain holds one (it then always runs as the pass of qg_approx.hip); ax_dev[k] = stage k's
-    // table on the device, ax_uniform = every table has the uniform form
-    int has_ax, ax_uniform;
-    QApproxTable* ax_dev[QG_MAX_EW];
-    // CMUL stages (qg_cmul.h): has_cmul = the complex chain holds one (it then runs as the one pass of qg_eltwise_cplx.hip, never as
-    // two k_eltwise launches); cx = the plan's copy of the caller's records, cm_dev = QG_MAX_EW pre-resolved records on the device
-    int has_cmul;
-    qgemul_cmul cx[QG_MAX_EW];
-    QCmulStage* cm_dev;
-    QCGeom pc_c;
-    void* cwork;
-    int32_t* wide_ws;     // single-limb MFMA with a left-shifting epilogue that leaves 32 bits: raw int32 dot products
-    void* hostc_pc;       // qgemul_execute_host_c on a kernel that cannot store the reference layout: its packed C
-    QComposite comp;      // composite linear plan (comp.on): limb groups x k-chunks of sub-GEMMs + an exact combine pass
-    void* comp_slabs;     // comp.ga * comp.gb slabs of raw dot products, one common packed-C layout
-    void* comp_acc;       // running exact sums between k-chunks (comp.nc > 1)
-    // batched plan (qgemul_plan_create_batched; batch > 0): `batch` GEMMs of desc at constant strides.  `member` is the plain plan of
-    // ONE member and owns every device resource; this object holds what belongs to the batch: info (packed_bytes of the whole
-    // batch), the packed operands' stride from member to member (mstride) and, in the block-diagonal form (bd: one launch of
-    // k_mfma's BD form over the stacked operands), the STACK's packed geometries in pa / pb — member's with batch times the
-    // rows, one plane-mask trailer and one row-sum array behind the planes of all members.  bd == 0: member by member on `member`
-    int64_t batch;
-    int bd, member_launches;
-    qgemul_plan* member;
-    int64_t mstride[3];
-    // element-wise chain on a batched plan (qgemul_plan_create_batched_epx: batch > 0 with has_ep).  ep / ept / pc (D) / pc_c (C) are
-    // the member's.  e_shared[k]: stage k's tensor operand is ONE M x N tensor for every member; estride[k]: bytes of one member's
-    // packed operand of stage k (0: no tensor operand) = the step from member to member of a per-member one.  With bd the chain runs
-    // inside the block-diagonal launch (bd_fused: k_mfma_ep_bd) or as one block-diagonal pass over the stack's packed C, which is
-    // this plan's cwork; without bd member by member through qgemul_execute_ep on `member`
-    uint8_t e_shared[QG_MAX_EW];
-    int bd_fused;
-    int64_t estride[QG_MAX_EW];
-};
+int qg_last_hip() { return g_last_hip; }
+void qg_set_last_hip(int e) { g_last_hip = e; }
 
 struct HostC { void* C; int64_t ld; };
 // an element-wise chain as the planner sees it: a real chain (im == nullptr) or the two part chains of a complex one
-struct EpView { const qgemul_epilogue* re; const qgemul_epilogue* im; const uint8_t* e_cplx; const qgemul_approx* const* ax; const qgemul_epilogue_cplx* epc; const qgemul_cmul* const* cx; };
 // a chain that came in through an _epcx entry point and holds a CMUL stage in either part (such a chain is planned in lock step)
 static bool view_has_cmul(const EpView* ev)
 {
@@ -160,7 +29,6 @@ static int pow2_bytes(int storage_bits)
     return c;
 }
 
-static bool same_fmt(const qfmt& x, const qfmt& y) { return x.I == y.I && x.F == y.F && x.S == y.S && x.Q == y.Q && x.O == y.O; }
 static int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 // ---- composite linear plans: geometry helpers (see QComposite) ----
@@ -259,19 +127,21 @@ static hipError_t comp_zero_rowsums(const qgemul_plan* p, int operand, void* pac
 }
 
 // fill info + geometry for a descriptor; no GPU access
-static int plan_geometry(const qgemul_desc* d, uint32_t flags, QAnalysis* an, qgemul_info* info, int* pLA, int* pLB, QMfmaCfg* pVar,
-                         QPackedGeom* pa, QPackedGeom* pb, QCGeom* pc, QHostElem* ha, QHostElem* hb, QHostElem* hc,
-                         const EpView* ev = nullptr, QEpTable* ept = nullptr, QCGeom* pc_c = nullptr, QEpTable* ept_im = nullptr,
-                         QComposite* pcomp = nullptr, QApproxTable* axt = nullptr, QCmulStage* cmt = nullptr, int64_t batch = 0, int* pbd = nullptr)
+// ev: the element-wise chain (nullptr: none); axt / cmt: receive the pre-resolved tables of APPROX / CMUL stages (nullptr: not wanted)
+static int plan_geometry(const qgemul_desc* d, uint32_t flags, const EpView* ev, int64_t batch, QPlanGeom* out, QApproxTable* axt, QCmulStage* cmt)
 {
+    QAnalysis* const an = &out->an;
+    qgemul_info* const info = &out->info;
+    QPackedGeom *const pa = &out->pa, *const pb = &out->pb;
+    QCGeom* const pc = &out->pc;
+    QHostElem *const ha = &out->ha, *const hb = &out->hb, *const hc = &out->hc;
+    QComposite& comp = out->comp;
     // batch > 0: the member of a batched plan.  Where k_mfma has a block-diagonal form for it, the tile geometry comes from
-    // qg_mfma_pick_batched (the batch's total tile count, the member's padding waste) and *pbd = 1: the packed layouts then belong
+    // qg_mfma_pick_batched (the batch's total tile count, the member's padding waste) and out->bd = 1: the packed layouts then belong
     // to the batched plan and may differ from the plain plan of the same descriptor
-    if (pbd) *pbd = 0;
+    out->bd = 0;
     bool bd = false;
     QMfmaCfg plain_cfg = {0, 0, 0, 0};   // what qg_mfma_pick chose for the member alone
-    QComposite comp_local;
-    QComposite& comp = pcomp ? *pcomp : comp_local;
     memset(&comp, 0, sizeof comp);
     const qgemul_epilogue* ep = ev ? ev->re : nullptr;
     qg_analyze(d, an);
@@ -470,7 +340,7 @@ static int plan_geometry(const qgemul_desc* d, uint32_t flags, QAnalysis* an, qg
         pc->Np = d->N;
         pc->tm = pc->tn = 0;
     }
-    if (pbd) *pbd = bd ? 1 : 0;
+    out->bd = bd ? 1 : 0;
     info->kernel = kernel;
     info->limbs[0] = LA;
     info->limbs[1] = LB;
@@ -540,10 +410,11 @@ static int plan_geometry(const qgemul_desc* d, uint32_t flags, QAnalysis* an, qg
         snprintf(info->reason, sizeof info->reason, "linear class: balanced base-256 limbs, nine products (two-group kernel, 128x128 tiles)");
     }
     info->packed_bytes[2] = (int64_t)parts * pc->Mp * pc->Np * pc->cbytes;
-    *pLA = LA;
-    *pLB = LB;
-    *pVar = cfg;
-    if (pc_c) *pc_c = *pc;
+    out->LA = LA;
+    out->LB = LB;
+    out->cfg = cfg;
+    out->variant = cfg.variant;
+    out->pc_c = *pc;
     if (ep && an->band) {
         info->supported = 0;
         snprintf(info->reason, sizeof info->reason, "element-wise chain after a plan whose C can leave its format (multi-word comparison artefact of the reference)");
@@ -556,8 +427,7 @@ static int plan_geometry(const qgemul_desc* d, uint32_t flags, QAnalysis* an, qg
             snprintf(info->reason, sizeof info->reason, d->is_complex ? "complex GEMM: the chain is a qgemul_epilogue_cplx" : "real GEMM: the chain is a qgemul_epilogue");
             return QG_EINVAL;
         }
-        QEpTable local[2];
-        QEpTable* t[2] = {ept ? ept : &local[0], ept_im ? ept_im : &local[1]};
+        QEpTable* t[2] = {&out->ept, &out->ept_im};
         qfmt df[2] = {ep->d, ep->d};
         const bool lockstep = view_has_cmul(ev);   // a CMUL stage needs both running values: the part chains are planned together
         if (ev->cx && !lockstep)
@@ -644,7 +514,7 @@ static int plan_geometry(const qgemul_desc* d, uint32_t flags, QAnalysis* an, qg
 // with finer fracBits can leave 32 bits before the overflow handling sees the value (found by tests/extended_fuzz.py:
 // int<10,-3> operands into Qu<5,7>, shift by 13).  Those descriptors store the raw dot products and convert them in the
 // 64-bit linear pass instead, which keeps the hot kernels' epilogue as it is.
-static bool wide_epilogue(const qgemul_plan* p)
+static bool wide_epilogue(const QPlanGeom* p)
 {
     if (p->comp.on || p->variant == QG_MFMA_RING) return false;   // (the combine pass / the ring kernel's epilogue convert in 64-bit arithmetic anyway)
     const QStep& q = p->an.lin.to_c[0];
@@ -701,21 +571,22 @@ static uint32_t* g_diag_stamps = nullptr;   // device buffer for in-kernel clock
 extern "C" void qgemul_diag_set_stamps(void* dev) { g_diag_stamps = (uint32_t*)dev; }
 #endif
 
-static bool fuses_epilogue(const qgemul_plan* p)
+static bool fuses_epilogue(const QPlanGeom* p, uint32_t flags, bool has_ax, bool has_cmul)
 {
-    if (p->has_ax) return false;   // (an APPROX stage: always the pass of qg_approx.hip)
-    if (p->has_cmul) return false; // (a CMUL stage: always the pass of qg_eltwise_cplx.hip)
+    if (has_ax) return false;   // (an APPROX stage: always the pass of qg_approx.hip)
+    if (has_cmul) return false; // (a CMUL stage: always the pass of qg_eltwise_cplx.hip)
     if (wide_epilogue(p) || p->comp.on || p->variant == QG_MFMA_RING) return false;
-    if (p->flags & QG_OPT_UNFUSED_EPILOGUE) return false;
+    if (flags & QG_OPT_UNFUSED_EPILOGUE) return false;
     if (!p->ept.bits32) return false;
     if (p->info.kernel == QG_KERNEL_MFMA_I8_LIMB && p->LA == 3 && p->LB == 3) return true;
-    return p->info.kernel == QG_KERNEL_MFMA_I8 && (p->flags & QG_OPT_FUSED_EPILOGUE);
+    return p->info.kernel == QG_KERNEL_MFMA_I8 && (flags & QG_OPT_FUSED_EPILOGUE);
 }
+static bool fuses_epilogue(const qgemul_plan* p) { return fuses_epilogue(p, p->flags, p->has_ax, p->has_cmul); }
 
 extern "C" {
 
 uint32_t qgemul_abi_version(void) { return QGEMUL_ABI_VERSION; }
-int qgemul_last_hip_error(void) { return g_last_hip; }
+int qgemul_last_hip_error(void) { return qg_last_hip(); }
 
 const char* qgemul_strerror(int st)
 {
@@ -733,18 +604,14 @@ const char* qgemul_strerror(int st)
 
 int qgemul_classify(const qgemul_desc* d, uint32_t opt_flags, qgemul_info* out) { return qgemul_classify_ep(d, nullptr, opt_flags, out); }
 
-static int classify_view(const qgemul_desc* d, const EpView* ev, uint32_t opt_flags, qgemul_info* out)
+int classify_view(const qgemul_desc* d, const EpView* ev, uint32_t opt_flags, qgemul_info* out)
 {
     if (!d || !out) return QG_EINVAL;
-    QAnalysis* an = new (std::nothrow) QAnalysis;
-    if (!an) return QG_EINVAL;
-    int LA, LB;
-    QMfmaCfg variant;
-    QPackedGeom pa, pb;
-    QCGeom pc;
-    QHostElem ha, hb, hc;
-    int st = plan_geometry(d, opt_flags, an, out, &LA, &LB, &variant, &pa, &pb, &pc, &ha, &hb, &hc, ev);
-    delete an;
+    QPlanGeom* g = new (std::nothrow) QPlanGeom();
+    if (!g) return QG_EINVAL;
+    const int st = plan_geometry(d, opt_flags, ev, 0, g, nullptr, nullptr);
+    *out = g->info;
+    delete g;
     return st;
 }
 
@@ -920,8 +787,6 @@ int qgemul_plan_create(qgemul_ctx* c, const qgemul_desc* d, uint32_t opt_flags, 
     return qgemul_plan_create_ep(c, d, nullptr, opt_flags, out);
 }
 
-static int plan_create_view(qgemul_ctx* c, const qgemul_desc* d, const EpView* ev, uint32_t opt_flags, qgemul_plan** out, int64_t batch = 0);
-
 int qgemul_plan_create_ep(qgemul_ctx* c, const qgemul_desc* d, const qgemul_epilogue* ep, uint32_t opt_flags, qgemul_plan** out)
 {
     const EpView v = {ep, nullptr, nullptr};
@@ -953,7 +818,7 @@ int qgemul_plan_create_epcx(qgemul_ctx* c, const qgemul_desc* d, const qgemul_ep
     return plan_create_view(c, d, &v, opt_flags, out);
 }
 
-static int plan_create_view(qgemul_ctx* c, const qgemul_desc* d, const EpView* ev, uint32_t opt_flags, qgemul_plan** out, int64_t batch)   // batch > 0: the member of a batched plan
+int plan_create_view(qgemul_ctx* c, const qgemul_desc* d, const EpView* ev, uint32_t opt_flags, qgemul_plan** out, int64_t batch)   // batch > 0: the member of a batched plan
 {
     if (!c || !d || !out) return QG_EINVAL;
     qgemul_plan* p = new (std::nothrow) qgemul_plan;
@@ -979,59 +844,31 @@ static int plan_create_view(qgemul_ctx* c, const qgemul_desc* d, const EpView* e
     QApproxTable* axt = p->has_ax ? new (std::nothrow) QApproxTable[QG_MAX_EW] : nullptr;
     if (p->has_ax && !axt) { delete p; return QG_EINVAL; }
     struct AxtGuard { QApproxTable* t; ~AxtGuard() { delete[] t; } } axt_guard = {axt};
-    int st = plan_geometry(d, opt_flags, &p->an, &p->info, &p->LA, &p->LB, &p->cfg, &p->pa, &p->pb, &p->pc, &p->ha, &p->hb, &p->hc,
-                           ev, &p->ept, &p->pc_c, &p->ept_im, &p->comp, axt, p->has_cmul ? cmt : nullptr, batch);
+    int st = plan_geometry(d, opt_flags, ev, batch, p, axt, p->has_cmul ? cmt : nullptr);
     if (st != QG_OK) { delete p; return st; }
-    p->variant = p->cfg.variant;
     p->tc = qg_tree_choice(&p->an, d, opt_flags, true);
+    // from here on the plan may own device memory: every failure leaves through qgemul_plan_destroy, which frees whatever there is
+    const auto fail = [p] { qgemul_plan_destroy(p); return QG_EHIP; };
     DeviceScope scope(c->device);
-    if (scope.err != hipSuccess || hipMalloc((void**)&p->dev_table, sizeof(QTreeTable)) != hipSuccess) {
-        delete p;
-        return QG_EHIP;
-    }
+    if (scope.err != hipSuccess || hipMalloc((void**)&p->dev_table, sizeof(QTreeTable)) != hipSuccess) return fail();
     if (hipMemcpyAsync(p->dev_table, &p->an.tree, sizeof(QTreeTable), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-        hipStreamSynchronize(c->stream) != hipSuccess) {
-        hipFree(p->dev_table);
-        delete p;
-        return QG_EHIP;
-    }
+        hipStreamSynchronize(c->stream) != hipSuccess)
+        return fail();
     if (p->info.kernel == QG_KERNEL_MFMA_CPLX) {
         const size_t ws = (size_t)(2 * p->pa.rows_p) * (size_t)(2 * p->pb.rows_p) * sizeof(int64_t);
-        if (hipMalloc((void**)&p->workspace, ws) != hipSuccess) {
-            hipFree(p->dev_table);
-            delete p;
-            return QG_EHIP;
-        }
+        if (hipMalloc((void**)&p->workspace, ws) != hipSuccess) return fail();
     }
-    if (wide_epilogue(p) && hipMalloc((void**)&p->wide_ws, (size_t)(p->pc_c.Mp * p->pc_c.Np) * sizeof(int32_t)) != hipSuccess) {
-        hipFree(p->dev_table);
-        hipFree(p->workspace);
-        delete p;
-        return QG_EHIP;
-    }
+    if (wide_epilogue(p) && hipMalloc((void**)&p->wide_ws, (size_t)(p->pc_c.Mp * p->pc_c.Np) * sizeof(int32_t)) != hipSuccess) return fail();
     if (p->comp.on) {
         const size_t n = (size_t)p->pa.rows_p * (size_t)p->pb.rows_p;
         const size_t sl = n * (size_t)(p->comp.ga * p->comp.gb) * (size_t)p->comp.slab_bytes;
         const size_t ac = p->comp.nc > 1 ? n * (p->comp.wide ? 16 : 8) : 0;
-        if (hipMalloc(&p->comp_slabs, sl ? sl : 16) != hipSuccess || (ac && hipMalloc(&p->comp_acc, ac) != hipSuccess)) {
-            hipFree(p->dev_table);
-            hipFree(p->comp_slabs);
-            delete p;
-            return QG_EHIP;
-        }
+        if (hipMalloc(&p->comp_slabs, sl ? sl : 16) != hipSuccess || (ac && hipMalloc(&p->comp_acc, ac) != hipSuccess)) return fail();
     }
     if (p->has_ep && !fuses_epilogue(p)) {
         // the tree kernels store C; the chain then runs as a pass over it
         const size_t cb = (size_t)(p->pc_c.parts * p->pc_c.Mp * p->pc_c.Np) * (size_t)p->pc_c.cbytes;
-        if (hipMalloc(&p->cwork, cb ? cb : 16) != hipSuccess) {
-            hipFree(p->dev_table);
-            hipFree(p->workspace);
-            hipFree(p->wide_ws);
-            hipFree(p->comp_slabs);
-            hipFree(p->comp_acc);
-            delete p;
-            return QG_EHIP;
-        }
+        if (hipMalloc(&p->cwork, cb ? cb : 16) != hipSuccess) return fail();
     }
     if (p->has_ax) {
         // the plan's copy of the tables, pre-resolved: one device buffer per APPROX stage
@@ -1043,18 +880,13 @@ static int plan_create_view(qgemul_ctx* c, const qgemul_desc* d, const EpView* e
             ok = hipMalloc((void**)&p->ax_dev[k], sizeof(QApproxTable)) == hipSuccess &&
                  hipMemcpyAsync(p->ax_dev[k], &axt[k], sizeof(QApproxTable), hipMemcpyHostToDevice, c->stream) == hipSuccess;
         }
-        if (!ok || hipStreamSynchronize(c->stream) != hipSuccess) {   // (the tables are host temporaries: copied before they go)
-            qgemul_plan_destroy(p);
-            return QG_EHIP;
-        }
+        if (!ok || hipStreamSynchronize(c->stream) != hipSuccess) return fail();   // (the tables are host temporaries: copied before they go)
     }
     if (p->has_cmul) {
         // the pre-resolved records of the CMUL stages: one device buffer (host temporaries: copied before they go)
         if (hipMalloc((void**)&p->cm_dev, sizeof cmt) != hipSuccess ||
-            hipMemcpyAsync(p->cm_dev, cmt, sizeof cmt, hipMemcpyHostToDevice, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
-            qgemul_plan_destroy(p);
-            return QG_EHIP;
-        }
+            hipMemcpyAsync(p->cm_dev, cmt, sizeof cmt, hipMemcpyHostToDevice, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
+            return fail();
     }
     *out = p;
     return QG_OK;
@@ -1209,7 +1041,7 @@ int qgemul_execute(qgemul_plan* p, void* packedC, const void* packedA, const voi
 
 // the kernels whose epilogue can store the reference layout: k_mfma_pp (QG_MFMA_PP) / k_mfma_ppl (QG_MFMA_PPL), real, 4- or 8-byte
 // container equal to the host element, no raw-dot-product detour
-static bool stores_host_c(const qgemul_plan* p)
+bool stores_host_c(const qgemul_plan* p)
 {
     if (p->has_ep || p->desc.is_complex || wide_epilogue(p) || p->comp.on) return false;
     if (p->info.kernel != QG_KERNEL_MFMA_I8 && p->info.kernel != QG_KERNEL_MFMA_I8_LIMB) return false;
@@ -1726,516 +1558,10 @@ int qgemul_time_execute_ep(qgemul_plan* p, void* packedD, const void* packedA, c
     return time_execute(p, packedD, packedA, packedB, args, warmup, iters, avg_ms);
 }
 
-int qgemul_run(const qgemul_desc* d, void* C, const void* A, const void* B, const qgemul_opts* o)
-{
-    return qgemul_run_ep(d, nullptr, C, A, B, nullptr, o);
-}
-
-// ---- the one-shot call keeps a per-thread cache: context, the plan of the last descriptor, grow-only device buffers ----
-// The reference is a synchronous library that user code calls in loops; creating a stream, a plan table and eight device
-// allocations per call cost 2.9 ms for the README's 4x4x4 example (tools/measure_run_latency.py).  The cache belongs to
-// the calling thread and is never touched by another one; qgemul_run_release() frees it, and so does the end of the thread
-// (RunCacheReaper below) — except once the process is exiting: a worker thread that is still alive or detached then may run its
-// thread-local destructors after HIP has been torn down, so the reaper only forgets its pointers (g_shutting_down).
-namespace {
-struct RunCache {
-    qgemul_ctx* ctx = nullptr;
-    int device = -2;
-    qgemul_plan* plan = nullptr;
-    qgemul_desc pd;
-    qgemul_epilogue_cplx pe;          // a real chain is part[0]
-    bool has_pe = false, pe_cplx = false;
-    qgemul_approx* pax = nullptr;     // QG_MAX_EW tables of the cached plan's APPROX stages (allocated at the first such plan)
-    uint8_t pax_on[QG_MAX_EW] = {};
-    qgemul_cmul pcx[QG_MAX_EW];       // the cached plan's CMUL records (pcx_on[k]: the caller passed cx[k])
-    uint8_t pcx_on[QG_MAX_EW] = {};
-    uint32_t pflags = 0;
-    int64_t pbatch = 0;       // > 0: the cached plan is a batched plan of that many members (qgemul_run_batched)
-    uint8_t pshared[QG_MAX_EW] = {};   // ... with a chain (qgemul_run_batched_epx): which stages' operands are shared
-    enum { NBUF = 6 + 16 };   // 0-5: host-layout A, B, C and packed A, B, C; behind them: the epilogue operands (2 per stage) or, on the
-                              // root of a sharded call, the landing buffers of the other bands
-    void* buf[NBUF] = {};
-    size_t cap[NBUF] = {};
-};
-thread_local RunCache g_run;
-// qgemul_run_sharded: one such cache per entry of the device list (slot i serves devices[i] of the calling thread's last list)
-enum { QG_MAX_SHARDS = 16 };
-thread_local RunCache g_shard[QG_MAX_SHARDS];
-thread_local hipEvent_t g_shard_ev[QG_MAX_SHARDS] = {};
-// What a thread has cached is released when the thread ends (worker threads that call Qgemul<>() and exit must not leak a stream
-// and device buffers each).  For the main thread this runs inside exit() BEFORE any static object — HIP's included — is torn down.
-std::atomic<bool> g_shutting_down{false};
-void forget_caches();
-struct RunCacheReaper {
-    bool armed = false;
-    ~RunCacheReaper()
-    {
-        if (!armed) return;
-        int n = 0;
-        // exit() has begun (atexit handlers run before static destruction, HIP's included) or the runtime no longer answers:
-        // no HIP call from here, the driver reclaims the memory with the process
-        if (g_shutting_down.load(std::memory_order_acquire) || hipGetDeviceCount(&n) != hipSuccess) { forget_caches(); return; }
-        qgemul_run_release();
-    }
-};
-thread_local RunCacheReaper g_reaper;
-struct ShutdownHook {
-    ShutdownHook() { atexit([] { g_shutting_down.store(true, std::memory_order_release); }); }
-};
-
-// descriptors are compared field by field: padding and reserved bytes of a caller's struct are not part of its meaning, and a
-// descriptor that was not built with `{}` must still hit the cache
-bool same_desc(const qgemul_desc& x, const qgemul_desc& y)
-{
-    if (x.abi != y.abi || x.transA != y.transA || x.is_complex != y.is_complex || x.cmul != y.cmul || x.flags != y.flags || x.M != y.M || x.N != y.N ||
-        x.K != y.K || x.n_levels != y.n_levels || x.n_levels > QG_MAX_LEVELS)
-        return false;
-    for (int p = 0; p < 2; ++p) {
-        if (!same_fmt(x.a[p], y.a[p]) || !same_fmt(x.b[p], y.b[p]) || !same_fmt(x.c[p], y.c[p])) return false;
-        for (uint32_t l = 0; l < x.n_levels; ++l)
-            if (!same_fmt(x.level_add[p][l], y.level_add[p][l]) || !same_fmt(x.level[p][l], y.level[p][l])) return false;
-    }
-    for (int i = 0; i < 8; ++i)
-        if (!same_fmt(x.mul[i], y.mul[i])) return false;
-    return true;
-}
-bool same_epilogue(const qgemul_epilogue& x, const qgemul_epilogue& y)
-{
-    if (x.n_stages != y.n_stages || x.n_stages > QG_MAX_EW || !same_fmt(x.d, y.d)) return false;
-    for (uint32_t k = 0; k < x.n_stages; ++k) {
-        const qgemul_ew_stage &a = x.stage[k], &b = y.stage[k];
-        if (a.op != b.op || a.x_first != b.x_first || a.e_scalar != b.e_scalar || !same_fmt(a.e, b.e) || !same_fmt(a.r, b.r) || !same_fmt(a.t, b.t))
-            return false;
-    }
-    return true;
-}
-
-bool same_approx(const qgemul_approx& x, const qgemul_approx& y)
-{
-    if (x.n_seg != y.n_seg || x.n_seg > QG_MAX_SEG) return false;
-    for (uint32_t g = 0; g < x.n_seg; ++g) {
-        const qgemul_approx_seg &a = x.seg[g], &b = y.seg[g];
-        if (memcmp(&a.breakpoint, &b.breakpoint, sizeof a.breakpoint) || a.n_coef != b.n_coef || a.n_coef > QG_MAX_COEF) return false;
-        for (uint32_t i = 0; i < a.n_coef; ++i)
-            if (!same_fmt(a.f[i], b.f[i]) || a.a[i] != b.a[i]) return false;
-    }
-    return true;
-}
-bool same_tables(const RunCache& c, const qgemul_approx* const* ax)
-{
-    for (int k = 0; k < QG_MAX_EW; ++k) {
-        const qgemul_approx* t = ax ? ax[k] : nullptr;
-        if ((t != nullptr) != (c.pax_on[k] != 0)) return false;
-        if (t && !same_approx(*t, c.pax[k])) return false;
-    }
-    return true;
-}
-
-bool same_cmul(const RunCache& c, const qgemul_cmul* const* cx)
-{
-    for (int k = 0; k < QG_MAX_EW; ++k) {
-        const qgemul_cmul* t = cx ? cx[k] : nullptr;
-        if ((t != nullptr) != (c.pcx_on[k] != 0)) return false;
-        if (!t) continue;
-        if (t->cmul != c.pcx[k].cmul) return false;
-        for (int i = 0; i < 8; ++i)
-            if (!same_fmt(t->mul[i], c.pcx[k].mul[i])) return false;
-    }
-    return true;
-}
-
-int cache_buffer(RunCache& c, int i, size_t bytes, void** out)   // (the caller has made the cache's device current)
-{
-    if (bytes > c.cap[i]) {
-        if (c.buf[i]) {
-            hipStreamSynchronize(c.ctx->stream);
-            hipFree(c.buf[i]);
-            c.buf[i] = nullptr;
-            c.cap[i] = 0;
-        }
-        const size_t want = bytes < 4096 ? 4096 : bytes;
-        hipError_t e = hipMalloc(&c.buf[i], want);
-        if (e != hipSuccess) { g_last_hip = (int)e; return QG_EHIP; }
-        c.cap[i] = want;
-    }
-    *out = c.buf[i];
-    return QG_OK;
-}
-} // namespace
-
-static void release_cache(RunCache& c)
-{
-    if (c.ctx) {
-        DeviceScope scope(c.ctx->device);
-        hipStreamSynchronize(c.ctx->stream);
-        if (c.plan) qgemul_plan_destroy(c.plan);
-        for (int i = 0; i < RunCache::NBUF; ++i) { if (c.buf[i]) hipFree(c.buf[i]); c.buf[i] = nullptr; c.cap[i] = 0; }
-        qgemul_ctx_destroy(c.ctx);
-    }
-    c.plan = nullptr;
-    c.ctx = nullptr;
-    c.device = -2;
-    delete[] c.pax;
-    c.pax = nullptr;
-    memset(c.pax_on, 0, sizeof c.pax_on);
-    memset(c.pcx_on, 0, sizeof c.pcx_on);
-}
-
-namespace {
-void forget_caches()
-{
-    auto forget = [](RunCache& c) {
-        c.plan = nullptr;
-        c.ctx = nullptr;
-        c.device = -2;
-        for (int i = 0; i < RunCache::NBUF; ++i) { c.buf[i] = nullptr; c.cap[i] = 0; }
-    };
-    forget(g_run);
-    for (int i = 0; i < QG_MAX_SHARDS; ++i) { g_shard_ev[i] = nullptr; forget(g_shard[i]); }
-}
-} // namespace
-
-void qgemul_run_release(void)
-{
-    release_cache(g_run);
-    for (int i = 0; i < QG_MAX_SHARDS; ++i) {
-        if (g_shard_ev[i]) { hipEventDestroy(g_shard_ev[i]); g_shard_ev[i] = nullptr; }
-        release_cache(g_shard[i]);
-    }
-}
-
-static int run_view(const qgemul_desc* d, const EpView* ev, void* C, const void* A, const void* B, const void* const* E, const qgemul_opts* o);
-
-int qgemul_run_ep(const qgemul_desc* d, const qgemul_epilogue* ep, void* C, const void* A, const void* B, const void* const* E,
-                  const qgemul_opts* o)
-{
-    const EpView v = {ep, nullptr, nullptr};
-    return run_view(d, ep ? &v : nullptr, C, A, B, E, o);
-}
-
-int qgemul_run_epx(const qgemul_desc* d, const qgemul_epilogue* ep, const qgemul_approx* const ax[QG_MAX_EW], void* C, const void* A, const void* B,
-                   const void* const* E, const qgemul_opts* o)
-{
-    if (!ep || !ax) return QG_EINVAL;
-    const EpView v = {ep, nullptr, nullptr, ax};
-    return run_view(d, &v, C, A, B, E, o);
-}
-
-int qgemul_run_epc(const qgemul_desc* d, const qgemul_epilogue_cplx* ep, void* C, const void* A, const void* B, const void* const* E,
-                   const qgemul_opts* o)
-{
-    if (!ep) return QG_EINVAL;
-    const EpView v = {&ep->part[0], &ep->part[1], ep->e_complex};
-    return run_view(d, &v, C, A, B, E, o);
-}
-
-int qgemul_run_epcx(const qgemul_desc* d, const qgemul_epilogue_cplx* ep, const qgemul_cmul* const cx[QG_MAX_EW], void* C, const void* A,
-                    const void* B, const void* const* E, const qgemul_opts* o)
-{
-    if (!ep || !cx) return QG_EINVAL;
-    const EpView v = {&ep->part[0], &ep->part[1], ep->e_complex, nullptr, ep, cx};
-    return run_view(d, &v, C, A, B, E, o);
-}
-
-static int run_view(const qgemul_desc* d, const EpView* ev, void* C, const void* A, const void* B, const void* const* E, const qgemul_opts* o)
-{
-    if (!d || !C || !A || !B) return QG_EINVAL;
-    const qgemul_epilogue* ep = ev ? ev->re : nullptr;
-    qgemul_opts opts;
-    memset(&opts, 0, sizeof opts);
-    opts.device = -1;
-    if (o) opts = *o;
-    g_reaper.armed = true;
-    static ShutdownHook hook;   // (installed once, at the first call: see RunCacheReaper)
-    RunCache& c = g_run;
-    if (opts.device < 0 && c.ctx) {   // "current device": follow hipSetDevice calls the caller made between two calls
-        int cur = c.device;
-        if (hipGetDevice(&cur) == hipSuccess) opts.device = cur;
-    }
-    if (opts.flags & QG_OPT_ALL_DEVICES) {
-        if (ep) return QG_EUNSUPPORTED;   // the element-wise chain runs on one device
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return QG_ENOGPU;
-        int list[QG_MAX_SHARDS];
-        int n = 0;
-        for (int i = 0; i < ndev && n < QG_MAX_SHARDS; ++i) list[n++] = i;
-        opts.flags &= ~(uint32_t)QG_OPT_ALL_DEVICES;
-        return qgemul_run_sharded(d, C, A, B, &opts, list, n);
-    }
-    const bool same_plan = c.plan && c.pbatch == 0 && c.pflags == opts.flags && same_desc(c.pd, *d) && c.has_pe == (ep != nullptr) &&
-                           (!ep || (same_epilogue(c.pe.part[0], *ep) && c.pe_cplx == (ev->im != nullptr) &&
-                                    (!ev->im || (same_epilogue(c.pe.part[1], *ev->im) && !memcmp(c.pe.e_complex, ev->e_cplx, ep->n_stages))) &&
-                                    same_tables(c, ev->ax) && same_cmul(c, ev->cx))) &&
-                           (opts.device < 0 || opts.device == c.device);
-    if (!same_plan) {
-        // validate before touching the device so that descriptor errors are reported without a GPU
-        qgemul_info info;
-        int st = classify_view(d, ev, opts.flags, &info);
-        if (st != QG_OK) return st;
-    }
-    if (ep)
-        for (uint32_t k = 0; k < ep->n_stages; ++k)
-            if (ep->stage[k].op != QG_EW_APPROX && (!E || !E[k])) return QG_EINVAL;   // (an APPROX stage reads no operand)
-    if (d->M == 0 || d->N == 0) return QG_OK;
-    int st = QG_OK;
-    if (!c.ctx || (opts.device >= 0 && opts.device != c.device)) {
-        release_cache(c);   // (only the single-device cache: the sharded entry's contexts and plans stay warm)
-        st = qgemul_ctx_create(opts.device, &c.ctx);
-        if (st != QG_OK) { c.ctx = nullptr; return st; }
-        c.device = c.ctx->device;
-    } else {
-        QG_HIP(hipSetDevice(c.device));
-    }
-    qgemul_ctx* ctx = c.ctx;
-    if (!same_plan) {
-        if (c.plan) { qgemul_plan_destroy(c.plan); c.plan = nullptr; }
-        st = plan_create_view(ctx, d, ev, opts.flags, &c.plan);
-        if (st != QG_OK) { c.plan = nullptr; return st; }
-        c.pd = *d;
-        c.has_pe = ep != nullptr;
-        c.pe_cplx = ev && ev->im;
-        if (ep) c.pe.part[0] = *ep;
-        if (c.pe_cplx) { c.pe.part[1] = *ev->im; memcpy(c.pe.e_complex, ev->e_cplx, sizeof c.pe.e_complex); }
-        memset(c.pax_on, 0, sizeof c.pax_on);
-        for (int k = 0; ev && ev->ax && k < QG_MAX_EW; ++k) {
-            if (!ev->ax[k]) continue;
-            if (!c.pax) c.pax = new qgemul_approx[QG_MAX_EW];
-            c.pax[k] = *ev->ax[k];
-            c.pax_on[k] = 1;
-        }
-        memset(c.pcx_on, 0, sizeof c.pcx_on);
-        for (int k = 0; ev && ev->cx && k < QG_MAX_EW; ++k) {
-            if (!ev->cx[k]) continue;
-            c.pcx[k] = *ev->cx[k];
-            c.pcx_on[k] = 1;
-        }
-        c.pflags = opts.flags;
-        c.pbatch = 0;
-    }
-    qgemul_plan* p = c.plan;
-    void *dA, *dB, *dC, *pA, *pB, *pC;
-    do {
-        const int64_t lda = opts.lda ? opts.lda : (d->transA ? d->K : d->M);
-        const int64_t ldb = opts.ldb ? opts.ldb : d->K;
-        const int64_t ldc = opts.ldc ? opts.ldc : d->M;
-        if (lda < (d->transA ? d->K : d->M) || ldb < d->K || ldc < d->M) { st = QG_EINVAL; break; }
-        const size_t bytesA = (size_t)(((d->transA ? d->M : d->K) - 1) * lda + (d->transA ? d->K : d->M)) * p->ha.size;
-        const size_t bytesB = (size_t)((d->N - 1) * ldb + d->K) * p->hb.size;
-        const size_t bytesC = (size_t)((d->N - 1) * ldc + d->M) * p->hc.size;
-        if ((st = cache_buffer(c, 0, bytesA, &dA)) || (st = cache_buffer(c, 1, bytesB, &dB)) || (st = cache_buffer(c, 2, bytesC, &dC)) ||
-            (st = cache_buffer(c, 3, (size_t)p->info.packed_bytes[0], &pA)) || (st = cache_buffer(c, 4, (size_t)p->info.packed_bytes[1], &pB)) ||
-            (st = cache_buffer(c, 5, (size_t)p->info.packed_bytes[2], &pC)))
-            break;
-        hipStream_t s = ctx->stream;
-        // everything below is queued on the context's stream; ONE synchronisation at the end (the source buffers are the
-        // caller's and the call is synchronous, so they stay valid until then)
-        if (hipMemcpyAsync(dA, A, bytesA, hipMemcpyHostToDevice, s) != hipSuccess || hipMemcpyAsync(dB, B, bytesB, hipMemcpyHostToDevice, s) != hipSuccess) { st = QG_EHIP; break; }
-        // the caller's C may have padding between columns (ldc > M): keep those bytes as they are
-        if (ldc != d->M && hipMemcpyAsync(dC, C, bytesC, hipMemcpyHostToDevice, s) != hipSuccess) { st = QG_EHIP; break; }
-        if ((st = qgemul_pack(p, QG_OPERAND_A, dA, lda, pA)) || (st = qgemul_pack(p, QG_OPERAND_B, dB, ldb, pB))) break;
-        if (!ep && stores_host_c(p)) {
-            // the kernel's epilogue writes the reference layout: no packed C, no unpack pass
-            if ((st = qgemul_execute_host_c(p, dC, ldc, pA, pB))) break;
-            if (hipMemcpyAsync(C, dC, bytesC, hipMemcpyDeviceToHost, s) != hipSuccess) { st = QG_EHIP; break; }
-            break;
-        }
-        if (!ep) {
-            if ((st = qgemul_execute(p, pC, pA, pB))) break;
-        } else {
-            qgemul_ep_args ea;
-            memset(&ea, 0, sizeof ea);
-            auto raw = [](const void* q, qfmt f) { return (1 + (int)f.I + (int)f.F) <= 32 ? (int64_t) * (const int32_t*)q : *(const int64_t*)q; };
-            for (uint32_t k = 0; k < ep->n_stages && !st; ++k) {
-                const qgemul_ew_stage& sr = ep->stage[k];
-                const qgemul_ew_stage* si = ev->im ? &ev->im->stage[k] : nullptr;
-                const bool cplx = si && ev->e_cplx[k];
-                if (sr.op == QG_EW_APPROX) continue;
-                const bool t_re = sr.op != QG_EW_PASS && !sr.e_scalar, t_im = si && si->op != QG_EW_PASS && !si->e_scalar;
-                if (!t_re && !t_im) {
-                    // scalar operand: one element ({re, im} for a complex one); a real scalar feeds both parts, except where the
-                    // imaginary part's stage takes the zero of the operand's type (real - complex, QuBLAS.h:3686)
-                    if (sr.op != QG_EW_PASS) ea.e_scalar[k] = raw(E[k], sr.e);
-                    if (si && si->op != QG_EW_PASS) {
-                        if (cplx) {
-                            const qfmt f[2] = {sr.e, si->e};
-                            ea.e_scalar_im[k] = raw((const char*)E[k] + qg_host_elem(f, 1).off[1], si->e);
-                        } else {
-                            ea.e_scalar_im[k] = si->op == QG_EW_MUL ? raw(E[k], si->e) : 0;
-                        }
-                    }
-                    continue;
-                }
-                const qfmt f[2] = {t_re ? sr.e : si->e, si ? si->e : sr.e};
-                const size_t bytesE = (size_t)d->M * (size_t)d->N * (size_t)qg_host_elem(f, cplx ? 1 : 0).size;
-                void *dE, *pE;
-                if ((st = cache_buffer(c, 6 + 2 * (int)k, bytesE, &dE)) || (st = cache_buffer(c, 7 + 2 * (int)k, (size_t)qgemul_packed_e_bytes(p, (int)k), &pE)))
-                    break;
-                if (hipMemcpyAsync(dE, E[k], bytesE, hipMemcpyHostToDevice, s) != hipSuccess) { st = QG_EHIP; break; }
-                if ((st = qgemul_pack_e(p, (int)k, dE, 0, pE))) break;
-                ea.e_packed[k] = pE;
-                // (real - complex with a tensor operand: the imaginary part's stage has the scalar 0, set by the memset above)
-            }
-            if (st) break;
-            if ((st = qgemul_execute_ep(p, pC, pA, pB, &ea))) break;
-        }
-        if ((st = qgemul_unpack_c(p, pC, dC, ldc))) break;
-        if (hipMemcpyAsync(C, dC, bytesC, hipMemcpyDeviceToHost, s) != hipSuccess) { st = QG_EHIP; break; }
-    } while (0);
-    const hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (st == QG_OK && e != hipSuccess) { g_last_hip = (int)e; st = QG_EHIP; }
-    return st;
-}
-
-// ---- several GPUs in one process: row bands of C, one per entry of the device list (include/qgemul.h) ----
-// One host thread drives every device: all work is queued asynchronously on each device's own stream (H2D of the band of A
-// and of B, pack, GEMM, peer copy of the packed C band to the root), the root's stream waits for each band's event, unpacks it
-// into the one host-layout C and copies that back.  Bands are whole blocks of 256 rows (every packed row tile divides 256).
-int qgemul_run_sharded(const qgemul_desc* d, void* C, const void* A, const void* B, const qgemul_opts* o, const int* devices, int n)
-{
-    if (!d || !C || !A || !B || !devices || n < 1 || n > QG_MAX_SHARDS) return QG_EINVAL;
-    g_reaper.armed = true;
-    static ShutdownHook hook;
-    qgemul_opts opts;
-    memset(&opts, 0, sizeof opts);
-    if (o) opts = *o;
-    opts.flags &= ~(uint32_t)QG_OPT_ALL_DEVICES;
-    {   // validate the whole problem before touching a device (a band of an unsupported descriptor is unsupported too)
-        qgemul_info info;
-        int st = qgemul_classify(d, opts.flags, &info);
-        if (st != QG_OK) return st;
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return QG_ENOGPU;
-    for (int i = 0; i < n; ++i)
-        if (devices[i] < 0 || devices[i] >= ndev) return QG_EINVAL;
-    if (d->M == 0 || d->N == 0) return QG_OK;
-    const int64_t lda = opts.lda ? opts.lda : (d->transA ? d->K : d->M);
-    const int64_t ldb = opts.ldb ? opts.ldb : d->K;
-    const int64_t ldc = opts.ldc ? opts.ldc : d->M;
-    if (lda < (d->transA ? d->K : d->M) || ldb < d->K || ldc < d->M) return QG_EINVAL;
-
-    // contiguous bands of whole 256-row blocks, sizes differing by at most one block (qublas_amd/dist.py: row_partition)
-    const int64_t ALIGN = 256, units = (d->M + ALIGN - 1) / ALIGN;
-    int64_t row0[QG_MAX_SHARDS], rows[QG_MAX_SHARDS];
-    {
-        int64_t u0 = 0;
-        for (int i = 0; i < n; ++i) {
-            const int64_t u = units / n + (i < units % n ? 1 : 0);
-            const int64_t r0 = u0 * ALIGN < d->M ? u0 * ALIGN : d->M, r1 = (u0 + u) * ALIGN < d->M ? (u0 + u) * ALIGN : d->M;
-            row0[i] = r0;
-            rows[i] = r1 - r0;
-            u0 += u;
-        }
-    }
-    int st = QG_OK;
-    const int root = 0;   // devices[0] assembles C
-    // contexts first: the root's is needed by every band
-    for (int i = 0; i < n && st == QG_OK; ++i) {
-        RunCache& c = g_shard[i];
-        if (c.ctx && c.device != devices[i]) release_cache(c);
-        if (!c.ctx) {
-            st = qgemul_ctx_create(devices[i], &c.ctx);
-            if (st != QG_OK) { c.ctx = nullptr; break; }
-            c.device = c.ctx->device;
-        }
-        if (!g_shard_ev[i]) {
-            DeviceScope scope(c.device);
-            if (hipEventCreateWithFlags(&g_shard_ev[i], hipEventDisableTiming) != hipSuccess) { g_shard_ev[i] = nullptr; st = QG_EHIP; }
-        }
-    }
-    if (st != QG_OK) return st;
-    RunCache& rc = g_shard[root];
-    const qfmt* cf = d->c;
-    const QHostElem hcel = qg_host_elem(cf, d->is_complex);
-    const size_t bytesC = (size_t)((d->N - 1) * ldc + d->M) * hcel.size;
-    void* dC = nullptr;   // host-layout C on the root
-    {
-        DeviceScope scope(rc.device);
-        if ((st = cache_buffer(rc, 2, bytesC, &dC)) != QG_OK) return st;
-        // the caller's C may have padding between columns (ldc > M): keep those bytes as they are
-        if (ldc != d->M && hipMemcpyAsync(dC, C, bytesC, hipMemcpyHostToDevice, rc.ctx->stream) != hipSuccess) return QG_EHIP;
-    }
-    for (int i = 0; i < n && st == QG_OK; ++i) {
-        if (rows[i] == 0) continue;
-        RunCache& c = g_shard[i];
-        DeviceScope scope(c.device);
-        if (scope.err != hipSuccess) { st = QG_EHIP; break; }
-        qgemul_desc bd = *d;
-        bd.M = rows[i];
-        if (!(c.plan && c.pflags == opts.flags && !c.has_pe && same_desc(c.pd, bd))) {
-            if (c.plan) { qgemul_plan_destroy(c.plan); c.plan = nullptr; }
-            st = qgemul_plan_create(c.ctx, &bd, opts.flags, &c.plan);
-            if (st != QG_OK) { c.plan = nullptr; break; }
-            c.pd = bd;
-            c.has_pe = false;
-            c.pflags = opts.flags;
-        }
-        qgemul_plan* p = c.plan;
-        hipStream_t s = c.ctx->stream;
-        const size_t ea = (size_t)p->ha.size, eb = (size_t)p->hb.size;
-        // the band of A in host layout, tight on the device: A declared dim<M,K> (column-major) is strided in the band's rows,
-        // A declared dim<K,M> (QgemulTransposedA) is one contiguous run of columns
-        const size_t bytesA = d->transA ? (size_t)((rows[i] - 1) * lda + d->K) * ea : (size_t)rows[i] * (size_t)d->K * ea;
-        const size_t bytesB = (size_t)((d->N - 1) * ldb + d->K) * eb;
-        void *dA, *dB, *pA, *pB, *pC, *pCroot = nullptr;
-        if ((st = cache_buffer(c, 0, bytesA, &dA)) || (st = cache_buffer(c, 1, bytesB, &dB)) ||
-            (st = cache_buffer(c, 3, (size_t)p->info.packed_bytes[0], &pA)) || (st = cache_buffer(c, 4, (size_t)p->info.packed_bytes[1], &pB)) ||
-            (st = cache_buffer(c, 5, (size_t)p->info.packed_bytes[2], &pC)))
-            break;
-        hipError_t he;
-        int64_t band_lda;
-        if (d->transA) {
-            he = hipMemcpyAsync(dA, (const char*)A + (size_t)row0[i] * (size_t)lda * ea, bytesA, hipMemcpyHostToDevice, s);
-            band_lda = lda;
-        } else {
-            he = hipMemcpy2DAsync(dA, (size_t)rows[i] * ea, (const char*)A + (size_t)row0[i] * ea, (size_t)lda * ea, (size_t)rows[i] * ea,
-                                  (size_t)d->K, hipMemcpyHostToDevice, s);
-            band_lda = rows[i];
-        }
-        if (he != hipSuccess || hipMemcpyAsync(dB, B, bytesB, hipMemcpyHostToDevice, s) != hipSuccess) { st = QG_EHIP; break; }
-        if ((st = qgemul_pack(p, QG_OPERAND_A, dA, band_lda, pA)) || (st = qgemul_pack(p, QG_OPERAND_B, dB, ldb, pB)) ||
-            (st = qgemul_execute(p, pC, pA, pB)))
-            break;
-        // the packed band goes to the root (a peer copy; the same device twice: a device-to-device copy), the root unpacks it
-        if (i == root) {
-            pCroot = pC;
-        } else {
-            // one landing buffer per band on the root: the slots behind the six fixed ones, grown on demand
-            const int slot = 6 + (i - 1);
-            if (slot >= RunCache::NBUF) { st = QG_EUNSUPPORTED; break; }
-            {
-                DeviceScope rscope(rc.device);
-                if ((st = cache_buffer(rc, slot, (size_t)p->info.packed_bytes[2], &pCroot)) != QG_OK) break;
-            }
-            if (hipMemcpyPeerAsync(pCroot, rc.device, pC, c.device, (size_t)p->info.packed_bytes[2], s) != hipSuccess) { st = QG_EHIP; break; }
-        }
-        if (hipEventRecord(g_shard_ev[i], s) != hipSuccess) { st = QG_EHIP; break; }
-        {
-            DeviceScope rscope(rc.device);
-            if (i != root && hipStreamWaitEvent(rc.ctx->stream, g_shard_ev[i], 0) != hipSuccess) { st = QG_EHIP; break; }
-            QCGeom g = p->pc;          // the band's packed geometry, written at row offset row0 of the full C
-            g.ldc = ldc;
-            char* dst = (char*)dC + (size_t)row0[i] * hcel.size;
-            if (qg_launch_unpack_c(g, pCroot, dst, rc.ctx->stream, (opts.flags & QG_OPT_GENERIC_LAYOUT) ? 1 : 0) != hipSuccess) { st = QG_EHIP; break; }
-        }
-    }
-    if (st == QG_OK) {
-        DeviceScope scope(rc.device);
-        if (hipMemcpyAsync(C, dC, bytesC, hipMemcpyDeviceToHost, rc.ctx->stream) != hipSuccess) st = QG_EHIP;
-    }
-    // the call is synchronous: every stream drains before the caller's buffers may change (root last: it waits for the others)
-    for (int i = n - 1; i >= 0; --i) {
-        if (!g_shard[i].ctx) continue;
-        DeviceScope scope(g_shard[i].device);
-        const hipError_t e = hipStreamSynchronize(g_shard[i].ctx->stream);
-        if (st == QG_OK && e != hipSuccess) { g_last_hip = (int)e; st = QG_EHIP; }
-    }
-    return st;
-}
 
 // ---- batched Qgemul: `batch` GEMMs of one descriptor at constant strides (include/qgemul.h) ----
 // kernel launches of one qgemul_execute on a plain plan (a 3 x 3 launch pair counts once: its partner returns in its first instructions)
-static int plan_launches(const qgemul_plan* p)
+static int plan_launches(const QPlanGeom* p)
 {
     if (p->comp.on) return p->comp.nc * (p->comp.ga * p->comp.gb + 1);
     switch (p->info.kernel) {
@@ -2246,8 +1572,7 @@ static int plan_launches(const qgemul_plan* p)
     }
 }
 
-// host elements one member of operand `operand` spans at leading dimension ld (0: tight); 0: ld is too small
-static int64_t member_extent(const qgemul_desc& d, int operand, int64_t ld)
+int64_t member_extent(const qgemul_desc& d, int operand, int64_t ld)
 {
     const int64_t rows = operand == QG_OPERAND_A ? (d.transA ? d.K : d.M) : operand == QG_OPERAND_B ? d.K : d.M;
     const int64_t cols = operand == QG_OPERAND_A ? (d.transA ? d.M : d.K) : d.N;
@@ -2258,22 +1583,15 @@ static int64_t member_extent(const qgemul_desc& d, int operand, int64_t ld)
 
 // the geometry of a batched plan, pure host code: m (zeroed) receives the member's, b (zeroed) the batch's
 // ev: the chain of a batched plan with one (qgemul_plan_create_batched_epx), bep: which of its tensor operands are shared
-static int batched_geometry(const qgemul_desc* d, int64_t batch, uint32_t flags, qgemul_plan* m, qgemul_plan* b, const EpView* ev = nullptr,
-                            const qgemul_batched_ep* bep = nullptr)
+static int batched_geometry(const qgemul_desc* d, int64_t batch, uint32_t flags, QPlanGeom* m, qgemul_plan* b, const EpView* ev, const qgemul_batched_ep* bep)
 {
     if (!d || batch < 1) return QG_EINVAL;
-    int bd = 0;
-    m->desc = *d;
-    m->flags = flags;
-    if (ev) {
-        m->has_ep = 1;
-        for (int k = 0; ev->ax && k < QG_MAX_EW; ++k) m->has_ax |= ev->ax[k] != nullptr;
-    }
-    const int st = plan_geometry(d, flags, &m->an, &m->info, &m->LA, &m->LB, &m->cfg, &m->pa, &m->pb, &m->pc, &m->ha, &m->hb, &m->hc, ev, &m->ept, &m->pc_c,
-                                 &m->ept_im, &m->comp, nullptr, nullptr, batch, &bd);
+    bool has_ax = false;
+    for (int k = 0; ev && ev->ax && k < QG_MAX_EW; ++k) has_ax |= ev->ax[k] != nullptr;
+    const int st = plan_geometry(d, flags, ev, batch, m, nullptr, nullptr);
     b->info = m->info;
     if (st != QG_OK) return st;
-    m->variant = m->cfg.variant;
+    const int bd = m->bd;
     b->desc = *d;
     b->flags = flags;
     b->batch = batch;
@@ -2292,14 +1610,14 @@ static int batched_geometry(const qgemul_desc* d, int64_t batch, uint32_t flags,
     if (ev) {
         // the chain is the member's; what one member's qgemul_execute_ep issues: its kernel and, unless fused, the chain's pass
         b->has_ep = 1;
-        b->has_ax = m->has_ax;
+        b->has_ax = has_ax;
         b->ep = *ev->re;
         b->ept = m->ept;
         b->pc_c = m->pc_c;
-        if (!fuses_epilogue(m)) b->member_launches += 1;
+        if (!fuses_epilogue(m, flags, has_ax, false)) b->member_launches += 1;
         // fused form: what fuses_epilogue accepts on arithmetic grounds, on request (the default between the two block-diagonal
         // forms is the pass until tools/measure_batched_ep.py has decided otherwise: DESIGN.md section 9)
-        b->bd_fused = bd && m->ept.bits32 && !m->has_ax && (flags & QG_OPT_FUSED_EPILOGUE) && !(flags & QG_OPT_UNFUSED_EPILOGUE);
+        b->bd_fused = bd && m->ept.bits32 && !has_ax && (flags & QG_OPT_FUSED_EPILOGUE) && !(flags & QG_OPT_UNFUSED_EPILOGUE);
         for (int k = 0; k < m->ept.n; ++k) {
             const QEpStage& s = m->ept.st[k];
             if (s.scalar || s.op == QG_EW_APPROX) continue;
@@ -2361,45 +1679,70 @@ static int batched_geometry(const qgemul_desc* d, int64_t batch, uint32_t flags,
     return QG_OK;
 }
 
+// a batched plan's host side: *out = the plan (heap, zeroed, then filled; the caller's to release with `delete`, whatever the status:
+// its info says why a descriptor was refused).  ev == nullptr: no chain
+static int batched_plan_new(const qgemul_desc* d, int64_t batch, uint32_t flags, const EpView* ev, const qgemul_batched_ep* bep, qgemul_plan** out)
+{
+    *out = nullptr;
+    qgemul_plan* b = new (std::nothrow) qgemul_plan();
+    QPlanGeom* m = new (std::nothrow) QPlanGeom();   // the member's geometry: needed only while the batch's is derived from it
+    const int st = b && m ? batched_geometry(d, batch, flags, m, b, ev, bep) : QG_EINVAL;
+    delete m;
+    if (!b) return QG_EINVAL;
+    *out = b;
+    return st;
+}
+
+int classify_batched_view(const qgemul_desc* d, int64_t batch, const EpView* ev, const qgemul_batched_ep* bep, uint32_t opt_flags, qgemul_info* out, int* launches)
+{
+    if (!d) return QG_EINVAL;
+    qgemul_plan* b = nullptr;
+    const int st = batched_plan_new(d, batch, opt_flags, ev, bep, &b);
+    if (!b) return st;
+    if (out && batch >= 1) *out = b->info;
+    if (launches && st == QG_OK) *launches = qgemul_plan_batched_launches(b);
+    delete b;
+    return st;
+}
+
 int qgemul_classify_batched(const qgemul_desc* d, int64_t batch, uint32_t opt_flags, qgemul_info* out)
 {
     if (!d || !out) return QG_EINVAL;
-    qgemul_plan* two = new (std::nothrow) qgemul_plan[2];
-    if (!two) return QG_EINVAL;
-    memset(two, 0, 2 * sizeof *two);
-    const int st = batched_geometry(d, batch, opt_flags, &two[0], &two[1]);
-    if (batch >= 1) *out = two[1].info;
-    delete[] two;
-    return st;
+    return classify_batched_view(d, batch, nullptr, nullptr, opt_flags, out, nullptr);
 }
 
 int qgemul_classify_batched_launches(const qgemul_desc* d, int64_t batch, uint32_t opt_flags)
 {
-    if (!d) return QG_EINVAL;
-    qgemul_plan* two = new (std::nothrow) qgemul_plan[2];
-    if (!two) return QG_EINVAL;
-    memset(two, 0, 2 * sizeof *two);
-    int st = batched_geometry(d, batch, opt_flags, &two[0], &two[1]);
-    if (st == QG_OK) st = qgemul_plan_batched_launches(&two[1]);
-    delete[] two;
-    return st;
+    int n = 0;
+    const int st = classify_batched_view(d, batch, nullptr, nullptr, opt_flags, nullptr, &n);
+    return st == QG_OK ? n : st;
+}
+
+// the member owns every device resource (with a chain: its device tables as well) except the block-diagonal pass form's packed C
+int plan_create_batched_view(qgemul_ctx* c, const qgemul_desc* d, int64_t batch, const EpView* ev, const qgemul_batched_ep* bep, uint32_t opt_flags, qgemul_plan** out)
+{
+    if (!c || !d || !out) return QG_EINVAL;
+    qgemul_plan* b = nullptr;
+    int st = batched_plan_new(d, batch, opt_flags, ev, bep, &b);
+    if (!b) return st;
+    if (st == QG_OK) st = plan_create_view(c, d, ev, opt_flags, &b->member, batch);
+    if (st != QG_OK) { delete b; return st; }
+    b->ctx = c;
+    if (b->has_ep && b->bd && !b->bd_fused) {   // the pass form: the stack's packed C between the two launches
+        DeviceScope scope(c->device);
+        const size_t cb = (size_t)batch * (size_t)(b->pc_c.Mp * b->pc_c.Np) * (size_t)b->pc_c.cbytes;
+        if (scope.err != hipSuccess || hipMalloc(&b->cwork, cb ? cb : 16) != hipSuccess) {
+            qgemul_plan_destroy(b);
+            return QG_EHIP;
+        }
+    }
+    *out = b;
+    return QG_OK;
 }
 
 int qgemul_plan_create_batched(qgemul_ctx* c, const qgemul_desc* d, int64_t batch, uint32_t opt_flags, qgemul_plan** out)
 {
-    if (!c || !d || !out) return QG_EINVAL;
-    qgemul_plan* two = new (std::nothrow) qgemul_plan[2];
-    qgemul_plan* b = new (std::nothrow) qgemul_plan;
-    if (!two || !b) { delete[] two; delete b; return QG_EINVAL; }
-    memset(two, 0, 2 * sizeof *two);
-    int st = batched_geometry(d, batch, opt_flags, &two[0], &two[1]);
-    *b = two[1];
-    delete[] two;
-    if (st == QG_OK) st = plan_create_view(c, d, nullptr, opt_flags, &b->member, batch);
-    if (st != QG_OK) { delete b; return st; }
-    b->ctx = c;
-    *out = b;
-    return QG_OK;
+    return plan_create_batched_view(c, d, batch, nullptr, nullptr, opt_flags, out);
 }
 
 int qgemul_plan_batched_launches(const qgemul_plan* p)
@@ -2490,104 +1833,25 @@ int qgemul_time_execute_batched(qgemul_plan* p, void* packedC, const void* packe
     return time_execute(p, packedC, packedA, packedB, nullptr, warmup, iters, avg_ms, true);
 }
 
-int qgemul_run_batched(const qgemul_desc* d, int64_t batch, void* C, const void* A, const void* B, int64_t strideC, int64_t strideA, int64_t strideB,
-                       const qgemul_opts* o)
-{
-    if (!d || !C || !A || !B || batch < 1) return QG_EINVAL;
-    qgemul_opts opts;
-    memset(&opts, 0, sizeof opts);
-    opts.device = -1;
-    if (o) opts = *o;
-    if (opts.flags & QG_OPT_ALL_DEVICES) return QG_EUNSUPPORTED;   // (the sharded entry has no batched form)
-    const int64_t extA = member_extent(*d, QG_OPERAND_A, opts.lda), extB = member_extent(*d, QG_OPERAND_B, opts.ldb), extC = member_extent(*d, QG_OPERAND_C, opts.ldc);
-    if (extA < 1 || extB < 1 || extC < 1 || strideA < extA || strideB < extB || strideC < extC) return QG_EINVAL;
-    g_reaper.armed = true;
-    static ShutdownHook hook;
-    RunCache& c = g_run;
-    if (opts.device < 0 && c.ctx) {
-        int cur = c.device;
-        if (hipGetDevice(&cur) == hipSuccess) opts.device = cur;
-    }
-    const bool same_plan = c.plan && c.pbatch == batch && c.pflags == opts.flags && same_desc(c.pd, *d) && !c.has_pe && (opts.device < 0 || opts.device == c.device);
-    if (!same_plan) {   // validate before touching the device
-        qgemul_info info;
-        if (const int st = qgemul_classify_batched(d, batch, opts.flags, &info); st != QG_OK) return st;
-    }
-    if (d->M == 0 || d->N == 0) return QG_OK;
-    int st = QG_OK;
-    if (!c.ctx || (opts.device >= 0 && opts.device != c.device)) {
-        release_cache(c);
-        st = qgemul_ctx_create(opts.device, &c.ctx);
-        if (st != QG_OK) { c.ctx = nullptr; return st; }
-        c.device = c.ctx->device;
-    } else {
-        QG_HIP(hipSetDevice(c.device));
-    }
-    if (!same_plan) {
-        if (c.plan) { qgemul_plan_destroy(c.plan); c.plan = nullptr; }
-        st = qgemul_plan_create_batched(c.ctx, d, batch, opts.flags, &c.plan);
-        if (st != QG_OK) { c.plan = nullptr; return st; }
-        c.pd = *d;
-        c.has_pe = false;
-        c.pe_cplx = false;
-        memset(c.pax_on, 0, sizeof c.pax_on);
-        memset(c.pcx_on, 0, sizeof c.pcx_on);
-        c.pflags = opts.flags;
-        c.pbatch = batch;
-    }
-    qgemul_plan* p = c.plan;
-    void *dA, *dB, *dC, *pA, *pB, *pC;
-    do {
-        const size_t bytesA = (size_t)((batch - 1) * strideA + extA) * p->ha.size;
-        const size_t bytesB = (size_t)((batch - 1) * strideB + extB) * p->hb.size;
-        const size_t bytesC = (size_t)((batch - 1) * strideC + extC) * p->hc.size;
-        if ((st = cache_buffer(c, 0, bytesA, &dA)) || (st = cache_buffer(c, 1, bytesB, &dB)) || (st = cache_buffer(c, 2, bytesC, &dC)) ||
-            (st = cache_buffer(c, 3, (size_t)p->info.packed_bytes[0], &pA)) || (st = cache_buffer(c, 4, (size_t)p->info.packed_bytes[1], &pB)) ||
-            (st = cache_buffer(c, 5, (size_t)p->info.packed_bytes[2], &pC)))
-            break;
-        hipStream_t s = c.ctx->stream;
-        if (hipMemcpyAsync(dA, A, bytesA, hipMemcpyHostToDevice, s) != hipSuccess || hipMemcpyAsync(dB, B, bytesB, hipMemcpyHostToDevice, s) != hipSuccess) { st = QG_EHIP; break; }
-        // the caller's C may have gaps between columns and between members: those bytes stay as they are
-        if ((strideC != d->M * d->N || (opts.ldc && opts.ldc != d->M)) && hipMemcpyAsync(dC, C, bytesC, hipMemcpyHostToDevice, s) != hipSuccess) { st = QG_EHIP; break; }
-        if ((st = qgemul_pack_batched(p, QG_OPERAND_A, dA, opts.lda, strideA, pA)) || (st = qgemul_pack_batched(p, QG_OPERAND_B, dB, opts.ldb, strideB, pB))) break;
-        if ((st = qgemul_execute_batched(p, pC, pA, pB))) break;
-        if ((st = qgemul_unpack_c_batched(p, pC, dC, opts.ldc, strideC))) break;
-        if (hipMemcpyAsync(C, dC, bytesC, hipMemcpyDeviceToHost, s) != hipSuccess) { st = QG_EHIP; break; }
-    } while (0);
-    const hipError_t e = hipStreamSynchronize(c.ctx->stream);
-    if (st == QG_OK && e != hipSuccess) { g_last_hip = (int)e; st = QG_EHIP; }
-    return st;
-}
-
 // ---- element-wise chains on batched plans (include/qgemul.h): member b is Qgemul<...>(C_b, A_b, B_b) followed by the chain ----
-static int classify_batched_epx(const qgemul_desc* d, int64_t batch, const qgemul_epilogue* ep, const qgemul_approx* const* ax, const qgemul_batched_ep* bep,
-                                uint32_t opt_flags, qgemul_info* out, int* launches)
-{
-    if (!d || !ep) return QG_EINVAL;
-    static const qgemul_approx* const no_ax[QG_MAX_EW] = {};
-    const EpView v = {ep, nullptr, nullptr, ax ? ax : no_ax};
-    qgemul_plan* two = new (std::nothrow) qgemul_plan[2];
-    if (!two) return QG_EINVAL;
-    memset(two, 0, 2 * sizeof *two);
-    int st = batched_geometry(d, batch, opt_flags, &two[0], &two[1], &v, bep);
-    if (out && batch >= 1) *out = two[1].info;
-    if (launches && st == QG_OK) *launches = qgemul_plan_batched_launches(&two[1]);
-    delete[] two;
-    return st;
-}
+// (ax == nullptr: a chain without APPROX stages)
+static const qgemul_approx* const g_no_ax[QG_MAX_EW] = {};
 
 int qgemul_classify_batched_epx(const qgemul_desc* d, int64_t batch, const qgemul_epilogue* ep, const qgemul_approx* const ax[QG_MAX_EW],
                                 const qgemul_batched_ep* bep, uint32_t opt_flags, qgemul_info* out)
 {
-    if (!out) return QG_EINVAL;
-    return classify_batched_epx(d, batch, ep, ax, bep, opt_flags, out, nullptr);
+    if (!out || !ep) return QG_EINVAL;
+    const EpView v = {ep, nullptr, nullptr, ax ? ax : g_no_ax};
+    return classify_batched_view(d, batch, &v, bep, opt_flags, out, nullptr);
 }
 
 int qgemul_classify_batched_epx_launches(const qgemul_desc* d, int64_t batch, const qgemul_epilogue* ep, const qgemul_approx* const ax[QG_MAX_EW],
                                          const qgemul_batched_ep* bep, uint32_t opt_flags)
 {
+    if (!ep) return QG_EINVAL;
+    const EpView v = {ep, nullptr, nullptr, ax ? ax : g_no_ax};
     int n = 0;
-    const int st = classify_batched_epx(d, batch, ep, ax, bep, opt_flags, nullptr, &n);
+    const int st = classify_batched_view(d, batch, &v, bep, opt_flags, nullptr, &n);
     return st == QG_OK ? n : st;
 }
 
@@ -2595,29 +1859,8 @@ int qgemul_plan_create_batched_epx(qgemul_ctx* c, const qgemul_desc* d, int64_t 
                                    const qgemul_batched_ep* bep, uint32_t opt_flags, qgemul_plan** out)
 {
     if (!c || !d || !ep || !out) return QG_EINVAL;
-    static const qgemul_approx* const no_ax[QG_MAX_EW] = {};
-    const EpView v = {ep, nullptr, nullptr, ax ? ax : no_ax};
-    qgemul_plan* two = new (std::nothrow) qgemul_plan[2];
-    qgemul_plan* b = new (std::nothrow) qgemul_plan;
-    if (!two || !b) { delete[] two; delete b; return QG_EINVAL; }
-    memset(two, 0, 2 * sizeof *two);
-    int st = batched_geometry(d, batch, opt_flags, &two[0], &two[1], &v, bep);
-    *b = two[1];
-    delete[] two;
-    b->ctx = c;
-    // the member owns the chain's device tables (APPROX) and, member by member, everything else
-    if (st == QG_OK) st = plan_create_view(c, d, &v, opt_flags, &b->member, batch);
-    if (st != QG_OK) { delete b; return st; }
-    if (b->bd && !b->bd_fused) {   // the pass form: the stack's packed C between the two launches
-        DeviceScope scope(c->device);
-        const size_t cb = (size_t)batch * (size_t)(b->pc_c.Mp * b->pc_c.Np) * (size_t)b->pc_c.cbytes;
-        if (scope.err != hipSuccess || hipMalloc(&b->cwork, cb ? cb : 16) != hipSuccess) {
-            qgemul_plan_destroy(b);
-            return QG_EHIP;
-        }
-    }
-    *out = b;
-    return QG_OK;
+    const EpView v = {ep, nullptr, nullptr, ax ? ax : g_no_ax};
+    return plan_create_batched_view(c, d, batch, &v, bep, opt_flags, out);
 }
 
 int qgemul_pack_e_batched(qgemul_plan* p, int stage, const void* src_dev, int64_t ld, int64_t member_stride, void* packed_dev)
@@ -2710,112 +1953,5 @@ int qgemul_time_execute_batched_ep(qgemul_plan* p, void* packedD, const void* pa
     return time_execute(p, packedD, packedA, packedB, args, warmup, iters, avg_ms, true);
 }
 
-int qgemul_run_batched_epx(const qgemul_desc* d, int64_t batch, const qgemul_epilogue* ep, const qgemul_approx* const ax[QG_MAX_EW], void* D, const void* A,
-                           const void* B, const void* const* E, int64_t strideD, int64_t strideA, int64_t strideB, const int64_t strideE[QG_MAX_EW],
-                           const qgemul_opts* o)
-{
-    if (!d || !ep || !D || !A || !B || batch < 1 || ep->n_stages > QG_MAX_EW) return QG_EINVAL;
-    qgemul_opts opts;
-    memset(&opts, 0, sizeof opts);
-    opts.device = -1;
-    if (o) opts = *o;
-    if (opts.flags & QG_OPT_ALL_DEVICES) return QG_EUNSUPPORTED;   // (the sharded entry has no batched form)
-    const int64_t extA = member_extent(*d, QG_OPERAND_A, opts.lda), extB = member_extent(*d, QG_OPERAND_B, opts.ldb), extD = member_extent(*d, QG_OPERAND_C, opts.ldc);
-    if (extA < 1 || extB < 1 || extD < 1 || strideA < extA || strideB < extB || strideD < extD) return QG_EINVAL;
-    const int64_t extE = member_extent(*d, QG_OPERAND_C, 0);   // (stage operands are tight)
-    qgemul_batched_ep bep;
-    memset(&bep, 0, sizeof bep);
-    for (uint32_t k = 0; k < ep->n_stages; ++k) {
-        const qgemul_ew_stage& s = ep->stage[k];
-        if (s.op == QG_EW_APPROX) continue;
-        if (!E || !E[k]) return QG_EINVAL;
-        if (s.e_scalar) continue;
-        if (!strideE || (strideE[k] != 0 && strideE[k] < extE)) return QG_EINVAL;
-        bep.e_shared[k] = strideE[k] == 0;
-    }
-    g_reaper.armed = true;
-    static ShutdownHook hook;
-    RunCache& c = g_run;
-    if (opts.device < 0 && c.ctx) {
-        int cur = c.device;
-        if (hipGetDevice(&cur) == hipSuccess) opts.device = cur;
-    }
-    const bool same_plan = c.plan && c.pbatch == batch && c.pflags == opts.flags && same_desc(c.pd, *d) && c.has_pe && !c.pe_cplx && same_epilogue(c.pe.part[0], *ep) &&
-                           same_tables(c, ax) && !memcmp(c.pshared, bep.e_shared, sizeof c.pshared) && (opts.device < 0 || opts.device == c.device);
-    if (!same_plan) {   // validate before touching the device
-        qgemul_info info;
-        if (const int st = qgemul_classify_batched_epx(d, batch, ep, ax, &bep, opts.flags, &info); st != QG_OK) return st;
-    }
-    if (d->M == 0 || d->N == 0) return QG_OK;
-    int st = QG_OK;
-    if (!c.ctx || (opts.device >= 0 && opts.device != c.device)) {
-        release_cache(c);
-        st = qgemul_ctx_create(opts.device, &c.ctx);
-        if (st != QG_OK) { c.ctx = nullptr; return st; }
-        c.device = c.ctx->device;
-    } else {
-        QG_HIP(hipSetDevice(c.device));
-    }
-    if (!same_plan) {
-        if (c.plan) { qgemul_plan_destroy(c.plan); c.plan = nullptr; }
-        st = qgemul_plan_create_batched_epx(c.ctx, d, batch, ep, ax, &bep, opts.flags, &c.plan);
-        if (st != QG_OK) { c.plan = nullptr; return st; }
-        c.pd = *d;
-        c.has_pe = true;
-        c.pe_cplx = false;
-        c.pe.part[0] = *ep;
-        memset(c.pax_on, 0, sizeof c.pax_on);
-        for (int k = 0; ax && k < QG_MAX_EW; ++k) {
-            if (!ax[k]) continue;
-            if (!c.pax) c.pax = new qgemul_approx[QG_MAX_EW];
-            c.pax[k] = *ax[k];
-            c.pax_on[k] = 1;
-        }
-        memset(c.pcx_on, 0, sizeof c.pcx_on);
-        memcpy(c.pshared, bep.e_shared, sizeof c.pshared);
-        c.pflags = opts.flags;
-        c.pbatch = batch;
-    }
-    qgemul_plan* p = c.plan;
-    void *dA, *dB, *dD, *pA, *pB, *pD;
-    do {
-        const size_t bytesA = (size_t)((batch - 1) * strideA + extA) * p->ha.size;
-        const size_t bytesB = (size_t)((batch - 1) * strideB + extB) * p->hb.size;
-        const size_t bytesD = (size_t)((batch - 1) * strideD + extD) * p->hc.size;
-        if ((st = cache_buffer(c, 0, bytesA, &dA)) || (st = cache_buffer(c, 1, bytesB, &dB)) || (st = cache_buffer(c, 2, bytesD, &dD)) ||
-            (st = cache_buffer(c, 3, (size_t)p->info.packed_bytes[0], &pA)) || (st = cache_buffer(c, 4, (size_t)p->info.packed_bytes[1], &pB)) ||
-            (st = cache_buffer(c, 5, (size_t)p->info.packed_bytes[2], &pD)))
-            break;
-        hipStream_t s = c.ctx->stream;
-        if (hipMemcpyAsync(dA, A, bytesA, hipMemcpyHostToDevice, s) != hipSuccess || hipMemcpyAsync(dB, B, bytesB, hipMemcpyHostToDevice, s) != hipSuccess) { st = QG_EHIP; break; }
-        // the caller's D may have gaps between columns and between members: those bytes stay as they are
-        if ((strideD != d->M * d->N || (opts.ldc && opts.ldc != d->M)) && hipMemcpyAsync(dD, D, bytesD, hipMemcpyHostToDevice, s) != hipSuccess) { st = QG_EHIP; break; }
-        if ((st = qgemul_pack_batched(p, QG_OPERAND_A, dA, opts.lda, strideA, pA)) || (st = qgemul_pack_batched(p, QG_OPERAND_B, dB, opts.ldb, strideB, pB))) break;
-        qgemul_ep_args ea;
-        memset(&ea, 0, sizeof ea);
-        for (uint32_t k = 0; k < ep->n_stages && !st; ++k) {
-            const qgemul_ew_stage& sr = ep->stage[k];
-            if (sr.op == QG_EW_APPROX) continue;
-            if (sr.e_scalar) {
-                ea.e_scalar[k] = (1 + (int)sr.e.I + (int)sr.e.F) <= 32 ? (int64_t) * (const int32_t*)E[k] : *(const int64_t*)E[k];
-                continue;
-            }
-            const qfmt f[2] = {sr.e, sr.e};
-            const size_t bytesE = (size_t)((bep.e_shared[k] ? 0 : (batch - 1) * strideE[k]) + extE) * (size_t)qg_host_elem(f, 0).size;
-            void *dE, *pE;
-            if ((st = cache_buffer(c, 6 + 2 * (int)k, bytesE, &dE)) || (st = cache_buffer(c, 7 + 2 * (int)k, (size_t)qgemul_packed_e_bytes(p, (int)k), &pE))) break;
-            if (hipMemcpyAsync(dE, E[k], bytesE, hipMemcpyHostToDevice, s) != hipSuccess) { st = QG_EHIP; break; }
-            if ((st = qgemul_pack_e_batched(p, (int)k, dE, 0, strideE[k], pE))) break;
-            ea.e_packed[k] = pE;
-        }
-        if (st) break;
-        if ((st = qgemul_execute_batched_ep(p, pD, pA, pB, &ea))) break;
-        if ((st = qgemul_unpack_c_batched(p, pD, dD, opts.ldc, strideD))) break;
-        if (hipMemcpyAsync(D, dD, bytesD, hipMemcpyDeviceToHost, s) != hipSuccess) { st = QG_EHIP; break; }
-    } while (0);
-    const hipError_t e = hipStreamSynchronize(c.ctx->stream);
-    if (st == QG_OK && e != hipSuccess) { g_last_hip = (int)e; st = QG_EHIP; }
-    return st;
-}
 
 } // extern "C"

@@ -19,7 +19,7 @@
 #include <mutex>
 #include <new>
 
-#include "../../include/qgemul.h"
+#include "qg_api_int.h"
 
 namespace {
 
@@ -112,9 +112,6 @@ struct qgemul_comm {
 
 extern "C" {
 
-// (declared in qg_api.hip's translation unit as well: the context's device and stream)
-void* qgemul_ctx_stream(qgemul_ctx* c);
-int qgemul_ctx_device(const qgemul_ctx* c);
 
 int qgemul_last_rccl_error(void) { return g_last_rccl; }
 

@@ -1,4 +1,4 @@
-// qg_kernels.h — launch interface between the C-ABI layer (qg_api.cpp) and the gfx950 kernels.
+// qg_kernels.h — launch interface between the C-ABI layer (qg_api.hip) and the gfx950 kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

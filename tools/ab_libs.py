@@ -3,9 +3,13 @@
 alternating child processes (one library per process), several rounds.  Used to price a change that is compiled in
 unconditionally (no switch to flip): build the previous commit's sources into qublas_amd/build/ab/libqugemm_prev.so and run
     python tools/ab_libs.py qublas_amd/build/ab/libqugemm_prev.so qublas_amd/libqugemm.so
-Prints one JSON line per (workload, library) with the per-round medians."""
+Prints one JSON line per (workload, library) with the per-round medians.
+With --script PATH in front, each child runs that measuring script instead (one that prints JSON lines with ONE float field each,
+tools/measure_run_latency.py for instance) with the library selected, and the lines are collected per round in the same way:
+    python tools/ab_libs.py --script tools/measure_run_latency.py qublas_amd/build/ab/libqugemm_prev.so qublas_amd/libqugemm.so 5"""
 import json
 import os
+import runpy
 import subprocess
 import sys
 
@@ -40,21 +44,45 @@ def child(path):
     print(json.dumps(out), flush=True)
 
 
+def child_script(path, script):
+    from qublas_amd import capi
+    capi.LIB_PATH = os.path.abspath(path)
+    runpy.run_path(script, run_name="__main__")
+
+
+def script_result(text):
+    """{the line's other fields: its one float} of a measuring script's JSON lines"""
+    out = {}
+    for ln in text.strip().splitlines():
+        r = json.loads(ln)
+        out[" ".join(f"{k}={v}" for k, v in r.items() if not isinstance(v, float))] = next(v for v in r.values() if isinstance(v, float))
+    return out
+
+
 def main():
     if len(sys.argv) == 3 and sys.argv[1] == "--child":
         return child(sys.argv[2])
+    if len(sys.argv) == 4 and sys.argv[1] == "--child-script":
+        return child_script(sys.argv[2], sys.argv[3])
+    script = None
+    if sys.argv[1] == "--script":
+        script = os.path.abspath(sys.argv[2])
+        del sys.argv[1:3]
     libs = sys.argv[1:3]
     rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 4
     res = {l: {} for l in libs}
     for _ in range(rounds):
         for l in libs:
-            r = json.loads(subprocess.check_output([sys.executable, os.path.abspath(__file__), "--child", l], text=True).strip().splitlines()[-1])
+            if script:
+                r = script_result(subprocess.check_output([sys.executable, os.path.abspath(__file__), "--child-script", l, script], text=True))
+            else:
+                r = json.loads(subprocess.check_output([sys.executable, os.path.abspath(__file__), "--child", l], text=True).strip().splitlines()[-1])
             for k, v in r.items():
                 res[l].setdefault(k, []).append(v)
     for k in next(iter(res.values())):
         for l in libs:
             v = sorted(res[l][k])
-            print(json.dumps({"workload": k, "library": l, "ms_rounds": [round(x, 5) for x in res[l][k]], "ms_median": v[len(v) // 2], "ms_min": v[0]}), flush=True)
+            print(json.dumps({"workload": k, "library": l, "ms_rounds": [round(x, 5) for x in res[l][k]], "ms_median": v[len(v) // 2], "ms_min": v[0], "ms_max": v[-1]}), flush=True)
 
 
 if __name__ == "__main__":
