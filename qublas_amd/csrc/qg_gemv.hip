@@ -26,6 +26,7 @@
 #include "qg_kernels.h"
 #include "qg_fix.h"
 #include "qg_step_all.h"
+#include "qg_tree_io.h"
 
 namespace {
 
@@ -261,14 +262,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv(QGemvArgs g)
         }
         typename std::conditional<MODE == QGF_WORD || MODE == QGF_WORD_RND, int64_t, T>::type r[1] = {root};   // (the words: a rounding addend on a full 32-bit word needs the 64-bit step)
         qg_step_all<typename std::conditional<MODE == QGF_WORD || MODE == QGF_WORD_RND, int64_t, T>::type, 1>(r, c_cvt);
-        if (lane == 0) {
-            switch (g.cbytes) {
-            case 1: ((int8_t*)g.C)[row] = (int8_t)r[0]; break;
-            case 2: ((int16_t*)g.C)[row] = (int16_t)r[0]; break;
-            case 4: ((int32_t*)g.C)[row] = (int32_t)r[0]; break;
-            default: ((int64_t*)g.C)[row] = (int64_t)r[0]; break;
-            }
-        }
+        if (lane == 0) qg_store_c(g.C, row, g.cbytes, r[0]);
     }
 }
 
@@ -365,6 +359,8 @@ __global__ __launch_bounds__(256) void k_gemv_short(QGemvArgs g)
             for (int u = 0; u < U; ++u) {
                 const int64_t row = (g0 + u) * RPL + rl;
                 if (row < g.M) {
+                    // (qg_store_c written out: under the call all 24 instantiations of this kernel lose 2 ... 17 instructions —
+                    // another instruction stream, tools/isa_diff.py; k_gemv's store above is the call)
                     switch (g.cbytes) {
                     case 1: ((int8_t*)g.C)[row] = (int8_t)x[u]; break;
                     case 2: ((int16_t*)g.C)[row] = (int16_t)x[u]; break;

@@ -14,14 +14,12 @@
 #include <hip/hip_runtime.h>
 
 #include "qg_kernels.h"
+#include "qg_tree_io.h"
 
 namespace {
 
-__device__ __forceinline__ int64_t ld_c(const char* p, int64_t idx, int cbytes)
-{
-    return cbytes == 4 ? (int64_t)((const int32_t*)p)[idx] : ((const int64_t*)p)[idx];
-}
-
+// qg_store_c (qg_tree_io.h) with the 16-byte containers of wide plans.  Written out: `cbytes == 16 ? the two words : qg_store_c(...)`
+// keeps every count of both instantiations of k_tree_generic but reorders their instructions (tools/isa_diff.py)
 template <class T>
 __device__ __forceinline__ void st_c(char* dst, int64_t idx, int cbytes, T v)
 {
@@ -114,8 +112,8 @@ __global__ __launch_bounds__(256) void k_tree_generic(const QTreeTable* __restri
             for (int p = 0; p < parts; ++p) {
                 int64_t va = 0, vb = 0;
                 if (k < K) {
-                    if (m0 + r < M) va = ld_c(A, ((int64_t)p * pa.rows_p + m0 + r) * pa.K_p + k, pa.cbytes);
-                    if (n0 + r < N) vb = ld_c(B, ((int64_t)p * pb.rows_p + n0 + r) * pb.K_p + k, pb.cbytes);
+                    if (m0 + r < M) va = qg_load_c(A, ((int64_t)p * pa.rows_p + m0 + r) * pa.K_p + k, pa.cbytes);
+                    if (n0 + r < N) vb = qg_load_c(B, ((int64_t)p * pb.rows_p + n0 + r) * pb.K_p + k, pb.cbytes);
                 }
                 sA[p][r][kk] = va;
                 sB[p][r][kk] = vb;

@@ -13,10 +13,12 @@
 
 #include "qg_kernels.h"
 #include "qg_step_all.h"
+#include "qg_tree_counter.h"
+#include "qg_tree_io.h"
 
 namespace {
 
-constexpr int KC = 32;
+constexpr int KC = QG_TREE_KC;
 constexpr int TMB = 32, TNB = 32;   // 16 x 16 threads x (2 x 2)
 constexpr int PITCH = KC + 2;
 
@@ -29,17 +31,13 @@ struct QTree64Args {
     int32_t abytes, bbytes, cbytes, pad_;
 };
 
-__device__ __forceinline__ int64_t ld64(const char* p, int64_t idx, int bytes)
-{
-    return bytes == 4 ? (int64_t)((const int32_t*)p)[idx] : ((const int64_t*)p)[idx];
-}
-
 __device__ __forceinline__ void node4(int64_t (&v)[4], const int64_t (&x)[4], const QTreeTable* __restrict__ t, int l)
 {
 #pragma unroll
     for (int o = 0; o < 4; ++o) v[o] = x[o] + v[o];   // x = the parked LEFT child, v = the arriving right child
     qg_step_all<int64_t, 4>(v, t->level_add[0][l].q);
 }
+#define NODE64(S, i, L) node4(v, S[i], tab, L)
 
 template <int MAXL>
 __global__ __launch_bounds__(256) void k_tree64(QTree64Args g)
@@ -62,8 +60,8 @@ __global__ __launch_bounds__(256) void k_tree64(QTree64Args g)
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const int idx = tid + 256 * c, r = idx >> 5, kk = idx & 31;
-            sA[r][kk] = (m0 + r < g.M) ? ld64(g.A, (m0 + r) * g.K + k0 + kk, g.abytes) : 0;
-            sB[r][kk] = (n0 + r < g.N) ? ld64(g.B, (n0 + r) * g.K + k0 + kk, g.bbytes) : 0;
+            sA[r][kk] = (m0 + r < g.M) ? qg_load_c(g.A, (m0 + r) * g.K + k0 + kk, g.abytes) : 0;
+            sB[r][kk] = (n0 + r < g.N) ? qg_load_c(g.B, (n0 + r) * g.K + k0 + kk, g.bbytes) : 0;
         }
         __syncthreads();
 #pragma unroll 1
@@ -75,46 +73,10 @@ __global__ __launch_bounds__(256) void k_tree64(QTree64Args g)
                 v[0] = a0 * b0; v[1] = a0 * b1; v[2] = a1 * b0; v[3] = a1 * b1;
                 qg_step_all<int64_t, 4>(v, tab->mul[0].q);
                 // lower four levels: binary counter on the compile-time leaf index
-                if ((kk & 1) == 0) {
-#pragma unroll
-                    for (int o = 0; o < 4; ++o) low[0][o] = v[o];
-                } else {
-                    node4(v, low[0], tab, 0);
-                    if ((kk & 2) == 0) {
-#pragma unroll
-                        for (int o = 0; o < 4; ++o) low[1][o] = v[o];
-                    } else {
-                        node4(v, low[1], tab, 1);
-                        if ((kk & 4) == 0) {
-#pragma unroll
-                            for (int o = 0; o < 4; ++o) low[2][o] = v[o];
-                        } else {
-                            node4(v, low[2], tab, 2);
-                            if ((kk & 8) == 0) {
-#pragma unroll
-                                for (int o = 0; o < 4; ++o) low[3][o] = v[o];
-                            } else {
-                                node4(v, low[3], tab, 3);
-                            }
-                        }
-                    }
-                }
+                QG_TREE_LOW(kk, low, v, QG_TREE_PARK, NODE64);
             }
             // v = the partial result of one 16-leaf block (an element of list 4): carry it up
-            const unsigned idx = (unsigned)((k0 >> 4) + kb);
-            bool parked = false;   // wave-uniform
-#pragma unroll
-            for (int u = 0; u < MAXL - 4; ++u) {
-                if (!parked && 4 + u < nl) {
-                    if (((idx >> u) & 1u) == 0) {
-#pragma unroll
-                        for (int o = 0; o < 4; ++o) up[u][o] = v[o];
-                        parked = true;
-                    } else {
-                        node4(v, up[u], tab, 4 + u);
-                    }
-                }
-            }
+            QG_TREE_UP(MAXL, (k0 >> 4) + kb, nl, up, v, QG_TREE_PARK, NODE64);
         }
     }
     qg_step_all<int64_t, 4>(v, tab->c_cvt[0]);
@@ -123,15 +85,7 @@ __global__ __launch_bounds__(256) void k_tree64(QTree64Args g)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int64_t m = m0 + ty * 2 + i, n = n0 + tx * 2 + j;
-            if (m < g.M && n < g.N) {
-                const int64_t idx = m * g.N + n, r = v[i * 2 + j];
-                switch (g.cbytes) {
-                case 1: ((int8_t*)g.C)[idx] = (int8_t)r; break;
-                case 2: ((int16_t*)g.C)[idx] = (int16_t)r; break;
-                case 4: ((int32_t*)g.C)[idx] = (int32_t)r; break;
-                default: ((int64_t*)g.C)[idx] = r; break;
-                }
-            }
+            if (m < g.M && n < g.N) qg_store_c(g.C, m * g.N + n, g.cbytes, v[i * 2 + j]);
         }
 }
 
@@ -140,12 +94,9 @@ __global__ __launch_bounds__(256) void k_tree64(QTree64Args g)
 hipError_t qg_launch_tree64(const QTreeTable* dev_table, int n_levels, const void* A, const void* B, void* C, int64_t M, int64_t N,
                             int64_t K, int abytes, int bbytes, int cbytes, hipStream_t st)
 {
-    if (K % KC != 0 || (K & (K - 1)) || n_levels < 5 || n_levels > 16) return hipErrorInvalidValue;
+    int64_t blocks;
+    if (K & (K - 1)) return hipErrorInvalidValue;
+    if (const hipError_t e = qg_tree_blocks(M, N, K, n_levels, TMB, TNB, blocks); e != hipSuccess || blocks == 0) return e;
     QTree64Args g{dev_table, (const char*)A, (const char*)B, (char*)C, M, N, K, abytes, bbytes, cbytes, 0};
-    const int64_t blocks = ((M + TMB - 1) / TMB) * ((N + TNB - 1) / TNB);
-    if (blocks <= 0) return hipSuccess;
-    if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
-    if (n_levels <= 12) hipLaunchKernelGGL((k_tree64<12>), dim3((unsigned)blocks), dim3(256), 0, st, g);
-    else hipLaunchKernelGGL((k_tree64<16>), dim3((unsigned)blocks), dim3(256), 0, st, g);
-    return hipGetLastError();
+    return qg_launch_by_levels(n_levels, k_tree64<12>, k_tree64<16>, blocks, st, g);
 }

@@ -24,10 +24,12 @@
 #include "qg_kernels.h"
 #include "qg_step_all.h"
 #include "qg_tile_walk.h"
+#include "qg_tree_counter.h"
+#include "qg_tree_io.h"
 
 namespace {
 
-constexpr int KC = 32;
+constexpr int KC = QG_TREE_KC;
 constexpr int TMB = 32, TNB = 32;  // 16x16 threads x (2x2)
 constexpr int PITCH = KC + 4;
 
@@ -250,6 +252,22 @@ __global__ __launch_bounds__(256, ((cplx_dense_waves<MODE, TF>) ? (MAXL == 12 ? 
     for (int p = 0; p < 2; ++p)
 #pragma unroll
         for (int o = 0; o < 4; ++o) v[p][o] = 0;
+    // the node of level L of both parts on slot i of S (low or up) and v: the counter's node operation (qg_tree_counter.h).
+    // QCF_LJ: RE / IM come from one saturating operation on clean values: 2^31 - 1 or clean.  One more saturating add keeps
+    // floor(v / 2^s) right; before the next one (after the even levels) the low bits are cleared
+#define NODE_CPLX(S, i, L)                                                                                                  \
+    do {                                                                                                                    \
+        if constexpr (MODE == QCF_LJ) {                                                                                     \
+            _Pragma("unroll") for (int o_ = 0; o_ < 4; ++o_) { v[0][o_] = sat_add(S[0][i][o_], v[0][o_]); v[1][o_] = sat_add(S[1][i][o_], v[1][o_]); } \
+            if (((L) & 1) == 0) { jmask4(v[0]); jmask4(v[1]); }                                                             \
+        } else if constexpr (MODE == QCF_UNIFORM) {                                                                         \
+            _Pragma("unroll") for (int o_ = 0; o_ < 4; ++o_) { v[0][o_] += S[0][i][o_]; v[1][o_] += S[1][i][o_]; }          \
+            uclamp4(v[0]);                                                                                                  \
+            uclamp4(v[1]);                                                                                                  \
+        } else {                                                                                                            \
+            op_node2<MODE, 4>(v[0], v[1], S[0][i], S[1][i], tab, L);                                                        \
+        }                                                                                                                   \
+    } while (0)
 
     for (int64_t k0 = 0; k0 < g.K; k0 += KC) {
         __syncthreads();
@@ -447,63 +465,13 @@ __global__ __launch_bounds__(256, ((cplx_dense_waves<MODE, TF>) ? (MAXL == 12 ? 
                         }
                     }
                     // ---- lower four levels (compile-time leaf index)
-                    {
-                        bool parked_low = false;
-#pragma unroll
-                        for (int l = 0; l < 4; ++l) {
-                            if (!parked_low) {
-                                if (((kk >> l) & 1) == 0) {
-#pragma unroll
-                                    for (int p = 0; p < 2; ++p)
-#pragma unroll
-                                        for (int o = 0; o < 4; ++o) low[p][l][o] = v[p][o];
-                                    parked_low = true;
-                                } else if constexpr (MODE == QCF_LJ) {
-                                    // RE / IM come from one saturating operation on clean values: 2^31 - 1 or clean.  One more
-                                    // saturating add keeps floor(v / 2^s) right; before the next one the low bits are cleared
-#pragma unroll
-                                    for (int o = 0; o < 4; ++o) { v[0][o] = sat_add(low[0][l][o], v[0][o]); v[1][o] = sat_add(low[1][l][o], v[1][o]); }
-                                    if ((l & 1) == 0) { jmask4(v[0]); jmask4(v[1]); }
-                                } else if constexpr (MODE == QCF_UNIFORM) {
-#pragma unroll
-                                    for (int o = 0; o < 4; ++o) { v[0][o] += low[0][l][o]; v[1][o] += low[1][l][o]; }
-                                    uclamp4(v[0]);
-                                    uclamp4(v[1]);
-                                } else {
-                                    op_node2<MODE, 4>(v[0], v[1], low[0][l], low[1][l], tab, l);
-                                }
-                            }
-                        }
-                    }
+                    QG_TREE_LOW_LOOP(kk, low, v, QG_TREE_PARK2, NODE_CPLX);
                 }
             }
-            const unsigned idx = (unsigned)((k0 >> 4) + kb);
-            bool parked = false;
-#pragma unroll
-            for (int u = 0; u < MAXL - 4; ++u) {
-                if (!parked && 4 + u < nl) {
-                    if (((idx >> u) & 1u) == 0) {
-#pragma unroll
-                        for (int p = 0; p < 2; ++p)
-#pragma unroll
-                            for (int o = 0; o < 4; ++o) up[p][u][o] = v[p][o];
-                        parked = true;
-                    } else if constexpr (MODE == QCF_LJ) {
-#pragma unroll
-                        for (int o = 0; o < 4; ++o) { v[0][o] = sat_add(up[0][u][o], v[0][o]); v[1][o] = sat_add(up[1][u][o], v[1][o]); }
-                        if ((u & 1) == 0) { jmask4(v[0]); jmask4(v[1]); }   // (level 4 + u: the even ones)
-                    } else if constexpr (MODE == QCF_UNIFORM) {
-#pragma unroll
-                        for (int o = 0; o < 4; ++o) { v[0][o] += up[0][u][o]; v[1][o] += up[1][u][o]; }
-                        uclamp4(v[0]);
-                        uclamp4(v[1]);
-                    } else {
-                        op_node2<MODE, 4>(v[0], v[1], up[0][u], up[1][u], tab, 4 + u);
-                    }
-                }
-            }
+            QG_TREE_UP(MAXL, (k0 >> 4) + kb, nl, up, v, QG_TREE_PARK2, NODE_CPLX);
         }
     }
+#undef NODE_CPLX
     if constexpr (MODE == QCF_LJ) {   // floor(v / 2^s): the value
 #pragma unroll
         for (int o = 0; o < 4; ++o) { v[0][o] >>= j_s; v[1][o] >>= j_s; }
@@ -517,16 +485,7 @@ __global__ __launch_bounds__(256, ((cplx_dense_waves<MODE, TF>) ? (MAXL == 12 ? 
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const int64_t m = m0 + ty * 2 + i, n = n0 + tx + 16 * j;
-                if (m < g.M && n < g.N) {
-                    const int64_t idx = ((int64_t)p * g.M + m) * g.N + n;
-                    const int r = v[p][i * 2 + j];
-                    switch (g.cbytes) {
-                    case 1: ((int8_t*)g.C)[idx] = (int8_t)r; break;
-                    case 2: ((int16_t*)g.C)[idx] = (int16_t)r; break;
-                    case 4: ((int32_t*)g.C)[idx] = r; break;
-                    default: ((int64_t*)g.C)[idx] = (int64_t)r; break;
-                    }
-                }
+                if (m < g.M && n < g.N) qg_store_c(g.C, ((int64_t)p * g.M + m) * g.N + n, g.cbytes, v[p][i * 2 + j]);
             }
 }
 
@@ -572,9 +531,9 @@ __global__ __launch_bounds__(256, 3) void k_tree_cplx_pk16(QTreeCplxArgs g)
     for (int p = 0; p < 2; ++p)
 #pragma unroll
         for (int o = 0; o < 4; ++o) v[p][o] = 0;
-#define NODE16C(X0, X1, L)                                                                                         \
+#define NODE16C(S, i, L)                                                                                           \
     do {                                                                                                           \
-        _Pragma("unroll") for (int o_ = 0; o_ < 4; ++o_) { v[0][o_] = pk_add_sat(X0[o_], v[0][o_]); v[1][o_] = pk_add_sat(X1[o_], v[1][o_]); } \
+        _Pragma("unroll") for (int o_ = 0; o_ < 4; ++o_) { v[0][o_] = pk_add_sat(S[0][i][o_], v[0][o_]); v[1][o_] = pk_add_sat(S[1][i][o_], v[1][o_]); } \
         if (((L) & 1) == 0) { _Pragma("unroll") for (int o_ = 0; o_ < 4; ++o_) { v[0][o_] &= mask2; v[1][o_] &= mask2; } }                   \
     } while (0)
 
@@ -654,12 +613,12 @@ __global__ __launch_bounds__(256, 3) void k_tree_cplx_pk16(QTreeCplxArgs g)
                     const int kk = kq * 4 + e;
                     int bv[NP];
 #pragma unroll
-                    for (int p = 0; p < NP; ++p) bv[p] = e == 0 ? b4[p].x : e == 1 ? b4[p].y : e == 2 ? b4[p].z : b4[p].w;
+                    for (int p = 0; p < NP; ++p) bv[p] = QG_LANE(b4[p], e);
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         int av[NP];
 #pragma unroll
-                        for (int p = 0; p < NP; ++p) av[p] = e < 2 ? a2[p][i].x : a2[p][i].y;
+                        for (int p = 0; p < NP; ++p) av[p] = QG_LANE2(a2[p][i], e >> 1);
                         if constexpr (TF) {   // A = (a+b) c, B = (c+d) b, C = (b-a) d; re = A - B, im = B - C
                             const int PA = ((e & 1) ? pk_mad_sat<1>(av[0], bv[0], t2[0]) : pk_mad_sat<0>(av[0], bv[0], t2[0])) & pm2[0];
                             const int PB = ((e & 1) ? pk_mad_sat<1>(av[1], bv[1], t2[1]) : pk_mad_sat<0>(av[1], bv[1], t2[1])) & pm2[1];
@@ -675,39 +634,10 @@ __global__ __launch_bounds__(256, 3) void k_tree_cplx_pk16(QTreeCplxArgs g)
                             v[1][i] = pk_add_sat(ad, bc);
                         }
                     }
-                    bool parked_low = false;
-#pragma unroll
-                    for (int l = 0; l < 4; ++l) {
-                        if (!parked_low) {
-                            if (((kk >> l) & 1) == 0) {
-#pragma unroll
-                                for (int p = 0; p < 2; ++p)
-#pragma unroll
-                                    for (int o = 0; o < 4; ++o) low[p][l][o] = v[p][o];
-                                parked_low = true;
-                            } else {
-                                NODE16C(low[0][l], low[1][l], l);
-                            }
-                        }
-                    }
+                    QG_TREE_LOW_LOOP(kk, low, v, QG_TREE_PARK2, NODE16C);
                 }
             }
-            const unsigned idx = (unsigned)((k0 >> 4) + kb);
-            bool parked = false;
-#pragma unroll
-            for (int u = 0; u < MAXL - 4; ++u) {
-                if (!parked && 4 + u < nl) {
-                    if (((idx >> u) & 1u) == 0) {
-#pragma unroll
-                        for (int p = 0; p < 2; ++p)
-#pragma unroll
-                            for (int o = 0; o < 4; ++o) up[p][u][o] = v[p][o];
-                        parked = true;
-                    } else {
-                        NODE16C(up[0][u], up[1][u], 4 + u);
-                    }
-                }
-            }
+            QG_TREE_UP(MAXL, (k0 >> 4) + kb, nl, up, v, QG_TREE_PARK2, NODE16C);
         }
     }
 #undef NODE16C
@@ -717,8 +647,8 @@ __global__ __launch_bounds__(256, 3) void k_tree_cplx_pk16(QTreeCplxArgs g)
         int r8[8];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            r8[i * 2 + 0] = ((int)((unsigned)v[p][i] << 16) >> 16) >> s16;
-            r8[i * 2 + 1] = (v[p][i] >> 16) >> s16;
+            r8[i * 2 + 0] = qg_pk16_root<false>(v[p][i], 0, s16);
+            r8[i * 2 + 1] = qg_pk16_root<false>(v[p][i], 1, s16);
         }
         qg_step_all<int, 8>(r8, tab->c_cvt[p]);
 #pragma unroll
@@ -726,16 +656,7 @@ __global__ __launch_bounds__(256, 3) void k_tree_cplx_pk16(QTreeCplxArgs g)
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const int64_t m = m0 + ty * 4 + i, n = n0 + tx + 16 * j;
-                if (m < g.M && n < g.N) {
-                    const int64_t idx = ((int64_t)p * g.M + m) * g.N + n;
-                    const int r = r8[i * 2 + j];
-                    switch (g.cbytes) {
-                    case 1: ((int8_t*)g.C)[idx] = (int8_t)r; break;
-                    case 2: ((int16_t*)g.C)[idx] = (int16_t)r; break;
-                    case 4: ((int32_t*)g.C)[idx] = r; break;
-                    default: ((int64_t*)g.C)[idx] = (int64_t)r; break;
-                    }
-                }
+                if (m < g.M && n < g.N) qg_store_c(g.C, ((int64_t)p * g.M + m) * g.N + n, g.cbytes, r8[i * 2 + j]);
             }
     }
 }
@@ -743,51 +664,34 @@ __global__ __launch_bounds__(256, 3) void k_tree_cplx_pk16(QTreeCplxArgs g)
 } // namespace
 
 template <int MODE>
-static hipError_t launch_cplx(int n_levels, int tf, dim3 grid, hipStream_t st, const QTreeCplxArgs& g)
+static hipError_t launch_cplx(int n_levels, int tf, int64_t blocks, hipStream_t st, const QTreeCplxArgs& g)
 {
-    if (tf) {
-        if (n_levels <= 12) hipLaunchKernelGGL((k_tree_cplx<12, MODE, true>), grid, dim3(256), 0, st, g);
-        else hipLaunchKernelGGL((k_tree_cplx<16, MODE, true>), grid, dim3(256), 0, st, g);
-    } else {
-        if (n_levels <= 12) hipLaunchKernelGGL((k_tree_cplx<12, MODE, false>), grid, dim3(256), 0, st, g);
-        else hipLaunchKernelGGL((k_tree_cplx<16, MODE, false>), grid, dim3(256), 0, st, g);
-    }
-    return hipGetLastError();
+    return tf ? qg_launch_by_levels(n_levels, k_tree_cplx<12, MODE, true>, k_tree_cplx<16, MODE, true>, blocks, st, g)
+              : qg_launch_by_levels(n_levels, k_tree_cplx<12, MODE, false>, k_tree_cplx<16, MODE, false>, blocks, st, g);
 }
 
 hipError_t qg_launch_tree_cplx_fast(const QTreeTable* dev_table, int n_levels, QCplxForm form, int tf, const void* A, const void* B, void* C, int64_t M,
                                     int64_t N, int64_t K, int cbytes, hipStream_t st)
 {
-    if (K % KC != 0 || n_levels < 5 || n_levels > 16) return hipErrorInvalidValue;
+    int64_t blocks;   // (the packed form's tiles have 64 rows)
+    if (const hipError_t e = qg_tree_blocks(M, N, K, n_levels, form == QCF_PK16 ? TM16 : TMB, TNB, blocks); e != hipSuccess || blocks == 0) return e;
     QTreeCplxArgs g{dev_table, (const int32_t*)A, (const int32_t*)B, (char*)C, M, N, K, cbytes};
-    const int64_t blocks = ((M + TMB - 1) / TMB) * ((N + TNB - 1) / TNB);
-    if (blocks <= 0) return hipSuccess;
-    if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)blocks);
     switch (form) {
-    case QCF_RUNTIME: return launch_cplx<QCF_RUNTIME>(n_levels, tf, grid, st, g);
-    case QCF_TABLE: return launch_cplx<QCF_TABLE>(n_levels, tf, grid, st, g);
-    case QCF_COMPACT: return launch_cplx<QCF_COMPACT>(n_levels, tf, grid, st, g);
-    case QCF_KINDS: return launch_cplx<QCF_KINDS>(n_levels, tf, grid, st, g);
-    case QCF_PK16: {
-        const dim3 grid16((unsigned)(((M + TM16 - 1) / TM16) * ((N + TNB - 1) / TNB)));
-        if (tf) {
-            if (n_levels <= 12) hipLaunchKernelGGL((k_tree_cplx_pk16<12, true>), grid16, dim3(256), 0, st, g);
-            else hipLaunchKernelGGL((k_tree_cplx_pk16<16, true>), grid16, dim3(256), 0, st, g);
-        } else {
-            if (n_levels <= 12) hipLaunchKernelGGL((k_tree_cplx_pk16<12, false>), grid16, dim3(256), 0, st, g);
-            else hipLaunchKernelGGL((k_tree_cplx_pk16<16, false>), grid16, dim3(256), 0, st, g);
-        }
-        return hipGetLastError();
-    }
-    case QCF_LJ: return launch_cplx<QCF_LJ>(n_levels, tf, grid, st, g);
-    case QCF_UNIFORM: return launch_cplx<QCF_UNIFORM>(n_levels, tf, grid, st, g);
-    case QCF_KINDS_R: return launch_cplx<QCF_KINDS_R>(n_levels, tf, grid, st, g);
-    case QCF_KINDS_Z: return launch_cplx<QCF_KINDS_Z>(n_levels, tf, grid, st, g);
-    case QCF_KINDS_RZ: return launch_cplx<QCF_KINDS_RZ>(n_levels, tf, grid, st, g);
-    case QCF_KINDS_W: return launch_cplx<QCF_KINDS_W>(n_levels, tf, grid, st, g);
-    case QCF_KINDS_RW: return launch_cplx<QCF_KINDS_RW>(n_levels, tf, grid, st, g);
-    case QCF_KINDS_ALL: return launch_cplx<QCF_KINDS_ALL>(n_levels, tf, grid, st, g);
+    case QCF_RUNTIME: return launch_cplx<QCF_RUNTIME>(n_levels, tf, blocks, st, g);
+    case QCF_TABLE: return launch_cplx<QCF_TABLE>(n_levels, tf, blocks, st, g);
+    case QCF_COMPACT: return launch_cplx<QCF_COMPACT>(n_levels, tf, blocks, st, g);
+    case QCF_KINDS: return launch_cplx<QCF_KINDS>(n_levels, tf, blocks, st, g);
+    case QCF_PK16:
+        return tf ? qg_launch_by_levels(n_levels, k_tree_cplx_pk16<12, true>, k_tree_cplx_pk16<16, true>, blocks, st, g)
+                  : qg_launch_by_levels(n_levels, k_tree_cplx_pk16<12, false>, k_tree_cplx_pk16<16, false>, blocks, st, g);
+    case QCF_LJ: return launch_cplx<QCF_LJ>(n_levels, tf, blocks, st, g);
+    case QCF_UNIFORM: return launch_cplx<QCF_UNIFORM>(n_levels, tf, blocks, st, g);
+    case QCF_KINDS_R: return launch_cplx<QCF_KINDS_R>(n_levels, tf, blocks, st, g);
+    case QCF_KINDS_Z: return launch_cplx<QCF_KINDS_Z>(n_levels, tf, blocks, st, g);
+    case QCF_KINDS_RZ: return launch_cplx<QCF_KINDS_RZ>(n_levels, tf, blocks, st, g);
+    case QCF_KINDS_W: return launch_cplx<QCF_KINDS_W>(n_levels, tf, blocks, st, g);
+    case QCF_KINDS_RW: return launch_cplx<QCF_KINDS_RW>(n_levels, tf, blocks, st, g);
+    case QCF_KINDS_ALL: return launch_cplx<QCF_KINDS_ALL>(n_levels, tf, blocks, st, g);
     }
     return hipErrorInvalidValue;
 }

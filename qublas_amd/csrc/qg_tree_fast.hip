@@ -20,97 +20,18 @@
 #include "qg_fix.h"
 #include "qg_forms.h"
 #include "qg_kernels.h"
+#include "qg_step_all.h"
 #include "qg_tile_walk.h"
+#include "qg_tree_counter.h"
+#include "qg_tree_io.h"
 
 namespace {
 
-constexpr int KC = 32;      // k-chunk staged in LDS
+constexpr int KC = QG_TREE_KC;   // k-chunk staged in LDS
 constexpr int TMB = 64;     // rows of C per block   (16 thread rows x 4)
 constexpr int TNB = 32;     // columns of C per block (16 thread cols x 2)
 constexpr int NOUT = 8;
 constexpr int PITCH = KC + 4;
-
-// round (d > 0) NOUT values in place; x = h*2^d + l is given as (h, l) when SPLIT, else as v itself
-__device__ __forceinline__ void round_all(int (&v)[NOUT], int d, int Q)
-{
-    if (d == 0) return;
-    if (d < 0) {
-#pragma unroll
-        for (int o = 0; o < NOUT; ++o) v[o] = (int)((unsigned)v[o] << (-d));
-        return;
-    }
-    const int mask = (1 << d) - 1, t = 1 << (d - 1);
-    switch (Q) {
-    case QG_TRN_TCPL:
-#pragma unroll
-        for (int o = 0; o < NOUT; ++o) v[o] >>= d;
-        break;
-    case QG_TRN_SMGN:
-#pragma unroll
-        for (int o = 0; o < NOUT; ++o) v[o] = (v[o] >> d) + ((v[o] < 0) & ((v[o] & mask) != 0));
-        break;
-    case QG_RND_POS_INF:
-#pragma unroll
-        for (int o = 0; o < NOUT; ++o) v[o] = (v[o] >> d) + ((v[o] & mask) >= t);
-        break;
-    case QG_RND_NEG_INF:
-#pragma unroll
-        for (int o = 0; o < NOUT; ++o) v[o] = (v[o] >> d) + ((v[o] & mask) > t);
-        break;
-    case QG_RND_ZERO:
-#pragma unroll
-        for (int o = 0; o < NOUT; ++o) { const int l = v[o] & mask; v[o] = (v[o] >> d) + ((l > t) | ((l == t) & (v[o] < 0))); }
-        break;
-    case QG_RND_INF:
-#pragma unroll
-        for (int o = 0; o < NOUT; ++o) { const int l = v[o] & mask; v[o] = (v[o] >> d) + ((l > t) | ((l == t) & (v[o] > 0))); }
-        break;
-    default: // RND::CONV
-#pragma unroll
-        for (int o = 0; o < NOUT; ++o) { const int l = v[o] & mask, h = v[o] >> d; v[o] = h + ((l > t) | ((l == t) & (h & 1))); }
-        break;
-    }
-}
-
-__device__ __forceinline__ void overflow_all(int (&v)[NOUT], const QStep& s)
-{
-    const int lo = (int)s.lo, hi = (int)s.hi;
-    switch (s.O) {
-    case QG_SAT_TCPL:
-#pragma unroll
-        for (int o = 0; o < NOUT; ++o) v[o] = qg_clamp_i32(v[o], lo, hi);
-        break;
-    case QG_SAT_ZERO: {
-        const unsigned span = (unsigned)(hi - lo);
-#pragma unroll
-        for (int o = 0; o < NOUT; ++o) v[o] = ((unsigned)(v[o] - lo) > span) ? 0 : v[o];
-        break;
-    }
-    case QG_SAT_SMGN: {
-        const int l2 = s.S ? -hi : 0;
-#pragma unroll
-        for (int o = 0; o < NOUT; ++o) v[o] = qg_clamp_i32(v[o], l2, hi);
-        break;
-    }
-    default: // WRP::TCPL
-        if (s.S) {
-            const int sh = 31 - s.W;
-#pragma unroll
-            for (int o = 0; o < NOUT; ++o) v[o] = (int)((unsigned)v[o] << sh) >> sh;
-        } else {
-#pragma unroll
-            for (int o = 0; o < NOUT; ++o) v[o] &= hi;
-        }
-        break;
-    }
-}
-
-__device__ __forceinline__ void step_all(int (&v)[NOUT], const QStep& s)
-{
-    if (s.identity) return;
-    round_all(v, s.d, s.Q);
-    overflow_all(v, s);
-}
 
 // node of level l: both children have the level's input format (no alignment shift for real GEMMs)
 template <int MODE>
@@ -151,8 +72,8 @@ __device__ __forceinline__ void node_all(int (&v)[NOUT], const int (&x)[NOUT], c
 {
 #pragma unroll
     for (int o = 0; o < NOUT; ++o) v[o] = x[o] + v[o];
-    step_all(v, t->level_add[0][l].q);
-    step_all(v, t->level_cvt[0][l]);
+    qg_step_all<int, NOUT>(v, t->level_add[0][l].q);
+    qg_step_all<int, NOUT>(v, t->level_cvt[0][l]);
 }
 
 // SPLIT leaf rounding from (h, l): x = h*2^s + l, 0 <= l < 2^s
@@ -202,19 +123,20 @@ struct QTreeFastArgs {
 // as literally configured), whose leaf needs no separate rounding step.  QTF_LJ: the operands are staged with the factors that
 // justify the product (rounding addend included): 3.3 instead of 5 vector instructions per MAC, and no split product (the
 // hardware saturates from the full 48-bit product).
-#define NODE(X, L)                                                         \
+// the node of level L on slot i of S (low or up) and v: QG_TREE_LOW / QG_TREE_UP's node operation (qg_tree_counter.h)
+#define NODE(S, i, L)                                                      \
     do {                                                                   \
         if (MODE == QTF_WORD_WRAP) {                                       \
-            _Pragma("unroll") for (int o_ = 0; o_ < NOUT; ++o_) v[o_] = (int)((unsigned)X[o_] + (unsigned)v[o_]);   \
+            _Pragma("unroll") for (int o_ = 0; o_ < NOUT; ++o_) v[o_] = (int)((unsigned)S[i][o_] + (unsigned)v[o_]);   \
         } else if (W32) {                                                  \
-            _Pragma("unroll") for (int o_ = 0; o_ < NOUT; ++o_) v[o_] = sat_add(X[o_], v[o_]);   \
+            _Pragma("unroll") for (int o_ = 0; o_ < NOUT; ++o_) v[o_] = sat_add(S[i][o_], v[o_]);   \
             if (WJ && ((L) & 1)) { _Pragma("unroll") for (int o_ = 0; o_ < NOUT; ++o_) v[o_] &= w_mask; }   \
         } else if (LJ) {                                                   \
-            _Pragma("unroll") for (int o_ = 0; o_ < NOUT; ++o_) v[o_] = MODE == QTF_LJ_U ? usat_add(X[o_], v[o_]) : sat_add(X[o_], v[o_]);   \
+            _Pragma("unroll") for (int o_ = 0; o_ < NOUT; ++o_) v[o_] = MODE == QTF_LJ_U ? usat_add(S[i][o_], v[o_]) : sat_add(S[i][o_], v[o_]);   \
             if ((L) & 1) { _Pragma("unroll") for (int o_ = 0; o_ < NOUT; ++o_) v[o_] &= lj_mask; }               \
-        } else if (MODE >= QTF_REC_CLAMP) { if ((L) < 4) node_fx_rec<MODE>(v, X, flow[(L) < 4 ? (L) : 0]); else node_fx<MODE>(v, X, tab, L); } \
-        else if (MODE != QTF_RUNTIME) node_fixed<MODE>(v, X, flo, fhi, bias, span);   \
-        else node_all(v, X, tab, L);                                       \
+        } else if (MODE >= QTF_REC_CLAMP) { if ((L) < 4) node_fx_rec<MODE>(v, S[i], flow[(L) < 4 ? (L) : 0]); else node_fx<MODE>(v, S[i], tab, L); } \
+        else if (MODE != QTF_RUNTIME) node_fixed<MODE>(v, S[i], flo, fhi, bias, span);   \
+        else node_all(v, S[i], tab, L);                                    \
     } while (0)
 
 template <bool SPLIT, bool MUL24, int MAXL, int MODE>
@@ -315,11 +237,11 @@ __global__ __launch_bounds__(256) void k_tree_fast(QTreeFastArgs g)
                     const int kk = kq * 4 + e; // compile-time leaf index inside the 16-leaf block
                     int av[4], bhv[2], blv[2];
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) av[i] = e == 0 ? a4[i].x : e == 1 ? a4[i].y : e == 2 ? a4[i].z : a4[i].w;
+                    for (int i = 0; i < 4; ++i) av[i] = QG_LANE(a4[i], e);
 #pragma unroll
                     for (int j = 0; j < 2; ++j) {
-                        bhv[j] = e == 0 ? bh4[j].x : e == 1 ? bh4[j].y : e == 2 ? bh4[j].z : bh4[j].w;
-                        if (SPLIT) blv[j] = e == 0 ? bl4[j].x : e == 1 ? bl4[j].y : e == 2 ? bl4[j].z : bl4[j].w;
+                        bhv[j] = QG_LANE(bh4[j], e);
+                        if (SPLIT) blv[j] = QG_LANE(bl4[j], e);
                     }
                     // ---- leaves: 8 quantised products
                     if (MODE == QTF_WORD_WRAP) {
@@ -446,57 +368,21 @@ __global__ __launch_bounds__(256) void k_tree_fast(QTreeFastArgs g)
                                 lw[i * 2 + j] = t & smask;
                             }
                         round_split_all(v, lw, s, pstep.Q);
-                        overflow_all(v, pstep);
+                        qg_overflow_all<int, NOUT>(v, pstep);
                     } else {
 #pragma unroll
                         for (int i = 0; i < 4; ++i)
 #pragma unroll
                             for (int j = 0; j < 2; ++j) v[i * 2 + j] = MUL24 ? __mul24(av[i], bhv[j]) : av[i] * bhv[j];
-                        round_all(v, pstep.d, pstep.Q);
-                        overflow_all(v, pstep);
+                        qg_round_all<int, NOUT>(v, pstep.d, pstep.Q);
+                        qg_overflow_all<int, NOUT>(v, pstep);
                     }
                     // ---- lower four levels: binary counter on the compile-time index kk
-                    if ((kk & 1) == 0) {
-#pragma unroll
-                        for (int o = 0; o < NOUT; ++o) low[0][o] = v[o];
-                    } else {
-                        NODE(low[0], 0);
-                        if ((kk & 2) == 0) {
-#pragma unroll
-                            for (int o = 0; o < NOUT; ++o) low[1][o] = v[o];
-                        } else {
-                            NODE(low[1], 1);
-                            if ((kk & 4) == 0) {
-#pragma unroll
-                                for (int o = 0; o < NOUT; ++o) low[2][o] = v[o];
-                            } else {
-                                NODE(low[2], 2);
-                                if ((kk & 8) == 0) {
-#pragma unroll
-                                    for (int o = 0; o < NOUT; ++o) low[3][o] = v[o];
-                                } else {
-                                    NODE(low[3], 3);
-                                }
-                            }
-                        }
-                    }
+                    QG_TREE_LOW(kk, low, v, QG_TREE_PARK, NODE);
                 }
             }
             // ---- upper levels: v is the partial sum of one 16-leaf block (an element of list 4)
-            const unsigned idx = (unsigned)((k0 >> 4) + kb);
-            bool parked = false; // wave-uniform: the carry stopped at a free slot
-#pragma unroll
-            for (int u = 0; u < MAXL - 4; ++u) {
-                if (!parked && 4 + u < nl) {
-                    if (((idx >> u) & 1u) == 0) {
-#pragma unroll
-                        for (int o = 0; o < NOUT; ++o) up[u][o] = v[o];
-                        parked = true;
-                    } else {
-                        NODE(up[u], 4 + u);
-                    }
-                }
-            }
+            QG_TREE_UP(MAXL, (k0 >> 4) + kb, nl, up, v, QG_TREE_PARK, NODE);
         }
     }
     // after the last block the counter has carried through every level: v holds the root
@@ -516,22 +402,13 @@ __global__ __launch_bounds__(256) void k_tree_fast(QTreeFastArgs g)
 #pragma unroll
         for (int o = 0; o < NOUT; ++o) v[o] >>= w_j;
     }
-    step_all(v, tab->c_cvt[0]);
+    qg_step_all<int, NOUT>(v, tab->c_cvt[0]);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int64_t m = m0 + ty * 4 + i, n = n0 + tx + 16 * j;
-            if (m < g.M && n < g.N) {
-                const int64_t idx = m * g.N + n;
-                const int r = v[i * 2 + j];
-                switch (g.cbytes) {
-                case 1: ((int8_t*)g.C)[idx] = (int8_t)r; break;
-                case 2: ((int16_t*)g.C)[idx] = (int16_t)r; break;
-                case 4: ((int32_t*)g.C)[idx] = r; break;
-                default: ((int64_t*)g.C)[idx] = (int64_t)r; break;
-                }
-            }
+            if (m < g.M && n < g.N) qg_store_c(g.C, m * g.N + n, g.cbytes, v[i * 2 + j]);
         }
 }
 
@@ -548,9 +425,9 @@ constexpr int PKP = 18;   // dwords per sA16 row (16 + 2: 8-byte reads stay alig
 // columns and drops the low ones — for a 16-bit format that IS the rounding's floor and no low bits exist to be cleared anywhere
 // (2.0 vector instructions per MAC); narrower formats clear the rest of the fraction with one v_and per pair and then follow the
 // packed form's rule (2.7 per MAC) — where QTF_LJ spends 3.5.
-#define NODE16(X, L)                                                                                     \
+#define NODE16(S, i, L)                                                                                  \
     do {                                                                                                 \
-        _Pragma("unroll") for (int o_ = 0; o_ < 4; ++o_) v[o_] = UNS ? pk_add_usat(X[o_], v[o_]) : pk_add_sat(X[o_], v[o_]);   \
+        _Pragma("unroll") for (int o_ = 0; o_ < 4; ++o_) v[o_] = UNS ? pk_add_usat(S[i][o_], v[o_]) : pk_add_sat(S[i][o_], v[o_]);   \
         if (((L) & 1) && HYB != 2) { _Pragma("unroll") for (int o_ = 0; o_ < 4; ++o_) v[o_] &= mask2; }       \
     } while (0)
 
@@ -637,13 +514,13 @@ __global__ __launch_bounds__(256) void k_tree_pk16(QTreeFastArgs g)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int kk = kq * 4 + e;
-                    const int bv = e == 0 ? b4.x : e == 1 ? b4.y : e == 2 ? b4.z : b4.w;
+                    const int bv = QG_LANE(b4, e);
                     if (HYB) {
-                        const int b0 = e == 0 ? b4h[0].x : e == 1 ? b4h[0].y : e == 2 ? b4h[0].z : b4h[0].w;
-                        const int b1 = e == 0 ? b4h[1].x : e == 1 ? b4h[1].y : e == 2 ? b4h[1].z : b4h[1].w;
+                        const int b0 = QG_LANE(b4h[0], e);
+                        const int b1 = QG_LANE(b4h[1], e);
 #pragma unroll
                         for (int i = 0; i < 4; ++i) {
-                            const int av = e == 0 ? a4[i].x : e == 1 ? a4[i].y : e == 2 ? a4[i].z : a4[i].w;
+                            const int av = QG_LANE(a4[i], e);
                             // the high halves of the two justified products: (column tx, column tx + 16); the dropped halves are the floor
                             v[i] = UNS ? (int)__builtin_amdgcn_perm((unsigned)usat_mad24_vvs(av, b1, t2), (unsigned)usat_mad24_vvs(av, b0, t2), 0x07060302u)
                                        : (int)__builtin_amdgcn_perm((unsigned)sat_mad24_vvs(av, b1, t2), (unsigned)sat_mad24_vvs(av, b0, t2), 0x07060302u);
@@ -652,136 +529,84 @@ __global__ __launch_bounds__(256) void k_tree_pk16(QTreeFastArgs g)
                     } else
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
-                        const int av = e < 2 ? a2[i].x : a2[i].y;
+                        const int av = QG_LANE2(a2[i], e >> 1);
                         v[i] = (UNS ? ((e & 1) ? pk_mad_usat<1>(av, bv, t2) : pk_mad_usat<0>(av, bv, t2)) : ((e & 1) ? pk_mad_sat<1>(av, bv, t2) : pk_mad_sat<0>(av, bv, t2))) & mask2;
                     }
-                    if ((kk & 1) == 0) {
-#pragma unroll
-                        for (int o = 0; o < 4; ++o) low[0][o] = v[o];
-                    } else {
-                        NODE16(low[0], 0);
-                        if ((kk & 2) == 0) {
-#pragma unroll
-                            for (int o = 0; o < 4; ++o) low[1][o] = v[o];
-                        } else {
-                            NODE16(low[1], 1);
-                            if ((kk & 4) == 0) {
-#pragma unroll
-                                for (int o = 0; o < 4; ++o) low[2][o] = v[o];
-                            } else {
-                                NODE16(low[2], 2);
-                                if ((kk & 8) == 0) {
-#pragma unroll
-                                    for (int o = 0; o < 4; ++o) low[3][o] = v[o];
-                                } else {
-                                    NODE16(low[3], 3);
-                                }
-                            }
-                        }
-                    }
+                    QG_TREE_LOW(kk, low, v, QG_TREE_PARK, NODE16);
                 }
             }
-            const unsigned idx = (unsigned)((k0 >> 4) + kb);
-            bool parked = false;
-#pragma unroll
-            for (int u = 0; u < MAXL - 4; ++u) {
-                if (!parked && 4 + u < nl) {
-                    if (((idx >> u) & 1u) == 0) {
-#pragma unroll
-                        for (int o = 0; o < 4; ++o) up[u][o] = v[o];
-                        parked = true;
-                    } else {
-                        NODE16(up[u], 4 + u);
-                    }
-                }
-            }
+            QG_TREE_UP(MAXL, (k0 >> 4) + kb, nl, up, v, QG_TREE_PARK, NODE16);
         }
     }
     // the root: floor(half / 2^s) of each half, then the conversion into C
     int r8[NOUT];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        r8[i * 2 + 0] = UNS ? (int)(((unsigned)v[i] & 0xffffu) >> s16) : ((int)((unsigned)v[i] << 16) >> 16) >> s16;
-        r8[i * 2 + 1] = UNS ? (int)(((unsigned)v[i] >> 16) >> s16) : (v[i] >> 16) >> s16;
+        r8[i * 2 + 0] = qg_pk16_root<UNS>(v[i], 0, s16);
+        r8[i * 2 + 1] = qg_pk16_root<UNS>(v[i], 1, s16);
     }
-    step_all(r8, tab->c_cvt[0]);
+    qg_step_all<int, NOUT>(r8, tab->c_cvt[0]);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int64_t m = m0 + ty * 4 + i, n = n0 + tx + 16 * j;
-            if (m < g.M && n < g.N) {
-                const int64_t idx = m * g.N + n;
-                const int r = r8[i * 2 + j];
-                switch (g.cbytes) {
-                case 1: ((int8_t*)g.C)[idx] = (int8_t)r; break;
-                case 2: ((int16_t*)g.C)[idx] = (int16_t)r; break;
-                case 4: ((int32_t*)g.C)[idx] = r; break;
-                default: ((int64_t*)g.C)[idx] = (int64_t)r; break;
-                }
-            }
+            if (m < g.M && n < g.N) qg_store_c(g.C, m * g.N + n, g.cbytes, r8[i * 2 + j]);
         }
 }
 
 } // namespace
 
 template <bool SPLIT, bool MUL24, int MODE>
-static hipError_t launch_tf(int n_levels, dim3 grid, hipStream_t st, const QTreeFastArgs& g)
+static hipError_t launch_tf(int n_levels, int64_t blocks, hipStream_t st, const QTreeFastArgs& g)
 {
-    if (n_levels <= 12) hipLaunchKernelGGL((k_tree_fast<SPLIT, MUL24, 12, MODE>), grid, dim3(256), 0, st, g);
-    else hipLaunchKernelGGL((k_tree_fast<SPLIT, MUL24, 16, MODE>), grid, dim3(256), 0, st, g);
-    return hipGetLastError();
+    return qg_launch_by_levels(n_levels, k_tree_fast<SPLIT, MUL24, 12, MODE>, k_tree_fast<SPLIT, MUL24, 16, MODE>, blocks, st, g);
 }
 
 // the forms that split the product at its rounding shift where it needs one (QAnalysis::split_s)
 template <bool SPLIT>
-static hipError_t launch_tf_split(QTreeForm form, int mul24, int n_levels, dim3 grid, hipStream_t st, const QTreeFastArgs& g)
+static hipError_t launch_tf_split(QTreeForm form, int mul24, int n_levels, int64_t blocks, hipStream_t st, const QTreeFastArgs& g)
 {
     switch (form) {
-    case QTF_ONE_ZERO: return launch_tf<SPLIT, true, QTF_ONE_ZERO>(n_levels, grid, st, g);
-    case QTF_ONE_TCPL: return launch_tf<SPLIT, true, QTF_ONE_TCPL>(n_levels, grid, st, g);
-    case QTF_REC_CLAMP: return launch_tf<SPLIT, true, QTF_REC_CLAMP>(n_levels, grid, st, g);
-    case QTF_REC_BIASED: return launch_tf<SPLIT, true, QTF_REC_BIASED>(n_levels, grid, st, g);
-    case QTF_REC_KINDS: return launch_tf<SPLIT, true, QTF_REC_KINDS>(n_levels, grid, st, g);
-    case QTF_RUNTIME: return mul24 ? launch_tf<SPLIT, true, QTF_RUNTIME>(n_levels, grid, st, g) : launch_tf<SPLIT, false, QTF_RUNTIME>(n_levels, grid, st, g);
+    case QTF_ONE_ZERO: return launch_tf<SPLIT, true, QTF_ONE_ZERO>(n_levels, blocks, st, g);
+    case QTF_ONE_TCPL: return launch_tf<SPLIT, true, QTF_ONE_TCPL>(n_levels, blocks, st, g);
+    case QTF_REC_CLAMP: return launch_tf<SPLIT, true, QTF_REC_CLAMP>(n_levels, blocks, st, g);
+    case QTF_REC_BIASED: return launch_tf<SPLIT, true, QTF_REC_BIASED>(n_levels, blocks, st, g);
+    case QTF_REC_KINDS: return launch_tf<SPLIT, true, QTF_REC_KINDS>(n_levels, blocks, st, g);
+    case QTF_RUNTIME: return mul24 ? launch_tf<SPLIT, true, QTF_RUNTIME>(n_levels, blocks, st, g) : launch_tf<SPLIT, false, QTF_RUNTIME>(n_levels, blocks, st, g);
     default: return hipErrorInvalidValue;
     }
 }
 
 template <int HYB, bool UNS>
-static hipError_t launch_pk16(int n_levels, dim3 grid, hipStream_t st, const QTreeFastArgs& g)
+static hipError_t launch_pk16(int n_levels, int64_t blocks, hipStream_t st, const QTreeFastArgs& g)
 {
-    if (n_levels <= 12) hipLaunchKernelGGL((k_tree_pk16<12, HYB, UNS>), grid, dim3(256), 0, st, g);
-    else hipLaunchKernelGGL((k_tree_pk16<16, HYB, UNS>), grid, dim3(256), 0, st, g);
-    return hipGetLastError();
+    return qg_launch_by_levels(n_levels, k_tree_pk16<12, HYB, UNS>, k_tree_pk16<16, HYB, UNS>, blocks, st, g);
 }
 
 hipError_t qg_launch_tree_fast(const QTreeTable* dev_table, int n_levels, int split_s, int mul24, QTreeForm form, const void* A, const void* B,
                                void* C, int64_t M, int64_t N, int64_t K, int cbytes, hipStream_t st)
 {
-    if (K % KC != 0 || n_levels < 5 || n_levels > 16) return hipErrorInvalidValue;
+    int64_t blocks;
+    if (const hipError_t e = qg_tree_blocks(M, N, K, n_levels, TMB, TNB, blocks); e != hipSuccess || blocks == 0) return e;
     QTreeFastArgs g{dev_table, (const int32_t*)A, (const int32_t*)B, (char*)C, M, N, K, cbytes, split_s};
-    const int64_t blocks = ((M + TMB - 1) / TMB) * ((N + TNB - 1) / TNB);
-    if (blocks <= 0) return hipSuccess;
-    if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
-    dim3 grid((unsigned)blocks);
     // (the word forms form exact 64-bit products; the others are built for 24-bit multiplies, except the run-time-mode form)
     if (!mul24 && form != QTF_RUNTIME && !(form >= QTF_WORD && form <= QTF_WORD_WRAP)) return hipErrorInvalidValue;
     switch (form) {
-    case QTF_WORD: return launch_tf<false, false, QTF_WORD>(n_levels, grid, st, g);
-    case QTF_WORD_WRAP: return launch_tf<false, false, QTF_WORD_WRAP>(n_levels, grid, st, g);
-    case QTF_JWORD: return launch_tf<false, false, QTF_JWORD>(n_levels, grid, st, g);
-    case QTF_JWORD_MAD: return launch_tf<false, false, QTF_JWORD_MAD>(n_levels, grid, st, g);
-    case QTF_WORD_MAD: return launch_tf<false, false, QTF_WORD_MAD>(n_levels, grid, st, g);
-    case QTF_PK16_U: return launch_pk16<0, true>(n_levels, grid, st, g);
-    case QTF_PK16_HYB_U: return launch_pk16<1, true>(n_levels, grid, st, g);
-    case QTF_PK16_HYB16_U: return launch_pk16<2, true>(n_levels, grid, st, g);
-    case QTF_PK16: return launch_pk16<0, false>(n_levels, grid, st, g);
-    case QTF_PK16_HYB: return launch_pk16<1, false>(n_levels, grid, st, g);
-    case QTF_PK16_HYB16: return launch_pk16<2, false>(n_levels, grid, st, g);
-    case QTF_LJ_U: return launch_tf<false, true, QTF_LJ_U>(n_levels, grid, st, g);
-    case QTF_LJ: return launch_tf<false, true, QTF_LJ>(n_levels, grid, st, g);   // (the left-justified forms are never split)
+    case QTF_WORD: return launch_tf<false, false, QTF_WORD>(n_levels, blocks, st, g);
+    case QTF_WORD_WRAP: return launch_tf<false, false, QTF_WORD_WRAP>(n_levels, blocks, st, g);
+    case QTF_JWORD: return launch_tf<false, false, QTF_JWORD>(n_levels, blocks, st, g);
+    case QTF_JWORD_MAD: return launch_tf<false, false, QTF_JWORD_MAD>(n_levels, blocks, st, g);
+    case QTF_WORD_MAD: return launch_tf<false, false, QTF_WORD_MAD>(n_levels, blocks, st, g);
+    case QTF_PK16_U: return launch_pk16<0, true>(n_levels, blocks, st, g);
+    case QTF_PK16_HYB_U: return launch_pk16<1, true>(n_levels, blocks, st, g);
+    case QTF_PK16_HYB16_U: return launch_pk16<2, true>(n_levels, blocks, st, g);
+    case QTF_PK16: return launch_pk16<0, false>(n_levels, blocks, st, g);
+    case QTF_PK16_HYB: return launch_pk16<1, false>(n_levels, blocks, st, g);
+    case QTF_PK16_HYB16: return launch_pk16<2, false>(n_levels, blocks, st, g);
+    case QTF_LJ_U: return launch_tf<false, true, QTF_LJ_U>(n_levels, blocks, st, g);
+    case QTF_LJ: return launch_tf<false, true, QTF_LJ>(n_levels, blocks, st, g);   // (the left-justified forms are never split)
     default:
-        return split_s > 0 ? launch_tf_split<true>(form, mul24, n_levels, grid, st, g) : launch_tf_split<false>(form, mul24, n_levels, grid, st, g);
+        return split_s > 0 ? launch_tf_split<true>(form, mul24, n_levels, blocks, st, g) : launch_tf_split<false>(form, mul24, n_levels, blocks, st, g);
     }
 }

@@ -20,7 +20,7 @@ import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
 SOURCES = ["qg_mfma.hip", "qg_mfma_pp.hip", "qg_mfma_ppl.hip", "qg_mfma_k6.hip", "qg_mfma_ring.hip", "qg_pack.hip", "qg_gemv.hip",
-           "qg_tree_fast.hip", "qg_tree_cplx.hip"]
+           "qg_tree_fast.hip", "qg_tree_cplx.hip", "qg_tree64.hip", "qg_tree.hip"]
 META = [("vgpr", ".vgpr_count"), ("agpr", ".agpr_count"), ("sgpr", ".sgpr_count"), ("vspill", ".vgpr_spill_count"),
         ("sspill", ".sgpr_spill_count"), ("scratch", ".private_segment_fixed_size"), ("lds", ".group_segment_fixed_size")]
 
