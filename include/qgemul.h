@@ -571,7 +571,8 @@ int qgemul_cmul_plan_form(const qgemul_desc* d, const qgemul_epilogue_cplx* ep, 
  *                             shared; E[k] of a scalar stage points to one element; stage tensors are tight (ld = M); lda / ldb /
  *                             ldc from opts.  The plan lives in the calling thread's cache like qgemul_run_batched's: a changed
  *                             batch count, chain or shared pattern re-plans.  QG_OPT_ALL_DEVICES: QG_EUNSUPPORTED
- * Not served: complex chains, per-member scalars, per-member shapes, a sharded form, BitStream export of a batched D. */
+ * Not served: complex chains, per-member scalars, a sharded form, BitStream export of a batched D (per-member shapes without a
+ * chain: the grouped plans below). */
 typedef struct qgemul_batched_ep {
     uint8_t e_shared[QG_MAX_EW];   /* tensor stage k: 1 = ONE M x N operand for every member, 0 = one operand per member;
                                       ignored for scalar and APPROX stages */
@@ -590,9 +591,62 @@ int qgemul_time_execute_batched_ep(qgemul_plan* p, void* packedD, const void* pa
 int qgemul_run_batched_epx(const qgemul_desc* d, int64_t batch, const qgemul_epilogue* ep, const qgemul_approx* const ax[QG_MAX_EW], void* D, const void* A,
                            const void* B, const void* const* E, int64_t strideD, int64_t strideA, int64_t strideB, const int64_t strideE[QG_MAX_EW],
                            const qgemul_opts* o);
-/* sizeof of an ABI struct as THIS library was compiled (language bindings check their mirrors against it); 0: unknown id */
+/* ---- grouped Qgemul: `groups` independent GEMMs of DIFFERENT shapes in one launch ----
+ * A group is groups >= 1 descriptors d[groups]; member g is exactly  Qgemul<...>(C_g, A_g, B_g)  as d[g] lowers it (a descriptor
+ * carries n_levels and the level formats, which depend on K, so the members are full descriptors).  Any list of descriptors that
+ * qgemul_plan_create accepts one by one is accepted; which members share the ONE grouped launch is the planner's business:
+ *   - a member is eligible if its batched analysis reports the block-diagonal form (64 x 64 tiles of the lock-step MFMA kernels);
+ *   - the launch key is what the kernel and its uniform arguments depend on: the limb counts and stored planes of A and B, the
+ *     k-tile size, the centres of A and B, C's container and the conversion into C; the key is that of the first eligible member
+ *     in list order, and the eligible members with that key go into the launch: their M, N, K and transA are free;
+ *   - every other member is a straggler (tree class, complex, ring, composite, raw-dot-product pass, a member the plain planner
+ *     gives to a two-group kernel or to 256 x 256 tiles, a different key) and runs on its own plain plan through the same entry
+ *     points.  qgemul_info.reason states how many members are in the launch and how many run alone.
+ * Packed A (B): the packed operands of the members in the launch back to back, each with its own padded rows and its own K_p,
+ * every start a multiple of 1024 bytes; behind all of them ONE plane-mask trailer (the OR over every member in the launch) and ONE
+ * row-sum array over the stack's rows; behind those the stragglers' packed operands in the layout of their own plain plans, at
+ * 256-byte-aligned offsets.  Packed C: the same order, without trailer.  qgemul_info.packed_bytes[] and ops are the whole group's.
+ * Pointer arrays are host arrays of `groups` device pointers (qgemul_run_grouped: of host pointers); ld[g] as in qgemul_pack, ld ==
+ * NULL: every member tight.  A member with M == 0 or N == 0 takes no tile and writes nothing (its pointers may be NULL).
+ * A grouped plan is destroyed with qgemul_plan_destroy and answers qgemul_plan_info; every plain and batched entry point refuses
+ * it (QG_EINVAL), and the grouped entry points refuse plain and batched plans.
+ * QG_EINVAL: groups < 1, a null member pointer, an ld below the member's rows, more than 2^31 - 1 tiles in the launch.
+ *   qgemul_classify_grouped            pure host code
+ *   qgemul_classify_grouped_launches   pure host code: what qgemul_plan_grouped_launches will answer (< 0: a status)
+ *   qgemul_plan_grouped_launches       kernel launches per qgemul_execute_grouped: (1 if any member is in the launch; a 3 x 3-limb
+ *                                      launch pair counts once) + what the stragglers' qgemul_execute calls issue
+ *   qgemul_plan_grouped_member         where member g lives
+ *   qgemul_pack_grouped / qgemul_unpack_c_grouped   layout steps, one launch per member
+ *   qgemul_execute_grouped             the hot path, asynchronous on the ctx stream
+ *   qgemul_run_grouped                 one-shot, host pointers, synchronous; lda / ldb / ldc per member (NULL: tight; those of opts
+ *                                      are not read); the plan lives in the calling thread's cache, keyed on the whole descriptor
+ *                                      list; QG_OPT_ALL_DEVICES: QG_EUNSUPPORTED
+ * Not served: element-wise chains on grouped plans, a sharded form, a second grouped launch for the stragglers, grouped forms of the
+ * tree, ring, complex and two-group kernels, BitStream export of a grouped C, 32 x 32 tiles. */
+typedef struct qgemul_grouped_member {
+    int32_t in_launch;     /* 1: in the one grouped launch; 0: a straggler on its own plain plan */
+    int32_t launches;      /* kernel launches of this member alone (0 in the launch) */
+    int64_t off[3];        /* byte offsets of the member inside packed A / B / C */
+    int64_t bytes[3];      /* its bytes there (in the launch: without the launch's trailer and row sums) */
+    int64_t tiles_m, tiles_n, k_tiles;   /* in the launch: 64 x 64 tiles and k-tiles; 0 for a straggler */
+} qgemul_grouped_member;
+int qgemul_classify_grouped(const qgemul_desc* d, int64_t groups, uint32_t opt_flags, qgemul_info* out);
+int qgemul_classify_grouped_launches(const qgemul_desc* d, int64_t groups, uint32_t opt_flags);
+int qgemul_classify_grouped_member(const qgemul_desc* d, int64_t groups, uint32_t opt_flags, int64_t g, qgemul_grouped_member* out);   /* pure host code */
+int qgemul_plan_create_grouped(qgemul_ctx* c, const qgemul_desc* d, int64_t groups, uint32_t opt_flags, qgemul_plan** out);
+int qgemul_plan_grouped_launches(const qgemul_plan* p);
+int qgemul_plan_grouped_member(const qgemul_plan* p, int64_t g, qgemul_grouped_member* out);
+int qgemul_pack_grouped(qgemul_plan* p, int operand, const void* const* src_dev, const int64_t* ld, void* packed_dev);
+int qgemul_unpack_c_grouped(qgemul_plan* p, const void* packed_dev, void* const* dst_dev, const int64_t* ld);
+int qgemul_execute_grouped(qgemul_plan* p, void* packedC, const void* packedA, const void* packedB);
+int qgemul_time_execute_grouped(qgemul_plan* p, void* packedC, const void* packedA, const void* packedB, int warmup, int iters, float* avg_ms);
+int qgemul_run_grouped(const qgemul_desc* d, int64_t groups, void* const* C, const void* const* A, const void* const* B, const int64_t* lda,
+                       const int64_t* ldb, const int64_t* ldc, const qgemul_opts* o);
+/* sizeof of an ABI struct as THIS library was compiled (language bindings check their mirrors against it); 0: unknown id
+ * (id 11 is not assigned: tests/test_cmul_plan.py pins it as an unknown id) */
 enum { QG_SIZEOF_QFMT = 0, QG_SIZEOF_DESC = 1, QG_SIZEOF_OPTS = 2, QG_SIZEOF_INFO = 3, QG_SIZEOF_EW_STAGE = 4, QG_SIZEOF_EPILOGUE = 5,
-       QG_SIZEOF_EP_ARGS = 6, QG_SIZEOF_EPILOGUE_CPLX = 7, QG_SIZEOF_APPROX_SEG = 8, QG_SIZEOF_APPROX = 9, QG_SIZEOF_CMUL = 10 };
+       QG_SIZEOF_EP_ARGS = 6, QG_SIZEOF_EPILOGUE_CPLX = 7, QG_SIZEOF_APPROX_SEG = 8, QG_SIZEOF_APPROX = 9, QG_SIZEOF_CMUL = 10,
+       QG_SIZEOF_GROUPED_MEMBER = 12 };
 size_t qgemul_sizeof(int which);
 
 /* ---- several GPUs in one process ----

@@ -18,6 +18,7 @@
 #include <array>
 #include <stdexcept>
 #include <string>
+#include <tuple>
 #include <type_traits>
 #include <utility>
 
@@ -246,6 +247,44 @@ void QgemulBatched(TC& C, const TA& A, const TB& B)
     opts.flags = QgemulRunFlags();
     const int st = qgemul_run_batched(&d, batch, C.data.data(), A.data.data(), B.data.data(), strides[0], strides[1], strides[2], &opts);
     if (st != QG_OK) throw std::runtime_error(std::string("QgemulBatched: ") + qgemul_strerror(st));
+}
+
+// ---- grouped Qgemul: GEMMs of DIFFERENT dim<> in one call ----
+//     QgemulGrouped<tags...>(std::tie(C0, C1, ...), std::tie(A0, A1, ...), std::tie(B0, B1, ...));   // member g: Qgemul<tags...>(Cg, Ag, Bg)
+// on 2-d tensors of any dim<> and one element type per operand.  Each triple is lowered by the Qgemul lowering (a shape mismatch
+// inside a triple stays a compile-time error) and the call is qgemul_run_grouped (qgemul.h): the small linear-class members of one
+// launch key run as ONE launch, every other member on its own plan.
+namespace qgemul_detail {
+template <typename... Tags>
+struct GroupedLower {
+    template <class TupC, class TupA, class TupB, size_t... I>
+    static std::array<qgemul_desc, sizeof...(I)> lower(const TupC& C, const TupA& A, const TupB& B, std::index_sequence<I...>)
+    {
+        return {{Qgemul_lower<Tags...>(std::get<I>(C), std::get<I>(A), std::get<I>(B))...}};
+    }
+};
+} // namespace qgemul_detail
+// the members' descriptors, in order
+template <typename... Tags, class... TC, class... TA, class... TB>
+std::array<qgemul_desc, sizeof...(TC)> QgemulGrouped_lower(const std::tuple<TC&...>& C, const std::tuple<TA&...>& A, const std::tuple<TB&...>& B)
+{
+    static_assert(sizeof...(TC) >= 1 && sizeof...(TC) == sizeof...(TA) && sizeof...(TC) == sizeof...(TB), "QgemulGrouped: as many As and Bs as Cs, at least one");
+    return qgemul_detail::GroupedLower<Tags...>::lower(C, A, B, std::index_sequence_for<TC...>{});
+}
+template <typename... Tags, class... TC, class... TA, class... TB>
+void QgemulGrouped(const std::tuple<TC&...>& C, const std::tuple<TA&...>& A, const std::tuple<TB&...>& B)
+{
+    constexpr size_t G = sizeof...(TC);
+    std::array<qgemul_desc, G> d = QgemulGrouped_lower<Tags...>(C, A, B);
+    for (auto& m : d) m.flags |= QgemulDescFlags();
+    const std::array<void*, G> pc = std::apply([](auto&... t) { return std::array<void*, G>{{(void*)t.data.data()...}}; }, C);
+    const std::array<const void*, G> pa = std::apply([](auto&... t) { return std::array<const void*, G>{{(const void*)t.data.data()...}}; }, A);
+    const std::array<const void*, G> pb = std::apply([](auto&... t) { return std::array<const void*, G>{{(const void*)t.data.data()...}}; }, B);
+    qgemul_opts opts{};
+    opts.device = -1;
+    opts.flags = QgemulRunFlags();
+    const int st = qgemul_run_grouped(d.data(), int64_t(G), pc.data(), pa.data(), pb.data(), nullptr, nullptr, nullptr, &opts);
+    if (st != QG_OK) throw std::runtime_error(std::string("QgemulGrouped: ") + qgemul_strerror(st));
 }
 
 // ---- element-wise operators after the GEMM (the header's lazy tensor operators, QuBLAS.h:3780-3877, :4079-4100) ----

@@ -13,7 +13,7 @@ from typing import Optional
 
 import numpy as np
 
-from .desc import (QG_MAX_EW, Qcomplex, Qu, host_layout, qfmt, qgemul_approx, qgemul_approx_form, qgemul_approx_seg, qgemul_batched_ep, batched_ep, qgemul_cmul, qgemul_cmul_form, qgemul_desc, qgemul_ep_args, qgemul_epilogue,
+from .desc import (QG_MAX_EW, Qcomplex, Qu, host_layout, qfmt, qgemul_approx, qgemul_approx_form, qgemul_approx_seg, qgemul_batched_ep, batched_ep, qgemul_grouped_member, qgemul_cmul, qgemul_cmul_form, qgemul_desc, qgemul_ep_args, qgemul_epilogue,
                    qgemul_epilogue_cplx, qgemul_ew_stage, qgemul_info, qgemul_opts)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -48,10 +48,12 @@ EXPORTS = [
     "qgemul_unpack_c_batched", "qgemul_execute_batched", "qgemul_time_execute_batched", "qgemul_run_batched",
     "qgemul_classify_batched_epx", "qgemul_classify_batched_epx_launches", "qgemul_plan_create_batched_epx", "qgemul_pack_e_batched", "qgemul_execute_batched_ep",
     "qgemul_time_execute_batched_ep", "qgemul_run_batched_epx",
+    "qgemul_classify_grouped", "qgemul_classify_grouped_launches", "qgemul_classify_grouped_member", "qgemul_plan_create_grouped", "qgemul_plan_grouped_launches",
+    "qgemul_plan_grouped_member", "qgemul_pack_grouped", "qgemul_unpack_c_grouped", "qgemul_execute_grouped", "qgemul_time_execute_grouped", "qgemul_run_grouped",
 ]
 # qgemul_sizeof ids (include/qgemul.h) and the ctypes mirror each one must match
 SIZEOF_MIRRORS = {0: qfmt, 1: qgemul_desc, 2: qgemul_opts, 3: qgemul_info, 4: qgemul_ew_stage, 5: qgemul_epilogue, 6: qgemul_ep_args,
-                  7: qgemul_epilogue_cplx, 8: qgemul_approx_seg, 9: qgemul_approx, 10: qgemul_cmul}
+                  7: qgemul_epilogue_cplx, 8: qgemul_approx_seg, 9: qgemul_approx, 10: qgemul_cmul, 12: qgemul_grouped_member}
 
 _lib = None
 
@@ -166,6 +168,18 @@ def lib() -> C.CDLL:
         L.qgemul_execute_batched_ep.argtypes = [vp, vp, vp, vp, pa]
         L.qgemul_time_execute_batched_ep.argtypes = [vp, vp, vp, vp, pa, C.c_int, C.c_int, C.POINTER(C.c_float)]
         L.qgemul_run_batched_epx.argtypes = [pd, i64, pe, pax, vp, vp, vp, C.POINTER(vp), i64, i64, i64, C.POINTER(i64), C.POINTER(qgemul_opts)]
+        pgm, pvp, pi64 = C.POINTER(qgemul_grouped_member), C.POINTER(vp), C.POINTER(i64)
+        L.qgemul_classify_grouped.argtypes = [pd, i64, u32, C.POINTER(qgemul_info)]
+        L.qgemul_classify_grouped_launches.argtypes = [pd, i64, u32]
+        L.qgemul_classify_grouped_member.argtypes = [pd, i64, u32, i64, pgm]
+        L.qgemul_plan_create_grouped.argtypes = [vp, pd, i64, u32, C.POINTER(vp)]
+        L.qgemul_plan_grouped_launches.argtypes = [vp]
+        L.qgemul_plan_grouped_member.argtypes = [vp, i64, pgm]
+        L.qgemul_pack_grouped.argtypes = [vp, C.c_int, pvp, pi64, vp]
+        L.qgemul_unpack_c_grouped.argtypes = [vp, vp, pvp, pi64]
+        L.qgemul_execute_grouped.argtypes = [vp, vp, vp, vp]
+        L.qgemul_time_execute_grouped.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(C.c_float)]
+        L.qgemul_run_grouped.argtypes = [pd, i64, pvp, pvp, pvp, pi64, pi64, pi64, C.POINTER(qgemul_opts)]
         L.qgemul_sizeof.argtypes = [C.c_int]
         L.qgemul_sizeof.restype = C.c_size_t
         _lib = L
@@ -323,6 +337,58 @@ def run_batched_status(desc: qgemul_desc, batch: int, C_out: np.ndarray, A: np.n
 def run_batched(desc: qgemul_desc, batch: int, C_out: np.ndarray, A: np.ndarray, B: np.ndarray, strideC: int, strideA: int, strideB: int, **kw) -> np.ndarray:
     _chk(run_batched_status(desc, batch, C_out, A, B, strideC, strideA, strideB, **kw), "qgemul_run_batched")
     return C_out
+
+
+# ---- grouped Qgemul (include/qgemul.h, qgemul_*_grouped): a list of descriptors, member g is Qgemul<...>(C_g, A_g, B_g) ----
+def _desc_array(descs):
+    arr = (qgemul_desc * len(descs))()
+    for g, d in enumerate(descs):
+        arr[g] = d
+    return arr
+
+
+def _ptr_array(ptrs):
+    return (C.c_void_p * len(ptrs))(*[C.c_void_p(int(p)) if p else C.c_void_p() for p in ptrs])
+
+
+def _ld_array(ld, n):
+    """None: every member tight"""
+    if ld is None:
+        return None
+    assert len(ld) == n
+    return (C.c_int64 * n)(*[int(x) for x in ld])
+
+
+def classify_grouped_status(descs, flags: int = 0):
+    """qgemul_classify_grouped: (status, info); info.packed_bytes and ops are the whole group's"""
+    info = qgemul_info()
+    st = lib().qgemul_classify_grouped(_desc_array(descs) if len(descs) else None, len(descs), flags, C.byref(info))
+    return st, info
+
+
+def classify_grouped_launches(descs, flags: int = 0) -> int:
+    """kernel launches per execute of the grouped plan; a negative value is a status"""
+    return int(lib().qgemul_classify_grouped_launches(_desc_array(descs) if len(descs) else None, len(descs), flags))
+
+
+def classify_grouped_member(descs, g: int, flags: int = 0) -> qgemul_grouped_member:
+    """where member g will live (pure host code: what GroupedPlan.member(g) answers)"""
+    out = qgemul_grouped_member()
+    _chk(lib().qgemul_classify_grouped_member(_desc_array(descs), len(descs), flags, g, C.byref(out)), "qgemul_classify_grouped_member")
+    return out
+
+
+def run_grouped_status(descs, Cs, As, Bs, *, lda=None, ldb=None, ldc=None, flags: int = 0, device: int = -1) -> int:
+    """qgemul_run_grouped on lists of host-layout numpy buffers (None for a member with M == 0 or N == 0); returns the status"""
+    n = len(descs)
+    o = qgemul_opts(device=device, flags=flags)
+    ptr = lambda xs: _ptr_array([x.ctypes.data if x is not None else 0 for x in xs])
+    return int(lib().qgemul_run_grouped(_desc_array(descs), n, ptr(Cs), ptr(As), ptr(Bs), _ld_array(lda, n), _ld_array(ldb, n), _ld_array(ldc, n), C.byref(o)))
+
+
+def run_grouped(descs, Cs, As, Bs, **kw):
+    _chk(run_grouped_status(descs, Cs, As, Bs, **kw), "qgemul_run_grouped")
+    return Cs
 
 
 def _shared(shared):
@@ -660,4 +726,46 @@ class BatchedPlan:
         ms = C.c_float()
         _chk(lib().qgemul_time_execute_batched_ep(self.h, C.c_void_p(pD), C.c_void_p(pA), C.c_void_p(pB), C.byref(args), warmup, iters, C.byref(ms)),
              "qgemul_time_execute_batched_ep")
+        return ms.value
+
+
+class GroupedPlan:
+    """A grouped plan (include/qgemul.h, qgemul_*_grouped): GEMMs of different shapes, the eligible ones of one launch key in ONE launch."""
+
+    def __init__(self, ctx: Context, descs, flags: int = 0):
+        self.ctx = ctx
+        self.descs = list(descs)
+        self.groups = len(self.descs)
+        self.h = C.c_void_p()
+        _chk(lib().qgemul_plan_create_grouped(ctx.h, _desc_array(self.descs), self.groups, flags, C.byref(self.h)), "qgemul_plan_create_grouped")
+        self.info = qgemul_info()
+        _chk(lib().qgemul_plan_info(self.h, C.byref(self.info)), "qgemul_plan_info")
+
+    def close(self):
+        if self.h:
+            lib().qgemul_plan_destroy(self.h)
+            self.h = C.c_void_p()
+
+    @property
+    def launches(self) -> int:
+        return int(lib().qgemul_plan_grouped_launches(self.h))
+
+    def member(self, g: int) -> qgemul_grouped_member:
+        out = qgemul_grouped_member()
+        _chk(lib().qgemul_plan_grouped_member(self.h, g, C.byref(out)), "qgemul_plan_grouped_member")
+        return out
+
+    def pack(self, operand: int, src_devs, packed_dev: int, ld=None):
+        """src_devs: one device pointer per member (0 / None for a member with M == 0 or N == 0); ld: one per member or None (tight)"""
+        _chk(lib().qgemul_pack_grouped(self.h, operand, _ptr_array(src_devs), _ld_array(ld, self.groups), C.c_void_p(packed_dev)), "qgemul_pack_grouped")
+
+    def execute(self, pC: int, pA: int, pB: int):
+        _chk(lib().qgemul_execute_grouped(self.h, C.c_void_p(pC), C.c_void_p(pA), C.c_void_p(pB)), "qgemul_execute_grouped")
+
+    def unpack_c(self, pC: int, dst_devs, ld=None):
+        _chk(lib().qgemul_unpack_c_grouped(self.h, C.c_void_p(pC), _ptr_array(dst_devs), _ld_array(ld, self.groups)), "qgemul_unpack_c_grouped")
+
+    def time_execute(self, pC: int, pA: int, pB: int, warmup: int, iters: int) -> float:
+        ms = C.c_float()
+        _chk(lib().qgemul_time_execute_grouped(self.h, C.c_void_p(pC), C.c_void_p(pA), C.c_void_p(pB), warmup, iters, C.byref(ms)), "qgemul_time_execute_grouped")
         return ms.value

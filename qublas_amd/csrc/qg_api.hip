@@ -665,6 +665,7 @@ size_t qgemul_sizeof(int which)
     case QG_SIZEOF_APPROX_SEG: return sizeof(qgemul_approx_seg);
     case QG_SIZEOF_APPROX: return sizeof(qgemul_approx);
     case QG_SIZEOF_CMUL: return sizeof(qgemul_cmul);
+    case QG_SIZEOF_GROUPED_MEMBER: return sizeof(qgemul_grouped_member);
     default: return 0;
     }
 }
@@ -896,8 +897,14 @@ void qgemul_plan_destroy(qgemul_plan* p)
 {
     if (!p) return;
     if (p->member) qgemul_plan_destroy(p->member);   // (a batched plan: its member owns the device resources)
+    if (p->grp) {                                      // (a grouped plan: the distinct descriptors' plans do)
+        for (int64_t u = 0; u < p->grp->n_uniq; ++u)
+            if (p->grp->up[u]) qgemul_plan_destroy(p->grp->up[u]);
+    }
     DeviceScope scope(p->ctx->device);
     hipStreamSynchronize(p->ctx->stream);
+    if (p->grp) hipFree(p->grp->tiles_dev);
+    delete p->grp;
     hipFree(p->dev_table);
     hipFree(p->workspace);
     hipFree(p->cwork);
@@ -1213,6 +1220,7 @@ int qgemul_plan_fuses_epilogue(const qgemul_plan* p)
 int qgemul_plan_packed_layout(const qgemul_plan* p, int operand, int64_t out[4])
 {
     if (!p || !out || (operand != QG_OPERAND_A && operand != QG_OPERAND_B)) return QG_EINVAL;
+    if (p->grp) return QG_EINVAL;   // a grouped plan answers qgemul_plan_grouped_member
     const QPackedGeom& g = operand == QG_OPERAND_A ? p->pa : p->pb;
     out[0] = p->comp.on ? 0 : g.trailer;
     out[1] = g.offs ? g.rowsum_off : 0;
@@ -1231,7 +1239,7 @@ static const QEpStage* stage_tensor(const qgemul_plan* p, int k)
 
 int64_t qgemul_packed_c_bytes(const qgemul_plan* p)
 {
-    return p && p->has_ep && !p->batch ? (int64_t)p->pc_c.parts * p->pc_c.Mp * p->pc_c.Np * p->pc_c.cbytes : 0;
+    return p && p->has_ep && p->batch < 1 ? (int64_t)p->pc_c.parts * p->pc_c.Mp * p->pc_c.Np * p->pc_c.cbytes : 0;
 }
 
 // a tensor of the GEMM result's own element type -> the packed C the chain's pass reads (qgemul_apply_epilogue)
@@ -1515,12 +1523,14 @@ int qgemul_export_bitstream(qgemul_plan* p, const void* packedC, int tensor_chun
 }
 
 static int time_execute(qgemul_plan* p, void* packedC, const void* packedA, const void* packedB, const qgemul_ep_args* args,
-                        int warmup, int iters, float* avg_ms, bool batched = false)
+                        int warmup, int iters, float* avg_ms, int kind = 0)   // kind: 0 a plain plan, 1 a batched one, 2 a grouped one
 {
-    if (!p || !avg_ms || iters < 1 || (p->batch != 0) != batched) return QG_EINVAL;
+    const bool batched = kind == 1;
+    if (!p || !avg_ms || iters < 1 || (kind == 2 ? !p->grp : (p->batch != 0) != batched)) return QG_EINVAL;
     QG_ON_DEVICE(p->ctx);
     hipStream_t st = p->ctx->stream;
     auto once = [&]() {
+        if (kind == 2) return qgemul_execute_grouped(p, packedC, packedA, packedB);
         if (batched) return p->has_ep ? qgemul_execute_batched_ep(p, packedC, packedA, packedB, args) : qgemul_execute_batched(p, packedC, packedA, packedB);
         return p->has_ep ? qgemul_execute_ep(p, packedC, packedA, packedB, args) : qgemul_execute(p, packedC, packedA, packedB);
     };
@@ -1747,7 +1757,7 @@ int qgemul_plan_create_batched(qgemul_ctx* c, const qgemul_desc* d, int64_t batc
 
 int qgemul_plan_batched_launches(const qgemul_plan* p)
 {
-    if (!p || !p->batch) return QG_EINVAL;
+    if (!p || p->batch < 1) return QG_EINVAL;
     if (p->bd) return p->has_ep && !p->bd_fused ? 2 : 1;
     const int64_t n = p->batch * p->member_launches;
     return n > 0x7fffffffll ? 0x7fffffff : (int)n;
@@ -1755,7 +1765,7 @@ int qgemul_plan_batched_launches(const qgemul_plan* p)
 
 int qgemul_pack_batched(qgemul_plan* p, int operand, const void* src_dev, int64_t ld, int64_t member_stride, void* packed_dev)
 {
-    if (!p || !p->batch || !src_dev || !packed_dev || (operand != QG_OPERAND_A && operand != QG_OPERAND_B)) return QG_EINVAL;
+    if (!p || p->batch < 1 || !src_dev || !packed_dev || (operand != QG_OPERAND_A && operand != QG_OPERAND_B)) return QG_EINVAL;
     const int64_t ext = member_extent(p->desc, operand, ld);
     if (ext < 1 || member_stride < ext) return QG_EINVAL;
     qgemul_plan* m = p->member;
@@ -1782,7 +1792,7 @@ int qgemul_pack_batched(qgemul_plan* p, int operand, const void* src_dev, int64_
 
 int qgemul_unpack_c_batched(qgemul_plan* p, const void* packed_dev, void* dst_dev, int64_t ld, int64_t member_stride)
 {
-    if (!p || !p->batch || !packed_dev || !dst_dev) return QG_EINVAL;
+    if (!p || p->batch < 1 || !packed_dev || !dst_dev) return QG_EINVAL;
     const int64_t ext = member_extent(p->desc, QG_OPERAND_C, ld);
     if (ext < 1 || member_stride < ext) return QG_EINVAL;
     for (int64_t b = 0; b < p->batch; ++b)   // (a layout step: one launch per member, the members' packed Cs back to back)
@@ -1811,7 +1821,7 @@ static QMfmaArgs bd_mfma_args(const qgemul_plan* p, void* packedC, const void* p
 
 int qgemul_execute_batched(qgemul_plan* p, void* packedC, const void* packedA, const void* packedB)
 {
-    if (!p || !p->batch || !packedC || !packedA || !packedB) return QG_EINVAL;
+    if (!p || p->batch < 1 || !packedC || !packedA || !packedB) return QG_EINVAL;
     if (p->has_ep) return QG_EINVAL;  // a batched plan with a chain runs through qgemul_execute_batched_ep
     if (p->desc.M == 0 || p->desc.N == 0) return QG_OK;
     qgemul_plan* m = p->member;
@@ -1865,7 +1875,7 @@ int qgemul_plan_create_batched_epx(qgemul_ctx* c, const qgemul_desc* d, int64_t 
 
 int qgemul_pack_e_batched(qgemul_plan* p, int stage, const void* src_dev, int64_t ld, int64_t member_stride, void* packed_dev)
 {
-    if (!p || !p->batch || !p->has_ep || !src_dev || !packed_dev || stage < 0 || stage >= p->ept.n) return QG_EINVAL;
+    if (!p || p->batch < 1 || !p->has_ep || !src_dev || !packed_dev || stage < 0 || stage >= p->ept.n) return QG_EINVAL;
     if (!p->estride[stage]) return QG_EINVAL;   // a scalar or APPROX stage has no tensor operand
     const int64_t ext = member_extent(p->desc, QG_OPERAND_C, ld);
     if (ext < 1) return QG_EINVAL;
@@ -1880,7 +1890,7 @@ int qgemul_pack_e_batched(qgemul_plan* p, int stage, const void* src_dev, int64_
 
 int qgemul_execute_batched_ep(qgemul_plan* p, void* packedD, const void* packedA, const void* packedB, const qgemul_ep_args* args)
 {
-    if (!p || !p->batch || !p->has_ep || !packedD || !packedA || !packedB) return QG_EINVAL;
+    if (!p || p->batch < 1 || !p->has_ep || !packedD || !packedA || !packedB) return QG_EINVAL;
     if (int s = ep_args_ok(p, args)) return s;
     if (p->desc.M == 0 || p->desc.N == 0) return QG_OK;
     qgemul_plan* m = p->member;
@@ -1953,5 +1963,366 @@ int qgemul_time_execute_batched_ep(qgemul_plan* p, void* packedD, const void* pa
     return time_execute(p, packedD, packedA, packedB, args, warmup, iters, avg_ms, true);
 }
 
+
+// ---- grouped Qgemul: GEMMs of different shapes in one launch (include/qgemul.h) ----
+// the launch key: what the instantiation of k_mfma_grp and its uniform arguments depend on
+static bool same_launch_key(const QPlanGeom& x, const QPlanGeom& y)
+{
+    return x.LA == y.LA && x.LB == y.LB && x.pa.limbs == y.pa.limbs && x.pb.limbs == y.pb.limbs && x.variant == y.variant && x.cfg.BK == y.cfg.BK &&
+           x.pa.offs == y.pa.offs && x.pb.offs == y.pb.offs && x.pa.bias == y.pa.bias && x.pb.bias == y.pb.bias && x.pc.cbytes == y.pc.cbytes &&
+           !memcmp(&x.an.lin.to_c[0], &y.an.lin.to_c[0], sizeof(QStep));
+}
+
+static bool grp_empty(const qgemul_desc& d) { return d.M == 0 || d.N == 0; }
+
+// the geometry of a grouped plan, pure host code: b (zeroed) receives info and grp
+static int grouped_geometry(const qgemul_desc* d, int64_t groups, uint32_t flags, qgemul_plan* b)
+{
+    if (!d || groups < 1 || groups > 0x7fffffffll) return QG_EINVAL;
+    QGrouped* G = new (std::nothrow) QGrouped();
+    if (!G) return QG_EINVAL;
+    b->grp = G;
+    b->batch = -1;
+    b->flags = flags;
+    b->desc = d[0];
+    G->groups = groups;
+    G->key = -1;
+    G->m = new (std::nothrow) QGrpMember[groups]();
+    G->ud = new (std::nothrow) qgemul_desc[groups];
+    if (!G->m || !G->ud) return QG_EINVAL;
+    // every distinct descriptor once (the comparison of the one-shot cache: qg_run_key.h)
+    for (int64_t g = 0; g < groups; ++g) {
+        int64_t u = 0;
+        while (u < G->n_uniq && !same_desc(G->ud[u], d[g])) ++u;
+        if (u == G->n_uniq) G->ud[G->n_uniq++] = d[g];
+        G->m[g].uniq = (int32_t)u;
+    }
+    G->ug = new (std::nothrow) QPlanGeom[G->n_uniq]();
+    G->u_in = new (std::nothrow) uint8_t[G->n_uniq]();
+    G->up = new (std::nothrow) qgemul_plan*[G->n_uniq]();
+    if (!G->ug || !G->u_in || !G->up) return QG_EINVAL;
+    // batch = groups: an eligible member gets the 64 x 64 geometry of qg_mfma_pick_batched
+    for (int64_t u = 0; u < G->n_uniq; ++u) {
+        const int st = plan_geometry(&G->ud[u], flags, nullptr, groups, &G->ug[u], nullptr, nullptr);
+        if (st != QG_OK) { b->info = G->ug[u].info; return st; }
+    }
+    auto eligible = [&](int64_t u) { return G->ug[u].bd && G->ug[u].pa.K_p >= G->ug[u].cfg.BK; };
+    for (int64_t g = 0; g < groups && G->key < 0; ++g)
+        if (eligible(G->m[g].uniq)) G->key = G->m[g].uniq;
+    for (int64_t u = 0; u < G->n_uniq; ++u)
+        G->u_in[u] = G->key >= 0 && eligible(u) && same_launch_key(G->ug[u], G->ug[G->key]);
+    for (int64_t u = 0; u < G->n_uniq; ++u) {
+        if (G->u_in[u]) continue;
+        // a straggler runs on its own PLAIN plan
+        G->ug[u] = QPlanGeom();
+        const int st = plan_geometry(&G->ud[u], flags, nullptr, 0, &G->ug[u], nullptr, nullptr);
+        if (st != QG_OK) { b->info = G->ug[u].info; return st; }
+    }
+    // layout: the members in the launch back to back, the launch's one trailer and one row-sum array, then the stragglers
+    bool over = false;
+    int64_t cur[3] = {0, 0, 0}, rows[2] = {0, 0}, tiles = 0;
+    double ops = 0;
+    for (int64_t g = 0; g < groups; ++g) {
+        QGrpMember& m = G->m[g];
+        const QPlanGeom& q = G->ug[m.uniq];
+        ops += q.info.ops;
+        m.in_launch = G->u_in[m.uniq];
+        if (!m.in_launch) continue;
+        ++G->n_in;
+        m.pa = q.pa;
+        m.pb = q.pb;
+        m.bytes[0] = (int64_t)q.pa.limbs * q.pa.rows_p * q.pa.K_p;
+        m.bytes[1] = (int64_t)q.pb.limbs * q.pb.rows_p * q.pb.K_p;
+        m.bytes[2] = q.pc.Mp * q.pc.Np * q.pc.cbytes;
+        m.row_a = rows[0];
+        m.row_b = rows[1];
+        for (int w = 0; w < 3; ++w) {
+            m.off[w] = cur[w];
+            over |= __builtin_add_overflow(cur[w], m.bytes[w], &cur[w]) || cur[w] > (1ll << 60);
+        }
+        rows[0] += q.pa.rows_p;
+        rows[1] += q.pb.rows_p;
+        tiles += (q.pa.rows_p / q.cfg.TM) * (q.pb.rows_p / q.cfg.TN);
+        over |= rows[0] > 0x7fffffffll || rows[1] > 0x7fffffffll || tiles > 0x7fffffffll || q.pa.K_p / q.cfg.BK > 0x7fffffffll;
+    }
+    G->n_tiles = tiles;
+    if (G->n_in && !over) {
+        const QPlanGeom& k = G->ug[G->key];
+        QPackedGeom* sg[2] = {&G->sa, &G->sb};
+        for (int w = 0; w < 2; ++w) {
+            QPackedGeom& s = *sg[w];
+            s = w ? k.pb : k.pa;
+            s.rows_p = rows[w];
+            s.K_p = 0;   // (every member has its own)
+            s.trailer = 0;
+            if (s.limbs > 1) { s.trailer = cur[w]; cur[w] += QG_TRAILER_BYTES; }   // ONE plane mask: the OR over every member in the launch
+            if (s.offs) {                                                           // ONE row-sum array over the stack's rows
+                s.rowsum_off = round_up(cur[w], 256);
+                cur[w] = s.rowsum_off + s.rows_p * 8;
+            }
+        }
+        for (int64_t g = 0; g < groups; ++g) {
+            QGrpMember& m = G->m[g];
+            if (!m.in_launch) continue;
+            QPackedGeom* mg[2] = {&m.pa, &m.pb};
+            for (int w = 0; w < 2; ++w) {
+                // trailer and row sums relative to the member's start (both stay positive: they lie behind the planes of ALL members)
+                mg[w]->trailer = sg[w]->trailer ? sg[w]->trailer - m.off[w] : 0;
+                if (sg[w]->offs) {
+                    mg[w]->offs = 2;   // adds to row sums its caller has zeroed
+                    mg[w]->rowsum_off = sg[w]->rowsum_off + (w ? m.row_b : m.row_a) * 8 - m.off[w];
+                }
+            }
+        }
+    }
+    int64_t launches = G->n_in ? 1 : 0;
+    for (int64_t g = 0; g < groups && !over; ++g) {
+        QGrpMember& m = G->m[g];
+        if (m.in_launch) continue;
+        const QPlanGeom& q = G->ug[m.uniq];
+        for (int w = 0; w < 3; ++w) {
+            m.off[w] = round_up(cur[w], 256);
+            m.bytes[w] = q.info.packed_bytes[w];
+            over |= __builtin_add_overflow(m.off[w], m.bytes[w], &cur[w]) || cur[w] > (1ll << 60);
+        }
+        if (!grp_empty(G->ud[m.uniq])) launches += plan_launches(&q);
+    }
+    b->info = G->ug[G->key >= 0 ? G->key : G->m[0].uniq].info;
+    if (over) {
+        b->info.supported = 0;
+        snprintf(b->info.reason, sizeof b->info.reason, "grouped plan: more than 2^31 - 1 tiles / packed operands beyond the address range");
+        return QG_EINVAL;
+    }
+    G->launches = launches > 0x7fffffffll ? 0x7fffffff : (int)launches;
+    for (int w = 0; w < 3; ++w) b->info.packed_bytes[w] = cur[w];
+    b->info.ops = ops;
+    snprintf(b->info.reason, sizeof b->info.reason, "grouped plan: %lld members in one launch (%lld 64x64 tiles), %lld run alone", (long long)G->n_in,
+             (long long)G->n_tiles, (long long)(groups - G->n_in));
+    // the schedule: one record per workgroup (qg_grp.h)
+    if (G->n_tiles > 0) {
+        const QPlanGeom& k = G->ug[G->key];
+        QGrpShape* sh = new (std::nothrow) QGrpShape[G->n_in];
+        int64_t* order = new (std::nothrow) int64_t[G->n_in];
+        G->tiles = new (std::nothrow) QGrpTile[G->n_tiles];
+        if (!sh || !order || !G->tiles) { delete[] sh; delete[] order; return QG_EINVAL; }
+        int64_t n = 0;
+        for (int64_t g = 0; g < groups; ++g) {
+            const QGrpMember& m = G->m[g];
+            if (!m.in_launch) continue;
+            const QPlanGeom& q = G->ug[m.uniq];
+            QGrpShape& s = sh[n++];
+            s.a_off = m.off[0];
+            s.b_off = m.off[1];
+            s.c_off = m.off[2] / q.pc.cbytes;
+            s.corr = (int64_t)((uint64_t)G->ud[m.uniq].K * (uint64_t)k.pa.bias * (uint64_t)k.pb.bias);
+            s.a_blk = (int64_t)q.pa.limbs * q.cfg.TM * q.cfg.BK;
+            s.b_blk = (int64_t)q.pb.limbs * q.cfg.TN * q.cfg.BK;
+            s.c_tile = (int64_t)q.cfg.TM * q.cfg.TN;
+            s.tiles_m = (int32_t)(q.pa.rows_p / q.cfg.TM);
+            s.tiles_n = (int32_t)(q.pb.rows_p / q.cfg.TN);
+            s.nk = (int32_t)(q.pa.K_p / q.cfg.BK);
+            s.row_a = (int32_t)m.row_a;
+            s.row_b = (int32_t)m.row_b;
+            s.tm = q.cfg.TM;
+            s.tn = q.cfg.TN;
+            s.member = (int32_t)g;
+        }
+        // (the alternative order exists in the diagnostic library only: tools/measure_grouped.py)
+        const bool member_order = QG_DIAG_ENV("QG_GRP_MEMBER_ORDER");
+        qg_grp_schedule(sh, n, member_order ? QG_GRP_MEMBER : QG_GRP_DEALT, order, G->tiles);
+        delete[] sh;
+        delete[] order;
+    }
+    return QG_OK;
+}
+
+int grouped_plan_new(const qgemul_desc* d, int64_t groups, uint32_t opt_flags, qgemul_plan** out)
+{
+    *out = nullptr;
+    qgemul_plan* b = new (std::nothrow) qgemul_plan();
+    if (!b) return QG_EINVAL;
+    *out = b;
+    return grouped_geometry(d, groups, opt_flags, b);
+}
+
+static void grouped_plan_drop(qgemul_plan* b)   // a plan that owns no device resource
+{
+    if (!b) return;
+    delete b->grp;
+    delete b;
+}
+
+static void grouped_member_out(const QGrouped* G, int64_t g, qgemul_grouped_member* out)
+{
+    const QGrpMember& m = G->m[g];
+    const QPlanGeom& q = G->ug[m.uniq];
+    memset(out, 0, sizeof *out);
+    out->in_launch = m.in_launch;
+    out->launches = m.in_launch || grp_empty(G->ud[m.uniq]) ? 0 : plan_launches(&q);
+    for (int w = 0; w < 3; ++w) { out->off[w] = m.off[w]; out->bytes[w] = m.bytes[w]; }
+    if (m.in_launch) {
+        out->tiles_m = q.pa.rows_p / q.cfg.TM;
+        out->tiles_n = q.pb.rows_p / q.cfg.TN;
+        out->k_tiles = q.pa.K_p / q.cfg.BK;
+    }
+}
+
+int qgemul_classify_grouped(const qgemul_desc* d, int64_t groups, uint32_t opt_flags, qgemul_info* out)
+{
+    if (!d || !out) return QG_EINVAL;
+    qgemul_plan* b = nullptr;
+    const int st = grouped_plan_new(d, groups, opt_flags, &b);
+    if (b && groups >= 1) *out = b->info;
+    grouped_plan_drop(b);
+    return st;
+}
+
+int qgemul_classify_grouped_launches(const qgemul_desc* d, int64_t groups, uint32_t opt_flags)
+{
+    if (!d) return QG_EINVAL;
+    qgemul_plan* b = nullptr;
+    const int st = grouped_plan_new(d, groups, opt_flags, &b);
+    const int n = st == QG_OK ? b->grp->launches : st;
+    grouped_plan_drop(b);
+    return n;
+}
+
+int qgemul_classify_grouped_member(const qgemul_desc* d, int64_t groups, uint32_t opt_flags, int64_t g, qgemul_grouped_member* out)
+{
+    if (!d || !out || g < 0 || g >= groups) return QG_EINVAL;
+    qgemul_plan* b = nullptr;
+    const int st = grouped_plan_new(d, groups, opt_flags, &b);
+    if (st == QG_OK) grouped_member_out(b->grp, g, out);
+    grouped_plan_drop(b);
+    return st;
+}
+
+// every distinct descriptor's plain plan owns its device resources; the grouped plan owns the schedule on the device
+int qgemul_plan_create_grouped(qgemul_ctx* c, const qgemul_desc* d, int64_t groups, uint32_t opt_flags, qgemul_plan** out)
+{
+    if (!c || !d || !out) return QG_EINVAL;
+    qgemul_plan* b = nullptr;
+    int st = grouped_plan_new(d, groups, opt_flags, &b);
+    if (st != QG_OK) { grouped_plan_drop(b); return st; }
+    b->ctx = c;
+    QGrouped* G = b->grp;
+    for (int64_t u = 0; u < G->n_uniq && st == QG_OK; ++u) st = plan_create_view(c, &G->ud[u], nullptr, opt_flags, &G->up[u], G->u_in[u] ? groups : 0);
+    if (st == QG_OK && G->n_tiles > 0) {
+        DeviceScope scope(c->device);
+        const size_t tb = (size_t)G->n_tiles * sizeof(QGrpTile);
+        hipError_t e = scope.err;
+        if (e == hipSuccess) e = hipMalloc((void**)&G->tiles_dev, tb);
+        if (e == hipSuccess) e = hipMemcpyAsync(G->tiles_dev, G->tiles, tb, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) { g_last_hip = (int)e; st = QG_EHIP; }
+    }
+    if (st != QG_OK) { qgemul_plan_destroy(b); return st; }
+    *out = b;
+    return QG_OK;
+}
+
+int qgemul_plan_grouped_launches(const qgemul_plan* p)
+{
+    if (!p || !p->grp) return QG_EINVAL;
+    return p->grp->launches;
+}
+
+int qgemul_plan_grouped_member(const qgemul_plan* p, int64_t g, qgemul_grouped_member* out)
+{
+    if (!p || !p->grp || !out || g < 0 || g >= p->grp->groups) return QG_EINVAL;
+    grouped_member_out(p->grp, g, out);
+    return QG_OK;
+}
+
+int qgemul_pack_grouped(qgemul_plan* p, int operand, const void* const* src_dev, const int64_t* ld, void* packed_dev)
+{
+    if (!p || !p->grp || !src_dev || !packed_dev || (operand != QG_OPERAND_A && operand != QG_OPERAND_B)) return QG_EINVAL;
+    const QGrouped* G = p->grp;
+    for (int64_t g = 0; g < G->groups; ++g) {   // every member is checked before the first launch
+        const qgemul_desc& d = G->ud[G->m[g].uniq];
+        if (grp_empty(d)) continue;
+        if (!src_dev[g] || member_extent(d, operand, ld ? ld[g] : 0) < 1) return QG_EINVAL;
+    }
+    QG_ON_DEVICE(p->ctx);
+    hipStream_t st = p->ctx->stream;
+    const int check = (p->flags & QG_OPT_CHECK_RANGE) ? 1 : 0;
+    const QPackedGeom& s = operand == QG_OPERAND_A ? G->sa : G->sb;
+    if (G->n_in) {
+        // what belongs to the launch is cleared ONCE; every member then ORs / adds into it (qg_launch_pack_stack does the same)
+        if (check) QG_HIP(hipMemsetAsync(p->ctx->flag_dev, 0, 4, st));
+        if (s.trailer) QG_HIP(hipMemsetAsync((char*)packed_dev + s.trailer, 0, QG_TRAILER_BYTES, st));
+        if (s.offs && s.rows_p) QG_HIP(hipMemsetAsync((char*)packed_dev + s.rowsum_off, 0, (size_t)s.rows_p * 8, st));
+        for (int64_t g = 0; g < G->groups; ++g) {
+            const QGrpMember& m = G->m[g];
+            if (!m.in_launch || grp_empty(G->ud[m.uniq])) continue;
+            const QOperandGeom og = operand_geom(G->up[m.uniq], operand, ld ? ld[g] : 0);
+            QG_HIP(qg_launch_pack_member(og, operand == QG_OPERAND_A ? m.pa : m.pb, src_dev[g], (char*)packed_dev + m.off[operand], check, p->ctx->flag_dev, st,
+                                         (p->flags & QG_OPT_GENERIC_LAYOUT) ? 1 : 0));
+        }
+        if (check) {
+            int flag = 0;
+            QG_HIP(hipMemcpyAsync(&flag, p->ctx->flag_dev, 4, hipMemcpyDeviceToHost, st));
+            QG_HIP(hipStreamSynchronize(st));
+            if (flag) return QG_ERANGE;
+        }
+    }
+    for (int64_t g = 0; g < G->groups; ++g) {
+        const QGrpMember& m = G->m[g];
+        if (m.in_launch || grp_empty(G->ud[m.uniq])) continue;
+        if (const int rc = qgemul_pack(G->up[m.uniq], operand, src_dev[g], ld ? ld[g] : 0, (char*)packed_dev + m.off[operand]); rc != QG_OK) return rc;
+    }
+    return QG_OK;
+}
+
+int qgemul_unpack_c_grouped(qgemul_plan* p, const void* packed_dev, void* const* dst_dev, const int64_t* ld)
+{
+    if (!p || !p->grp || !packed_dev || !dst_dev) return QG_EINVAL;
+    const QGrouped* G = p->grp;
+    for (int64_t g = 0; g < G->groups; ++g) {
+        const qgemul_desc& d = G->ud[G->m[g].uniq];
+        if (grp_empty(d)) continue;
+        if (!dst_dev[g] || member_extent(d, QG_OPERAND_C, ld ? ld[g] : 0) < 1) return QG_EINVAL;
+    }
+    for (int64_t g = 0; g < G->groups; ++g) {   // (a layout step: one launch per member)
+        const QGrpMember& m = G->m[g];
+        if (grp_empty(G->ud[m.uniq])) continue;
+        if (const int rc = qgemul_unpack_c(G->up[m.uniq], (const char*)packed_dev + m.off[2], dst_dev[g], ld ? ld[g] : 0); rc != QG_OK) return rc;
+    }
+    return QG_OK;
+}
+
+int qgemul_execute_grouped(qgemul_plan* p, void* packedC, const void* packedA, const void* packedB)
+{
+    if (!p || !p->grp || !packedC || !packedA || !packedB) return QG_EINVAL;
+    const QGrouped* G = p->grp;
+    if (G->n_tiles > 0) {
+        QG_ON_DEVICE(p->ctx);
+        const QPlanGeom& k = G->ug[G->key];
+        QMfmaGrpArgs a;
+        memset((void*)&a, 0, sizeof a);
+        (QMfmaArgs&)a = mfma_args(G->sa, G->sb, k.variant, packedA, packedB, packedC, k.pc.cbytes);
+        a.to_c = k.an.lin.to_c[0];
+        if (G->sa.offs) {   // centred operands: one centre per operand for the whole launch, K biasA biasB per member (the records)
+            a.rsA = (const int64_t*)((const char*)packedA + G->sa.rowsum_off);
+            a.rsB = (const int64_t*)((const char*)packedB + G->sb.rowsum_off);
+            a.biasA = G->sa.bias;
+            a.biasB = G->sb.bias;
+        }
+        a.tiles = G->tiles_dev;
+        QG_HIP(qg_launch_mfma_grp(k.LA, k.LB, a, G->n_tiles, p->ctx->stream));
+    }
+    for (int64_t g = 0; g < G->groups; ++g) {
+        const QGrpMember& m = G->m[g];
+        if (m.in_launch) continue;
+        if (const int rc = qgemul_execute(G->up[m.uniq], (char*)packedC + m.off[2], (const char*)packedA + m.off[0], (const char*)packedB + m.off[1]); rc != QG_OK)
+            return rc;
+    }
+    return QG_OK;
+}
+
+int qgemul_time_execute_grouped(qgemul_plan* p, void* packedC, const void* packedA, const void* packedB, int warmup, int iters, float* avg_ms)
+{
+    return time_execute(p, packedC, packedA, packedB, nullptr, warmup, iters, avg_ms, 2);
+}
 
 } // extern "C"

@@ -101,6 +101,39 @@ struct QPlanGeom {
     int bd;               // the member of a batched plan: k_mfma's block-diagonal form takes it (a batched plan: it launches that form)
 };
 
+// Grouped plan (qgemul_plan_create_grouped): `groups` descriptors, analysed once per DISTINCT descriptor (ug / up: its geometry and its
+// plain plan, which owns the device resources and serves pack, unpack and — for a straggler — execute).  The members in the one
+// grouped launch have the batched analysis' 64 x 64 geometry; their packed operands sit back to back in front of the launch's one
+// trailer and one row-sum array (sa / sb: the stack's geometry), the stragglers' behind them.  tiles: the schedule (qg_grp.h).
+struct QGrpMember {
+    int32_t uniq, in_launch;
+    int64_t off[3], bytes[3];   // inside packed A / B / C
+    int64_t row_a, row_b;       // in the launch: first row of the member in the stack's row sums
+    QPackedGeom pa, pb;         // in the launch: the member's geometry with trailer / row sums relative to ITS start (qg_launch_pack_member)
+};
+struct QGrouped {
+    int64_t groups, n_uniq, n_in, n_tiles;
+    qgemul_desc* ud;            // [n_uniq]
+    QPlanGeom* ug;              // [n_uniq]
+    uint8_t* u_in;              // [n_uniq]: in the launch
+    qgemul_plan** up;           // [n_uniq]; nullptr entries while classifying
+    QGrpMember* m;              // [groups]
+    int64_t key;                // the distinct descriptor whose launch key the launch has (-1: no member is eligible)
+    QPackedGeom sa, sb;
+    int launches;
+    QGrpTile* tiles;            // [n_tiles] host
+    QGrpTile* tiles_dev;
+    ~QGrouped()
+    {
+        delete[] ud;
+        delete[] ug;
+        delete[] u_in;
+        delete[] up;
+        delete[] m;
+        delete[] tiles;
+    }
+};
+
 struct qgemul_plan : QPlanGeom {
     qgemul_ctx* ctx;
     qgemul_desc desc;
@@ -147,6 +180,9 @@ struct qgemul_plan : QPlanGeom {
     uint8_t e_shared[QG_MAX_EW];
     int bd_fused;
     int64_t estride[QG_MAX_EW];
+    // grouped plan (qgemul_plan_create_grouped): batch == -1, so that the plain entry points refuse it as they refuse a batched plan and
+    // the batched ones as they refuse a plain plan; everything else is in grp
+    QGrouped* grp;
 };
 
 // (defined next to the entry points of include/qgemul.h, inside their extern "C" block)
@@ -155,6 +191,8 @@ QG_INTERNAL int classify_view(const qgemul_desc* d, const EpView* ev, uint32_t o
 QG_INTERNAL int plan_create_view(qgemul_ctx* c, const qgemul_desc* d, const EpView* ev, uint32_t opt_flags, qgemul_plan** out, int64_t batch = 0);   // batch > 0: the member of a batched plan
 // batched plans: ev == nullptr: no chain; bep: which tensor operands of the chain are shared
 QG_INTERNAL int classify_batched_view(const qgemul_desc* d, int64_t batch, const EpView* ev, const qgemul_batched_ep* bep, uint32_t opt_flags, qgemul_info* out, int* launches);
+// grouped plans: the geometry alone (pure host; *out is the caller's to `delete`, whatever the status) / the plan
+QG_INTERNAL int grouped_plan_new(const qgemul_desc* d, int64_t groups, uint32_t opt_flags, qgemul_plan** out);
 QG_INTERNAL int plan_create_batched_view(qgemul_ctx* c, const qgemul_desc* d, int64_t batch, const EpView* ev, const qgemul_batched_ep* bep, uint32_t opt_flags, qgemul_plan** out);
 QG_INTERNAL bool stores_host_c(const qgemul_plan* p);
 // host elements one member of operand `operand` spans at leading dimension ld (0: tight); 0: ld is too small

@@ -8,6 +8,7 @@
 #include <atomic>
 
 #include "qg_eltwise_args.h"
+#include "qg_grp.h"
 #include "qg_plan.h"
 #include "qg_ring.h"
 
@@ -226,6 +227,26 @@ hipError_t qg_launch_mfma_ep_bd(int LA, int LB, const QMfmaEpBdArgs& a, int64_t 
 // `batch` GEMMs of one member shape in ONE launch of k_mfma's block-diagonal form (qg_mfma.hip): the variants qg_mfma_pick_batched
 // returns, no element-wise chain, no Karatsuba digits; anything else is hipErrorInvalidValue
 hipError_t qg_launch_mfma_bd(int LA, int LB, const QMfmaArgs& a, int64_t batch, hipStream_t st);
+// Grouped Qgemul: GEMMs of DIFFERENT shapes in one launch of k_mfma_grp (qg_mfma_grp.hip), the body of k_mfma with GRP.  A, B and C
+// are the members' packed operands back to back (every member with its own padded rows and its own K_p), maskA / maskB the launch's
+// one plane mask per operand (the OR over every member), rsA / rsB one row-sum array per operand over the stack's rows, and
+// tiles[] the host's schedule (qg_grp.h): one record per workgroup.  Mp, Np, Kp, corr, bd_tm and bd_tn are not read.  The kernel has
+// an argument struct of its own: QMfmaArgs is what it was.
+struct QMfmaGrpArgs : QMfmaArgs {
+    const QGrpTile* tiles;
+};
+// the schedule of a kernel's argument struct (kernels whose arguments have none never evaluate the result)
+template <class G>
+QG_HD auto qg_grp_tiles_of(const G& g, int) -> decltype(g.tiles) { return g.tiles; }
+template <class G>
+QG_HD const QGrpTile* qg_grp_tiles_of(const G&, long) { return nullptr; }
+// n_tiles workgroups, the ten geometries of qg_launch_mfma_bd (a 3 x 3 launch is the pair <3,3> + <2,2 on three-plane storage>,
+// both reading the same records); anything else is hipErrorInvalidValue
+hipError_t qg_launch_mfma_grp(int LA, int LB, const QMfmaGrpArgs& a, int64_t n_tiles, hipStream_t st);
+// one member of a stack the caller has cleared (trailer, row sums): qg_launch_pack without the clearing, as qg_launch_pack_stack
+// packs its members (p.trailer and p.rowsum_off relative to dst, p.offs == 2 for centred operands)
+hipError_t qg_launch_pack_member(const QOperandGeom& g, const QPackedGeom& p, const void* src, void* dst, int check_range, int* range_flag,
+                                 hipStream_t st, int generic = 0);
 // tile geometry of a batched plan; variant 0: no block-diagonal form for this member (it runs member by member on `plain`, the
 // member's own qg_mfma_pick)
 QMfmaCfg qg_mfma_pick_batched(int LA, int LB, int64_t batch, const QMfmaCfg& plain);

@@ -55,14 +55,14 @@ typedef int v16i __attribute__((ext_vector_type(16)));
 template <int LA, int LB, int BK, int WGM, int WGN, int TI, int TJ, int NSTAGE, int ABL, bool EP, int SA = LA, int SB = LB, bool KARA = false, int KS = 1>   // EP: fused element-wise epilogue
 __global__ __launch_bounds__(64 * WGM * WGN * KS) void k_mfma(QMfmaArgs g)
 {
-    constexpr bool BD = false;
+    constexpr bool BD = false, GRP = false;
 #include "qg_mfma_body.h"
 }
 template <int LA, int LB, int BK, int WGM, int WGN, int TI, int TJ, int NSTAGE, int SA = LA, int SB = LB>
 __global__ __launch_bounds__(64 * WGM * WGN) void k_mfma_bd(QMfmaArgs g)
 {
     constexpr int ABL = 0, KS = 1;
-    constexpr bool EP = false, KARA = false, BD = true;
+    constexpr bool EP = false, KARA = false, BD = true, GRP = false;
 #include "qg_mfma_body.h"
 }
 

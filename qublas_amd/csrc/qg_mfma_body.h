@@ -1,7 +1,7 @@
 // qg_mfma_body.h — the body of k_mfma and k_mfma_bd (qg_mfma.hip) and of k_mfma_ep_bd (qg_mfma_ep_bd.hip), included INSIDE the
 // kernels: no include guard, nothing at namespace scope.  In scope where it is included: the kernel argument `QMfmaArgs g` (BD with
-// EP: a QMfmaEpBdArgs) and the compile-time constants LA, LB, BK, WGM, WGN, TI, TJ, NSTAGE, ABL, EP, SA, SB, KARA, KS, BD (their
-// meaning: the comment in front of k_mfma).
+// EP: a QMfmaEpBdArgs; GRP: a QMfmaGrpArgs) and the compile-time constants LA, LB, BK, WGM, WGN, TI, TJ, NSTAGE, ABL, EP, SA, SB, KARA,
+// KS, BD, GRP (their meaning: the comment in front of k_mfma; GRP: k_mfma_grp, qg_mfma_grp.hip).
     if constexpr (SA == 3 && SB == 3 && ABL == 0) {
         const unsigned ma = qg_plane_mask(g.maskA);
         const unsigned mb = qg_plane_mask(g.maskB);
@@ -33,6 +33,21 @@
     int tile_m, tile_n;
     int64_t bd_c_tile = 0;   // BD: this workgroup's tile of the batch's packed C
     int bd_member = 0;       // BD: the member that tile belongs to (wave-uniform)
+    int64_t grp_a = 0, grp_b = 0, grp_c = 0, grp_corr = 0;   // GRP: this workgroup's record of the host's schedule (qg_grp.h)
+    int grp_nk = 0;
+    if constexpr (GRP) {
+        // grouped launch: block bid reads record bid — where its A and B blocks start, where its C tile goes, its k-tile count, its
+        // rows of the stack's row sums and its member's K biasA biasB.  One wave-uniform load of 48 bytes; no division, no tile walk
+        static_assert(!GRP || (!BD && KS == 1 && !KARA && ABL == 0 && !EP && TM == 64 && TN == 64), "grouped form: the plain lock-step body on 64 x 64 tiles");
+        const QGrpTile rec = qg_grp_tiles_of(g, 0)[blockIdx.x];
+        grp_a = rec.a_off;
+        grp_b = rec.b_off;
+        grp_c = rec.c_off;
+        grp_corr = rec.corr;
+        grp_nk = rec.nk;
+        tile_m = (int)((unsigned)rec.row_a / (unsigned)TM);   // (the row sums' rows: tile_m * TM, tile_n * TN)
+        tile_n = (int)((unsigned)rec.row_b / (unsigned)TN);
+    } else
     if constexpr (BD) {
         // tiles_m, tiles_n count the STACK's row tiles; the batch has gridDim.x = batch * bd_tm * bd_tn tiles on its diagonal
         static_assert(!BD || (KS == 1 && !KARA && ABL == 0), "block-diagonal form: the plain lock-step body");
@@ -47,13 +62,13 @@
 
     // operands are pre-tiled: block (row tile, k tile) of A is LA*TM*BK contiguous bytes that are
     // already the swizzled LDS image; same for B.  A stage is two linear copies.
-    const int nk_all = (int)(g.Kp / BK);
+    const int nk_all = GRP ? grp_nk : (int)(g.Kp / BK);
     const int nk = nk_all / KS;                                         // k-tiles of this group (the launcher checks divisibility)
     constexpr int A_BYTES = LA * TM * BK, B_BYTES = LB * TN * BK;       // copied per stage (the first LA / LB planes)
     constexpr int A_STORED = SA * TM * BK, B_STORED = SB * TN * BK;     // stride of a (row tile, k tile) block in memory
     constexpr int A_PIECES = A_BYTES / 1024;
-    const int8_t* Ag = g.A + ((int64_t)tile_m * nk_all + (int64_t)kg * nk) * A_STORED + lane * 16;
-    const int8_t* Bg = g.B + ((int64_t)tile_n * nk_all + (int64_t)kg * nk) * B_STORED + lane * 16;
+    const int8_t* Ag = g.A + (GRP ? grp_a : ((int64_t)tile_m * nk_all + (int64_t)kg * nk) * A_STORED) + lane * 16;
+    const int8_t* Bg = g.B + (GRP ? grp_b : ((int64_t)tile_n * nk_all + (int64_t)kg * nk) * B_STORED) + lane * 16;
 
     auto issue = [&](int stage, int kt) {
         char* sbase = smem + stage * STAGE;
@@ -229,7 +244,7 @@
     // run of 4 rows is one 4/8/16/32-byte store per lane.
     const QStep st = g.to_c;
     char* C = (char*)g.C;
-    const int64_t tile_base = (BD ? bd_c_tile : ((int64_t)tile_m * tiles_n + tile_n)) * TM * TN;
+    const int64_t tile_base = GRP ? grp_c : (BD ? bd_c_tile : ((int64_t)tile_m * tiles_n + tile_n)) * TM * TN;
     using S = std::conditional_t<(NW == 1), int32_t, int64_t>;  // one limb pair: the int32 accumulator is the dot product
 #pragma unroll
     for (int i = 0; i < TI; ++i)
@@ -254,7 +269,7 @@
                 }
                 if constexpr (NW > 1) {
                     if (g.rsA) {   // centred operands (QPackedGeom::offs): sum a b = sum a'b' - biasB rsA[row] - biasA rsB[col] + K biasA biasB (wrapping)
-                        const uint64_t cj = (uint64_t)g.corr - (uint64_t)g.biasA * (uint64_t)g.rsB[(int64_t)tile_n * TN + (wn * TJ + j) * 32 + fr];
+                        const uint64_t cj = (uint64_t)(GRP ? grp_corr : g.corr) - (uint64_t)g.biasA * (uint64_t)g.rsB[(int64_t)tile_n * TN + (wn * TJ + j) * 32 + fr];
                         const int64_t* ra = g.rsA + (int64_t)tile_m * TM + (wm * TI + i) * 32 + 4 * fh;
 #pragma unroll
                         for (int e = 0; e < 16; ++e) s[e] = (S)((uint64_t)s[e] + cj - (uint64_t)g.biasB * (uint64_t)ra[(e & 3) + 8 * (e >> 2)]);
@@ -264,7 +279,7 @@
             bool converted = false;
             if constexpr (NW == 1 && !KARA) {
                 if (g.rsA) {   // a centred single-limb pair: the sum needs 64 bits, its image in C (at most 31 bits: qg_api.hip) does not
-                    const uint64_t cj = (uint64_t)g.corr - (uint64_t)g.biasA * (uint64_t)g.rsB[(int64_t)tile_n * TN + (wn * TJ + j) * 32 + fr];
+                    const uint64_t cj = (uint64_t)(GRP ? grp_corr : g.corr) - (uint64_t)g.biasA * (uint64_t)g.rsB[(int64_t)tile_n * TN + (wn * TJ + j) * 32 + fr];
                     const int64_t* ra = g.rsA + (int64_t)tile_m * TM + (wm * TI + i) * 32 + 4 * fh;
 #pragma unroll
                     for (int e = 0; e < 16; ++e)

@@ -28,7 +28,7 @@ template <int LA, int LB, int BK, int WGM, int WGN, int TI, int TJ, int NSTAGE, 
 __global__ __launch_bounds__(64 * WGM * WGN) void k_mfma_ep_bd(QMfmaEpBdArgs g)
 {
     constexpr int ABL = 0, KS = 1;
-    constexpr bool EP = true, KARA = false, BD = true;
+    constexpr bool EP = true, KARA = false, BD = true, GRP = false;
 #include "qg_mfma_body.h"
 }
 

@@ -608,6 +608,13 @@ hipError_t qg_launch_pack(const QOperandGeom& g, const QPackedGeom& p, const voi
     return launch_pack(g, p, src, dst, check_range, range_flag, st, generic, true);
 }
 
+hipError_t qg_launch_pack_member(const QOperandGeom& g, const QPackedGeom& p, const void* src, void* dst, int check_range, int* range_flag,
+                                 hipStream_t st, int generic)
+{
+    if (p.limbs < 1 || p.digit6 || g.parts != 1) return hipErrorInvalidValue;
+    return launch_pack(g, p, src, dst, check_range, range_flag, st, generic, false);
+}
+
 hipError_t qg_launch_pack_stack(const QOperandGeom& g, const QPackedGeom& member, const QPackedGeom& stack, int64_t batch, const void* src,
                                 int64_t stride_bytes, void* dst, int check_range, int* range_flag, hipStream_t st, int generic)
 {

@@ -375,6 +375,126 @@ int qgemul_run_batched_epx(const qgemul_desc* d, int64_t batch, const qgemul_epi
     return run_one_shot(r);
 }
 
+// ---- grouped Qgemul: `groups` GEMMs of different shapes (include/qgemul.h) ----
+// The plan lives in the calling thread's one-plan cache, keyed on the WHOLE descriptor list: g_grp_key holds the list the cached
+// plan was made from, and the cache's QRunKey marks the plan as a grouped one (batch = -groups: no plain or batched request has it).
+namespace {
+struct GrpKey {
+    qgemul_desc* d = nullptr;
+    int64_t n = 0;
+    ~GrpKey() { delete[] d; }
+};
+thread_local GrpKey g_grp_key;
+bool grp_key_equal(const qgemul_desc* d, int64_t groups)
+{
+    if (g_grp_key.n != groups || !g_grp_key.d) return false;
+    for (int64_t g = 0; g < groups; ++g)
+        if (!same_desc(g_grp_key.d[g], d[g])) return false;
+    return true;
+}
+int64_t up256(int64_t x) { return (x + 255) / 256 * 256; }
+} // namespace
+
+int qgemul_run_grouped(const qgemul_desc* d, int64_t groups, void* const* C, const void* const* A, const void* const* B, const int64_t* lda,
+                       const int64_t* ldb, const int64_t* ldc, const qgemul_opts* o)
+{
+    if (!d || !C || !A || !B || groups < 1 || groups > 0x7fffffffll) return QG_EINVAL;
+    qgemul_opts opts = resolve_opts(o);
+    if (opts.flags & QG_OPT_ALL_DEVICES) return QG_EUNSUPPORTED;   // (the sharded entry has no grouped form)
+    bool gaps = false;
+    for (int64_t g = 0; g < groups; ++g) {
+        if (d[g].M == 0 || d[g].N == 0) continue;
+        if (!C[g] || !A[g] || !B[g]) return QG_EINVAL;
+        if (member_extent(d[g], QG_OPERAND_A, lda ? lda[g] : 0) < 1 || member_extent(d[g], QG_OPERAND_B, ldb ? ldb[g] : 0) < 1 ||
+            member_extent(d[g], QG_OPERAND_C, ldc ? ldc[g] : 0) < 1)
+            return QG_EINVAL;
+        gaps |= ldc && ldc[g] && ldc[g] != d[g].M;
+    }
+    arm_reaper();
+    RunCache& c = g_run;
+    if (opts.device < 0 && c.ctx) {
+        int cur = c.device;
+        if (hipGetDevice(&cur) == hipSuccess) opts.device = cur;
+    }
+    qg_run_key_set(g_want, d[0], opts.flags, -groups, nullptr, nullptr);
+    const bool same_plan = c.plan && qg_run_key_equal(c.key, g_want) && grp_key_equal(d, groups) && (opts.device < 0 || opts.device == c.device);
+    if (!same_plan) {   // validate before touching the device
+        qgemul_info info;
+        if (const int st = qgemul_classify_grouped(d, groups, opts.flags, &info); st != QG_OK) return st;
+    }
+    int st = QG_OK;
+    const bool warm = c.ctx && (opts.device < 0 || opts.device == c.device);
+    if ((st = cache_context(c, opts.device))) return st;
+    if (warm) QG_HIP(hipSetDevice(c.device));
+    if (!same_plan) {
+        if (c.plan) { qgemul_plan_destroy(c.plan); c.plan = nullptr; }
+        st = qgemul_plan_create_grouped(c.ctx, d, groups, opts.flags, &c.plan);
+        if (st != QG_OK) { c.plan = nullptr; return st; }
+        c.key = g_want;
+        delete[] g_grp_key.d;
+        g_grp_key.d = new (std::nothrow) qgemul_desc[groups];
+        g_grp_key.n = g_grp_key.d ? groups : 0;
+        for (int64_t g = 0; g < g_grp_key.n; ++g) g_grp_key.d[g] = d[g];
+    }
+    qgemul_plan* p = c.plan;
+    // the members' host-layout tensors back to back on the device, every start 256-byte aligned
+    int64_t* off = new (std::nothrow) int64_t[3 * groups + 3];
+    const void** dptr = new (std::nothrow) const void*[3 * groups];
+    do {
+        if (!off || !dptr) { st = QG_EINVAL; break; }
+        int64_t tot[3] = {0, 0, 0};
+        for (int64_t g = 0; g < groups; ++g) {
+            const bool empty = d[g].M == 0 || d[g].N == 0;
+            const int64_t ld[3] = {lda ? lda[g] : 0, ldb ? ldb[g] : 0, ldc ? ldc[g] : 0};
+            for (int w = 0; w < 3; ++w) {
+                off[3 * g + w] = tot[w];
+                const qfmt* f = w == 0 ? d[g].a : w == 1 ? d[g].b : d[g].c;
+                if (!empty) tot[w] += up256(member_extent(d[g], w, ld[w]) * (int64_t)qg_host_elem(f, d[g].is_complex).size);
+            }
+        }
+        void *dA, *dB, *dC, *pA, *pB, *pC;
+        if ((st = cache_buffer(c, 0, (size_t)tot[0], &dA)) || (st = cache_buffer(c, 1, (size_t)tot[1], &dB)) || (st = cache_buffer(c, 2, (size_t)tot[2], &dC)) ||
+            (st = cache_buffer(c, 3, (size_t)p->info.packed_bytes[0], &pA)) || (st = cache_buffer(c, 4, (size_t)p->info.packed_bytes[1], &pB)) ||
+            (st = cache_buffer(c, 5, (size_t)p->info.packed_bytes[2], &pC)))
+            break;
+        hipStream_t s = c.ctx->stream;
+        void* base[3] = {dA, dB, dC};
+        auto bytes_of = [&](int64_t g, int w) {
+            const int64_t ld = w == 0 ? (lda ? lda[g] : 0) : w == 1 ? (ldb ? ldb[g] : 0) : (ldc ? ldc[g] : 0);
+            const qfmt* f = w == 0 ? d[g].a : w == 1 ? d[g].b : d[g].c;
+            return (size_t)(member_extent(d[g], w, ld) * (int64_t)qg_host_elem(f, d[g].is_complex).size);
+        };
+        for (int64_t g = 0; g < groups && st == QG_OK; ++g) {
+            const bool empty = d[g].M == 0 || d[g].N == 0;
+            for (int w = 0; w < 3; ++w) dptr[3 * g + w] = empty ? nullptr : (const char*)base[w] + off[3 * g + w];
+            if (empty) continue;
+            if (hipMemcpyAsync((void*)dptr[3 * g], A[g], bytes_of(g, 0), hipMemcpyHostToDevice, s) != hipSuccess ||
+                hipMemcpyAsync((void*)dptr[3 * g + 1], B[g], bytes_of(g, 1), hipMemcpyHostToDevice, s) != hipSuccess ||
+                (gaps && hipMemcpyAsync((void*)dptr[3 * g + 2], C[g], bytes_of(g, 2), hipMemcpyHostToDevice, s) != hipSuccess))   // (bytes between columns stay)
+                st = QG_EHIP;
+        }
+        if (st != QG_OK) break;
+        // (the pointer arrays of the entry points: one per operand)
+        const void** pa_ = new (std::nothrow) const void*[3 * groups];
+        if (!pa_) { st = QG_EINVAL; break; }
+        for (int64_t g = 0; g < groups; ++g)
+            for (int w = 0; w < 3; ++w) pa_[w * groups + g] = dptr[3 * g + w];
+        if (!(st = qgemul_pack_grouped(p, QG_OPERAND_A, pa_, lda, pA)) && !(st = qgemul_pack_grouped(p, QG_OPERAND_B, pa_ + groups, ldb, pB)) &&
+            !(st = qgemul_execute_grouped(p, pC, pA, pB)))
+            st = qgemul_unpack_c_grouped(p, pC, (void* const*)(pa_ + 2 * groups), ldc);
+        delete[] pa_;
+        for (int64_t g = 0; g < groups && st == QG_OK; ++g) {
+            if (d[g].M == 0 || d[g].N == 0) continue;
+            if (hipMemcpyAsync(C[g], dptr[3 * g + 2], bytes_of(g, 2), hipMemcpyDeviceToHost, s) != hipSuccess) st = QG_EHIP;
+        }
+    } while (0);
+    const hipError_t e = hipStreamSynchronize(c.ctx->stream);
+    delete[] off;
+    delete[] dptr;
+    if (st == QG_OK && e != hipSuccess) { qg_set_last_hip((int)e); st = QG_EHIP; }
+    return st;
+}
+
 // ---- several GPUs in one process: row bands of C, one per entry of the device list (include/qgemul.h) ----
 // One host thread drives every device: all work is queued asynchronously on each device's own stream (H2D of the band of A
 // and of B, pack, GEMM, peer copy of the packed C band to the root), the root's stream waits for each band's event, unpacks it

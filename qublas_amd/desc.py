@@ -126,6 +126,12 @@ def batched_ep(shared=()) -> "qgemul_batched_ep":
     return b
 
 
+class qgemul_grouped_member(C.Structure):
+    """where member g of a grouped plan lives (include/qgemul.h)"""
+    _fields_ = [("in_launch", C.c_int32), ("launches", C.c_int32), ("off", C.c_int64 * 3), ("bytes", C.c_int64 * 3),
+                ("tiles_m", C.c_int64), ("tiles_n", C.c_int64), ("k_tiles", C.c_int64)]
+
+
 class qgemul_cmul_form(C.Structure):
     _fields_ = [("has_cmul", C.c_int32), ("bits32", C.c_int32), ("max_bits", C.c_int32), ("reserved", C.c_int32)]
 
