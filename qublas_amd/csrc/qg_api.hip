@@ -1,4 +1,5 @@
-// qg_api.hip — the C-ABI of include/qgemul.h: contexts, classification, plans, packing, execution (the one-shot calls: qg_run.hip).
+// qg_api.hip — the C-ABI of include/qgemul.h: contexts, the entry points, plans and their device resources, packing, execution (the
+// planner behind classification and plans: qg_geom.cpp; the one-shot calls: qg_run.hip).
 //
 // There is deliberately no CPU arithmetic path in this library: without a gfx950 device every
 // compute entry point returns QG_ENOGPU.  (The CPU restatement lives in oracle/ and is test
@@ -9,94 +10,7 @@ static thread_local int g_last_hip = 0;
 int qg_last_hip() { return g_last_hip; }
 void qg_set_last_hip(int e) { g_last_hip = e; }
 
-struct HostC { void* C; int64_t ld; };
-// an element-wise chain as the planner sees it: a real chain (im == nullptr) or the two part chains of a complex one
-// a chain that came in through an _epcx entry point and holds a CMUL stage in either part (such a chain is planned in lock step)
-static bool view_has_cmul(const EpView* ev)
-{
-    if (!ev || !ev->cx || !ev->im) return false;
-    for (int p = 0; p < 2; ++p)
-        for (uint32_t k = 0; k < ev->epc->part[p].n_stages && k < QG_MAX_EW; ++k)
-            if (ev->epc->part[p].stage[k].op == QG_EW_CMUL) return true;
-    return false;
-}   // execute_kernel: store the reference layout directly (kernels that can)
-
-static int pow2_bytes(int storage_bits)
-{
-    int b = (storage_bits + 7) / 8;
-    int c = 1;
-    while (c < b) c *= 2;
-    return c;
-}
-
-static int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
-
-// ---- composite linear plans: geometry helpers (see QComposite) ----
-static int64_t comp_sub_bytes(int limbs, int64_t rows_p, int64_t K_p)
-{
-    return round_up((int64_t)limbs * rows_p * K_p + (limbs > 1 ? QG_TRAILER_BYTES : 0), 256);
-}
-// reduction indices of chunk c
-static int64_t comp_chunk_len(const QComposite& q, int64_t K, int c) { return c + 1 < q.nc ? q.kc : K - (int64_t)(q.nc - 1) * q.kc; }
-// the packed sub-operand (chunk c, group g) of operand `which` (0 A, 1 B): its geometry and its byte offset in the packed operand
-static QPackedGeom comp_sub_geom(const QComposite& q, const QPackedGeom& base, int which, int64_t K, int c, int g, int64_t* off)
-{
-    const int* L = which ? q.lb : q.la;
-    const int* L0 = which ? q.lb0 : q.la0;
-    const int ng = which ? q.gb : q.ga;
-    const int64_t K_p = round_up(comp_chunk_len(q, K, c), base.bk);
-    QPackedGeom s = base;
-    s.K_p = K_p;
-    s.limbs = L[g];
-    s.limb0 = L0[g];
-    s.trailer = L[g] > 1 ? (int64_t)L[g] * base.rows_p * K_p : 0;
-    s.digit6 = 0;
-    int64_t o = (int64_t)c * q.chunk_bytes[which];
-    for (int h = 0; h < g && h < ng; ++h) o += comp_sub_bytes(L[h], base.rows_p, K_p);
-    if (off) *off = o;
-    if (base.offs) {   // centred operand: ONE row-sum array behind all sub-operands; the groups that hold digit 0 add their k-chunk to it
-        s.offs = L0[g] == 0 ? 2 : 3;
-        s.rowsum_off = base.rowsum_off - o;
-    }
-    return s;
-}
-// groups of 2-3 limbs, low limbs first
-static int comp_split(int L, int* sizes, int* first)
-{
-    static const int tab[9][3] = {{0, 0, 0}, {1, 0, 0}, {2, 0, 0}, {3, 0, 0}, {2, 2, 0}, {3, 2, 0}, {3, 3, 0}, {3, 2, 2}, {3, 3, 2}};
-    if (L < 1 || L > 8) return 0;
-    int n = 0, f = 0;
-    for (int i = 0; i < 3 && tab[L][i]; ++i) { sizes[n] = tab[L][i]; first[n] = f; f += tab[L][i]; ++n; }
-    return n;
-}
-static bool comp_geometry(int LA, int LB, const qgemul_desc* d, uint32_t flags, QComposite* q, QMfmaCfg* cfg)
-{
-    memset(q, 0, sizeof *q);
-    q->ga = comp_split(LA, q->la, q->la0);
-    q->gb = comp_split(LB, q->lb, q->lb0);
-    if (!q->ga || !q->gb) return false;
-    int maxa = 0, maxb = 0;
-    bool single = true;
-    for (int i = 0; i < q->ga; ++i)
-        for (int j = 0; j < q->gb; ++j) {
-            const QMfmaCfg c = qg_mfma_pick(q->la[i], q->lb[j], d->M, d->N, flags);
-            if (!c.variant) return false;
-            if (i + j == 0) *cfg = c;
-            else if (c.TM != cfg->TM || c.TN != cfg->TN || c.BK != cfg->BK) return false;   // (one packed layout for all pairs)
-            q->var[i][j] = c.variant;
-            if (q->la[i] > maxa) maxa = q->la[i];
-            if (q->lb[j] > maxb) maxb = q->lb[j];
-            single = single && q->la[i] == 1 && q->lb[j] == 1;
-        }
-    // int32 accumulators of a limb weight collect min(la, lb) products of magnitude <= 2^14 per reduction index
-    const int mn = maxa < maxb ? maxa : maxb;
-    const int64_t kmax = (((1ll << 17) - 1) / mn) / 256 * 256;
-    q->nc = (int)((d->K + kmax - 1) / kmax);
-    q->kc = q->nc > 1 ? kmax : d->K;
-    q->slab_bytes = single ? 4 : 8;
-    q->on = 1;
-    return true;
-}
+struct HostC { void* C; int64_t ld; };   // execute_kernel: store the reference layout directly (kernels that can)
 
 // composite plans: run `fn` on every (k-chunk, limb group) sub-operand of A or B — its view of the host tensor (the chunk's
 // reduction indices), its packed geometry, its byte offset inside the packed operand
@@ -109,10 +23,10 @@ static hipError_t comp_for_each_sub(const qgemul_plan* p, int operand, const QOp
     for (int c = 0; c < q.nc; ++c)
         for (int gi = 0; gi < (w ? q.gb : q.ga); ++gi) {
             int64_t off = 0;
-            const QPackedGeom sp = comp_sub_geom(q, base, w, p->desc.K, c, gi, &off);
+            const QPackedGeom sp = qg_comp_sub_geom(q, base, w, p->desc.K, c, gi, &off);
             QOperandGeom sg = g;
             sg.k0 = (int64_t)c * q.kc;
-            sg.K = comp_chunk_len(q, p->desc.K, c);
+            sg.K = qg_comp_chunk_len(q, p->desc.K, c);
             if (hipError_t e = fn(sg, sp, off); e != hipSuccess) return e;
         }
     return hipSuccess;
@@ -126,412 +40,32 @@ static hipError_t comp_zero_rowsums(const qgemul_plan* p, int operand, void* pac
     return hipMemsetAsync((char*)packed_dev + base.rowsum_off, 0, (size_t)base.rows_p * 8, p->ctx->stream);
 }
 
-// fill info + geometry for a descriptor; no GPU access
-// ev: the element-wise chain (nullptr: none); axt / cmt: receive the pre-resolved tables of APPROX / CMUL stages (nullptr: not wanted)
-static int plan_geometry(const qgemul_desc* d, uint32_t flags, const EpView* ev, int64_t batch, QPlanGeom* out, QApproxTable* axt, QCmulStage* cmt)
+// centred operands (QPackedGeom::offs) and base-64 digit layouts (digit6): the limb kernels' epilogues take the bias back out with the
+// row sums before the one round + overflow.  One bias per operand for everything the launch covers; K = 0: no corr (a grouped launch:
+// its records carry K biasA biasB per member)
+static void centre_args(QMfmaArgs& a, const QPackedGeom& ga, const QPackedGeom& gb, const void* packedA, const void* packedB, int64_t K)
 {
-    QAnalysis* const an = &out->an;
-    qgemul_info* const info = &out->info;
-    QPackedGeom *const pa = &out->pa, *const pb = &out->pb;
-    QCGeom* const pc = &out->pc;
-    QHostElem *const ha = &out->ha, *const hb = &out->hb, *const hc = &out->hc;
-    QComposite& comp = out->comp;
-    // batch > 0: the member of a batched plan.  Where k_mfma has a block-diagonal form for it, the tile geometry comes from
-    // qg_mfma_pick_batched (the batch's total tile count, the member's padding waste) and out->bd = 1: the packed layouts then belong
-    // to the batched plan and may differ from the plain plan of the same descriptor
-    out->bd = 0;
-    bool bd = false;
-    QMfmaCfg plain_cfg = {0, 0, 0, 0};   // what qg_mfma_pick chose for the member alone
-    memset(&comp, 0, sizeof comp);
-    const qgemul_epilogue* ep = ev ? ev->re : nullptr;
-    qg_analyze(d, an);
-    memset(info, 0, sizeof *info);
-    snprintf(info->reason, sizeof info->reason, "%s", an->reason);
-    if (an->status != QG_OK) {
-        info->supported = 0;
-        return an->status;
-    }
-    const int parts = d->is_complex ? 2 : 1;
-    *ha = qg_host_elem(d->a, d->is_complex);
-    *hb = qg_host_elem(d->b, d->is_complex);
-    *hc = qg_host_elem(d->c, d->is_complex);
-    info->cls = an->cls;
-    info->max_bits = an->max_bits;
-    info->supported = 1;
-    auto sbits = [&](const qfmt* f) {
-        int m = 0;
-        for (int p = 0; p < parts; ++p) {
-            int b = 1 + (int)f[p].I + (int)f[p].F;
-            if (b > m) m = b;
-        }
-        return m;
-    };
-    info->in_bits[0] = sbits(d->a);
-    info->in_bits[1] = sbits(d->b);
-    info->host_elem_bytes[0] = ha->size;
-    info->host_elem_bytes[1] = hb->size;
-    info->host_elem_bytes[2] = hc->size;
-    info->host_imag_off[0] = ha->off[1];
-    info->host_imag_off[1] = hb->off[1];
-    info->host_imag_off[2] = hc->off[1];
-    const double mnk = (double)d->M * (double)d->N * (double)d->K;
-    info->ops = !d->is_complex ? 2.0 * mnk : (d->cmul == QG_CMUL_TF ? 6.0 * mnk : 8.0 * mnk);
+    if (!ga.offs && !ga.digit6) return;
+    a.rsA = (const int64_t*)((const char*)packedA + ga.rowsum_off);
+    a.rsB = (const int64_t*)((const char*)packedB + gb.rowsum_off);
+    a.biasA = ga.bias;
+    a.biasB = gb.bias;
+    a.corr = (int64_t)((uint64_t)K * (uint64_t)ga.bias * (uint64_t)gb.bias);
+}
 
-    int LA = 0, LB = 0, kernel = QG_KERNEL_NONE;
-    int64_t centreA = 0, centreB = 0;
-    bool centred = false;
-    QMfmaCfg cfg = {0, 0, 0, 0};
-    // RING plans (qg_plan.cpp: ring_plan; qg_mfma_ring.hip): product and every level wrap into one signed format of n <= 32 bits, so
-    // the tree is the dot product modulo 2^n.  The operands keep their first min(L, limbs) balanced digits, L = ceil(n / 8) — no
-    // centring, no base-64 digits, no plane-mask shortcut —, and ONE launch takes any K: the accumulators may wrap.  Descriptors
-    // that are exact anyway keep their exact linear plan, one output column the one-column kernels walk stays with them, and
-    // QG_OPT_FORCE_TREE selects today's tree plan (the invariance arm of the tests).
-    const bool ring = an->ring_ok && !(flags & QG_OPT_FORCE_TREE);
-    if (ring) {
-        const int L = qg_ring_digits(an->ring_n);
-        LA = qg_limbs_for(d->a[0]) < L ? qg_limbs_for(d->a[0]) : L;
-        LB = qg_limbs_for(d->b[0]) < L ? qg_limbs_for(d->b[0]) : L;
-        cfg = QMfmaCfg{QG_MFMA_RING, QG_RING_TM, QG_RING_TN, QG_RING_BK};
-        kernel = L == 1 ? QG_KERNEL_MFMA_I8 : QG_KERNEL_MFMA_I8_LIMB;
-        const int np = qg_ring_products(LA, LB, L);
-        snprintf(info->reason, sizeof info->reason, "linear class: wrapping ring mod 2^%d, %d limb product%s", an->ring_n, np, np == 1 ? "" : "s");
-    } else if (an->linear_ok && !(flags & QG_OPT_FORCE_TREE)) {
-        LA = qg_limbs_for(d->a[0]);
-        LB = qg_limbs_for(d->b[0]);
-        if (d->is_complex) {  // parts are stacked along the row axis and share one limb count
-            const int la2 = qg_limbs_for(d->a[1]), lb2 = qg_limbs_for(d->b[1]);
-            if (la2 > LA) LA = la2;
-            if (lb2 > LB) LB = lb2;
-        }
-        // CENTRED operands (qg_plan.h: qg_limbs_centred; QPackedGeom::offs): x - c in balanced limbs where that saves a limb — signed
-        // formats of 16 / 24 / 32 bits (3 -> 2, 4 -> 3, 5 -> 4 limbs), unsigned formats (uint8: 2 -> 1) — the centre taken back out
-        // with row sums after the dot product.  Real descriptors only (stacked complex parts have different centres).
-        if (!d->is_complex && !(flags & QG_OPT_BALANCED_LIMBS)) {
-            int64_t c = 0;
-            int l = qg_limbs_centred(d->a[0], &c);
-            if (l < LA) { LA = l; centreA = c; centred = true; }
-            l = qg_limbs_centred(d->b[0], &c);
-            if (l < LB) { LB = l; centreB = c; centred = true; }
-            // the row sums are int64.  A 64-bit plan may let them wrap (its whole correction is arithmetic modulo 2^64 and the sum
-            // itself fits); a wide plan (128-bit combine) may not: there an operand's row sums must fit — |x'| < 2^(8 L - 1) * 1.01,
-            // K of them (found by the wide fuzzer: a 56-bit operand over K = 43 519 next to a centred 32-bit one)
-            if (centred && an->wide) {
-                int lgk = 0;
-                while (((int64_t)1 << lgk) < d->K) ++lgk;
-                const bool fitA = 8 * LA + lgk <= 62, fitB = 8 * LB + lgk <= 62;
-                if ((centreB != 0 && !fitA) || (centreA != 0 && !fitB)) {
-                    LA = qg_limbs_for(d->a[0]);
-                    LB = qg_limbs_for(d->b[0]);
-                    centreA = centreB = 0;
-                    centred = false;
-                }
-            }
-        }
-        const int mn = LA < LB ? LA : LB;
-        cfg = qg_mfma_pick(LA, LB, d->M * parts, d->N * parts, (ep ? QG_OPT_LOCKSTEP_TILES : 0u) | flags);   // (the fused / unfused element-wise chain keeps the kernel it was measured on)
-        if (batch > 0 && !d->is_complex && (!ep || !ev->im)) {   // (with a real chain: qgemul_plan_create_batched_epx)
-            const QMfmaCfg bc = qg_mfma_pick_batched(LA, LB, batch, cfg);
-            if (bc.variant) { plain_cfg = cfg; cfg = bc; bd = true; }
-        }
-        // (wide plans: the kernels' own epilogues are 64-bit; the composite plan's combine pass is not.  Centred single-limb pairs: the
-        //  single-limb kernels' epilogue is 32-bit, sum a b of two uint8 operands is not: raw int32 slab + combine pass)
-        // (... except where its image in C fits 31 bits and no element-wise chain follows: the single-limb kernels' epilogues then restore
-        //  the sum in 64 bits themselves)
-        const QStep& tc = an->lin.to_c[0];
-        const bool pp_centred = cfg.variant && !ep && sbits(d->c) <= 31 && (tc.identity || (tc.d >= 0 && tc.W <= 30));   // (every single-limb kernel has the 64-bit branch)
-        if (cfg.variant && (int64_t)mn * d->K <= (1ll << 17) - 1 && !an->wide && !an->generic_only && !(centred && LA == 1 && LB == 1 && !pp_centred))
-            kernel = d->is_complex ? QG_KERNEL_MFMA_CPLX : ((LA == 1 && LB == 1) ? QG_KERNEL_MFMA_I8 : QG_KERNEL_MFMA_I8_LIMB);
-        // (one output column whose tree the one-column kernels can walk: those stream A once at HBM rate; a composite plan would read
-        // it once per limb group and write slabs — the batched Qreduce of 32-bit words with exact level types stays there)
-        else if (!d->is_complex && !(d->N == 1 && (an->gemv_ok || an->gemv_wide_ok) && !(flags & QG_OPT_GENERIC_TREE)) &&
-                 comp_geometry(LA, LB, d, flags, &comp, &cfg)) {
-            // more than 3 limbs, or K beyond the int32 accumulators' exact range: limb groups x k-chunks on the same kernels
-            kernel = (LA == 1 && LB == 1) ? QG_KERNEL_MFMA_I8 : QG_KERNEL_MFMA_I8_LIMB;
-            comp.wide = an->wide;
-            snprintf(info->reason, sizeof info->reason, "linear class: %d k-chunk(s) x %d x %d limb groups on the MFMA kernels, exact %s combine", comp.nc, comp.ga, comp.gb,
-                     comp.wide ? "128-bit" : "64-bit");
-        } else {
-            LA = LB = 0;
-            centred = false;
-            snprintf(info->reason, sizeof info->reason, "linear class, but limbs/K outside the MFMA kernels' range: tree kernel");
-        }
-        if (bd) {
-            // the block-diagonal form takes what ONE launch of a lock-step kernel with its own conversion serves: no composite plan, no
-            // raw-dot-product detour (wide_epilogue below).  A member without it runs on the plain plan's own geometry
-            const QStep& q = an->lin.to_c[0];
-            const bool raw_pass = kernel == QG_KERNEL_MFMA_I8 && !q.identity && (q.W > 30 || (q.d < 0 && an->dot_bits - q.d > 31));
-            if (comp.on || raw_pass || (kernel != QG_KERNEL_MFMA_I8 && kernel != QG_KERNEL_MFMA_I8_LIMB)) {
-                bd = false;
-                if (!comp.on) cfg = plain_cfg;
-            }
-        }
-    }
-    pc->M = d->M;
-    pc->N = d->N;
-    pc->parts = parts;
-    pc->cbytes = pow2_bytes(sbits(d->c));
-    // (a multi-word value in the band the reference mis-compares comes out as its low WORD — int32_t / int64_t — whatever C's
-    // format says: such plans keep the host element's width in packed C)
-    if (an->band && pc->cbytes < (hc->sb[0] > hc->sb[1] ? hc->sb[0] : hc->sb[1])) pc->cbytes = hc->sb[0] > hc->sb[1] ? hc->sb[0] : hc->sb[1];
-    pc->ldc = d->M;
-    pc->elem_bytes = hc->size;
-    for (int p = 0; p < 2; ++p) { pc->off[p] = hc->off[p]; pc->sb[p] = hc->sb[p]; }
-    // Three-digit Karatsuba (qg_mfma_k6.hip): both operands of 17 / 18 value+sign bits (3 limbs each; operands of 2 limbs take 4 or
-    // 6 schoolbook products already), real, not centred, no element-wise chain, a shape the two-group 3 x 3 kernel takes, C in a 4-
-    // or 8-byte container, and ONE product per int32 accumulator exact: K * 126^2 < 2^31.  The planes then hold the unsigned base-64
-    // digits of x + bias on 96-row tiles of A; QG_OPT_SCHOOLBOOK_LIMBS / QG_OPT_LOCKSTEP_TILES keep the balanced limbs.
-    bool k6 = false, ppl33 = false;
-    {
-        static const bool no_kara3 = QG_DIAG_ENV("QG_NO_KARA3");   // A/B switch
-        auto ubits = [](qfmt f) { return (int)f.I + (int)f.F + (f.S ? 1 : 0); };
-        const int cb = pow2_bytes(sbits(d->c));
-        // (what k_mfma_ppl's 3 x 3 body takes: qg_mfma_ppl_applies)
-        ppl33 = kernel == QG_KERNEL_MFMA_I8_LIMB && !comp.on && !d->is_complex && !ep && LA == 3 && LB == 3 && cfg.variant == QG_MFMA_PPL && (cb == 4 || cb == 8);
-        k6 = ppl33 && !no_kara3 && !(flags & QG_OPT_SCHOOLBOOK_LIMBS) && !centred && !an->band && ubits(d->a[0]) >= 13 && ubits(d->a[0]) <= 18 &&
-             ubits(d->b[0]) >= 13 && ubits(d->b[0]) <= 18 && d->K * (int64_t)(126 * 126) < (1ll << 31);
-        if (k6) cfg = QMfmaCfg{QG_MFMA_K6, QG_K6_TM, QG_K6_TN, QG_K6_BK};
-    }
-    if (kernel != QG_KERNEL_NONE) {
-        *pa = QPackedGeom{round_up(d->M, cfg.TM), round_up(d->K, cfg.BK), 1, LA, cfg.TM, cfg.BK};
-        *pb = QPackedGeom{round_up(d->N, cfg.TN), round_up(d->K, cfg.BK), 1, LB, cfg.TN, cfg.BK};
-        if (comp.on) {   // pa / pb: the first sub-operand (group 0 of chunk 0); the others through comp_sub_geom
-            pa->K_p = pb->K_p = round_up(comp.kc, cfg.BK);
-            pa->limbs = comp.la[0];
-            pb->limbs = comp.lb[0];
-        }
-        pc->Mp = pa->rows_p;
-        pc->Np = pb->rows_p;
-        pc->tm = cfg.TM;
-        pc->tn = cfg.TN;
-        if (k6) {   // packed C keeps the 128 x 128 tiles of the other limb plans: callers that size or move packed C see no change
-            pc->Mp = round_up(d->M, 128);
-            pc->tm = 128;
-        }
-        if (d->is_complex) {
-            // the MFMA kernel writes the raw 2Mh x 2Nh dot products into the plan's workspace; the combine
-            // pass writes the packed complex C row-major [2][M][N]
-            pc->Mp = d->M;
-            pc->Np = d->N;
-            pc->tm = pc->tn = 0;
-        }
-    } else {
-        const bool fast = !(flags & QG_OPT_GENERIC_TREE);
-        const QTreeChoice tc = qg_tree_choice(an, d, flags, false);
-        kernel = tc.kernel;
-        // which form of the kernel's steps this descriptor gets (tests assert their coverage through it)
-        if (kernel == QG_KERNEL_TREE_I128)
-            snprintf(info->reason, sizeof info->reason, "exact tree evaluation on 128-bit values (intermediates of %d bits)", an->max_bits);
-        if (kernel == QG_KERNEL_TREE_I32)
-            snprintf(info->reason, sizeof info->reason, "exact tree evaluation; tree kernel steps: %s", qg_form_name(tc.tree));
-        if (kernel == QG_KERNEL_GEMV_I64)
-            snprintf(info->reason, sizeof info->reason, "exact tree evaluation; one-column kernel steps: run-time modes, 64-bit values");
-        if (kernel == QG_KERNEL_GEMV_I32)
-            snprintf(info->reason, sizeof info->reason, "exact tree evaluation; one-column kernel steps: %s", qg_form_name(tc.gemv));
-        if (kernel == QG_KERNEL_TREE_CPLX_I32)
-            snprintf(info->reason, sizeof info->reason, "exact tree evaluation; complex kernel steps: %s", qg_form_name(tc.cplx));
-        // the 32-bit tree kernels walk a perfect binary tree: their operands are zero-padded along K to 2^n_levels leaves
-        // (a node whose right child is a zero leaf / zero subtree is the reference's converting copy of an odd leftover)
-        const bool t64 = kernel == QG_KERNEL_TREE_I64 && an->tree64_ok && fast;   // the 2x2-per-lane 64-bit kernel, not the general one
-        const int64_t Kt = (kernel == QG_KERNEL_TREE_I32 || kernel == QG_KERNEL_TREE_CPLX_I32 || kernel == QG_KERNEL_GEMV_I32 || kernel == QG_KERNEL_GEMV_I64 || t64)
-                               ? ((int64_t)1 << an->tree.n_levels_k) : d->K;   // (n_levels_k: at least 5 levels, qg_plan.h)
-        *pa = QPackedGeom{d->M, Kt, info->in_bits[0] <= 32 ? 4 : 8, 0, 0, 0};
-        *pb = QPackedGeom{d->N, Kt, info->in_bits[1] <= 32 ? 4 : 8, 0, 0, 0};
-        pc->Mp = d->M;
-        pc->Np = d->N;
-        pc->tm = pc->tn = 0;
-    }
-    out->bd = bd ? 1 : 0;
-    info->kernel = kernel;
-    info->limbs[0] = LA;
-    info->limbs[1] = LB;
-    info->packed_bytes[0] = (int64_t)parts * (pa->limbs ? pa->limbs : 1) * pa->rows_p * pa->K_p * pa->cbytes;
-    info->packed_bytes[1] = (int64_t)parts * (pb->limbs ? pb->limbs : 1) * pb->rows_p * pb->K_p * pb->cbytes;
-    // multi-limb operands carry their plane mask in a trailer behind the planes (QPackedGeom::trailer)
-    if (pa->limbs > 1) { pa->trailer = info->packed_bytes[0]; info->packed_bytes[0] += QG_TRAILER_BYTES; }
-    if (pb->limbs > 1) { pb->trailer = info->packed_bytes[1]; info->packed_bytes[1] += QG_TRAILER_BYTES; }
-    if (comp.on) {
-        // the packed operand = every (chunk, group) sub-operand back to back
-        for (int w = 0; w < 2; ++w) {
-            const QPackedGeom& base = w ? *pb : *pa;
-            const int ng = w ? comp.gb : comp.ga;
-            const int* L = w ? comp.lb : comp.la;
-            int64_t full = 0, last = 0;
-            const int64_t Kl = round_up(comp_chunk_len(comp, d->K, comp.nc - 1), base.bk);
-            for (int g = 0; g < ng; ++g) { full += comp_sub_bytes(L[g], base.rows_p, base.K_p); last += comp_sub_bytes(L[g], base.rows_p, Kl); }
-            comp.chunk_bytes[w] = full;
-            info->packed_bytes[w] = (int64_t)(comp.nc - 1) * full + last;
-        }
-        pa->trailer = pb->trailer = 0;   // (per sub-operand: comp_sub_geom)
-        if ((int64_t)comp.ga * comp.gb * pa->rows_p * pb->rows_p * comp.slab_bytes > (64ll << 30)) {
-            info->supported = 0;
-            snprintf(info->reason, sizeof info->reason, "composite linear plan: the slabs of raw dot products would exceed 64 GiB");
-            return QG_EUNSUPPORTED;
-        }
-    }
-    if (centred && kernel != QG_KERNEL_NONE) {   // both operands carry row sums (an uncentred partner: bias 0), behind everything else
-        pa->offs = pb->offs = 1;
-        pa->bias = -centreA;
-        pb->bias = -centreB;
-        pa->rowsum_off = round_up(info->packed_bytes[0], 256);
-        pb->rowsum_off = round_up(info->packed_bytes[1], 256);
-        info->packed_bytes[0] = pa->rowsum_off + pa->rows_p * 8;
-        info->packed_bytes[1] = pb->rowsum_off + pb->rows_p * 8;
-    }
-    // Karatsuba (qg_mfma.hip, KARA): two-limb operands whose biased values fit 12 bits are stored as two unsigned base-64
-    // digits each, and the product takes 3 MFMAs per k-step instead of 4
-    if (!comp.on && !centred) {
-        static const bool no_kara = QG_DIAG_ENV("QG_NO_KARA");   // A/B switch
-        auto ubits = [](qfmt f) { return (int)f.I + (int)f.F + (f.S ? 1 : 0); };
-        // (problems small enough for the 64x64 tiles are latency-bound: measured 9.5 vs 8.9 us at 1024^3, schoolbook kept there)
-        if (!no_kara && !d->is_complex && LA == 2 && LB == 2 && (kernel == QG_KERNEL_MFMA_I8_LIMB) && (cfg.variant == QG_MFMA_LIMB_128 || cfg.variant == QG_MFMA_PPL) && ubits(d->a[0]) <= 12 &&
-            ubits(d->b[0]) <= 12 && d->K * (int64_t)(126 * 126) < (1ll << 31)) {
-            cfg.variant = QG_MFMA_LIMB_128;   // three products on the lock-step Karatsuba kernel (same tiles and k-tiles as QG_MFMA_PPL)
-            for (QPackedGeom* g : {pa, pb}) {
-                const qfmt f = g == pa ? d->a[0] : d->b[0];
-                g->digit6 = 1;
-                g->bias = f.S ? ((int64_t)1 << ((int)f.I + (int)f.F)) : 0;
-                g->rowsum_off = g->trailer + QG_TRAILER_BYTES;
-            }
-            info->packed_bytes[0] += pa->rows_p * 8;
-            info->packed_bytes[1] += pb->rows_p * 8;
-        }
-    }
-    if (k6) {
-        for (QPackedGeom* g : {pa, pb}) {
-            const qfmt f = g == pa ? d->a[0] : d->b[0];
-            g->digit6 = 1;
-            g->bias = f.S ? ((int64_t)1 << ((int)f.I + (int)f.F)) : 0;
-            g->rowsum_off = g->trailer + QG_TRAILER_BYTES;
-        }
-        info->packed_bytes[0] += pa->rows_p * 8;
-        info->packed_bytes[1] += pb->rows_p * 8;
-        snprintf(info->reason, sizeof info->reason, "linear class: three base-64 digits per operand, six products (two-group kernel, 96x128 tiles)");
-    } else if (ppl33) {
-        snprintf(info->reason, sizeof info->reason, "linear class: balanced base-256 limbs, nine products (two-group kernel, 128x128 tiles)");
-    }
-    info->packed_bytes[2] = (int64_t)parts * pc->Mp * pc->Np * pc->cbytes;
-    out->LA = LA;
-    out->LB = LB;
-    out->cfg = cfg;
-    out->variant = cfg.variant;
-    out->pc_c = *pc;
-    if (ep && an->band) {
-        info->supported = 0;
-        snprintf(info->reason, sizeof info->reason, "element-wise chain after a plan whose C can leave its format (multi-word comparison artefact of the reference)");
-        return QG_EUNSUPPORTED;
-    }
-    if (ep) {
-        // D replaces C as the stored result: same index space, D's container and host element
-        if ((d->is_complex != 0) != (ev->im != nullptr)) {
-            info->supported = 0;
-            snprintf(info->reason, sizeof info->reason, d->is_complex ? "complex GEMM: the chain is a qgemul_epilogue_cplx" : "real GEMM: the chain is a qgemul_epilogue");
-            return QG_EINVAL;
-        }
-        QEpTable* t[2] = {&out->ept, &out->ept_im};
-        qfmt df[2] = {ep->d, ep->d};
-        const bool lockstep = view_has_cmul(ev);   // a CMUL stage needs both running values: the part chains are planned together
-        if (ev->cx && !lockstep)
-            for (int k = 0; k < QG_MAX_EW; ++k)
-                if (ev->cx[k]) {
-                    info->supported = 0;
-                    snprintf(info->reason, sizeof info->reason, "a CMUL record for a stage that is no CMUL stage");
-                    return QG_EINVAL;
-                }
-        QEpTable both[2];
-        for (int part = 0; part < parts; ++part) {
-            const qgemul_epilogue* e = part ? ev->im : ep;
-            int ep_bits = 0;
-            char why[96];
-            int st = QG_OK;
-            if (lockstep) {
-                if (part == 0) {
-                    st = qg_analyze_epcx(d->c, ev->epc, ev->cx, both, cmt, &ep_bits, why, sizeof why);
-                    *t[0] = both[0];
-                    *t[1] = both[1];
-                }
-            } else {
-                st = qg_analyze_epx(d->c[part], e, part ? nullptr : ev->ax, t[part], part ? nullptr : axt, &ep_bits, why, sizeof why);
-            }
-            if (st != QG_OK) {
-                info->supported = 0;
-                snprintf(info->reason, sizeof info->reason, "%s", why);
-                return st;
-            }
-            if (ep_bits > info->max_bits) info->max_bits = ep_bits;
-            df[part] = e->d;
-            if (!d->is_complex)
-                for (uint32_t k = 0; k < e->n_stages; ++k)
-                    if (e->stage[k].op == QG_EW_PASS) {
-                        info->supported = 0;
-                        snprintf(info->reason, sizeof info->reason, "QG_EW_PASS: complex chains only");
-                        return QG_EINVAL;
-                    }
-        }
-        if (d->is_complex) {
-            // the two chains describe the same operators: same length; a tensor operand is one packed buffer in one container;
-            // a real operand has no imaginary half to read
-            if (ev->im->n_stages != ep->n_stages) {
-                info->supported = 0;
-                snprintf(info->reason, sizeof info->reason, "complex chain: the part chains differ in length");
-                return QG_EINVAL;
-            }
-            for (int k = 0; k < t[0]->n; ++k) {
-                QEpStage &a = t[0]->st[k], &b = t[1]->st[k];
-                const bool ta = a.op != QG_EW_PASS && !a.scalar, tb = b.op != QG_EW_PASS && !b.scalar;
-                if (ev->e_cplx[k] && ta != tb) {
-                    info->supported = 0;
-                    snprintf(info->reason, sizeof info->reason, "complex chain: a complex tensor operand feeds both parts");
-                    return QG_EINVAL;
-                }
-                if (!ev->e_cplx[k] && ta && tb && !same_fmt(ep->stage[k].e, ev->im->stage[k].e)) {
-                    info->supported = 0;
-                    snprintf(info->reason, sizeof info->reason, "complex chain: a real tensor operand has one format");
-                    return QG_EINVAL;
-                }
-                if (ta && tb) a.ebytes = b.ebytes = a.ebytes > b.ebytes ? a.ebytes : b.ebytes;
-            }
-            t[0]->dbytes = t[1]->dbytes = t[0]->dbytes > t[1]->dbytes ? t[0]->dbytes : t[1]->dbytes;
-        }
-        *hc = qg_host_elem(df, d->is_complex);
-        pc->cbytes = t[0]->dbytes;
-        pc->elem_bytes = hc->size;
-        for (int part = 0; part < 2; ++part) { pc->off[part] = hc->off[part]; pc->sb[part] = hc->sb[part]; }
-        info->host_elem_bytes[2] = hc->size;
-        info->host_imag_off[2] = hc->off[1];
-        info->packed_bytes[2] = (int64_t)parts * pc->Mp * pc->Np * pc->cbytes;
-    }
+// QG_OPT_CHECK_RANGE: the packs between the two raise the context's flag on a raw value outside its declared format
+static int range_check_begin(const qgemul_plan* p, int check)
+{
+    if (check) QG_HIP(hipMemsetAsync(p->ctx->flag_dev, 0, 4, p->ctx->stream));
     return QG_OK;
 }
-
-// Where the chain runs (measurements: profiles/r01v_eltwise.jsonl, chain = scale + bias into C's own type):
-//   3x3-limb kernel, 4096^3: plain 0.458 ms, chain fused into the kernel's epilogue 0.473, chain as a pass 0.490
-//   single-limb 256^2-tile kernel, 8192^2 x 4096: plain 0.280, fused 0.503, pass 0.436  (the fused epilogue spills:
-//   128 accumulator registers stay live; and with one workgroup per CU the matrix cores idle meanwhile)
-// so the default fuses on the limb kernel only, and only chains the planner has bounded by 32-bit arithmetic (a 64-bit
-// chain inside the kernel was measured slower than the pass on every kernel).  Everything else runs as ONE linear,
-// HBM-bound pass over the stored C (all stages and the final conversion in that pass, 5-6 TB/s).
-// The single-limb MFMA kernels keep the dot product in int32 and run their epilogue in 32 bits.  An exact LEFT shift into a C
-// with finer fracBits can leave 32 bits before the overflow handling sees the value (found by tests/extended_fuzz.py:
-// int<10,-3> operands into Qu<5,7>, shift by 13).  Those descriptors store the raw dot products and convert them in the
-// 64-bit linear pass instead, which keeps the hot kernels' epilogue as it is.
-static bool wide_epilogue(const QPlanGeom* p)
+static int range_check_end(const qgemul_plan* p, int check)
 {
-    if (p->comp.on || p->variant == QG_MFMA_RING) return false;   // (the combine pass / the ring kernel's epilogue convert in 64-bit arithmetic anyway)
-    const QStep& q = p->an.lin.to_c[0];
-    // ... and a C format beyond 31 value bits does not fit the 32-bit epilogue's clamp bounds at all (second find of the
-    // extended fuzz runs: int<7,-2> x int<7,-1> into Qu<24,9>)
-    return p->info.kernel == QG_KERNEL_MFMA_I8 && !q.identity && (q.W > 30 || (q.d < 0 && p->an.dot_bits - q.d > 31));
-}
-
-// centred operands (QPackedGeom::offs): the limb kernels' epilogues take the centres back out before the one round + overflow
-static void centre_args(const qgemul_plan* p, QMfmaArgs& a, const void* packedA, const void* packedB)
-{
-    if (!p->pa.offs || p->comp.on) return;
-    a.rsA = (const int64_t*)((const char*)packedA + p->pa.rowsum_off);
-    a.rsB = (const int64_t*)((const char*)packedB + p->pb.rowsum_off);
-    a.biasA = p->pa.bias;
-    a.biasB = p->pb.bias;
-    a.corr = (int64_t)((uint64_t)p->desc.K * (uint64_t)p->pa.bias * (uint64_t)p->pb.bias);
+    int flag = 0;
+    if (!check) return QG_OK;
+    QG_HIP(hipMemcpyAsync(&flag, p->ctx->flag_dev, 4, hipMemcpyDeviceToHost, p->ctx->stream));
+    QG_HIP(hipStreamSynchronize(p->ctx->stream));
+    return flag ? QG_ERANGE : QG_OK;
 }
 
 // plane mask of a packed multi-limb operand (QPackedGeom::trailer); nullptr: all planes
@@ -562,7 +96,7 @@ static QMfmaArgs mfma_args(const qgemul_plan* p, const void* A, const void* B, v
 {
     QMfmaArgs a = mfma_args(p->pa, p->pb, p->variant, A, B, C, cbytes);
     a.to_c = p->an.lin.to_c[0];
-    centre_args(p, a, A, B);
+    if (!p->comp.on) centre_args(a, p->pa, p->pb, A, B, p->desc.K);
     return a;
 }
 
@@ -571,17 +105,33 @@ static uint32_t* g_diag_stamps = nullptr;   // device buffer for in-kernel clock
 extern "C" void qgemul_diag_set_stamps(void* dev) { g_diag_stamps = (uint32_t*)dev; }
 #endif
 
-static bool fuses_epilogue(const QPlanGeom* p, uint32_t flags, bool has_ax, bool has_cmul)
+// the mean time of `iters` calls of once() on the plan's stream, by HIP events, after `warmup` untimed ones
+template <class F>
+static int time_calls(qgemul_plan* p, int warmup, int iters, float* avg_ms, F once)
 {
-    if (has_ax) return false;   // (an APPROX stage: always the pass of qg_approx.hip)
-    if (has_cmul) return false; // (a CMUL stage: always the pass of qg_eltwise_cplx.hip)
-    if (wide_epilogue(p) || p->comp.on || p->variant == QG_MFMA_RING) return false;
-    if (flags & QG_OPT_UNFUSED_EPILOGUE) return false;
-    if (!p->ept.bits32) return false;
-    if (p->info.kernel == QG_KERNEL_MFMA_I8_LIMB && p->LA == 3 && p->LB == 3) return true;
-    return p->info.kernel == QG_KERNEL_MFMA_I8 && (flags & QG_OPT_FUSED_EPILOGUE);
+    QG_ON_DEVICE(p->ctx);
+    hipStream_t st = p->ctx->stream;
+    for (int i = 0; i < warmup; ++i)
+        if (int s = once()) return s;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    int rc = QG_OK;
+    float ms = 0;
+    hipError_t he = hipEventCreate(&e0);
+    if (he == hipSuccess) he = hipEventCreate(&e1);
+    if (he == hipSuccess) he = hipEventRecord(e0, st);
+    for (int i = 0; he == hipSuccess && rc == QG_OK && i < iters; ++i) rc = once();
+    if (he == hipSuccess && rc == QG_OK) he = hipEventRecord(e1, st);
+    if (he == hipSuccess && rc == QG_OK) he = hipEventSynchronize(e1);
+    if (he == hipSuccess && rc == QG_OK) he = hipEventElapsedTime(&ms, e0, e1);
+    if (e0) hipEventDestroy(e0);   // (released on every path)
+    if (e1) hipEventDestroy(e1);
+    if (he != hipSuccess) { g_last_hip = (int)he; return QG_EHIP; }
+    if (rc != QG_OK) return rc;
+    *avg_ms = ms / (float)iters;
+    return QG_OK;
 }
-static bool fuses_epilogue(const qgemul_plan* p) { return fuses_epilogue(p, p->flags, p->has_ax, p->has_cmul); }
+
+static bool fuses_epilogue(const qgemul_plan* p) { return qg_fuses_epilogue(p, p->flags, p->has_ax, p->has_cmul); }
 
 extern "C" {
 
@@ -609,7 +159,7 @@ int classify_view(const qgemul_desc* d, const EpView* ev, uint32_t opt_flags, qg
     if (!d || !out) return QG_EINVAL;
     QPlanGeom* g = new (std::nothrow) QPlanGeom();
     if (!g) return QG_EINVAL;
-    const int st = plan_geometry(d, opt_flags, ev, 0, g, nullptr, nullptr);
+    const int st = qg_plan_geometry(d, opt_flags, ev, 0, g, nullptr, nullptr);
     *out = g->info;
     delete g;
     return st;
@@ -690,7 +240,7 @@ int qgemul_cmul_plan_form(const qgemul_desc* d, const qgemul_epilogue_cplx* ep, 
     memset(out, 0, sizeof *out);
     if (!d->is_complex) return QG_EINVAL;
     const EpView v = {&ep->part[0], &ep->part[1], ep->e_complex, nullptr, ep, cx};
-    if (!view_has_cmul(&v)) {
+    if (!qg_view_has_cmul(&v)) {
         for (int k = 0; k < QG_MAX_EW; ++k)
             if (cx[k]) return QG_EINVAL;
         return QG_OK;
@@ -837,7 +387,7 @@ int plan_create_view(qgemul_ctx* c, const qgemul_desc* d, const EpView* ev, uint
             memcpy(p->e_cplx, ev->e_cplx, sizeof p->e_cplx);
         }
         for (int k = 0; ev->ax && k < QG_MAX_EW; ++k) p->has_ax |= ev->ax[k] != nullptr;
-        p->has_cmul = view_has_cmul(ev) ? 1 : 0;
+        p->has_cmul = qg_view_has_cmul(ev) ? 1 : 0;
         for (int k = 0; p->has_cmul && k < QG_MAX_EW; ++k)
             if (ev->cx[k]) p->cx[k] = *ev->cx[k];
     }
@@ -845,7 +395,7 @@ int plan_create_view(qgemul_ctx* c, const qgemul_desc* d, const EpView* ev, uint
     QApproxTable* axt = p->has_ax ? new (std::nothrow) QApproxTable[QG_MAX_EW] : nullptr;
     if (p->has_ax && !axt) { delete p; return QG_EINVAL; }
     struct AxtGuard { QApproxTable* t; ~AxtGuard() { delete[] t; } } axt_guard = {axt};
-    int st = plan_geometry(d, opt_flags, ev, batch, p, axt, p->has_cmul ? cmt : nullptr);
+    int st = qg_plan_geometry(d, opt_flags, ev, batch, p, axt, p->has_cmul ? cmt : nullptr);
     if (st != QG_OK) { delete p; return st; }
     p->tc = qg_tree_choice(&p->an, d, opt_flags, true);
     // from here on the plan may own device memory: every failure leaves through qgemul_plan_destroy, which frees whatever there is
@@ -859,7 +409,7 @@ int plan_create_view(qgemul_ctx* c, const qgemul_desc* d, const EpView* ev, uint
         const size_t ws = (size_t)(2 * p->pa.rows_p) * (size_t)(2 * p->pb.rows_p) * sizeof(int64_t);
         if (hipMalloc((void**)&p->workspace, ws) != hipSuccess) return fail();
     }
-    if (wide_epilogue(p) && hipMalloc((void**)&p->wide_ws, (size_t)(p->pc_c.Mp * p->pc_c.Np) * sizeof(int32_t)) != hipSuccess) return fail();
+    if (qg_wide_epilogue(p) && hipMalloc((void**)&p->wide_ws, (size_t)(p->pc_c.Mp * p->pc_c.Np) * sizeof(int32_t)) != hipSuccess) return fail();
     if (p->comp.on) {
         const size_t n = (size_t)p->pa.rows_p * (size_t)p->pb.rows_p;
         const size_t sl = n * (size_t)(p->comp.ga * p->comp.gb) * (size_t)p->comp.slab_bytes;
@@ -963,7 +513,7 @@ int qgemul_pack(qgemul_plan* p, int operand, const void* src_dev, int64_t ld, vo
     QOperandGeom g = operand_geom(p, operand, ld);
     const QPackedGeom& pg = operand == QG_OPERAND_A ? p->pa : p->pb;
     const int check = (p->flags & QG_OPT_CHECK_RANGE) ? 1 : 0;
-    if (check) QG_HIP(hipMemsetAsync(p->ctx->flag_dev, 0, 4, p->ctx->stream));
+    if (const int st = range_check_begin(p, check); st != QG_OK) return st;
     if (p->comp.on) {
         QG_HIP(comp_zero_rowsums(p, operand, packed_dev));
         QG_HIP(comp_for_each_sub(p, operand, g, [&](const QOperandGeom& sg, const QPackedGeom& sp, int64_t off) {
@@ -971,13 +521,7 @@ int qgemul_pack(qgemul_plan* p, int operand, const void* src_dev, int64_t ld, vo
         }));
     } else
     QG_HIP(qg_launch_pack(g, pg, src_dev, packed_dev, check, p->ctx->flag_dev, p->ctx->stream, (p->flags & QG_OPT_GENERIC_LAYOUT) ? 1 : 0));
-    if (check) {
-        int flag = 0;
-        QG_HIP(hipMemcpyAsync(&flag, p->ctx->flag_dev, 4, hipMemcpyDeviceToHost, p->ctx->stream));
-        QG_HIP(hipStreamSynchronize(p->ctx->stream));
-        if (flag) return QG_ERANGE;
-    }
-    return QG_OK;
+    return range_check_end(p, check);
 }
 
 int qgemul_pack_f64(qgemul_plan* p, int operand, const double* src_dev, int64_t ld, void* packed_dev)
@@ -1050,7 +594,7 @@ int qgemul_execute(qgemul_plan* p, void* packedC, const void* packedA, const voi
 // container equal to the host element, no raw-dot-product detour
 bool stores_host_c(const qgemul_plan* p)
 {
-    if (p->has_ep || p->desc.is_complex || wide_epilogue(p) || p->comp.on) return false;
+    if (p->has_ep || p->desc.is_complex || qg_wide_epilogue(p) || p->comp.on) return false;
     if (p->info.kernel != QG_KERNEL_MFMA_I8 && p->info.kernel != QG_KERNEL_MFMA_I8_LIMB) return false;
     if (p->variant != QG_MFMA_PP && p->variant != QG_MFMA_PPL && p->variant != QG_MFMA_K6) return false;
     if (p->variant == QG_MFMA_PPL && (p->pa.rows_p / p->cfg.TM) * (p->pb.rows_p / p->cfg.TN) < 256) return false;   // (falls back to the lock-step kernel)
@@ -1164,26 +708,7 @@ int qgemul_apply_epilogue(qgemul_plan* p, void* packedD, const void* packedC, co
 int qgemul_time_apply_epilogue(qgemul_plan* p, void* packedD, const void* packedC, const qgemul_ep_args* args, int warmup, int iters, float* avg_ms)
 {
     if (!p || !avg_ms || iters < 1) return QG_EINVAL;
-    for (int i = 0; i < warmup; ++i)
-        if (int s = qgemul_apply_epilogue(p, packedD, packedC, args)) return s;
-    QG_ON_DEVICE(p->ctx);
-    hipStream_t st = p->ctx->stream;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int rc = QG_OK;
-    float ms = 0;
-    hipError_t he = hipEventCreate(&e0);
-    if (he == hipSuccess) he = hipEventCreate(&e1);
-    if (he == hipSuccess) he = hipEventRecord(e0, st);
-    for (int i = 0; he == hipSuccess && rc == QG_OK && i < iters; ++i) rc = qgemul_apply_epilogue(p, packedD, packedC, args);
-    if (he == hipSuccess && rc == QG_OK) he = hipEventRecord(e1, st);
-    if (he == hipSuccess && rc == QG_OK) he = hipEventSynchronize(e1);
-    if (he == hipSuccess && rc == QG_OK) he = hipEventElapsedTime(&ms, e0, e1);
-    if (e0) hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-    if (he != hipSuccess) { g_last_hip = (int)he; return QG_EHIP; }
-    if (rc != QG_OK) return rc;
-    *avg_ms = ms / (float)iters;
-    return QG_OK;
+    return time_calls(p, warmup, iters, avg_ms, [&] { return qgemul_apply_epilogue(p, packedD, packedC, args); });
 }
 
 int qgemul_execute_ep(qgemul_plan* p, void* packedD, const void* packedA, const void* packedB, const qgemul_ep_args* args)
@@ -1294,8 +819,8 @@ static int execute_composite(qgemul_plan* p, void* packedC, const void* packedA,
         for (int i = 0; i < q.ga; ++i)
             for (int j = 0; j < q.gb; ++j) {
                 int64_t offA = 0, offB = 0;
-                const QPackedGeom sa = comp_sub_geom(q, p->pa, 0, p->desc.K, c, i, &offA);
-                const QPackedGeom sb = comp_sub_geom(q, p->pb, 1, p->desc.K, c, j, &offB);
+                const QPackedGeom sa = qg_comp_sub_geom(q, p->pa, 0, p->desc.K, c, i, &offA);
+                const QPackedGeom sb = qg_comp_sub_geom(q, p->pb, 1, p->desc.K, c, j, &offB);
                 char* slab = (char*)p->comp_slabs + (size_t)(i * q.gb + j) * (size_t)n * (size_t)q.slab_bytes;
                 QMfmaArgs a = mfma_args(sa, sb, q.var[i][j], (const char*)packedA + offA, (const char*)packedB + offB, slab, q.slab_bytes);
                 a.to_c.identity = 1;   // raw dot products
@@ -1356,15 +881,10 @@ static int execute_kernel(qgemul_plan* p, void* packedC, const void* packedA, co
         a.dbg = g_diag_stamps;
 #endif
         if (p->pa.digit6) {
-            a.kara = 1;
-            a.rsA = (const int64_t*)((const char*)packedA + p->pa.rowsum_off);
-            a.rsB = (const int64_t*)((const char*)packedB + p->pb.rowsum_off);
-            a.biasA = p->pa.bias;
-            a.biasB = p->pb.bias;
-            a.corr = p->desc.K * p->pa.bias * p->pb.bias;
+            a.kara = 1;   // (row sums, biases and corr: centre_args)
             a.Mc = pcg.Mp;
         }
-        if (wide_epilogue(p)) {
+        if (qg_wide_epilogue(p)) {
             a.C = p->wide_ws;
             a.cbytes = 4;
             memset(&a.to_c, 0, sizeof a.to_c);
@@ -1527,33 +1047,11 @@ static int time_execute(qgemul_plan* p, void* packedC, const void* packedA, cons
 {
     const bool batched = kind == 1;
     if (!p || !avg_ms || iters < 1 || (kind == 2 ? !p->grp : (p->batch != 0) != batched)) return QG_EINVAL;
-    QG_ON_DEVICE(p->ctx);
-    hipStream_t st = p->ctx->stream;
-    auto once = [&]() {
+    return time_calls(p, warmup, iters, avg_ms, [&] {
         if (kind == 2) return qgemul_execute_grouped(p, packedC, packedA, packedB);
         if (batched) return p->has_ep ? qgemul_execute_batched_ep(p, packedC, packedA, packedB, args) : qgemul_execute_batched(p, packedC, packedA, packedB);
         return p->has_ep ? qgemul_execute_ep(p, packedC, packedA, packedB, args) : qgemul_execute(p, packedC, packedA, packedB);
-    };
-    for (int i = 0; i < warmup; ++i) {
-        int s = once();
-        if (s) return s;
-    }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int rc = QG_OK;
-    float ms = 0;
-    hipError_t he = hipEventCreate(&e0);
-    if (he == hipSuccess) he = hipEventCreate(&e1);
-    if (he == hipSuccess) he = hipEventRecord(e0, st);
-    for (int i = 0; he == hipSuccess && rc == QG_OK && i < iters; ++i) rc = once();
-    if (he == hipSuccess && rc == QG_OK) he = hipEventRecord(e1, st);
-    if (he == hipSuccess && rc == QG_OK) he = hipEventSynchronize(e1);
-    if (he == hipSuccess && rc == QG_OK) he = hipEventElapsedTime(&ms, e0, e1);
-    if (e0) hipEventDestroy(e0);   // (released on every path)
-    if (e1) hipEventDestroy(e1);
-    if (he != hipSuccess) { g_last_hip = (int)he; return QG_EHIP; }
-    if (rc != QG_OK) return rc;
-    *avg_ms = ms / (float)iters;
-    return QG_OK;
+    });
 }
 
 int qgemul_time_execute(qgemul_plan* p, void* packedC, const void* packedA, const void* packedB, int warmup, int iters,
@@ -1570,148 +1068,18 @@ int qgemul_time_execute_ep(qgemul_plan* p, void* packedD, const void* packedA, c
 
 
 // ---- batched Qgemul: `batch` GEMMs of one descriptor at constant strides (include/qgemul.h) ----
-// kernel launches of one qgemul_execute on a plain plan (a 3 x 3 launch pair counts once: its partner returns in its first instructions)
-static int plan_launches(const QPlanGeom* p)
-{
-    if (p->comp.on) return p->comp.nc * (p->comp.ga * p->comp.gb + 1);
-    switch (p->info.kernel) {
-    case QG_KERNEL_MFMA_I8:
-    case QG_KERNEL_MFMA_I8_LIMB: return p->variant != QG_MFMA_RING && wide_epilogue(p) ? 2 : 1;
-    case QG_KERNEL_MFMA_CPLX: return 2;
-    default: return 1;
-    }
-}
-
-int64_t member_extent(const qgemul_desc& d, int operand, int64_t ld)
-{
-    const int64_t rows = operand == QG_OPERAND_A ? (d.transA ? d.K : d.M) : operand == QG_OPERAND_B ? d.K : d.M;
-    const int64_t cols = operand == QG_OPERAND_A ? (d.transA ? d.M : d.K) : d.N;
-    if (!ld) ld = rows;
-    if (ld < rows) return 0;
-    return cols > 0 && rows > 0 ? (cols - 1) * ld + rows : 1;
-}
-
-// the geometry of a batched plan, pure host code: m (zeroed) receives the member's, b (zeroed) the batch's
-// ev: the chain of a batched plan with one (qgemul_plan_create_batched_epx), bep: which of its tensor operands are shared
-static int batched_geometry(const qgemul_desc* d, int64_t batch, uint32_t flags, QPlanGeom* m, qgemul_plan* b, const EpView* ev, const qgemul_batched_ep* bep)
-{
-    if (!d || batch < 1) return QG_EINVAL;
-    bool has_ax = false;
-    for (int k = 0; ev && ev->ax && k < QG_MAX_EW; ++k) has_ax |= ev->ax[k] != nullptr;
-    const int st = plan_geometry(d, flags, ev, batch, m, nullptr, nullptr);
-    b->info = m->info;
-    if (st != QG_OK) return st;
-    const int bd = m->bd;
-    b->desc = *d;
-    b->flags = flags;
-    b->batch = batch;
-    b->bd = bd;
-    b->LA = m->LA;
-    b->LB = m->LB;
-    b->cfg = m->cfg;
-    b->variant = m->variant;
-    b->ha = m->ha;
-    b->hb = m->hb;
-    b->hc = m->hc;
-    b->pc = m->pc;
-    b->member_launches = plan_launches(m);
-    int64_t total[3];
-    bool over = false;
-    if (ev) {
-        // the chain is the member's; what one member's qgemul_execute_ep issues: its kernel and, unless fused, the chain's pass
-        b->has_ep = 1;
-        b->has_ax = has_ax;
-        b->ep = *ev->re;
-        b->ept = m->ept;
-        b->pc_c = m->pc_c;
-        if (!fuses_epilogue(m, flags, has_ax, false)) b->member_launches += 1;
-        // fused form: what fuses_epilogue accepts on arithmetic grounds, on request (the default between the two block-diagonal
-        // forms is the pass until tools/measure_batched_ep.py has decided otherwise: DESIGN.md section 9)
-        b->bd_fused = bd && m->ept.bits32 && !has_ax && (flags & QG_OPT_FUSED_EPILOGUE) && !(flags & QG_OPT_UNFUSED_EPILOGUE);
-        for (int k = 0; k < m->ept.n; ++k) {
-            const QEpStage& s = m->ept.st[k];
-            if (s.scalar || s.op == QG_EW_APPROX) continue;
-            b->e_shared[k] = bep && bep->e_shared[k] ? 1 : 0;
-            // (member by member: 256-byte steps like the other packed operands', so that every member's operand keeps the alignment the
-            // pass's 16-byte loads have on a plain plan)
-            int64_t stack = 0;
-            over |= __builtin_mul_overflow(m->pc.Mp * m->pc.Np, (int64_t)s.ebytes, &b->estride[k]);
-            if (!bd) b->estride[k] = round_up(b->estride[k], 256);
-            over |= __builtin_mul_overflow(b->estride[k], batch, &stack) || stack > (1ll << 60);
-        }
-    }
-    if (bd) {
-        int64_t tiles = 0;
-        over |= __builtin_mul_overflow((m->pa.rows_p / m->cfg.TM) * (m->pb.rows_p / m->cfg.TN), batch, &tiles) || tiles > 0x7fffffffll;
-        QPackedGeom* sg[2] = {&b->pa, &b->pb};
-        const QPackedGeom* mg[2] = {&m->pa, &m->pb};
-        for (int w = 0; w < 2 && !over; ++w) {
-            QPackedGeom& s = *sg[w];
-            s = *mg[w];
-            int64_t planes = 0;
-            over |= __builtin_mul_overflow(s.rows_p, batch, &s.rows_p) || __builtin_mul_overflow((int64_t)s.limbs * s.K_p, s.rows_p, &planes) || planes > (1ll << 60);
-            b->mstride[w] = (int64_t)mg[w]->limbs * mg[w]->rows_p * mg[w]->K_p;
-            int64_t bytes = planes;
-            s.trailer = 0;
-            if (s.limbs > 1) { s.trailer = bytes; bytes += QG_TRAILER_BYTES; }   // ONE plane mask: the OR over every member
-            if (s.offs) {                                                         // ONE row-sum array behind the planes of all members
-                s.rowsum_off = round_up(bytes, 256);
-                bytes = s.rowsum_off + s.rows_p * 8;
-            }
-            total[w] = bytes;
-        }
-        b->mstride[2] = m->info.packed_bytes[2];
-        over |= __builtin_mul_overflow(b->mstride[2], batch, &total[2]);
-        snprintf(b->info.reason, sizeof b->info.reason, "linear class: %lld members in one block-diagonal launch, %dx%d tiles", (long long)batch, m->cfg.TM, m->cfg.TN);
-        if (ev)
-            snprintf(b->info.reason, sizeof b->info.reason, b->bd_fused ? "linear class: %lld members, chain fused into one block-diagonal launch" : "linear class: %lld members, block-diagonal launch + one chain pass over the stack",
-                     (long long)batch);
-    } else {
-        for (int w = 0; w < 3; ++w) {
-            b->mstride[w] = round_up(m->info.packed_bytes[w], 256);
-            over |= __builtin_mul_overflow(b->mstride[w], batch, &total[w]) || total[w] > (1ll << 60);
-        }
-        b->pa = m->pa;
-        b->pb = m->pb;
-        if (ev) {
-            char why[sizeof m->info.reason];
-            memcpy(why, m->info.reason, sizeof why);
-            snprintf(b->info.reason, sizeof b->info.reason, "chain member by member: %.70s", why);
-        }
-    }
-    if (over) {
-        b->info.supported = 0;
-        snprintf(b->info.reason, sizeof b->info.reason, "batched plan: more than 2^31 - 1 tiles / packed operands beyond the address range");
-        return QG_EINVAL;
-    }
-    for (int w = 0; w < 3; ++w) b->info.packed_bytes[w] = total[w];
-    b->info.ops = m->info.ops * (double)batch;
-    return QG_OK;
-}
-
-// a batched plan's host side: *out = the plan (heap, zeroed, then filled; the caller's to release with `delete`, whatever the status:
-// its info says why a descriptor was refused).  ev == nullptr: no chain
-static int batched_plan_new(const qgemul_desc* d, int64_t batch, uint32_t flags, const EpView* ev, const qgemul_batched_ep* bep, qgemul_plan** out)
-{
-    *out = nullptr;
-    qgemul_plan* b = new (std::nothrow) qgemul_plan();
-    QPlanGeom* m = new (std::nothrow) QPlanGeom();   // the member's geometry: needed only while the batch's is derived from it
-    const int st = b && m ? batched_geometry(d, batch, flags, m, b, ev, bep) : QG_EINVAL;
-    delete m;
-    if (!b) return QG_EINVAL;
-    *out = b;
-    return st;
-}
+// what qg_batched_geometry fills (zeroed; on the heap: a QPlanGeom holds the whole analysis)
+struct BatchedGeoms { QPlanGeom m, s; QBatchGeom b; };
 
 int classify_batched_view(const qgemul_desc* d, int64_t batch, const EpView* ev, const qgemul_batched_ep* bep, uint32_t opt_flags, qgemul_info* out, int* launches)
 {
     if (!d) return QG_EINVAL;
-    qgemul_plan* b = nullptr;
-    const int st = batched_plan_new(d, batch, opt_flags, ev, bep, &b);
-    if (!b) return st;
-    if (out && batch >= 1) *out = b->info;
-    if (launches && st == QG_OK) *launches = qgemul_plan_batched_launches(b);
-    delete b;
+    BatchedGeoms* g = new (std::nothrow) BatchedGeoms();
+    if (!g) return QG_EINVAL;
+    const int st = qg_batched_geometry(d, batch, opt_flags, ev, bep, &g->m, &g->s, &g->b);
+    if (out && batch >= 1) *out = g->s.info;
+    if (launches && st == QG_OK) *launches = qg_batched_launches(&g->s, &g->b, ev != nullptr);
+    delete g;
     return st;
 }
 
@@ -1732,10 +1100,22 @@ int qgemul_classify_batched_launches(const qgemul_desc* d, int64_t batch, uint32
 int plan_create_batched_view(qgemul_ctx* c, const qgemul_desc* d, int64_t batch, const EpView* ev, const qgemul_batched_ep* bep, uint32_t opt_flags, qgemul_plan** out)
 {
     if (!c || !d || !out) return QG_EINVAL;
-    qgemul_plan* b = nullptr;
-    int st = batched_plan_new(d, batch, opt_flags, ev, bep, &b);
-    if (!b) return st;
-    if (st == QG_OK) st = plan_create_view(c, d, ev, opt_flags, &b->member, batch);
+    BatchedGeoms* g = new (std::nothrow) BatchedGeoms();
+    qgemul_plan* b = new (std::nothrow) qgemul_plan();
+    int st = g && b ? qg_batched_geometry(d, batch, opt_flags, ev, bep, &g->m, &g->s, &g->b) : QG_EINVAL;
+    if (st == QG_OK) {
+        static_cast<QPlanGeom&>(*b) = g->s;
+        static_cast<QBatchGeom&>(*b) = g->b;
+        b->desc = *d;
+        b->flags = opt_flags;
+        if (ev) {   // the chain is the member's
+            b->has_ep = 1;
+            b->ep = *ev->re;
+            for (int k = 0; ev->ax && k < QG_MAX_EW; ++k) b->has_ax |= ev->ax[k] != nullptr;
+        }
+        st = plan_create_view(c, d, ev, opt_flags, &b->member, batch);
+    }
+    delete g;
     if (st != QG_OK) { delete b; return st; }
     b->ctx = c;
     if (b->has_ep && b->bd && !b->bd_fused) {   // the pass form: the stack's packed C between the two launches
@@ -1758,15 +1138,13 @@ int qgemul_plan_create_batched(qgemul_ctx* c, const qgemul_desc* d, int64_t batc
 int qgemul_plan_batched_launches(const qgemul_plan* p)
 {
     if (!p || p->batch < 1) return QG_EINVAL;
-    if (p->bd) return p->has_ep && !p->bd_fused ? 2 : 1;
-    const int64_t n = p->batch * p->member_launches;
-    return n > 0x7fffffffll ? 0x7fffffff : (int)n;
+    return qg_batched_launches(p, p, p->has_ep != 0);
 }
 
 int qgemul_pack_batched(qgemul_plan* p, int operand, const void* src_dev, int64_t ld, int64_t member_stride, void* packed_dev)
 {
     if (!p || p->batch < 1 || !src_dev || !packed_dev || (operand != QG_OPERAND_A && operand != QG_OPERAND_B)) return QG_EINVAL;
-    const int64_t ext = member_extent(p->desc, operand, ld);
+    const int64_t ext = qg_member_extent(p->desc, operand, ld);
     if (ext < 1 || member_stride < ext) return QG_EINVAL;
     qgemul_plan* m = p->member;
     const int64_t eb = operand == QG_OPERAND_A ? p->ha.size : p->hb.size;
@@ -1778,22 +1156,16 @@ int qgemul_pack_batched(qgemul_plan* p, int operand, const void* src_dev, int64_
     QG_ON_DEVICE(p->ctx);
     const QOperandGeom g = operand_geom(m, operand, ld);
     const int check = (p->flags & QG_OPT_CHECK_RANGE) ? 1 : 0;
-    if (check) QG_HIP(hipMemsetAsync(p->ctx->flag_dev, 0, 4, p->ctx->stream));
+    if (const int st = range_check_begin(p, check); st != QG_OK) return st;
     QG_HIP(qg_launch_pack_stack(g, operand == QG_OPERAND_A ? m->pa : m->pb, operand == QG_OPERAND_A ? p->pa : p->pb, p->batch, src_dev, member_stride * eb,
                                 packed_dev, check, p->ctx->flag_dev, p->ctx->stream, (p->flags & QG_OPT_GENERIC_LAYOUT) ? 1 : 0));
-    if (check) {
-        int flag = 0;
-        QG_HIP(hipMemcpyAsync(&flag, p->ctx->flag_dev, 4, hipMemcpyDeviceToHost, p->ctx->stream));
-        QG_HIP(hipStreamSynchronize(p->ctx->stream));
-        if (flag) return QG_ERANGE;
-    }
-    return QG_OK;
+    return range_check_end(p, check);
 }
 
 int qgemul_unpack_c_batched(qgemul_plan* p, const void* packed_dev, void* dst_dev, int64_t ld, int64_t member_stride)
 {
     if (!p || p->batch < 1 || !packed_dev || !dst_dev) return QG_EINVAL;
-    const int64_t ext = member_extent(p->desc, QG_OPERAND_C, ld);
+    const int64_t ext = qg_member_extent(p->desc, QG_OPERAND_C, ld);
     if (ext < 1 || member_stride < ext) return QG_EINVAL;
     for (int64_t b = 0; b < p->batch; ++b)   // (a layout step: one launch per member, the members' packed Cs back to back)
         if (const int st = qgemul_unpack_c(p->member, (const char*)packed_dev + b * p->mstride[2], (char*)dst_dev + b * member_stride * p->hc.size, ld); st != QG_OK) return st;
@@ -1807,13 +1179,7 @@ static QMfmaArgs bd_mfma_args(const qgemul_plan* p, void* packedC, const void* p
     const qgemul_plan* m = p->member;
     QMfmaArgs a = mfma_args(p->pa, p->pb, p->variant, packedA, packedB, packedC, cbytes);
     a.to_c = m->an.lin.to_c[0];
-    if (p->pa.offs) {   // centred operands: one centre per operand for the whole stack (centre_args)
-        a.rsA = (const int64_t*)((const char*)packedA + p->pa.rowsum_off);
-        a.rsB = (const int64_t*)((const char*)packedB + p->pb.rowsum_off);
-        a.biasA = p->pa.bias;
-        a.biasB = p->pb.bias;
-        a.corr = (int64_t)((uint64_t)p->desc.K * (uint64_t)p->pa.bias * (uint64_t)p->pb.bias);
-    }
+    centre_args(a, p->pa, p->pb, packedA, packedB, p->desc.K);
     a.bd_tm = (int32_t)(m->pa.rows_p / p->cfg.TM);
     a.bd_tn = (int32_t)(m->pb.rows_p / p->cfg.TN);
     return a;
@@ -1877,7 +1243,7 @@ int qgemul_pack_e_batched(qgemul_plan* p, int stage, const void* src_dev, int64_
 {
     if (!p || p->batch < 1 || !p->has_ep || !src_dev || !packed_dev || stage < 0 || stage >= p->ept.n) return QG_EINVAL;
     if (!p->estride[stage]) return QG_EINVAL;   // a scalar or APPROX stage has no tensor operand
-    const int64_t ext = member_extent(p->desc, QG_OPERAND_C, ld);
+    const int64_t ext = qg_member_extent(p->desc, QG_OPERAND_C, ld);
     if (ext < 1) return QG_EINVAL;
     if (p->e_shared[stage] ? member_stride != 0 : member_stride < ext) return QG_EINVAL;
     const qfmt f[2] = {p->ep.stage[stage].e, p->ep.stage[stage].e};
@@ -1965,235 +1331,32 @@ int qgemul_time_execute_batched_ep(qgemul_plan* p, void* packedD, const void* pa
 
 
 // ---- grouped Qgemul: GEMMs of different shapes in one launch (include/qgemul.h) ----
-// the launch key: what the instantiation of k_mfma_grp and its uniform arguments depend on
-static bool same_launch_key(const QPlanGeom& x, const QPlanGeom& y)
-{
-    return x.LA == y.LA && x.LB == y.LB && x.pa.limbs == y.pa.limbs && x.pb.limbs == y.pb.limbs && x.variant == y.variant && x.cfg.BK == y.cfg.BK &&
-           x.pa.offs == y.pa.offs && x.pb.offs == y.pb.offs && x.pa.bias == y.pa.bias && x.pb.bias == y.pb.bias && x.pc.cbytes == y.pc.cbytes &&
-           !memcmp(&x.an.lin.to_c[0], &y.an.lin.to_c[0], sizeof(QStep));
-}
-
-static bool grp_empty(const qgemul_desc& d) { return d.M == 0 || d.N == 0; }
-
-// the geometry of a grouped plan, pure host code: b (zeroed) receives info and grp
-static int grouped_geometry(const qgemul_desc* d, int64_t groups, uint32_t flags, qgemul_plan* b)
-{
-    if (!d || groups < 1 || groups > 0x7fffffffll) return QG_EINVAL;
-    QGrouped* G = new (std::nothrow) QGrouped();
-    if (!G) return QG_EINVAL;
-    b->grp = G;
-    b->batch = -1;
-    b->flags = flags;
-    b->desc = d[0];
-    G->groups = groups;
-    G->key = -1;
-    G->m = new (std::nothrow) QGrpMember[groups]();
-    G->ud = new (std::nothrow) qgemul_desc[groups];
-    if (!G->m || !G->ud) return QG_EINVAL;
-    // every distinct descriptor once (the comparison of the one-shot cache: qg_run_key.h)
-    for (int64_t g = 0; g < groups; ++g) {
-        int64_t u = 0;
-        while (u < G->n_uniq && !same_desc(G->ud[u], d[g])) ++u;
-        if (u == G->n_uniq) G->ud[G->n_uniq++] = d[g];
-        G->m[g].uniq = (int32_t)u;
-    }
-    G->ug = new (std::nothrow) QPlanGeom[G->n_uniq]();
-    G->u_in = new (std::nothrow) uint8_t[G->n_uniq]();
-    G->up = new (std::nothrow) qgemul_plan*[G->n_uniq]();
-    if (!G->ug || !G->u_in || !G->up) return QG_EINVAL;
-    // batch = groups: an eligible member gets the 64 x 64 geometry of qg_mfma_pick_batched
-    for (int64_t u = 0; u < G->n_uniq; ++u) {
-        const int st = plan_geometry(&G->ud[u], flags, nullptr, groups, &G->ug[u], nullptr, nullptr);
-        if (st != QG_OK) { b->info = G->ug[u].info; return st; }
-    }
-    auto eligible = [&](int64_t u) { return G->ug[u].bd && G->ug[u].pa.K_p >= G->ug[u].cfg.BK; };
-    for (int64_t g = 0; g < groups && G->key < 0; ++g)
-        if (eligible(G->m[g].uniq)) G->key = G->m[g].uniq;
-    for (int64_t u = 0; u < G->n_uniq; ++u)
-        G->u_in[u] = G->key >= 0 && eligible(u) && same_launch_key(G->ug[u], G->ug[G->key]);
-    for (int64_t u = 0; u < G->n_uniq; ++u) {
-        if (G->u_in[u]) continue;
-        // a straggler runs on its own PLAIN plan
-        G->ug[u] = QPlanGeom();
-        const int st = plan_geometry(&G->ud[u], flags, nullptr, 0, &G->ug[u], nullptr, nullptr);
-        if (st != QG_OK) { b->info = G->ug[u].info; return st; }
-    }
-    // layout: the members in the launch back to back, the launch's one trailer and one row-sum array, then the stragglers
-    bool over = false;
-    int64_t cur[3] = {0, 0, 0}, rows[2] = {0, 0}, tiles = 0;
-    double ops = 0;
-    for (int64_t g = 0; g < groups; ++g) {
-        QGrpMember& m = G->m[g];
-        const QPlanGeom& q = G->ug[m.uniq];
-        ops += q.info.ops;
-        m.in_launch = G->u_in[m.uniq];
-        if (!m.in_launch) continue;
-        ++G->n_in;
-        m.pa = q.pa;
-        m.pb = q.pb;
-        m.bytes[0] = (int64_t)q.pa.limbs * q.pa.rows_p * q.pa.K_p;
-        m.bytes[1] = (int64_t)q.pb.limbs * q.pb.rows_p * q.pb.K_p;
-        m.bytes[2] = q.pc.Mp * q.pc.Np * q.pc.cbytes;
-        m.row_a = rows[0];
-        m.row_b = rows[1];
-        for (int w = 0; w < 3; ++w) {
-            m.off[w] = cur[w];
-            over |= __builtin_add_overflow(cur[w], m.bytes[w], &cur[w]) || cur[w] > (1ll << 60);
-        }
-        rows[0] += q.pa.rows_p;
-        rows[1] += q.pb.rows_p;
-        tiles += (q.pa.rows_p / q.cfg.TM) * (q.pb.rows_p / q.cfg.TN);
-        over |= rows[0] > 0x7fffffffll || rows[1] > 0x7fffffffll || tiles > 0x7fffffffll || q.pa.K_p / q.cfg.BK > 0x7fffffffll;
-    }
-    G->n_tiles = tiles;
-    if (G->n_in && !over) {
-        const QPlanGeom& k = G->ug[G->key];
-        QPackedGeom* sg[2] = {&G->sa, &G->sb};
-        for (int w = 0; w < 2; ++w) {
-            QPackedGeom& s = *sg[w];
-            s = w ? k.pb : k.pa;
-            s.rows_p = rows[w];
-            s.K_p = 0;   // (every member has its own)
-            s.trailer = 0;
-            if (s.limbs > 1) { s.trailer = cur[w]; cur[w] += QG_TRAILER_BYTES; }   // ONE plane mask: the OR over every member in the launch
-            if (s.offs) {                                                           // ONE row-sum array over the stack's rows
-                s.rowsum_off = round_up(cur[w], 256);
-                cur[w] = s.rowsum_off + s.rows_p * 8;
-            }
-        }
-        for (int64_t g = 0; g < groups; ++g) {
-            QGrpMember& m = G->m[g];
-            if (!m.in_launch) continue;
-            QPackedGeom* mg[2] = {&m.pa, &m.pb};
-            for (int w = 0; w < 2; ++w) {
-                // trailer and row sums relative to the member's start (both stay positive: they lie behind the planes of ALL members)
-                mg[w]->trailer = sg[w]->trailer ? sg[w]->trailer - m.off[w] : 0;
-                if (sg[w]->offs) {
-                    mg[w]->offs = 2;   // adds to row sums its caller has zeroed
-                    mg[w]->rowsum_off = sg[w]->rowsum_off + (w ? m.row_b : m.row_a) * 8 - m.off[w];
-                }
-            }
-        }
-    }
-    int64_t launches = G->n_in ? 1 : 0;
-    for (int64_t g = 0; g < groups && !over; ++g) {
-        QGrpMember& m = G->m[g];
-        if (m.in_launch) continue;
-        const QPlanGeom& q = G->ug[m.uniq];
-        for (int w = 0; w < 3; ++w) {
-            m.off[w] = round_up(cur[w], 256);
-            m.bytes[w] = q.info.packed_bytes[w];
-            over |= __builtin_add_overflow(m.off[w], m.bytes[w], &cur[w]) || cur[w] > (1ll << 60);
-        }
-        if (!grp_empty(G->ud[m.uniq])) launches += plan_launches(&q);
-    }
-    b->info = G->ug[G->key >= 0 ? G->key : G->m[0].uniq].info;
-    if (over) {
-        b->info.supported = 0;
-        snprintf(b->info.reason, sizeof b->info.reason, "grouped plan: more than 2^31 - 1 tiles / packed operands beyond the address range");
-        return QG_EINVAL;
-    }
-    G->launches = launches > 0x7fffffffll ? 0x7fffffff : (int)launches;
-    for (int w = 0; w < 3; ++w) b->info.packed_bytes[w] = cur[w];
-    b->info.ops = ops;
-    snprintf(b->info.reason, sizeof b->info.reason, "grouped plan: %lld members in one launch (%lld 64x64 tiles), %lld run alone", (long long)G->n_in,
-             (long long)G->n_tiles, (long long)(groups - G->n_in));
-    // the schedule: one record per workgroup (qg_grp.h)
-    if (G->n_tiles > 0) {
-        const QPlanGeom& k = G->ug[G->key];
-        QGrpShape* sh = new (std::nothrow) QGrpShape[G->n_in];
-        int64_t* order = new (std::nothrow) int64_t[G->n_in];
-        G->tiles = new (std::nothrow) QGrpTile[G->n_tiles];
-        if (!sh || !order || !G->tiles) { delete[] sh; delete[] order; return QG_EINVAL; }
-        int64_t n = 0;
-        for (int64_t g = 0; g < groups; ++g) {
-            const QGrpMember& m = G->m[g];
-            if (!m.in_launch) continue;
-            const QPlanGeom& q = G->ug[m.uniq];
-            QGrpShape& s = sh[n++];
-            s.a_off = m.off[0];
-            s.b_off = m.off[1];
-            s.c_off = m.off[2] / q.pc.cbytes;
-            s.corr = (int64_t)((uint64_t)G->ud[m.uniq].K * (uint64_t)k.pa.bias * (uint64_t)k.pb.bias);
-            s.a_blk = (int64_t)q.pa.limbs * q.cfg.TM * q.cfg.BK;
-            s.b_blk = (int64_t)q.pb.limbs * q.cfg.TN * q.cfg.BK;
-            s.c_tile = (int64_t)q.cfg.TM * q.cfg.TN;
-            s.tiles_m = (int32_t)(q.pa.rows_p / q.cfg.TM);
-            s.tiles_n = (int32_t)(q.pb.rows_p / q.cfg.TN);
-            s.nk = (int32_t)(q.pa.K_p / q.cfg.BK);
-            s.row_a = (int32_t)m.row_a;
-            s.row_b = (int32_t)m.row_b;
-            s.tm = q.cfg.TM;
-            s.tn = q.cfg.TN;
-            s.member = (int32_t)g;
-        }
-        // (the alternative order exists in the diagnostic library only: tools/measure_grouped.py)
-        const bool member_order = QG_DIAG_ENV("QG_GRP_MEMBER_ORDER");
-        qg_grp_schedule(sh, n, member_order ? QG_GRP_MEMBER : QG_GRP_DEALT, order, G->tiles);
-        delete[] sh;
-        delete[] order;
-    }
-    return QG_OK;
-}
-
-int grouped_plan_new(const qgemul_desc* d, int64_t groups, uint32_t opt_flags, qgemul_plan** out)
-{
-    *out = nullptr;
-    qgemul_plan* b = new (std::nothrow) qgemul_plan();
-    if (!b) return QG_EINVAL;
-    *out = b;
-    return grouped_geometry(d, groups, opt_flags, b);
-}
-
-static void grouped_plan_drop(qgemul_plan* b)   // a plan that owns no device resource
-{
-    if (!b) return;
-    delete b->grp;
-    delete b;
-}
-
-static void grouped_member_out(const QGrouped* G, int64_t g, qgemul_grouped_member* out)
-{
-    const QGrpMember& m = G->m[g];
-    const QPlanGeom& q = G->ug[m.uniq];
-    memset(out, 0, sizeof *out);
-    out->in_launch = m.in_launch;
-    out->launches = m.in_launch || grp_empty(G->ud[m.uniq]) ? 0 : plan_launches(&q);
-    for (int w = 0; w < 3; ++w) { out->off[w] = m.off[w]; out->bytes[w] = m.bytes[w]; }
-    if (m.in_launch) {
-        out->tiles_m = q.pa.rows_p / q.cfg.TM;
-        out->tiles_n = q.pb.rows_p / q.cfg.TN;
-        out->k_tiles = q.pa.K_p / q.cfg.BK;
-    }
-}
-
 int qgemul_classify_grouped(const qgemul_desc* d, int64_t groups, uint32_t opt_flags, qgemul_info* out)
 {
     if (!d || !out) return QG_EINVAL;
-    qgemul_plan* b = nullptr;
-    const int st = grouped_plan_new(d, groups, opt_flags, &b);
-    if (b && groups >= 1) *out = b->info;
-    grouped_plan_drop(b);
+    QGrouped G{};
+    qgemul_info info{};
+    const int st = qg_grouped_geometry(d, groups, opt_flags, &G, &info);
+    if (groups >= 1) *out = info;
     return st;
 }
 
 int qgemul_classify_grouped_launches(const qgemul_desc* d, int64_t groups, uint32_t opt_flags)
 {
     if (!d) return QG_EINVAL;
-    qgemul_plan* b = nullptr;
-    const int st = grouped_plan_new(d, groups, opt_flags, &b);
-    const int n = st == QG_OK ? b->grp->launches : st;
-    grouped_plan_drop(b);
-    return n;
+    QGrouped G{};
+    qgemul_info info{};
+    const int st = qg_grouped_geometry(d, groups, opt_flags, &G, &info);
+    return st == QG_OK ? G.launches : st;
 }
 
 int qgemul_classify_grouped_member(const qgemul_desc* d, int64_t groups, uint32_t opt_flags, int64_t g, qgemul_grouped_member* out)
 {
     if (!d || !out || g < 0 || g >= groups) return QG_EINVAL;
-    qgemul_plan* b = nullptr;
-    const int st = grouped_plan_new(d, groups, opt_flags, &b);
-    if (st == QG_OK) grouped_member_out(b->grp, g, out);
-    grouped_plan_drop(b);
+    QGrouped G{};
+    qgemul_info info{};
+    const int st = qg_grouped_geometry(d, groups, opt_flags, &G, &info);
+    if (st == QG_OK) qg_grouped_member_out(&G, g, out);
     return st;
 }
 
@@ -2201,11 +1364,15 @@ int qgemul_classify_grouped_member(const qgemul_desc* d, int64_t groups, uint32_
 int qgemul_plan_create_grouped(qgemul_ctx* c, const qgemul_desc* d, int64_t groups, uint32_t opt_flags, qgemul_plan** out)
 {
     if (!c || !d || !out) return QG_EINVAL;
-    qgemul_plan* b = nullptr;
-    int st = grouped_plan_new(d, groups, opt_flags, &b);
-    if (st != QG_OK) { grouped_plan_drop(b); return st; }
+    qgemul_plan* b = new (std::nothrow) qgemul_plan();
+    QGrouped* G = new (std::nothrow) QGrouped();
+    int st = b && G ? qg_grouped_geometry(d, groups, opt_flags, G, &b->info) : QG_EINVAL;
+    if (st != QG_OK) { delete G; delete b; return st; }   // (nothing on the device yet)
     b->ctx = c;
-    QGrouped* G = b->grp;
+    b->grp = G;
+    b->batch = -1;
+    b->flags = opt_flags;
+    b->desc = d[0];
     for (int64_t u = 0; u < G->n_uniq && st == QG_OK; ++u) st = plan_create_view(c, &G->ud[u], nullptr, opt_flags, &G->up[u], G->u_in[u] ? groups : 0);
     if (st == QG_OK && G->n_tiles > 0) {
         DeviceScope scope(c->device);
@@ -2230,7 +1397,7 @@ int qgemul_plan_grouped_launches(const qgemul_plan* p)
 int qgemul_plan_grouped_member(const qgemul_plan* p, int64_t g, qgemul_grouped_member* out)
 {
     if (!p || !p->grp || !out || g < 0 || g >= p->grp->groups) return QG_EINVAL;
-    grouped_member_out(p->grp, g, out);
+    qg_grouped_member_out(p->grp, g, out);
     return QG_OK;
 }
 
@@ -2240,8 +1407,8 @@ int qgemul_pack_grouped(qgemul_plan* p, int operand, const void* const* src_dev,
     const QGrouped* G = p->grp;
     for (int64_t g = 0; g < G->groups; ++g) {   // every member is checked before the first launch
         const qgemul_desc& d = G->ud[G->m[g].uniq];
-        if (grp_empty(d)) continue;
-        if (!src_dev[g] || member_extent(d, operand, ld ? ld[g] : 0) < 1) return QG_EINVAL;
+        if (qg_grp_empty(d)) continue;
+        if (!src_dev[g] || qg_member_extent(d, operand, ld ? ld[g] : 0) < 1) return QG_EINVAL;
     }
     QG_ON_DEVICE(p->ctx);
     hipStream_t st = p->ctx->stream;
@@ -2249,26 +1416,21 @@ int qgemul_pack_grouped(qgemul_plan* p, int operand, const void* const* src_dev,
     const QPackedGeom& s = operand == QG_OPERAND_A ? G->sa : G->sb;
     if (G->n_in) {
         // what belongs to the launch is cleared ONCE; every member then ORs / adds into it (qg_launch_pack_stack does the same)
-        if (check) QG_HIP(hipMemsetAsync(p->ctx->flag_dev, 0, 4, st));
+        if (const int rc = range_check_begin(p, check); rc != QG_OK) return rc;
         if (s.trailer) QG_HIP(hipMemsetAsync((char*)packed_dev + s.trailer, 0, QG_TRAILER_BYTES, st));
         if (s.offs && s.rows_p) QG_HIP(hipMemsetAsync((char*)packed_dev + s.rowsum_off, 0, (size_t)s.rows_p * 8, st));
         for (int64_t g = 0; g < G->groups; ++g) {
             const QGrpMember& m = G->m[g];
-            if (!m.in_launch || grp_empty(G->ud[m.uniq])) continue;
+            if (!m.in_launch || qg_grp_empty(G->ud[m.uniq])) continue;
             const QOperandGeom og = operand_geom(G->up[m.uniq], operand, ld ? ld[g] : 0);
             QG_HIP(qg_launch_pack_member(og, operand == QG_OPERAND_A ? m.pa : m.pb, src_dev[g], (char*)packed_dev + m.off[operand], check, p->ctx->flag_dev, st,
                                          (p->flags & QG_OPT_GENERIC_LAYOUT) ? 1 : 0));
         }
-        if (check) {
-            int flag = 0;
-            QG_HIP(hipMemcpyAsync(&flag, p->ctx->flag_dev, 4, hipMemcpyDeviceToHost, st));
-            QG_HIP(hipStreamSynchronize(st));
-            if (flag) return QG_ERANGE;
-        }
+        if (const int rc = range_check_end(p, check); rc != QG_OK) return rc;
     }
     for (int64_t g = 0; g < G->groups; ++g) {
         const QGrpMember& m = G->m[g];
-        if (m.in_launch || grp_empty(G->ud[m.uniq])) continue;
+        if (m.in_launch || qg_grp_empty(G->ud[m.uniq])) continue;
         if (const int rc = qgemul_pack(G->up[m.uniq], operand, src_dev[g], ld ? ld[g] : 0, (char*)packed_dev + m.off[operand]); rc != QG_OK) return rc;
     }
     return QG_OK;
@@ -2280,12 +1442,12 @@ int qgemul_unpack_c_grouped(qgemul_plan* p, const void* packed_dev, void* const*
     const QGrouped* G = p->grp;
     for (int64_t g = 0; g < G->groups; ++g) {
         const qgemul_desc& d = G->ud[G->m[g].uniq];
-        if (grp_empty(d)) continue;
-        if (!dst_dev[g] || member_extent(d, QG_OPERAND_C, ld ? ld[g] : 0) < 1) return QG_EINVAL;
+        if (qg_grp_empty(d)) continue;
+        if (!dst_dev[g] || qg_member_extent(d, QG_OPERAND_C, ld ? ld[g] : 0) < 1) return QG_EINVAL;
     }
     for (int64_t g = 0; g < G->groups; ++g) {   // (a layout step: one launch per member)
         const QGrpMember& m = G->m[g];
-        if (grp_empty(G->ud[m.uniq])) continue;
+        if (qg_grp_empty(G->ud[m.uniq])) continue;
         if (const int rc = qgemul_unpack_c(G->up[m.uniq], (const char*)packed_dev + m.off[2], dst_dev[g], ld ? ld[g] : 0); rc != QG_OK) return rc;
     }
     return QG_OK;
@@ -2302,12 +1464,7 @@ int qgemul_execute_grouped(qgemul_plan* p, void* packedC, const void* packedA, c
         memset((void*)&a, 0, sizeof a);
         (QMfmaArgs&)a = mfma_args(G->sa, G->sb, k.variant, packedA, packedB, packedC, k.pc.cbytes);
         a.to_c = k.an.lin.to_c[0];
-        if (G->sa.offs) {   // centred operands: one centre per operand for the whole launch, K biasA biasB per member (the records)
-            a.rsA = (const int64_t*)((const char*)packedA + G->sa.rowsum_off);
-            a.rsB = (const int64_t*)((const char*)packedB + G->sb.rowsum_off);
-            a.biasA = G->sa.bias;
-            a.biasB = G->sb.bias;
-        }
+        centre_args(a, G->sa, G->sb, packedA, packedB, 0);
         a.tiles = G->tiles_dev;
         QG_HIP(qg_launch_mfma_grp(k.LA, k.LB, a, G->n_tiles, p->ctx->stream));
     }

@@ -384,7 +384,7 @@ hipError_t launch_gemv_short(const QGemvArgs& g, hipStream_t st)
     return hipGetLastError();
 }
 
-template <int KK>   // (no 32-bit words: long rows only, qg_api.hip keeps short rows on the 64-bit form)
+template <int KK>   // (no 32-bit words: long rows only, qg_geom.cpp keeps short rows on the 64-bit form)
 hipError_t launch_gemv_short(QGemvForm form, const QGemvArgs& g, hipStream_t st)
 {
     switch (form) {

@@ -1,4 +1,4 @@
-// qg_kernels.h — launch interface between the C-ABI layer (qg_api.hip) and the gfx950 kernels.
+// qg_kernels.h — launch interface between the C-ABI layer (qg_api.hip) and the gfx950 kernels; the layouts it launches on: qg_geom.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -8,57 +8,10 @@
 #include <atomic>
 
 #include "qg_eltwise_args.h"
+#include "qg_geom.h"
 #include "qg_grp.h"
 #include "qg_plan.h"
 #include "qg_ring.h"
-
-// geometry of one operand in host (reference) layout as seen by pack / fill / unpack kernels
-struct QOperandGeom {
-    int64_t rows, K;        // logical rows (M for A, N for B) and reduction length
-    int64_t rs, ks;         // host element index of (r,k) = r*rs + k*ks   (column-major tensors)
-    int32_t elem_bytes;     // host element size (complex: whole struct)
-    int32_t off[2], sb[2];  // byte offset / byte width (4|8) of each part inside the element
-    int32_t parts;          // 1 real, 2 complex
-    int32_t W[2], S[2];     // format of each part (range check, synthetic fill)
-    int32_t F[2], Q[2], O[2]; // quantise-on-load: fracBits, QuMode, OfMode of each part
-    int64_t k0;             // this packed operand holds the reduction indices [k0, k0 + K) of the host tensor (a k-chunk of a
-                            // composite linear plan, qg_api.hip; 0 otherwise)
-};
-
-// packed (device-private) layouts
-//   tree  : [part][rows_p][K_p] containers of cbytes (4|8), K contiguous
-//   limbs : int8 balanced base-256 digits, PRE-TILED and PRE-SWIZZLED for the MFMA kernel:
-//           [row tile][k tile][limb][tr rows][bk bytes], where the 16-byte chunk c of row r sits at
-//           slot c ^ ((r / (256/bk)) % (bk/16)).  One (row tile, k tile) block is exactly the LDS
-//           image of that operand for one pipeline stage, so the kernel streams it with lane-linear
-//           LDS-DMA (1 KiB per wave instruction, fully sequential in HBM; no row pitch, hence no
-//           power-of-two-stride channel camping).
-struct QPackedGeom {
-    int64_t rows_p, K_p;    // padded extents (rows_p per part: complex limb operands stack their parts along rows)
-    int32_t cbytes;         // container bytes (tree layout), 1 for limb layout
-    int32_t limbs;          // 0 = tree layout, >0 = limb layout
-    int32_t tr, bk;         // limb layout: rows per tile, k bytes per tile
-    // limb layout with limbs > 1: the planes are followed by a 256-byte trailer whose first word is the OR over all
-    // elements of (1 << l) for every limb l that is non-zero somewhere ("plane mask", written by the pack kernels).  The
-    // MFMA kernel skips the products of planes that are zero everywhere: data that stays inside [-32640, 32639] never
-    // touches the third int8 limb of a 17-bit format, and 4 instead of 9 products are exact for it.
-    int64_t trailer;        // byte offset of the trailer (0: none)
-    // Karatsuba layout (2 x 2 digits, operands of at most 12 value+sign bits): the two planes hold the UNSIGNED base-64 digits
-    // of x + bias (bias = 2^W for a signed format, so the biased value is non-negative; padding holds 0), and int64
-    // row_sum[rows_p] = sum_k (x + bias) follows the trailer — the kernel's epilogue takes the bias back out with it.
-    int32_t digit6;
-    // limb layout: the planes hold digits limb0 .. limb0 + limbs - 1 of the balanced base-256 expansion (a limb GROUP of an
-    // operand of more than 3 limbs, composite linear plans; 0 otherwise)
-    int32_t limb0;
-    // CENTRED operands (offs != 0; qg_plan.h: qg_limbs_centred): the planes hold the balanced digits of x + bias (bias = -centre;
-    // padding holds 0) and int64 row_sum[rows_p] = sum_k (x + bias) sits at rowsum_off — sum a b = sum a'b' - biasB rsA[i]
-    // - biasA rsB[j] + K biasA biasB, taken back out by the MFMA kernels' epilogues / the composite plan's combine pass.
-    // offs 1: this packed operand owns its row sums (the pack zeroes and fills them); 2: a sub-operand of a composite plan adding
-    // its k-chunk to the operand's one array (zeroed by the caller; only the groups with limb0 == 0 add); 3: ... a group that does not
-    int32_t offs, pad_;
-    int64_t bias, rowsum_off;
-};
-enum { QG_TRAILER_BYTES = 256, QG_MASK_WORDS = 64 };
 
 // The plane mask lives in ALL 64 words of the trailer: a pack kernel's waves OR their findings into word (wave id % 64) — on
 // one word the 16 384 atomics of a 4096^2 operand serialise (0.2 ms against 0.03 ms for the pack itself, found when bench.py
@@ -73,15 +26,6 @@ __device__ __forceinline__ unsigned qg_plane_mask(const uint32_t* m)
     return (unsigned)__builtin_amdgcn_readfirstlane(v);
 }
 #endif
-
-struct QCGeom {
-    int64_t M, N, Mp, Np;   // logical / padded extents of packed C
-    int32_t tm, tn;         // 0: row-major [part][Mp][Np]; else tiled [part][Mp/tm][Np/tn][tn cols][tm rows]
-    int32_t cbytes;         // 1|2|4|8 container
-    int32_t parts;
-    int64_t ldc;            // host leading dimension (elements)
-    int32_t elem_bytes, off[2], sb[2];
-};
 
 // element index of (part, m, n) in packed C
 __host__ __device__ inline int64_t qg_c_index(const QCGeom& c, int part, int64_t m, int64_t n)
@@ -163,12 +107,7 @@ hipError_t qg_launch_gemv(const QTreeTable* dev_table, int n_levels, int b_is_bi
 hipError_t qg_launch_tree_cplx_fast(const QTreeTable* dev_table, int n_levels, QCplxForm form, int tf, const void* A, const void* B, void* C,
                                     int64_t M, int64_t N, int64_t K, int cbytes, hipStream_t st);
 
-// linear class on int8 MFMA with LA x LB limbs
-struct QMfmaCfg {
-    int variant;    // QMfmaVariant; 0 = no kernel for this limb combination
-    int TM, TN, BK; // output tile and k-tile (bytes) the packed operands are padded to
-};
-QMfmaCfg qg_mfma_pick(int LA, int LB, int64_t M, int64_t N, uint32_t opt_flags = 0);
+// linear class on int8 MFMA with LA x LB limbs (QMfmaCfg, qg_mfma_pick: qg_geom.h)
 struct QMfmaArgs {
     const int8_t* A;  // [LA][Mp][Kp]
     const int8_t* B;  // [LB][Np][Kp]
@@ -247,9 +186,6 @@ hipError_t qg_launch_mfma_grp(int LA, int LB, const QMfmaGrpArgs& a, int64_t n_t
 // packs its members (p.trailer and p.rowsum_off relative to dst, p.offs == 2 for centred operands)
 hipError_t qg_launch_pack_member(const QOperandGeom& g, const QPackedGeom& p, const void* src, void* dst, int check_range, int* range_flag,
                                  hipStream_t st, int generic = 0);
-// tile geometry of a batched plan; variant 0: no block-diagonal form for this member (it runs member by member on `plain`, the
-// member's own qg_mfma_pick)
-QMfmaCfg qg_mfma_pick_batched(int LA, int LB, int64_t batch, const QMfmaCfg& plain);
 // single limb, 256x256 tiles, 128-byte k-tiles, two wave groups alternating on the matrix cores (qg_mfma_pp.hip; variant 9)
 hipError_t qg_launch_mfma_pp(const QMfmaArgs& a, hipStream_t st);
 // 3 x 3 and 2 x 2 limbs, 128x128 tiles, the two-group scheme with one A limb plane per phase (qg_mfma_ppl.hip; variant 10)
@@ -257,28 +193,9 @@ bool qg_mfma_ppl_applies(int LA, int LB, const QMfmaArgs& a);
 hipError_t qg_launch_mfma_ppl(int limbs, const QMfmaArgs& a, hipStream_t st);   // limbs: 3 (3 x 3, plane masks) or 2 (2 x 2 on two-plane storage)
 // three unsigned base-64 digits per operand, six products, 96x128 tiles, the two-group scheme (qg_mfma_k6.hip; variant 11).  Its
 // packed operands (QPackedGeom::digit6 with 3 planes, 96-row tiles of A) belong to this kernel alone; packed C is the 128 x 128-tiled
-// layout of the other limb plans
-enum { QG_K6_VARIANT = 11, QG_K6_TM = 96, QG_K6_TN = 128, QG_K6_BK = 64 };
+// layout of the other limb plans (QG_K6_*: qg_geom.h)
 bool qg_mfma_k6_applies(const QMfmaArgs& a);
 hipError_t qg_launch_mfma_k6(const QMfmaArgs& a, hipStream_t st);
-
-// QMfmaCfg::variant / QMfmaArgs::variant: which kernel qg_mfma_pick() and plan_geometry (qg_api.hip) chose and qg_launch_mfma
-// starts.  Output tile x k-tile bytes; "limb": any LA x LB other than 1 x 1.
-enum QMfmaVariant {
-    QG_MFMA_NONE = 0,
-    QG_MFMA_128 = 1,         // single limb, k_mfma (32x32x32), 128x128 x 64: more than one workgroup per CU, too few for 256x256
-    QG_MFMA_256 = 2,         // single limb, k_mfma16 (16x16x64), 256x256 x 64, lock-step (QG_OPT_LOCKSTEP_TILES, fused chains)
-    QG_MFMA_LIMB_128 = 3,    // limb, k_mfma16's row-step form (k_mfma where that has no instantiation), 128x128 x 64; Karatsuba 2 x 2
-    QG_MFMA_64 = 5,          // single limb, k_mfma, 64x64 x 64 (diagnostic build: QG_BK64)
-    QG_MFMA_LIMB_64 = 6,     // limb, k_mfma, 64x64 x 64 (small problems; a 5-stage ring at one workgroup per CU)
-    QG_MFMA_64_BK128 = 7,    // single limb, k_mfma, 64x64 x 128 (small problems; two k groups per workgroup for long k)
-    QG_MFMA_128_BK128 = 8,   // single limb, k_mfma, 128x128 x 128 (at most one workgroup per CU)
-    QG_MFMA_PP = 9,          // single limb, k_mfma_pp, 256x256 x 128, two wave groups, persistent (qg_mfma_pp.hip)
-    QG_MFMA_PPL = 10,        // 3 x 3 / 2 x 2 limbs, k_mfma_ppl / k_mfma_ppl22, 128x128 x 64, two wave groups, persistent
-                             // (qg_mfma_ppl.hip); fused chains and narrow C run QG_MFMA_LIMB_128 on the same packed layout
-    QG_MFMA_K6 = QG_K6_VARIANT,       // 11: three base-64 digits, k_mfma_k6, 96x128 x 64 (qg_mfma_k6.hip)
-    QG_MFMA_RING = QG_RING_VARIANT,   // 12: ring plans, k_mfma_ring, 128x128 x 64 (qg_ring.h; launched by qg_launch_mfma_ring)
-};
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is set once per DEVICE (one process may drive several: qgemul_run_sharded);
 // `done` holds one bit per device ordinal of the calling thread's current device
@@ -322,14 +239,6 @@ inline hipError_t qg_persistent_grid(int64_t tiles, unsigned* grid)
 // the conversion into C's format that the epilogues specialise at compile time (FAST): truncation (TRN::TCPL, right shift
 // d >= 0) + SAT::TCPL, a shift and a clamp per value
 inline bool qg_step_is_shift_clamp(const QStep& q) { return !q.identity && q.O == QG_SAT_TCPL && q.Q == QG_TRN_TCPL && q.d >= 0; }
-
-// A/B and ablation switches read from the environment exist only in the diagnostic build (libqugemm_diag.so, -DQG_DIAG,
-// used by tools/); the product library ignores the environment altogether.
-#ifdef QG_DIAG
-#define QG_DIAG_ENV(name) (getenv(name) != nullptr)
-#else
-#define QG_DIAG_ENV(name) false
-#endif
 
 // element-wise epilogue as its own pass (kernels that do not fuse it) and the operand packer; see qg_eltwise.h
 hipError_t qg_launch_eltwise(const QEltwiseArgs& g, hipStream_t st);

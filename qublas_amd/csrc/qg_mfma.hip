@@ -492,66 +492,6 @@ hipError_t launch_ksplit(const QMfmaArgs& a, hipStream_t st)
 
 } // namespace
 
-QMfmaCfg qg_mfma_pick(int LA, int LB, int64_t M, int64_t N, uint32_t opt_flags)
-{
-    QMfmaCfg c = {QG_MFMA_NONE, 0, 0, 0};
-    if (LA < 1 || LB < 1 || LA > 3 || LB > 3) return c;
-    if (LA == 1 && LB == 1) {
-        // 256x256 tiles halve the L2->LDS traffic per MAC; use them once they fill the 256 CUs
-        const int64_t big = ((M + 255) / 256) * ((N + 255) / 256);
-        // two wave groups alternating on the matrix cores, 128-byte k-tiles (qg_mfma_pp.hip); QG_OPT_LOCKSTEP_TILES keeps k_mfma16
-        if (big >= 256) return (opt_flags & QG_OPT_LOCKSTEP_TILES) ? QMfmaCfg{QG_MFMA_256, 256, 256, 64} : QMfmaCfg{QG_MFMA_PP, 256, 256, 128};
-        // small problems: 64x64 tiles once 128x128 ones would leave more than half of the 256 CUs without a workgroup
-        // (1024^2: 64 -> 256 workgroups)
-        const int64_t mid = ((M + 127) / 128) * ((N + 127) / 128);
-        static const bool no_small = QG_DIAG_ENV("QG_NO_SMALL_TILES");   // A/B switch for tools/measure_small.py
-        if (!no_small && mid <= 128 && ((M + 63) / 64) * ((N + 63) / 64) > mid) {
-            // 128-byte k-tiles: these launches are bound by the per-k-tile barrier, DMA issue and exposed fragment reads of a
-            // one-wave-per-SIMD workgroup (~0.2 us per 64-byte k-tile whatever the ring depth), so half as many k-tiles:
-            // 1024^3 5.97 -> 5.35 us, 512^2 x 4096 13.3 -> 10.2 us (profiles/r03n_small_ring.jsonl).  QG_BK64 for A/B.
-            static const bool bk64 = QG_DIAG_ENV("QG_BK64");
-            return bk64 ? QMfmaCfg{QG_MFMA_64, 64, 64, 64} : QMfmaCfg{QG_MFMA_64_BK128, 64, 64, 128};
-        }
-        {   // at most one workgroup per CU: 128-byte k-tiles here as well (2048^2 x 8192 55.3 -> 44.8 us, 1792^2 x 4096 30.8 -> 24.4 us,
-            // 2048^3 15.3 -> 15.2 us); with more workgroups the 96 KB LDS image would cost co-residency.  QG_BK64 for A/B.
-            static const bool bk64 = QG_DIAG_ENV("QG_BK64");
-            if (!bk64 && mid <= 256) return QMfmaCfg{QG_MFMA_128_BK128, 128, 128, 128};
-        }
-        return QMfmaCfg{QG_MFMA_128, 128, 128, 64};
-    }
-    {   // limb kernels: the same small-problem rule (1024^2 outputs: 64 -> 256 workgroups)
-        static const bool no_small = QG_DIAG_ENV("QG_NO_SMALL_TILES");
-        const int64_t mid = ((M + 127) / 128) * ((N + 127) / 128);
-        // 3 x 3 limbs with at least a tile per CU: the two-group kernel (qg_mfma_ppl.hip; same packed layout as QG_MFMA_LIMB_128)
-        // (2 x 2: unless the operands are Karatsuba-eligible, which plan_geometry decides and then returns to QG_MFMA_LIMB_128)
-        if (((LA == 3 && LB == 3) || (LA == 2 && LB == 2)) && mid >= 256 && !(opt_flags & QG_OPT_LOCKSTEP_TILES)) return QMfmaCfg{QG_MFMA_PPL, 128, 128, 64};
-        if (!no_small && mid <= 128 && ((M + 63) / 64) * ((N + 63) / 64) > mid) return QMfmaCfg{QG_MFMA_LIMB_64, 64, 64, 64};
-    }
-    return QMfmaCfg{QG_MFMA_LIMB_128, 128, 128, 64};
-}
-
-// Tile geometry of a batched plan.  The block-diagonal launch exists for members that alone would leave CUs idle: a member the
-// plain planner gives to a two-group kernel or to 256x256 tiles (a tile per CU on its own) has no such form and runs member by
-// member.  Every other member gets 64x64 tiles, the small-problem kernels of qg_mfma_pick: single limb on 128-byte k-tiles,
-// limbs on 64-byte ones.  This rule is NOT the outcome of a 64x64-against-128x128 timing: no 128x128 block-diagonal kernel
-// exists to time.  The single-limb 128x128 instantiation of the body keeps a 320-byte private array in scratch (hipcc's resource
-// report; its non-batched twin does too), which the block-diagonal form may not have (tests/test_batched_resources.py), and
-// the 128x128 limb geometries have not been instantiated.  So neither the batch's total tile count nor
-// the member's padding waste enters yet: with one tile size there is nothing for them to choose between.  What WAS measured is
-// the 64x64 form against the loop of plain launches, 33x to 1100x at the twelve points of tools/measure_batched.py
-// (profiles/batched_measure.jsonl): the loop is bound by its launches, 3 to 11 us per member.
-QMfmaCfg qg_mfma_pick_batched(int LA, int LB, int64_t batch, const QMfmaCfg& plain)
-{
-    const QMfmaCfg none = {QG_MFMA_NONE, 0, 0, 0};
-    if (batch < 1 || LA < 1 || LB < 1 || LA > 3 || LB > 3) return none;
-    switch (plain.variant) {
-    case QG_MFMA_128: case QG_MFMA_64: case QG_MFMA_LIMB_64: case QG_MFMA_64_BK128: case QG_MFMA_128_BK128: case QG_MFMA_LIMB_128: break;
-    default: return none;   // two-group kernels, 256x256 tiles, three-digit and ring plans
-    }
-    if (LA != 1 || LB != 1) return QMfmaCfg{QG_MFMA_LIMB_64, 64, 64, 64};
-    return QMfmaCfg{QG_MFMA_64_BK128, 64, 64, 128};
-}
-
 hipError_t qg_launch_mfma_bd(int LA, int LB, const QMfmaArgs& a, int64_t batch, hipStream_t st)
 {
     if (LA == 1 && LB == 1) {

@@ -278,7 +278,7 @@
             }
             bool converted = false;
             if constexpr (NW == 1 && !KARA) {
-                if (g.rsA) {   // a centred single-limb pair: the sum needs 64 bits, its image in C (at most 31 bits: qg_api.hip) does not
+                if (g.rsA) {   // a centred single-limb pair: the sum needs 64 bits, its image in C (at most 31 bits: qg_geom.cpp) does not
                     const uint64_t cj = (uint64_t)(GRP ? grp_corr : g.corr) - (uint64_t)g.biasA * (uint64_t)g.rsB[(int64_t)tile_n * TN + (wn * TJ + j) * 32 + fr];
                     const int64_t* ra = g.rsA + (int64_t)tile_m * TM + (wm * TI + i) * 32 + 4 * fh;
 #pragma unroll
@@ -295,7 +295,7 @@
             if constexpr (EP) {
                 // the value just converted into C's element type goes through the element-wise chain and is stored
                 // as D: C itself never reaches memory (qg_eltwise.h); 32-bit arithmetic when the planner allows it
-                // (fused only for chains the planner has bounded by 32 bits: qg_api.hip, fuses_epilogue)
+                // (fused only for chains the planner has bounded by 32 bits: qg_geom.cpp, qg_fuses_epilogue)
                 int32_t v[16];
 #pragma unroll
                 for (int e = 0; e < 16; ++e) v[e] = (int32_t)s[e];

@@ -9,7 +9,7 @@
 // k-tile count, its rows of the stack's row sums and its member's K biasA biasB.  The table is const and read-only, the load is
 // wave-uniform; no division and no tile walk happen in the kernel.  The order of the records is the host's schedule.
 // What every workgroup shares travels in QMfmaArgs as before: the limb counts and stored planes (template parameters), the k-tile
-// size, the centres of A and B, C's container and the one conversion into C — the launch key of the planner (qg_api.hip).
+// size, the centres of A and B, C's container and the one conversion into C — the launch key of the planner (qg_geom.cpp).
 // The kernels live in this file, under this name: tests/test_batched_resources.py pins the block-diagonal instantiations of
 // qg_mfma.hip by name and by count.
 #include <hip/hip_runtime.h>

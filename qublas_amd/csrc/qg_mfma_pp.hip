@@ -314,7 +314,7 @@ __global__ __launch_bounds__(512) void k_mfma_pp(QMfmaArgs g)
             }
         };
         // centred operands (QPackedGeom::offs; k_mfma): sum a b = acc - biasB rsA[row] - biasA rsB[col] + K biasA biasB needs more than
-        // 32 bits, its image in C's format (at most 31 bits on this path: qg_api.hip) does not.  rowf / colf: tile-local row and
+        // 32 bits, its image in C's format (at most 31 bits on this path: qg_geom.cpp) does not.  rowf / colf: tile-local row and
         // column of value o of the 16
         auto convert16c = [&](int32_t (&v)[16], auto rowf, auto colf) {
             if (!g.rsA) { convert16(v); return; }

@@ -40,7 +40,7 @@ struct Ctx {
     {
         if (out->status == QG_OK) {
             out->status = st;
-            snprintf(out->reason, sizeof out->reason, "%s", why);
+            snprintf(out->reason, sizeof out->reason, "%.*s", (int)sizeof out->reason - 1, why);   // (a long reason is cut to the field, on purpose)
         }
     }
     void note(Rng r)
@@ -1126,7 +1126,7 @@ void qg_analyze(const qgemul_desc* d, QAnalysis* out)
     // exact 64-bit product of two elements of at most 32 bits.  Then a node is ONE v_add_i32 ... clamp, where the 64-bit tree
     // kernel spends a 64-bit add and a 64-bit clamp; the product is v_mul_hi / v_mul_lo, the shift and a saturation to the word.
     // Runs on the 32-bit tree kernel's frame, which has no run-time-mode form for such a format: the plan
-    // flag QG_OPT_RUNTIME_MODES sends the descriptor to the 64-bit kernel (qg_api.hip).
+    // flag QG_OPT_RUNTIME_MODES sends the descriptor to the 64-bit kernel (qg_geom.cpp).
     if (!out->tree_fast_ok && !cx && !out->wide && !out->generic_only && d->n_levels <= 16 && T.n_levels_k <= 16) {
         const QStep& pq = T.mul[0].q;
         const int bitsA = 1 + (int)d->a[0].I + (int)d->a[0].F, bitsB = 1 + (int)d->b[0].I + (int)d->b[0].F;

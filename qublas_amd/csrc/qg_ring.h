@@ -9,10 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "qg_geom.h"   // QG_RING_*, qg_ring_digits, qg_ring_products: the planner's part
 #include "qg_ops.h"
-
-// QMfmaCfg::variant of a ring plan and the one tile geometry of its kernel (packed C: the 128 x 128 tiles of every limb plan)
-enum { QG_RING_VARIANT = 12, QG_RING_TM = 128, QG_RING_TN = 128, QG_RING_BK = 64 };
 
 struct QRingArgs {
     const int8_t* A;   // [row tile][k tile][LA][128 rows][64 bytes]: the first LA balanced base-256 digits of a (QPackedGeom)
@@ -26,14 +24,5 @@ struct QRingArgs {
     QStep to_c;        // R -> C (identity when C is R)
 };
 
-// digits of a ring of n bits, and the limb products A_i B_j (i < LA, j < LB) of weight i + j below it
-inline int qg_ring_digits(int n) { return (n + 7) / 8; }
-inline int qg_ring_products(int LA, int LB, int L)
-{
-    int c = 0;
-    for (int i = 0; i < LA; ++i)
-        for (int j = 0; j < LB; ++j) c += i + j < L ? 1 : 0;
-    return c;
-}
 // LA, LB: planes stored per operand (1 .. 4, at most L); L: digits of the ring.  hipErrorInvalidValue for anything else
 hipError_t qg_launch_mfma_ring(int LA, int LB, int L, const QRingArgs& a, hipStream_t st);

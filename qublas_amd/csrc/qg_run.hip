@@ -219,7 +219,7 @@ int run_one_shot(const RunRequest& r)
     void *dA, *dB, *dC, *pA, *pB, *pC;
     do {
         // host elements of one member (the plain call: of the whole operand) and, from there, of all of them
-        const int64_t extA = member_extent(*d, QG_OPERAND_A, opts.lda), extB = member_extent(*d, QG_OPERAND_B, opts.ldb), extC = member_extent(*d, QG_OPERAND_C, opts.ldc);
+        const int64_t extA = qg_member_extent(*d, QG_OPERAND_A, opts.lda), extB = qg_member_extent(*d, QG_OPERAND_B, opts.ldb), extC = qg_member_extent(*d, QG_OPERAND_C, opts.ldc);
         if (extA < 1 || extB < 1 || extC < 1) { st = QG_EINVAL; break; }
         const int64_t more = batch > 0 ? batch - 1 : 0;
         const size_t bytesA = (size_t)(more * r.strideA + extA) * p->ha.size;
@@ -286,7 +286,7 @@ int run_view(const qgemul_desc* d, const EpView* ev, void* C, const void* A, con
 int batched_args_ok(const qgemul_desc& d, const qgemul_opts& opts, int64_t strideC, int64_t strideA, int64_t strideB)
 {
     if (opts.flags & QG_OPT_ALL_DEVICES) return QG_EUNSUPPORTED;   // (the sharded entry has no batched form)
-    const int64_t extA = member_extent(d, QG_OPERAND_A, opts.lda), extB = member_extent(d, QG_OPERAND_B, opts.ldb), extC = member_extent(d, QG_OPERAND_C, opts.ldc);
+    const int64_t extA = qg_member_extent(d, QG_OPERAND_A, opts.lda), extB = qg_member_extent(d, QG_OPERAND_B, opts.ldb), extC = qg_member_extent(d, QG_OPERAND_C, opts.ldc);
     if (extA < 1 || extB < 1 || extC < 1 || strideA < extA || strideB < extB || strideC < extC) return QG_EINVAL;
     return QG_OK;
 }
@@ -358,7 +358,7 @@ int qgemul_run_batched_epx(const qgemul_desc* d, int64_t batch, const qgemul_epi
     if (!d || !ep || !D || !A || !B || batch < 1 || ep->n_stages > QG_MAX_EW) return QG_EINVAL;
     const qgemul_opts opts = resolve_opts(o);
     if (const int st = batched_args_ok(*d, opts, strideD, strideA, strideB)) return st;
-    const int64_t extE = member_extent(*d, QG_OPERAND_C, 0);   // (stage operands are tight)
+    const int64_t extE = qg_member_extent(*d, QG_OPERAND_C, 0);   // (stage operands are tight)
     qgemul_batched_ep bep;
     memset(&bep, 0, sizeof bep);
     for (uint32_t k = 0; k < ep->n_stages; ++k) {
@@ -405,8 +405,8 @@ int qgemul_run_grouped(const qgemul_desc* d, int64_t groups, void* const* C, con
     for (int64_t g = 0; g < groups; ++g) {
         if (d[g].M == 0 || d[g].N == 0) continue;
         if (!C[g] || !A[g] || !B[g]) return QG_EINVAL;
-        if (member_extent(d[g], QG_OPERAND_A, lda ? lda[g] : 0) < 1 || member_extent(d[g], QG_OPERAND_B, ldb ? ldb[g] : 0) < 1 ||
-            member_extent(d[g], QG_OPERAND_C, ldc ? ldc[g] : 0) < 1)
+        if (qg_member_extent(d[g], QG_OPERAND_A, lda ? lda[g] : 0) < 1 || qg_member_extent(d[g], QG_OPERAND_B, ldb ? ldb[g] : 0) < 1 ||
+            qg_member_extent(d[g], QG_OPERAND_C, ldc ? ldc[g] : 0) < 1)
             return QG_EINVAL;
         gaps |= ldc && ldc[g] && ldc[g] != d[g].M;
     }
@@ -449,7 +449,7 @@ int qgemul_run_grouped(const qgemul_desc* d, int64_t groups, void* const* C, con
             for (int w = 0; w < 3; ++w) {
                 off[3 * g + w] = tot[w];
                 const qfmt* f = w == 0 ? d[g].a : w == 1 ? d[g].b : d[g].c;
-                if (!empty) tot[w] += up256(member_extent(d[g], w, ld[w]) * (int64_t)qg_host_elem(f, d[g].is_complex).size);
+                if (!empty) tot[w] += up256(qg_member_extent(d[g], w, ld[w]) * (int64_t)qg_host_elem(f, d[g].is_complex).size);
             }
         }
         void *dA, *dB, *dC, *pA, *pB, *pC;
@@ -462,7 +462,7 @@ int qgemul_run_grouped(const qgemul_desc* d, int64_t groups, void* const* C, con
         auto bytes_of = [&](int64_t g, int w) {
             const int64_t ld = w == 0 ? (lda ? lda[g] : 0) : w == 1 ? (ldb ? ldb[g] : 0) : (ldc ? ldc[g] : 0);
             const qfmt* f = w == 0 ? d[g].a : w == 1 ? d[g].b : d[g].c;
-            return (size_t)(member_extent(d[g], w, ld) * (int64_t)qg_host_elem(f, d[g].is_complex).size);
+            return (size_t)(qg_member_extent(d[g], w, ld) * (int64_t)qg_host_elem(f, d[g].is_complex).size);
         };
         for (int64_t g = 0; g < groups && st == QG_OK; ++g) {
             const bool empty = d[g].M == 0 || d[g].N == 0;

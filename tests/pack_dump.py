@@ -65,11 +65,12 @@ def dump(flags):
             pcd = ctx.alloc(pb[2])
             ctx.h2d(pcd, pc)
             ldc = M + pad
-            hc = ctx.alloc(ldc * N * 4)
-            ctx.h2d(hc, np.full(ldc * N, 77, dtype=np.int32))
+            words = ldc * N * int(plan.info.host_elem_bytes[2]) // 4   # (a C of more than 32 storage bits has 8-byte host elements)
+            hc = ctx.alloc(words * 4)
+            ctx.h2d(hc, np.full(words, 77, dtype=np.int32))
             plan.unpack_c(pcd, hc, ldc)
             ctx.sync()
-            res = np.zeros(ldc * N, dtype=np.int32)
+            res = np.zeros(words, dtype=np.int32)
             ctx.d2h(res, hc)
             rec["C"] = hashlib.sha256(res.tobytes()).hexdigest()
             out.append(rec)

@@ -1,4 +1,4 @@
-"""The block-diagonal batched Qgemul (k_mfma_bd, qg_launch_pack_stack, the batched branch of plan_geometry) where tests/test_gpu_batched.py
+"""The block-diagonal batched Qgemul (k_mfma_bd, qg_launch_pack_stack, the batched branch of qg_plan_geometry) where tests/test_gpu_batched.py
 stops (run with -m gpu).  Every case compares each member with the oracle (qoracle_gemm) AND byte for byte with qgemul_execute +
 qgemul_unpack_c of that member through a plain plan; host buffers carry poison between the members and C's gaps must survive; the
 limbs and the launch count the planner answers are asserted BEFORE any device work, so that a case that silently left the form it

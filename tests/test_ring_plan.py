@@ -1,4 +1,4 @@
-"""Which descriptors are ring plans (qublas_amd/csrc/qg_plan.cpp: ring_plan; qg_api.hip: plan_geometry).  Product and every tree level
+"""Which descriptors are ring plans (qublas_amd/csrc/qg_plan.cpp: ring_plan; qg_geom.cpp: qg_plan_geometry).  Product and every tree level
 in ONE signed WRP::TCPL format of n <= 32 bits, entered by an exact left shift: the linear class on the int8 matrix cores, with the
 limb products of weight below 2^n only and no bound on K.  The neighbours — anything that rounds or clamps between the additions —
 keep the tree kernels they had, asserted by kernel name.  CPU only: classification needs no GPU."""

@@ -60,7 +60,7 @@ def test_every_instantiation_fits_two_waves_per_simd(report):
 def test_lds_ring_fits_a_compute_unit():
     src = open(SRC).read()
     assert re.search(r"enum \{ QG_RING_VARIANT = 12, QG_RING_TM = 128, QG_RING_TN = 128, QG_RING_BK = 64 \};",
-                     open(os.path.join(os.path.dirname(SRC), "qg_ring.h")).read())
+                     open(os.path.join(os.path.dirname(SRC), "qg_geom.h")).read())
     lds_max = eval(re.search(r"constexpr int LDS_MAX = ([0-9* ]+);", src).group(1))
     assert lds_max == 160 * 1024
     assert "return 3 * (LA * TM + LB * TN) * BK <= LDS_MAX ? 3 : 2;" in src          # ring_stages
