@@ -640,15 +640,29 @@ struct ApproxStage {
     static constexpr qgemul_approx tab = table();
 };
 
+// operands of a stage of QgemulGrouped (below): std::tie(E0, E1, …) holds one tensor per member; PerMember(s0, s1, …) one scalar per member
+template <class T, size_t G>
+struct PerMemberValues {
+    std::array<T, G> v;
+};
+template <class O> struct is_member_tuple : std::false_type {};
+template <class... T> struct is_member_tuple<std::tuple<T&...>> : std::true_type {};
+template <class O> struct is_per_member : std::false_type {};
+template <class T, size_t G> struct is_per_member<PerMemberValues<T, G>> : std::true_type {};
+
 template <int OP, bool XFIRST, class Into, class Operand, typename... Tags>
 struct EwStage {
     const Operand& e;
     static constexpr bool approx = false;
     static constexpr int op = OP;
     static constexpr bool x_first = XFIRST;
-    static constexpr bool scalar = !requires { typename Operand::elem_t; };   // tensors have an element type
+    static constexpr bool member_tensors = is_member_tuple<Operand>::value;    // QgemulGrouped: one tensor per member
+    static constexpr bool per_member = is_per_member<Operand>::value;          // QgemulGrouped: one scalar per member
+    static constexpr bool scalar = !member_tensors && !requires { typename Operand::elem_t; };   // tensors have an element type
     template <class O, bool = !requires { typename O::elem_t; }> struct elem { using type = O; };
     template <class O> struct elem<O, false> { using type = typename O::elem_t; };
+    template <class T0, class... T> struct elem<std::tuple<T0&, T&...>, true> { using type = typename std::remove_cvref_t<T0>::elem_t; };
+    template <class T, size_t G> struct elem<PerMemberValues<T, G>, true> { using type = T; };
     using e_t = typename elem<Operand>::type;
     static constexpr bool e_complex = e_t::is_complex;
     static constexpr Fmt efmt = re_fmt<e_t>();
@@ -895,6 +909,79 @@ void QgemulBatched(TD& D, const TA& A, const TB& B, const S0& s0, const Stages&.
     opts.flags = QgemulRunFlags();
     const int rc = qgemul_run_batched_epx(&d, batch, &ep, ax.data(), D.data.data(), A.data.data(), B.data.data(), E, strides[0], strides[1], strides[2], strideE, &opts);
     if (rc != QG_OK) throw std::runtime_error(std::string("QgemulBatched: ") + qgemul_strerror(rc));
+}
+
+// ---- the same on a group: member g of D is the chain applied to Qgemul<…>(Cg, Ag, Bg), every member with its own dim<> ----
+//     QgemulGrouped<…, QgemulResult<CT>>(std::tie(D0, D1, …), std::tie(A0, A1, …), std::tie(B0, B1, …),
+//                                        ThenMul<…>(PerMember(s0, s1, …)), ThenAdd<…>(std::tie(Bias0, Bias1, …)), ThenApprox<…>());
+// ONE chain serves the group.  A tensor operand is a std::tie of the members' tensors (member g's has Dg's dim<>); a scalar operand is
+// either one scalar for all members or PerMember(s0, s1, …), one per member: each layer of a model has its own scale.  Real chains
+// (qgemul_run_grouped_epx, qgemul.h): the small linear-class members of one launch key run as one launch (and one pass), every other
+// member on its own plan.
+template <class T, class... R>
+auto PerMember(const T& s0, const R&... r)
+{
+    return detail::PerMemberValues<T, 1 + sizeof...(R)>{{{s0, T(r)...}}};
+}
+template <typename... Tags, class... TD, class... TA, class... TB, class S0, class... Stages>
+void QgemulGrouped(const std::tuple<TD&...>& D, const std::tuple<TA&...>& A, const std::tuple<TB&...>& B, const S0& s0, const Stages&... st)
+{
+    using CT = typename detail::pick_result<Tags...>::type;
+    using DT = typename std::remove_cvref_t<std::tuple_element_t<0, std::tuple<TD...>>>::elem_t;
+    static_assert(!std::is_void_v<CT>, "QgemulGrouped with element-wise operators needs QgemulResult<CT>");
+    static_assert(!CT::is_complex && !DT::is_complex, "QgemulGrouped: element-wise chains on a group are real chains");
+    static_assert((std::is_same_v<typename TD::elem_t, DT> && ...), "QgemulGrouped: one element type for every D");
+    constexpr size_t G = sizeof...(TD);
+    static_assert(G >= 1 && G == sizeof...(TA) && G == sizeof...(TB), "QgemulGrouped: as many As and Bs as Ds, at least one");
+    // member g's descriptor: the Qgemul lowering of (a tensor of Dg's dim<> and the result type CT, Ag, Bg)
+    std::array<qgemul_desc, G> d = [&]<size_t... I>(std::index_sequence<I...>) {
+        return std::array<qgemul_desc, G>{{Qgemul_lower_types<Tags...>(std::type_identity<Qu_s<typename std::remove_cvref_t<std::tuple_element_t<I, std::tuple<TD...>>>::size, CT>>{},
+                                                                        std::type_identity<std::remove_cvref_t<std::tuple_element_t<I, std::tuple<TA...>>>>{},
+                                                                        std::type_identity<std::remove_cvref_t<std::tuple_element_t<I, std::tuple<TB...>>>>{})...}};
+    }(std::make_index_sequence<G>{});
+    for (auto& m : d) m.flags |= QgemulDescFlags();
+    const std::array<void*, G> pd = std::apply([](auto&... t) { return std::array<void*, G>{{(void*)t.data.data()...}}; }, D);
+    const std::array<const void*, G> pa = std::apply([](auto&... t) { return std::array<const void*, G>{{(const void*)t.data.data()...}}; }, A);
+    const std::array<const void*, G> pb = std::apply([](auto&... t) { return std::array<const void*, G>{{(const void*)t.data.data()...}}; }, B);
+    std::array<std::array<const void*, G>, QG_MAX_EW> e{};
+    std::array<std::array<int64_t, G>, QG_MAX_EW> sc{};
+    const void* const* E[QG_MAX_EW] = {};
+    const int64_t* S[QG_MAX_EW] = {};
+    qgemul_grouped_ep gep{};
+    uint32_t k = 0;
+    auto one = [&](const auto& stage) {
+        using St = std::remove_cvref_t<decltype(stage)>;
+        if constexpr (St::approx) {
+            // reads no operand
+        } else if constexpr (St::per_member) {
+            static_assert(std::tuple_size_v<decltype(stage.e.v)> == G, "PerMember: one scalar per member");
+            for (size_t g = 0; g < G; ++g) sc[k][g] = int64_t(stage.e.v[g].data);   // the raw value, as qgemul_ep_args carries it
+            S[k] = sc[k].data();
+            gep.scalar_per_member[k] = 1;
+        } else if constexpr (St::member_tensors) {
+            static_assert(std::tuple_size_v<std::remove_cvref_t<decltype(stage.e)>> == G, "a tensor operand: one tensor per member");
+            e[k] = std::apply([](auto&... t) { return std::array<const void*, G>{{(const void*)t.data.data()...}}; }, stage.e);
+            [&]<size_t... I>(std::index_sequence<I...>) {
+                static_assert((std::is_same_v<typename std::remove_cvref_t<std::tuple_element_t<I, std::remove_cvref_t<decltype(stage.e)>>>::size,
+                                              typename std::remove_cvref_t<std::tuple_element_t<I, std::tuple<TD...>>>::size> && ...), "member g's tensor operand has Dg's shape");
+            }(std::make_index_sequence<G>{});
+            E[k] = e[k].data();
+        } else {
+            static_assert(St::scalar, "a tensor operand of QgemulGrouped is a std::tie of the members' tensors");
+            e[k][0] = &stage.e;                                                      // one element as the tensors store them
+            E[k] = e[k].data();
+        }
+        ++k;
+    };
+    one(s0);
+    (one(st), ...);
+    const qgemul_epilogue ep = detail::lower_chain<S0, Stages...>(CT::fmt, DT::fmt);
+    const auto ax = Qgemul_lower_approx(s0, st...);
+    qgemul_opts opts{};
+    opts.device = -1;
+    opts.flags = QgemulRunFlags();
+    const int rc = qgemul_run_grouped_epx(d.data(), int64_t(G), &ep, ax.data(), &gep, pd.data(), pa.data(), pb.data(), E, S, nullptr, nullptr, nullptr, &opts);
+    if (rc != QG_OK) throw std::runtime_error(std::string("QgemulGrouped: ") + qgemul_strerror(rc));
 }
 
 // ------------------------------------------------------------------ Qreduce (SURVEY.md §8-f "next" #1)

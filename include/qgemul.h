@@ -571,8 +571,8 @@ int qgemul_cmul_plan_form(const qgemul_desc* d, const qgemul_epilogue_cplx* ep, 
  *                             shared; E[k] of a scalar stage points to one element; stage tensors are tight (ld = M); lda / ldb /
  *                             ldc from opts.  The plan lives in the calling thread's cache like qgemul_run_batched's: a changed
  *                             batch count, chain or shared pattern re-plans.  QG_OPT_ALL_DEVICES: QG_EUNSUPPORTED
- * Not served: complex chains, per-member scalars, a sharded form, BitStream export of a batched D (per-member shapes without a
- * chain: the grouped plans below). */
+ * Not served: complex chains, per-member scalars (grouped plans with a chain have them: below), a sharded form, BitStream export of
+ * a batched D (per-member shapes: the grouped plans below). */
 typedef struct qgemul_batched_ep {
     uint8_t e_shared[QG_MAX_EW];   /* tensor stage k: 1 = ONE M x N operand for every member, 0 = one operand per member;
                                       ignored for scalar and APPROX stages */
@@ -621,8 +621,9 @@ int qgemul_run_batched_epx(const qgemul_desc* d, int64_t batch, const qgemul_epi
  *   qgemul_run_grouped                 one-shot, host pointers, synchronous; lda / ldb / ldc per member (NULL: tight; those of opts
  *                                      are not read); the plan lives in the calling thread's cache, keyed on the whole descriptor
  *                                      list; QG_OPT_ALL_DEVICES: QG_EUNSUPPORTED
- * Not served: element-wise chains on grouped plans, a sharded form, a second grouped launch for the stragglers, grouped forms of the
- * tree, ring, complex and two-group kernels, BitStream export of a grouped C, 32 x 32 tiles. */
+ * Element-wise chains on grouped plans: the _grouped_ep entry points further down.
+ * Not served: a sharded form, a second grouped launch for the stragglers, grouped forms of the tree, ring, complex and two-group
+ * kernels, BitStream export of a grouped C, 32 x 32 tiles. */
 typedef struct qgemul_grouped_member {
     int32_t in_launch;     /* 1: in the one grouped launch; 0: a straggler on its own plain plan */
     int32_t launches;      /* kernel launches of this member alone (0 in the launch) */
@@ -642,11 +643,66 @@ int qgemul_execute_grouped(qgemul_plan* p, void* packedC, const void* packedA, c
 int qgemul_time_execute_grouped(qgemul_plan* p, void* packedC, const void* packedA, const void* packedB, int warmup, int iters, float* avg_ms);
 int qgemul_run_grouped(const qgemul_desc* d, int64_t groups, void* const* C, const void* const* A, const void* const* B, const int64_t* lda,
                        const int64_t* ldb, const int64_t* ldc, const qgemul_opts* o);
+/* ---- element-wise chains on grouped plans: scale, bias and activation per member in one launch ----
+ * Member g of the group is exactly  Qgemul<...>(C_g, A_g, B_g)  followed by the chain qgemul_execute_ep runs on a plain plan of d[g]
+ * with that member's operands: a list of differently shaped layers of one element type, each with its own scale and bias.  ONE chain
+ * (a real qgemul_epilogue of 0 .. QG_MAX_EW stages, APPROX stages included, ax as in qgemul_plan_create_epx; NULL: no APPROX stage)
+ * serves the whole group.  Tensor operands are per member (the shapes differ: there is no shared form).  A scalar stage takes either
+ * qgemul_ep_args.e_scalar[k] for all members or, with scalar_per_member[k] = 1, one raw value per member from a table of the plan.
+ * Status: whatever qgemul_classify_epx answers for any member descriptor, wherever it stands in the list (a complex member is refused
+ * exactly as there); the size checks of the grouped plan, and scalar_per_member on a tensor or APPROX stage, are QG_EINVAL.
+ * The planner is that of the grouped plans, with two additions: the launch key also compares C's whole format (the chain's analysis
+ * depends on it), and a straggler runs its own plain _epx plan with the member's scalars.  Three forms; qgemul_info.reason names the
+ * one that runs and how many members are in the launch and alone, qgemul_plan_grouped_launches counts the launches:
+ *   pass   the default: the grouped launch writes a packed C of the launch's members that the plan owns, then ONE pass over those
+ *          tiles writes D (k_eltwise_grp / k_approx_grp; the workgroup's member comes from a tile -> member table of the plan).
+ *          Launches: 1 (a 3 x 3 pair counts once) + 1 + the stragglers' own
+ *   fused  on QG_OPT_FUSED_EPILOGUE only, a chain bounded by 32-bit arithmetic without an APPROX stage: the chain runs in the epilogue
+ *          of the one launch (k_mfma_ep_grp).  Launches: 1 + the stragglers' own.  QG_OPT_UNFUSED_EPILOGUE forces the pass
+ *   no member eligible   every member runs alone
+ * Packed D takes the place of packed C (qgemul_plan_grouped_member: off[2] / bytes[2] describe D; qgemul_unpack_c_grouped unpacks
+ * D).  Packed E of stage k follows packed D: the members in the launch back to back at the element offsets they have in D, then the
+ * stragglers in the layout of their own plain _ep plans at 256-byte-aligned offsets; qgemul_packed_e_bytes answers for the group.
+ *   qgemul_pack_e_grouped        a layout step, one launch per member, like qgemul_pack_grouped; a scalar or APPROX stage: QG_EINVAL
+ *   qgemul_grouped_set_scalars   a layout step: per-member values are model constants like packed weights.  host_values[groups] in
+ *                                the caller's member order, treated exactly as qgemul_execute_ep treats e_scalar[k]; the plan keeps
+ *                                a host copy (the stragglers') and uploads the values into a device table it owns, ordered on the ctx
+ *                                stream: a later execute sees the new values.  A stage that is not per member: QG_EINVAL
+ *   qgemul_execute_grouped_ep    the hot path.  QG_EINVAL while a per-member stage's table was never set, and as qgemul_execute_ep for
+ *                                a missing operand; e_packed[k] is the group's packed E of stage k
+ *   qgemul_run_grouped_epx       one-shot, host pointers, synchronous.  E[k][g]: member g's tight M x N operand of tensor stage k (one
+ *                                element for a scalar stage that is not per member); scalars[k][g]: the per-member values of stage
+ *                                k (NULL for other stages).  The plan lives in the calling thread's cache: a changed list, chain or
+ *                                per-member pattern re-plans, changed scalar values do not.  QG_OPT_ALL_DEVICES: QG_EUNSUPPORTED
+ * qgemul_execute_grouped refuses a grouped plan with a chain, the _grouped_ep entries refuse one without, plain and batched plans;
+ * the plain and batched entry points refuse the new plan (QG_EINVAL).
+ * Not served: complex chains, shared tensor operands, a second grouped launch for the stragglers, BitStream export of a grouped D, a
+ * sharded form. */
+typedef struct qgemul_grouped_ep {
+    uint8_t scalar_per_member[QG_MAX_EW]; /* scalar stage k: 1 = one raw scalar per member from the plan's table, 0 = qgemul_ep_args.e_scalar[k] for all */
+    uint8_t reserved[4];
+} qgemul_grouped_ep;                      /* NULL: no stage is per member */
+int qgemul_classify_grouped_epx(const qgemul_desc* d, int64_t groups, const qgemul_epilogue* ep, const qgemul_approx* const ax[QG_MAX_EW],
+                                const qgemul_grouped_ep* gep, uint32_t opt_flags, qgemul_info* out);   /* pure host code, like the next two */
+int qgemul_classify_grouped_epx_launches(const qgemul_desc* d, int64_t groups, const qgemul_epilogue* ep, const qgemul_approx* const ax[QG_MAX_EW],
+                                         const qgemul_grouped_ep* gep, uint32_t opt_flags);
+int qgemul_classify_grouped_epx_member(const qgemul_desc* d, int64_t groups, const qgemul_epilogue* ep, const qgemul_approx* const ax[QG_MAX_EW],
+                                       const qgemul_grouped_ep* gep, uint32_t opt_flags, int64_t g, qgemul_grouped_member* out);
+int qgemul_plan_create_grouped_epx(qgemul_ctx* c, const qgemul_desc* d, int64_t groups, const qgemul_epilogue* ep, const qgemul_approx* const ax[QG_MAX_EW],
+                                   const qgemul_grouped_ep* gep, uint32_t opt_flags, qgemul_plan** out);
+int qgemul_grouped_set_scalars(qgemul_plan* p, int stage, const int64_t* host_values);
+int qgemul_pack_e_grouped(qgemul_plan* p, int stage, const void* const* src_dev, const int64_t* ld, void* packed_dev);
+int qgemul_execute_grouped_ep(qgemul_plan* p, void* packedD, const void* packedA, const void* packedB, const qgemul_ep_args* args);
+int qgemul_time_execute_grouped_ep(qgemul_plan* p, void* packedD, const void* packedA, const void* packedB, const qgemul_ep_args* args, int warmup, int iters,
+                                   float* avg_ms);
+int qgemul_run_grouped_epx(const qgemul_desc* d, int64_t groups, const qgemul_epilogue* ep, const qgemul_approx* const ax[QG_MAX_EW], const qgemul_grouped_ep* gep,
+                           void* const* D, const void* const* A, const void* const* B, const void* const* const E[QG_MAX_EW],
+                           const int64_t* const scalars[QG_MAX_EW], const int64_t* lda, const int64_t* ldb, const int64_t* ldd, const qgemul_opts* o);
 /* sizeof of an ABI struct as THIS library was compiled (language bindings check their mirrors against it); 0: unknown id
  * (id 11 is not assigned: tests/test_cmul_plan.py pins it as an unknown id) */
 enum { QG_SIZEOF_QFMT = 0, QG_SIZEOF_DESC = 1, QG_SIZEOF_OPTS = 2, QG_SIZEOF_INFO = 3, QG_SIZEOF_EW_STAGE = 4, QG_SIZEOF_EPILOGUE = 5,
        QG_SIZEOF_EP_ARGS = 6, QG_SIZEOF_EPILOGUE_CPLX = 7, QG_SIZEOF_APPROX_SEG = 8, QG_SIZEOF_APPROX = 9, QG_SIZEOF_CMUL = 10,
-       QG_SIZEOF_GROUPED_MEMBER = 12 };
+       QG_SIZEOF_GROUPED_MEMBER = 12, QG_SIZEOF_GROUPED_EP = 13 };
 size_t qgemul_sizeof(int which);
 
 /* ---- several GPUs in one process ----

@@ -13,7 +13,7 @@ from typing import Optional
 
 import numpy as np
 
-from .desc import (QG_MAX_EW, Qcomplex, Qu, host_layout, qfmt, qgemul_approx, qgemul_approx_form, qgemul_approx_seg, qgemul_batched_ep, batched_ep, qgemul_grouped_member, qgemul_cmul, qgemul_cmul_form, qgemul_desc, qgemul_ep_args, qgemul_epilogue,
+from .desc import (QG_MAX_EW, Qcomplex, Qu, host_layout, qfmt, qgemul_approx, qgemul_approx_form, qgemul_approx_seg, qgemul_batched_ep, batched_ep, qgemul_grouped_ep, grouped_ep, qgemul_grouped_member, qgemul_cmul, qgemul_cmul_form, qgemul_desc, qgemul_ep_args, qgemul_epilogue,
                    qgemul_epilogue_cplx, qgemul_ew_stage, qgemul_info, qgemul_opts)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -50,10 +50,12 @@ EXPORTS = [
     "qgemul_time_execute_batched_ep", "qgemul_run_batched_epx",
     "qgemul_classify_grouped", "qgemul_classify_grouped_launches", "qgemul_classify_grouped_member", "qgemul_plan_create_grouped", "qgemul_plan_grouped_launches",
     "qgemul_plan_grouped_member", "qgemul_pack_grouped", "qgemul_unpack_c_grouped", "qgemul_execute_grouped", "qgemul_time_execute_grouped", "qgemul_run_grouped",
+    "qgemul_classify_grouped_epx", "qgemul_classify_grouped_epx_launches", "qgemul_classify_grouped_epx_member", "qgemul_plan_create_grouped_epx",
+    "qgemul_grouped_set_scalars", "qgemul_pack_e_grouped", "qgemul_execute_grouped_ep", "qgemul_time_execute_grouped_ep", "qgemul_run_grouped_epx",
 ]
 # qgemul_sizeof ids (include/qgemul.h) and the ctypes mirror each one must match
 SIZEOF_MIRRORS = {0: qfmt, 1: qgemul_desc, 2: qgemul_opts, 3: qgemul_info, 4: qgemul_ew_stage, 5: qgemul_epilogue, 6: qgemul_ep_args,
-                  7: qgemul_epilogue_cplx, 8: qgemul_approx_seg, 9: qgemul_approx, 10: qgemul_cmul, 12: qgemul_grouped_member}
+                  7: qgemul_epilogue_cplx, 8: qgemul_approx_seg, 9: qgemul_approx, 10: qgemul_cmul, 12: qgemul_grouped_member, 13: qgemul_grouped_ep}
 
 _lib = None
 
@@ -180,6 +182,16 @@ def lib() -> C.CDLL:
         L.qgemul_execute_grouped.argtypes = [vp, vp, vp, vp]
         L.qgemul_time_execute_grouped.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(C.c_float)]
         L.qgemul_run_grouped.argtypes = [pd, i64, pvp, pvp, pvp, pi64, pi64, pi64, C.POINTER(qgemul_opts)]
+        pge = C.POINTER(qgemul_grouped_ep)
+        L.qgemul_classify_grouped_epx.argtypes = [pd, i64, pe, pax, pge, u32, C.POINTER(qgemul_info)]
+        L.qgemul_classify_grouped_epx_launches.argtypes = [pd, i64, pe, pax, pge, u32]
+        L.qgemul_classify_grouped_epx_member.argtypes = [pd, i64, pe, pax, pge, u32, i64, pgm]
+        L.qgemul_plan_create_grouped_epx.argtypes = [vp, pd, i64, pe, pax, pge, u32, C.POINTER(vp)]
+        L.qgemul_grouped_set_scalars.argtypes = [vp, C.c_int, pi64]
+        L.qgemul_pack_e_grouped.argtypes = [vp, C.c_int, pvp, pi64, vp]
+        L.qgemul_execute_grouped_ep.argtypes = [vp, vp, vp, vp, pa]
+        L.qgemul_time_execute_grouped_ep.argtypes = [vp, vp, vp, vp, pa, C.c_int, C.c_int, C.POINTER(C.c_float)]
+        L.qgemul_run_grouped_epx.argtypes = [pd, i64, pe, pax, pge, pvp, pvp, pvp, C.POINTER(pvp), C.POINTER(pi64), pi64, pi64, pi64, C.POINTER(qgemul_opts)]
         L.qgemul_sizeof.argtypes = [C.c_int]
         L.qgemul_sizeof.restype = C.c_size_t
         _lib = L
@@ -389,6 +401,68 @@ def run_grouped_status(descs, Cs, As, Bs, *, lda=None, ldb=None, ldc=None, flags
 def run_grouped(descs, Cs, As, Bs, **kw):
     _chk(run_grouped_status(descs, Cs, As, Bs, **kw), "qgemul_run_grouped")
     return Cs
+
+
+# ---- element-wise chains on grouped plans (include/qgemul.h, qgemul_*_grouped_ep*): ONE chain, scalars per member where asked ----
+def _per_member(per_member):
+    """a qgemul_grouped_ep from a sequence of flags (None: no stage is per member)"""
+    return C.byref(grouped_ep(per_member)) if per_member is not None else None
+
+
+def _ax(approx):
+    return _tables(approx) if approx is not None else None
+
+
+def classify_grouped_epx_status(descs, ep: qgemul_epilogue, approx=None, per_member=None, flags: int = 0):
+    """qgemul_classify_grouped_epx: (status, info); approx[k] = stage k's qgemul_approx or None, per_member[k] = scalar stage k takes a value per member"""
+    info = qgemul_info()
+    st = lib().qgemul_classify_grouped_epx(_desc_array(descs) if len(descs) else None, len(descs), C.byref(ep) if ep is not None else None, _ax(approx),
+                                           _per_member(per_member), flags, C.byref(info))
+    return st, info
+
+
+def classify_grouped_epx_launches(descs, ep: qgemul_epilogue, approx=None, per_member=None, flags: int = 0) -> int:
+    """kernel launches per execute_ep of the grouped plan; a negative value is a status"""
+    return int(lib().qgemul_classify_grouped_epx_launches(_desc_array(descs) if len(descs) else None, len(descs), C.byref(ep), _ax(approx), _per_member(per_member), flags))
+
+
+def classify_grouped_epx_member(descs, ep: qgemul_epilogue, g: int, approx=None, per_member=None, flags: int = 0) -> qgemul_grouped_member:
+    """where member g will live (off[2] / bytes[2]: in packed D)"""
+    out = qgemul_grouped_member()
+    _chk(lib().qgemul_classify_grouped_epx_member(_desc_array(descs), len(descs), C.byref(ep), _ax(approx), _per_member(per_member), flags, g, C.byref(out)),
+         "qgemul_classify_grouped_epx_member")
+    return out
+
+
+def run_grouped_epx_status(descs, ep: qgemul_epilogue, approx, per_member, Ds, As, Bs, E, scalars, *, lda=None, ldb=None, ldd=None, flags: int = 0,
+                           device: int = -1) -> int:
+    """qgemul_run_grouped_epx on lists of host-layout numpy buffers.  E[k]: the members' tight operands of tensor stage k (a list), the one
+    scalar element of a scalar stage that is not per member (an array), or None; scalars[k]: the per-member raw values of stage k or None.
+    Returns the status."""
+    n = len(descs)
+    o = qgemul_opts(device=device, flags=flags)
+    ptr = lambda xs: _ptr_array([x.ctypes.data if x is not None else 0 for x in xs])
+    keep = []
+    Ep = (C.POINTER(C.c_void_p) * QG_MAX_EW)()
+    Sp = (C.POINTER(C.c_int64) * QG_MAX_EW)()
+    for k in range(QG_MAX_EW):
+        e = E[k] if E is not None and k < len(E) else None
+        if e is not None:
+            arr = ptr(list(e) if isinstance(e, (list, tuple)) else [e] * n)
+            keep.append(arr)
+            Ep[k] = C.cast(arr, C.POINTER(C.c_void_p))
+        sc = scalars[k] if scalars is not None and k < len(scalars) else None
+        if sc is not None:
+            arr = (C.c_int64 * n)(*[int(x) for x in sc])
+            keep.append(arr)
+            Sp[k] = C.cast(arr, C.POINTER(C.c_int64))
+    return int(lib().qgemul_run_grouped_epx(_desc_array(descs), n, C.byref(ep), _ax(approx), _per_member(per_member), ptr(Ds), ptr(As), ptr(Bs), Ep, Sp,
+                                            _ld_array(lda, n), _ld_array(ldb, n), _ld_array(ldd, n), C.byref(o)))
+
+
+def run_grouped_epx(descs, ep, approx, per_member, Ds, As, Bs, E, scalars, **kw):
+    _chk(run_grouped_epx_status(descs, ep, approx, per_member, Ds, As, Bs, E, scalars, **kw), "qgemul_run_grouped_epx")
+    return Ds
 
 
 def _shared(shared):
@@ -732,12 +806,18 @@ class BatchedPlan:
 class GroupedPlan:
     """A grouped plan (include/qgemul.h, qgemul_*_grouped): GEMMs of different shapes, the eligible ones of one launch key in ONE launch."""
 
-    def __init__(self, ctx: Context, descs, flags: int = 0):
+    def __init__(self, ctx: Context, descs, flags: int = 0, ep=None, approx=None, per_member=None):
+        """ep: ONE element-wise chain after every member's GEMM (qgemul_plan_create_grouped_epx); approx[k]: stage k's table or None;
+        per_member[k]: scalar stage k takes one raw value per member (set_scalars)"""
         self.ctx = ctx
         self.descs = list(descs)
         self.groups = len(self.descs)
         self.h = C.c_void_p()
-        _chk(lib().qgemul_plan_create_grouped(ctx.h, _desc_array(self.descs), self.groups, flags, C.byref(self.h)), "qgemul_plan_create_grouped")
+        if ep is None:
+            _chk(lib().qgemul_plan_create_grouped(ctx.h, _desc_array(self.descs), self.groups, flags, C.byref(self.h)), "qgemul_plan_create_grouped")
+        else:
+            _chk(lib().qgemul_plan_create_grouped_epx(ctx.h, _desc_array(self.descs), self.groups, C.byref(ep), _ax(approx), _per_member(per_member), flags,
+                                                      C.byref(self.h)), "qgemul_plan_create_grouped_epx")
         self.info = qgemul_info()
         _chk(lib().qgemul_plan_info(self.h, C.byref(self.info)), "qgemul_plan_info")
 
@@ -769,3 +849,29 @@ class GroupedPlan:
         ms = C.c_float()
         _chk(lib().qgemul_time_execute_grouped(self.h, C.c_void_p(pC), C.c_void_p(pA), C.c_void_p(pB), warmup, iters, C.byref(ms)), "qgemul_time_execute_grouped")
         return ms.value
+
+    # ---- with a chain (ep) ----
+    def fuses(self) -> int:
+        """1: the chain runs inside the one grouped launch"""
+        return int(lib().qgemul_plan_fuses_epilogue(self.h))
+
+    def packed_e_bytes(self, stage: int) -> int:
+        """bytes of stage `stage`'s packed tensor operand for the whole group"""
+        return int(lib().qgemul_packed_e_bytes(self.h, stage))
+
+    def pack_e(self, stage: int, src_devs, packed_dev: int, ld=None):
+        _chk(lib().qgemul_pack_e_grouped(self.h, stage, _ptr_array(src_devs), _ld_array(ld, self.groups), C.c_void_p(packed_dev)), "qgemul_pack_e_grouped")
+
+    def set_scalars(self, stage: int, values):
+        """the per-member raw values of scalar stage `stage`, in the caller's member order"""
+        assert len(values) == self.groups
+        _chk(lib().qgemul_grouped_set_scalars(self.h, stage, (C.c_int64 * self.groups)(*[int(v) for v in values])), "qgemul_grouped_set_scalars")
+
+    def execute_ep(self, pD: int, pA: int, pB: int, args: qgemul_ep_args):
+        _chk(lib().qgemul_execute_grouped_ep(self.h, C.c_void_p(pD), C.c_void_p(pA), C.c_void_p(pB), C.byref(args)), "qgemul_execute_grouped_ep")
+
+    def time_execute_ep(self, pD: int, pA: int, pB: int, args: qgemul_ep_args, warmup: int, iters: int) -> float:
+        ms = C.c_float()
+        _chk(lib().qgemul_time_execute_grouped_ep(self.h, C.c_void_p(pD), C.c_void_p(pA), C.c_void_p(pB), C.byref(args), warmup, iters, C.byref(ms)),
+             "qgemul_time_execute_grouped_ep")
+        return float(ms.value)

@@ -216,6 +216,7 @@ size_t qgemul_sizeof(int which)
     case QG_SIZEOF_APPROX: return sizeof(qgemul_approx);
     case QG_SIZEOF_CMUL: return sizeof(qgemul_cmul);
     case QG_SIZEOF_GROUPED_MEMBER: return sizeof(qgemul_grouped_member);
+    case QG_SIZEOF_GROUPED_EP: return sizeof(qgemul_grouped_ep);
     default: return 0;
     }
 }
@@ -453,7 +454,12 @@ void qgemul_plan_destroy(qgemul_plan* p)
     }
     DeviceScope scope(p->ctx->device);
     hipStreamSynchronize(p->ctx->stream);
-    if (p->grp) hipFree(p->grp->tiles_dev);
+    if (p->grp) {
+        hipFree(p->grp->tiles_dev);
+        hipFree(p->grp->tile_member_dev);
+        hipFree(p->grp->cwork_dev);
+        for (int k = 0; k < QG_MAX_EW; ++k) hipFree(p->grp->scal_dev[k]);
+    }
     delete p->grp;
     hipFree(p->dev_table);
     hipFree(p->workspace);
@@ -738,6 +744,7 @@ int qgemul_execute_ep(qgemul_plan* p, void* packedD, const void* packedA, const 
 
 int qgemul_plan_fuses_epilogue(const qgemul_plan* p)
 {
+    if (p && p->grp) return p->grp->has_ep && p->grp->fused && p->grp->n_in ? 1 : 0;   // (the members in the launch)
     if (p && p->batch) return p->has_ep && (p->bd ? p->bd_fused : fuses_epilogue(p->member)) ? 1 : 0;
     return p && p->has_ep && fuses_epilogue(p) ? 1 : 0;
 }
@@ -783,6 +790,7 @@ int qgemul_pack_c(qgemul_plan* p, const void* src_dev, int64_t ld, void* packed_
 int64_t qgemul_packed_e_bytes(const qgemul_plan* p, int stage)
 {
     if (!p || !p->has_ep || stage < 0 || stage >= p->ept.n) return 0;
+    if (p->grp) return p->grp->ebytes[stage];   // (the whole group's)
     if (p->batch) return p->e_shared[stage] ? p->estride[stage] : p->batch * p->estride[stage];   // (one member's / the stack's)
     const QEpStage* t = stage_tensor(p, stage);
     if (!t) return 0;
@@ -1043,11 +1051,12 @@ int qgemul_export_bitstream(qgemul_plan* p, const void* packedC, int tensor_chun
 }
 
 static int time_execute(qgemul_plan* p, void* packedC, const void* packedA, const void* packedB, const qgemul_ep_args* args,
-                        int warmup, int iters, float* avg_ms, int kind = 0)   // kind: 0 a plain plan, 1 a batched one, 2 a grouped one
+                        int warmup, int iters, float* avg_ms, int kind = 0)   // kind: 0 a plain plan, 1 a batched one, 2 a grouped one, 3 a grouped one with a chain
 {
     const bool batched = kind == 1;
-    if (!p || !avg_ms || iters < 1 || (kind == 2 ? !p->grp : (p->batch != 0) != batched)) return QG_EINVAL;
+    if (!p || !avg_ms || iters < 1 || (kind >= 2 ? !p->grp : (p->batch != 0) != batched)) return QG_EINVAL;
     return time_calls(p, warmup, iters, avg_ms, [&] {
+        if (kind == 3) return qgemul_execute_grouped_ep(p, packedC, packedA, packedB, args);
         if (kind == 2) return qgemul_execute_grouped(p, packedC, packedA, packedB);
         if (batched) return p->has_ep ? qgemul_execute_batched_ep(p, packedC, packedA, packedB, args) : qgemul_execute_batched(p, packedC, packedA, packedB);
         return p->has_ep ? qgemul_execute_ep(p, packedC, packedA, packedB, args) : qgemul_execute(p, packedC, packedA, packedB);
@@ -1360,32 +1369,59 @@ int qgemul_classify_grouped_member(const qgemul_desc* d, int64_t groups, uint32_
     return st;
 }
 
-// every distinct descriptor's plain plan owns its device resources; the grouped plan owns the schedule on the device
-int qgemul_plan_create_grouped(qgemul_ctx* c, const qgemul_desc* d, int64_t groups, uint32_t opt_flags, qgemul_plan** out)
+// every distinct descriptor's plain plan owns its device resources; the grouped plan owns the schedule on the device and, with a chain
+// (ev), the pass form's packed C of the launch, its tile -> member table and the per-member scalar tables
+static int plan_create_grouped_view(qgemul_ctx* c, const qgemul_desc* d, int64_t groups, const EpView* ev, const qgemul_grouped_ep* gep, uint32_t opt_flags,
+                                    qgemul_plan** out)
 {
     if (!c || !d || !out) return QG_EINVAL;
     qgemul_plan* b = new (std::nothrow) qgemul_plan();
     QGrouped* G = new (std::nothrow) QGrouped();
-    int st = b && G ? qg_grouped_geometry(d, groups, opt_flags, G, &b->info) : QG_EINVAL;
+    int st = b && G ? qg_grouped_geometry(d, groups, opt_flags, G, &b->info, ev, gep) : QG_EINVAL;
     if (st != QG_OK) { delete G; delete b; return st; }   // (nothing on the device yet)
     b->ctx = c;
     b->grp = G;
     b->batch = -1;
     b->flags = opt_flags;
     b->desc = d[0];
-    for (int64_t u = 0; u < G->n_uniq && st == QG_OK; ++u) st = plan_create_view(c, &G->ud[u], nullptr, opt_flags, &G->up[u], G->u_in[u] ? groups : 0);
-    if (st == QG_OK && G->n_tiles > 0) {
+    if (ev) {   // the one chain of the group (its stage kinds and containers are every member's)
+        b->has_ep = 1;
+        b->ep = *ev->re;
+        b->ept = G->ug[G->key >= 0 ? G->key : 0].ept;
+        b->has_ax = G->has_ax;
+    }
+    for (int64_t u = 0; u < G->n_uniq && st == QG_OK; ++u) st = plan_create_view(c, &G->ud[u], ev, opt_flags, &G->up[u], G->u_in[u] ? groups : 0);
+    if (st == QG_OK) {
         DeviceScope scope(c->device);
-        const size_t tb = (size_t)G->n_tiles * sizeof(QGrpTile);
         hipError_t e = scope.err;
-        if (e == hipSuccess) e = hipMalloc((void**)&G->tiles_dev, tb);
-        if (e == hipSuccess) e = hipMemcpyAsync(G->tiles_dev, G->tiles, tb, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess && G->n_tiles > 0) {
+            const size_t tb = (size_t)G->n_tiles * sizeof(QGrpTile);
+            e = hipMalloc((void**)&G->tiles_dev, tb);
+            if (e == hipSuccess) e = hipMemcpyAsync(G->tiles_dev, G->tiles, tb, hipMemcpyHostToDevice, c->stream);
+        }
+        if (e == hipSuccess && G->tile_member) {   // the pass form: the launch's packed C between the two launches, and whose tile is whose
+            const size_t mb = (size_t)G->n_tiles * sizeof(int32_t);
+            e = hipMalloc(&G->cwork_dev, (size_t)G->launch_elems * (size_t)G->ug[G->key].pc_c.cbytes);
+            if (e == hipSuccess) e = hipMalloc((void**)&G->tile_member_dev, mb);
+            if (e == hipSuccess) e = hipMemcpyAsync(G->tile_member_dev, G->tile_member, mb, hipMemcpyHostToDevice, c->stream);
+        }
+        for (int k = 0; k < QG_MAX_EW && e == hipSuccess; ++k) {
+            if (!G->per_member[k]) continue;
+            G->scal[k] = new (std::nothrow) int64_t[groups]();
+            if (!G->scal[k]) { st = QG_EINVAL; break; }
+            e = hipMalloc((void**)&G->scal_dev[k], (size_t)groups * sizeof(int64_t));
+        }
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) { g_last_hip = (int)e; st = QG_EHIP; }
     }
     if (st != QG_OK) { qgemul_plan_destroy(b); return st; }
     *out = b;
     return QG_OK;
+}
+
+int qgemul_plan_create_grouped(qgemul_ctx* c, const qgemul_desc* d, int64_t groups, uint32_t opt_flags, qgemul_plan** out)
+{
+    return plan_create_grouped_view(c, d, groups, nullptr, nullptr, opt_flags, out);
 }
 
 int qgemul_plan_grouped_launches(const qgemul_plan* p)
@@ -1457,6 +1493,7 @@ int qgemul_execute_grouped(qgemul_plan* p, void* packedC, const void* packedA, c
 {
     if (!p || !p->grp || !packedC || !packedA || !packedB) return QG_EINVAL;
     const QGrouped* G = p->grp;
+    if (G->has_ep) return QG_EINVAL;   // a grouped plan with a chain runs through qgemul_execute_grouped_ep
     if (G->n_tiles > 0) {
         QG_ON_DEVICE(p->ctx);
         const QPlanGeom& k = G->ug[G->key];
@@ -1480,6 +1517,175 @@ int qgemul_execute_grouped(qgemul_plan* p, void* packedC, const void* packedA, c
 int qgemul_time_execute_grouped(qgemul_plan* p, void* packedC, const void* packedA, const void* packedB, int warmup, int iters, float* avg_ms)
 {
     return time_execute(p, packedC, packedA, packedB, nullptr, warmup, iters, avg_ms, 2);
+}
+
+// ---- element-wise chains on grouped plans (include/qgemul.h): member g is Qgemul<...>(C_g, A_g, B_g) followed by the chain ----
+static int grouped_ep_geometry(const qgemul_desc* d, int64_t groups, const qgemul_epilogue* ep, const qgemul_approx* const ax[QG_MAX_EW], const qgemul_grouped_ep* gep,
+                               uint32_t opt_flags, QGrouped* G, qgemul_info* info)
+{
+    if (!d || !ep) return QG_EINVAL;
+    const EpView v = {ep, nullptr, nullptr, ax ? ax : g_no_ax};
+    return qg_grouped_geometry(d, groups, opt_flags, G, info, &v, gep);
+}
+
+int qgemul_classify_grouped_epx(const qgemul_desc* d, int64_t groups, const qgemul_epilogue* ep, const qgemul_approx* const ax[QG_MAX_EW],
+                                const qgemul_grouped_ep* gep, uint32_t opt_flags, qgemul_info* out)
+{
+    if (!out) return QG_EINVAL;
+    QGrouped G{};
+    qgemul_info info{};
+    const int st = grouped_ep_geometry(d, groups, ep, ax, gep, opt_flags, &G, &info);
+    if (d && ep && groups >= 1) *out = info;
+    return st;
+}
+
+int qgemul_classify_grouped_epx_launches(const qgemul_desc* d, int64_t groups, const qgemul_epilogue* ep, const qgemul_approx* const ax[QG_MAX_EW],
+                                         const qgemul_grouped_ep* gep, uint32_t opt_flags)
+{
+    QGrouped G{};
+    qgemul_info info{};
+    const int st = grouped_ep_geometry(d, groups, ep, ax, gep, opt_flags, &G, &info);
+    return st == QG_OK ? G.launches : st;
+}
+
+int qgemul_classify_grouped_epx_member(const qgemul_desc* d, int64_t groups, const qgemul_epilogue* ep, const qgemul_approx* const ax[QG_MAX_EW],
+                                       const qgemul_grouped_ep* gep, uint32_t opt_flags, int64_t g, qgemul_grouped_member* out)
+{
+    if (!out || g < 0 || g >= groups) return QG_EINVAL;
+    QGrouped G{};
+    qgemul_info info{};
+    const int st = grouped_ep_geometry(d, groups, ep, ax, gep, opt_flags, &G, &info);
+    if (st == QG_OK) qg_grouped_member_out(&G, g, out);
+    return st;
+}
+
+int qgemul_plan_create_grouped_epx(qgemul_ctx* c, const qgemul_desc* d, int64_t groups, const qgemul_epilogue* ep, const qgemul_approx* const ax[QG_MAX_EW],
+                                   const qgemul_grouped_ep* gep, uint32_t opt_flags, qgemul_plan** out)
+{
+    if (!c || !d || !ep || !out) return QG_EINVAL;
+    const EpView v = {ep, nullptr, nullptr, ax ? ax : g_no_ax};
+    return plan_create_grouped_view(c, d, groups, &v, gep, opt_flags, out);
+}
+
+// per-member values are model constants: the host copy serves the stragglers, the device table the launch; the upload has ended when
+// this returns, so every later execute sees the new values
+int qgemul_grouped_set_scalars(qgemul_plan* p, int stage, const int64_t* host_values)
+{
+    if (!p || !p->grp || !p->grp->has_ep || !host_values || stage < 0 || stage >= p->ept.n || !p->grp->per_member[stage]) return QG_EINVAL;
+    QGrouped* G = p->grp;
+    QG_ON_DEVICE(p->ctx);
+    // (an execute queued earlier may still read the table: the copy is ordered behind it on the stream, and its source is the plan's)
+    QG_HIP(hipStreamSynchronize(p->ctx->stream));
+    memcpy(G->scal[stage], host_values, (size_t)G->groups * sizeof(int64_t));
+    QG_HIP(hipMemcpyAsync(G->scal_dev[stage], G->scal[stage], (size_t)G->groups * sizeof(int64_t), hipMemcpyHostToDevice, p->ctx->stream));
+    QG_HIP(hipStreamSynchronize(p->ctx->stream));
+    G->scal_set[stage] = 1;
+    return QG_OK;
+}
+
+int qgemul_pack_e_grouped(qgemul_plan* p, int stage, const void* const* src_dev, const int64_t* ld, void* packed_dev)
+{
+    if (!p || !p->grp || !p->grp->has_ep || !src_dev || !packed_dev || stage < 0 || stage >= p->ept.n) return QG_EINVAL;
+    const QGrouped* G = p->grp;
+    if (p->ept.st[stage].scalar) return QG_EINVAL;   // a scalar or APPROX stage has no tensor operand
+    for (int64_t g = 0; g < G->groups; ++g) {   // every member is checked before the first launch
+        const qgemul_desc& d = G->ud[G->m[g].uniq];
+        if (qg_grp_empty(d)) continue;
+        if (!src_dev[g] || qg_member_extent(d, QG_OPERAND_C, ld ? ld[g] : 0) < 1) return QG_EINVAL;
+    }
+    for (int64_t g = 0; g < G->groups; ++g) {   // (a layout step: one launch per member)
+        const QGrpMember& m = G->m[g];
+        if (qg_grp_empty(G->ud[m.uniq])) continue;
+        if (const int rc = qgemul_pack_e(G->up[m.uniq], stage, src_dev[g], ld ? ld[g] : 0, (char*)packed_dev + m.eoff[stage]); rc != QG_OK) return rc;
+    }
+    return QG_OK;
+}
+
+int qgemul_execute_grouped_ep(qgemul_plan* p, void* packedD, const void* packedA, const void* packedB, const qgemul_ep_args* args)
+{
+    if (!p || !p->grp || !p->grp->has_ep || !packedD || !packedA || !packedB) return QG_EINVAL;
+    const QGrouped* G = p->grp;
+    if (int s = ep_args_ok(p, args)) return s;
+    for (int k = 0; k < p->ept.n; ++k)
+        if (G->per_member[k] && !G->scal_set[k]) return QG_EINVAL;   // qgemul_grouped_set_scalars has not filled the stage's table
+    if (G->n_tiles > 0) {
+        QG_ON_DEVICE(p->ctx);
+        hipStream_t st = p->ctx->stream;
+        const QPlanGeom& k = G->ug[G->key];
+        const QEpArgs ea = ep_device_args(p, args);
+        QGrpEp ge;
+        memset(&ge, 0, sizeof ge);
+        for (int s = 0; s < p->ept.n; ++s)
+            if (G->per_member[s]) ge.scal[s] = G->scal_dev[s];
+        // the launch's uniform arguments: those of qgemul_execute_grouped, with the kernel's own C container
+        QMfmaGrpArgs a;
+        memset((void*)&a, 0, sizeof a);
+        (QMfmaArgs&)a = mfma_args(G->sa, G->sb, k.variant, packedA, packedB, G->fused ? packedD : G->cwork_dev, k.pc_c.cbytes);
+        a.to_c = k.an.lin.to_c[0];
+        centre_args(a, G->sa, G->sb, packedA, packedB, 0);
+        a.tiles = G->tiles_dev;
+        if (G->fused) {
+            // ONE launch: the grouped kernel's epilogue runs the chain on the value it has just converted into C's type
+            QMfmaEpGrpArgs f;
+            memset((void*)&f, 0, sizeof f);
+            (QMfmaArgs&)f = a;
+            f.tiles = a.tiles;
+            f.has_ep = 1;
+            f.ep = k.ept;
+            f.epa = ea;
+            f.ge = ge;
+            QG_HIP(qg_launch_mfma_ep_grp(k.LA, k.LB, f, G->n_tiles, st));
+        } else {
+            // TWO launches: the grouped kernel as it is into the plan's packed C of the launch, then ONE pass over its tiles into D
+            QG_HIP(qg_launch_mfma_grp(k.LA, k.LB, a, G->n_tiles, st));
+            QEltwiseArgs g;
+            memset(&g, 0, sizeof g);
+            g.C = (const char*)G->cwork_dev;
+            g.D = (char*)packedD;
+            g.n = G->launch_elems;
+            g.cbytes = k.pc_c.cbytes;
+            g.t = k.ept;
+            g.a = ea;
+            if (G->has_ax) {
+                QApproxGrpArgs x;
+                memset(&x, 0, sizeof x);
+                x.x.g = g;
+                for (int s = 0; s < QG_MAX_EW; ++s) x.x.ax[s] = G->up[G->key]->ax_dev[s];
+                x.x.force_general = (p->flags & QG_OPT_APPROX_GENERAL) ? 1 : 0;
+                x.tile_member = G->tile_member_dev;
+                x.ge = ge;
+                QG_HIP(qg_launch_approx_grp(x, st));
+            } else {
+                QEltwiseGrpArgs e;
+                memset(&e, 0, sizeof e);
+                e.g = g;
+                e.tile_member = G->tile_member_dev;
+                e.ge = ge;
+                QG_HIP(qg_launch_eltwise_grp(e, st));
+            }
+        }
+    }
+    // the stragglers: their own plain _epx plans, with the member's scalars and its part of every packed tensor operand
+    for (int64_t g = 0; g < G->groups; ++g) {
+        const QGrpMember& m = G->m[g];
+        if (m.in_launch) continue;
+        qgemul_ep_args ma;
+        memset(&ma, 0, sizeof ma);
+        for (int k = 0; k < p->ept.n; ++k) {
+            ma.e_scalar[k] = G->per_member[k] ? G->scal[k][g] : args->e_scalar[k];
+            if (!p->ept.st[k].scalar) ma.e_packed[k] = (const char*)args->e_packed[k] + m.eoff[k];
+        }
+        if (const int rc = qgemul_execute_ep(G->up[m.uniq], (char*)packedD + m.off[2], (const char*)packedA + m.off[0], (const char*)packedB + m.off[1], &ma); rc != QG_OK)
+            return rc;
+    }
+    return QG_OK;
+}
+
+int qgemul_time_execute_grouped_ep(qgemul_plan* p, void* packedD, const void* packedA, const void* packedB, const qgemul_ep_args* args, int warmup, int iters,
+                                   float* avg_ms)
+{
+    if (!p || !p->grp || !p->grp->has_ep) return QG_EINVAL;
+    return time_execute(p, packedD, packedA, packedB, args, warmup, iters, avg_ms, 3);
 }
 
 } // extern "C"

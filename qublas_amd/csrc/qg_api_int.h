@@ -17,6 +17,7 @@
 #include "qg_approx.h"
 #include "qg_cmul.h"
 #include "qg_bd_ep.h"
+#include "qg_grp_ep.h"
 #include "qg_run_key.h"
 
 #define QG_INTERNAL __attribute__((visibility("hidden")))
@@ -99,7 +100,8 @@ struct qgemul_plan : QPlanGeom, QBatchGeom {
     // is this plan's cwork
     qgemul_plan* member;
     // grouped plan (qgemul_plan_create_grouped): batch == -1, so that the plain entry points refuse it as they refuse a batched plan and
-    // the batched ones as they refuse a plain plan; everything else is in grp
+    // the batched ones as they refuse a plain plan; everything else is in grp.  With a chain (qgemul_plan_create_grouped_epx): has_ep, ep, ept
+    // and has_ax are the group's one chain, the device tables of its APPROX stages are the key plan's (grp->up[grp->key])
     QGrouped* grp;
 };
 

@@ -119,6 +119,34 @@ __device__ __forceinline__ void qg_ep_apply_runs_bd(T (&v)[4 * NR], const QEpTab
     qg_step_all<T, 4 * NR>(v, t.to_d);
 }
 
+// ... of a grouped plan (QGrpEp, qg_eltwise_args.h): the element index runs over the whole launch, as D and every tensor operand do, and
+// comes in two parts: ubase, wave-uniform (the workgroup's tile), which goes into the operand's base pointer, and the lane's 32-bit
+// index lane0 behind it; run q starts at lane0 + q * stride.  A scalar stage with a table takes the table's entry of `member`
+// (wave-uniform, like the table pointer: a scalar load)
+template <class T, int NR>
+__device__ __forceinline__ void qg_ep_apply_runs_grp(T (&v)[4 * NR], const QEpTable& t, const QEpArgs& a, int64_t ubase, uint32_t lane0, uint32_t stride, const QGrpEp& ge, int member)
+{
+    for (int k = 0; k < t.n; ++k) {
+        T e[4 * NR];
+        if (t.st[k].scalar) {
+            const int64_t* tab = ge.scal[k];
+            const int64_t raw = tab ? tab[member] : a.scalar[k];
+            // (wave-uniform by construction; said so, so that the value lives in scalar registers like a call-wide scalar does)
+            const int64_t sc = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(raw >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)raw));
+#pragma unroll
+            for (int o = 0; o < 4 * NR; ++o) e[o] = (T)sc;
+        } else {
+            // (the lane's BYTE offset in 32 bits as well: one register per run instead of a 64-bit pair per run and container)
+            const uint32_t eb = (uint32_t)t.st[k].ebytes;
+            const char* p = a.e[k] + ubase * t.st[k].ebytes;
+#pragma unroll
+            for (int q = 0; q < NR; ++q) qg_ep_load_run<4, T>(p + (lane0 + q * stride) * eb, 0, t.st[k].ebytes, e + 4 * q);
+        }
+        qg_ep_stage<T, 4 * NR>(v, e, t.st[k]);
+    }
+    qg_step_all<T, 4 * NR>(v, t.to_d);
+}
+
 // RUN consecutive packed elements of `bytes` each, starting at element index idx
 template <class T>
 __device__ __forceinline__ void qg_ep_store_run(char* D, int64_t idx, int bytes, const T* v)

@@ -8,6 +8,12 @@ struct QEpArgs {
     int64_t scalar[QG_MAX_EW];
 };
 
+// a grouped plan's chain (qgemul_plan_create_grouped_epx): scal[k] != nullptr: scalar stage k takes the raw value scal[k][member], one
+// entry per member of the caller's list, instead of QEpArgs::scalar[k]
+struct QGrpEp {
+    const int64_t* scal[QG_MAX_EW];
+};
+
 // arguments of the stand-alone pass: packed C (cbytes containers, n elements incl. padding) -> packed D
 struct QEltwiseArgs {
     const char* C;

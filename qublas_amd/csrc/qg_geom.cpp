@@ -718,9 +718,18 @@ bool qg_same_launch_key(const QPlanGeom& x, const QPlanGeom& y)
            !memcmp(&x.an.lin.to_c[0], &y.an.lin.to_c[0], sizeof(QStep));
 }
 
+// a chain's stage kinds: a tensor operand / a scalar one (an APPROX stage has neither)
+static bool stage_has_tensor(const QEpStage& s) { return !s.scalar && s.op != QG_EW_APPROX; }
+static bool stage_is_scalar(const QEpStage& s) { return s.scalar && s.op != QG_EW_APPROX && s.op != QG_EW_PASS; }
+// what a straggler's own execute issues: its kernel and, with a chain that its plain plan does not fuse, the chain's pass
+static int straggler_launches(const QGrouped* G, const QPlanGeom& q, uint32_t flags)
+{
+    return qg_plan_launches(&q) + (G->has_ep && !qg_fuses_epilogue(&q, flags, G->has_ax != 0, false) ? 1 : 0);
+}
+
 // every distinct descriptor once, with the geometry it has in the group: in the launch (u_in) the batched analysis' 64 x 64
 // geometry, a straggler its plain plan's
-static int grouped_distinct(const qgemul_desc* d, int64_t groups, uint32_t flags, QGrouped* G, qgemul_info* info)
+static int grouped_distinct(const qgemul_desc* d, int64_t groups, uint32_t flags, const EpView* ev, QGrouped* G, qgemul_info* info)
 {
     // (the comparison of the one-shot cache: qg_run_key.h)
     for (int64_t g = 0; g < groups; ++g) {
@@ -735,19 +744,20 @@ static int grouped_distinct(const qgemul_desc* d, int64_t groups, uint32_t flags
     if (!G->ug || !G->u_in || !G->up) return QG_EINVAL;
     // batch = groups: an eligible member gets the 64 x 64 geometry of qg_mfma_pick_batched
     for (int64_t u = 0; u < G->n_uniq; ++u) {
-        const int st = qg_plan_geometry(&G->ud[u], flags, nullptr, groups, &G->ug[u], nullptr, nullptr);
+        const int st = qg_plan_geometry(&G->ud[u], flags, ev, groups, &G->ug[u], nullptr, nullptr);
         if (st != QG_OK) { *info = G->ug[u].info; return st; }
     }
     auto eligible = [&](int64_t u) { return G->ug[u].bd && G->ug[u].pa.K_p >= G->ug[u].cfg.BK; };
     for (int64_t g = 0; g < groups && G->key < 0; ++g)
         if (eligible(G->m[g].uniq)) G->key = G->m[g].uniq;
     for (int64_t u = 0; u < G->n_uniq; ++u)
-        G->u_in[u] = G->key >= 0 && eligible(u) && qg_same_launch_key(G->ug[u], G->ug[G->key]);
+        // (with a chain the key also holds C's whole format: the chain's analysis depends on it, and to_c alone does not pin it)
+        G->u_in[u] = G->key >= 0 && eligible(u) && qg_same_launch_key(G->ug[u], G->ug[G->key]) && (!ev || same_fmt(G->ud[u].c[0], G->ud[G->key].c[0]));
     for (int64_t u = 0; u < G->n_uniq; ++u) {
         if (G->u_in[u]) continue;
         // a straggler runs on its own PLAIN plan
         G->ug[u] = QPlanGeom();
-        const int st = qg_plan_geometry(&G->ud[u], flags, nullptr, 0, &G->ug[u], nullptr, nullptr);
+        const int st = qg_plan_geometry(&G->ud[u], flags, ev, 0, &G->ug[u], nullptr, nullptr);
         if (st != QG_OK) { *info = G->ug[u].info; return st; }
     }
     return QG_OK;
@@ -777,6 +787,13 @@ static bool grouped_launch_layout(QGrouped* G, int64_t cur[3], double* ops)
             m.off[w] = cur[w];
             over |= __builtin_add_overflow(cur[w], m.bytes[w], &cur[w]) || cur[w] > (1ll << 60);
         }
+        // a chain's tensor operands: the members at the element offsets they have in D (q.pc is D, whole 64 x 64 tiles per member)
+        for (int k = 0; G->has_ep && k < q.ept.n; ++k) {
+            if (!stage_has_tensor(q.ept.st[k])) continue;
+            m.eoff[k] = G->launch_elems * q.ept.st[k].ebytes;
+            over |= __builtin_add_overflow(m.eoff[k], q.pc.Mp * q.pc.Np * q.ept.st[k].ebytes, &G->ebytes[k]) || G->ebytes[k] > (1ll << 60);
+        }
+        G->launch_elems += q.pc.Mp * q.pc.Np;
         rows[0] += q.pa.rows_p;
         rows[1] += q.pb.rows_p;
         tiles += (q.pa.rows_p / q.cfg.TM) * (q.pb.rows_p / q.cfg.TN);
@@ -821,7 +838,9 @@ static int grouped_schedule(QGrouped* G)
     QGrpShape* sh = new (std::nothrow) QGrpShape[G->n_in];
     int64_t* order = new (std::nothrow) int64_t[G->n_in];
     G->tiles = new (std::nothrow) QGrpTile[G->n_tiles];
-    if (!sh || !order || !G->tiles) { delete[] sh; delete[] order; return QG_EINVAL; }
+    const bool pass = G->has_ep && !G->fused;   // the chain's pass over the launch's packed C: the member of every C tile
+    if (pass) G->tile_member = new (std::nothrow) int32_t[G->n_tiles];
+    if (!sh || !order || !G->tiles || (pass && !G->tile_member)) { delete[] sh; delete[] order; return QG_EINVAL; }
     int64_t n = 0;
     for (int64_t g = 0; g < G->groups; ++g) {
         const QGrpMember& m = G->m[g];
@@ -847,25 +866,45 @@ static int grouped_schedule(QGrouped* G)
     // (the alternative order exists in the diagnostic library only: tools/measure_grouped.py)
     const bool member_order = QG_DIAG_ENV("QG_GRP_MEMBER_ORDER");
     qg_grp_schedule(sh, n, member_order ? QG_GRP_MEMBER : QG_GRP_DEALT, order, G->tiles);
+    if (pass) qg_grp_tile_members(sh, n, G->tile_member);
     delete[] sh;
     delete[] order;
     return QG_OK;
 }
 
-int qg_grouped_geometry(const qgemul_desc* d, int64_t groups, uint32_t flags, QGrouped* G, qgemul_info* info)
+int qg_grouped_geometry(const qgemul_desc* d, int64_t groups, uint32_t flags, QGrouped* G, qgemul_info* info, const EpView* ev, const qgemul_grouped_ep* gep)
 {
     if (!d || groups < 1 || groups > 0x7fffffffll) return QG_EINVAL;
     G->groups = groups;
+    G->flags = flags;
     G->key = -1;
     G->m = new (std::nothrow) QGrpMember[groups]();
     G->ud = new (std::nothrow) qgemul_desc[groups];
     if (!G->m || !G->ud) return QG_EINVAL;
-    if (const int st = grouped_distinct(d, groups, flags, G, info); st != QG_OK) return st;
+    G->has_ep = ev ? 1 : 0;
+    for (int k = 0; ev && ev->ax && k < QG_MAX_EW; ++k) G->has_ax |= ev->ax[k] != nullptr;
+    if (const int st = grouped_distinct(d, groups, flags, ev, G, info); st != QG_OK) return st;
+    if (ev) {
+        // per-member values belong to scalar stages (the stage kinds depend on the chain alone: any member's table shows them)
+        const QEpTable& t = G->ug[0].ept;
+        for (int k = 0; gep && k < QG_MAX_EW; ++k) {
+            if (!gep->scalar_per_member[k]) continue;
+            if (k >= t.n || !stage_is_scalar(t.st[k])) {
+                *info = G->ug[0].info;
+                info->supported = 0;
+                snprintf(info->reason, sizeof info->reason, "grouped chain: scalar_per_member on stage %d, which is no scalar stage", k);
+                return QG_EINVAL;
+            }
+            G->per_member[k] = 1;
+        }
+        // fused form: what the 32-bit epilogue can carry, on request (the default between the two forms is the pass: DESIGN.md section 9)
+        G->fused = G->key >= 0 && G->ug[G->key].ept.bits32 && !G->has_ax && (flags & QG_OPT_FUSED_EPILOGUE) && !(flags & QG_OPT_UNFUSED_EPILOGUE);
+    }
     int64_t cur[3] = {0, 0, 0};
     double ops = 0;
     bool over = grouped_launch_layout(G, cur, &ops);
     // ... then the stragglers
-    int64_t launches = G->n_in ? 1 : 0;
+    int64_t launches = G->n_in ? (ev && !G->fused ? 2 : 1) : 0;
     for (int64_t g = 0; g < groups && !over; ++g) {
         QGrpMember& m = G->m[g];
         if (m.in_launch) continue;
@@ -875,7 +914,12 @@ int qg_grouped_geometry(const qgemul_desc* d, int64_t groups, uint32_t flags, QG
             m.bytes[w] = q.info.packed_bytes[w];
             over |= __builtin_add_overflow(m.off[w], m.bytes[w], &cur[w]) || cur[w] > (1ll << 60);
         }
-        if (!qg_grp_empty(G->ud[m.uniq])) launches += qg_plan_launches(&q);
+        for (int k = 0; ev && k < q.ept.n; ++k) {
+            if (!stage_has_tensor(q.ept.st[k])) continue;
+            m.eoff[k] = qg_round_up(G->ebytes[k], 256);
+            over |= __builtin_add_overflow(m.eoff[k], q.pc.Mp * q.pc.Np * q.ept.st[k].ebytes, &G->ebytes[k]) || G->ebytes[k] > (1ll << 60);
+        }
+        if (!qg_grp_empty(G->ud[m.uniq])) launches += straggler_launches(G, q, flags);
     }
     *info = G->ug[G->key >= 0 ? G->key : G->m[0].uniq].info;
     if (over) {
@@ -888,6 +932,12 @@ int qg_grouped_geometry(const qgemul_desc* d, int64_t groups, uint32_t flags, QG
     info->ops = ops;
     snprintf(info->reason, sizeof info->reason, "grouped plan: %lld members in one launch (%lld 64x64 tiles), %lld run alone", (long long)G->n_in,
              (long long)G->n_tiles, (long long)(groups - G->n_in));
+    if (ev && !G->n_in)
+        snprintf(info->reason, sizeof info->reason, "grouped chain: no member eligible, %lld run alone", (long long)groups);
+    else if (ev)
+        snprintf(info->reason, sizeof info->reason, G->fused ? "grouped chain fused: %lld members in one launch (%lld 64x64 tiles), %lld run alone"
+                                                             : "grouped chain pass: %lld members in one launch (%lld 64x64 tiles) + one pass, %lld run alone",
+                 (long long)G->n_in, (long long)G->n_tiles, (long long)(groups - G->n_in));
     return G->n_tiles > 0 ? grouped_schedule(G) : QG_OK;
 }
 
@@ -897,7 +947,7 @@ void qg_grouped_member_out(const QGrouped* G, int64_t g, qgemul_grouped_member* 
     const QPlanGeom& q = G->ug[m.uniq];
     memset(out, 0, sizeof *out);
     out->in_launch = m.in_launch;
-    out->launches = m.in_launch || qg_grp_empty(G->ud[m.uniq]) ? 0 : qg_plan_launches(&q);
+    out->launches = m.in_launch || qg_grp_empty(G->ud[m.uniq]) ? 0 : straggler_launches(G, q, G->flags);
     for (int w = 0; w < 3; ++w) { out->off[w] = m.off[w]; out->bytes[w] = m.bytes[w]; }
     if (m.in_launch) {
         out->tiles_m = q.pa.rows_p / q.cfg.TM;

@@ -178,6 +178,7 @@ struct QGrpMember {
     int64_t off[3], bytes[3];   // inside packed A / B / C
     int64_t row_a, row_b;       // in the launch: first row of the member in the stack's row sums
     QPackedGeom pa, pb;         // in the launch: the member's geometry with trailer / row sums relative to ITS start (qg_launch_pack_member)
+    int64_t eoff[QG_MAX_EW];    // with a chain: byte offset of the member inside stage k's packed tensor operand
 };
 struct QGrouped {
     int64_t groups, n_uniq, n_in, n_tiles;
@@ -191,7 +192,27 @@ struct QGrouped {
     int launches;
     QGrpTile* tiles;            // [n_tiles] host
     QGrpTile* tiles_dev;
-    ~QGrouped() { delete[] ud, delete[] ug, delete[] u_in, delete[] up, delete[] m, delete[] tiles; }
+    // Element-wise chain (qgemul_plan_create_grouped_epx; has_ep).  ONE chain serves the group: off[2] / bytes[2] of a member then describe
+    // packed D, and stage k's packed tensor operand follows D's layout (QGrpMember::eoff, ebytes[k] = the whole group's bytes; 0: no
+    // tensor operand).  The members in the launch run the chain inside the launch's epilogue (fused: k_mfma_ep_grp) or as ONE pass over
+    // the launch's packed C (cwork_dev, launch_elems elements) whose workgroup w finds its member in tile_member[w] (qg_grp.h); a
+    // straggler runs its own plain _epx plan.  per_member[k]: scalar stage k takes member g's raw value scal[k][g] (host copy for the
+    // stragglers, scal_dev[k] for the launch; scal_set[k]: qgemul_grouped_set_scalars has filled them) instead of the call's e_scalar[k].
+    int has_ep, has_ax, fused;
+    uint32_t flags;             // the plan's option flags
+    int64_t launch_elems;
+    uint8_t per_member[QG_MAX_EW], scal_set[QG_MAX_EW];
+    int64_t ebytes[QG_MAX_EW];
+    int32_t* tile_member;       // [n_tiles] host (pass form)
+    int32_t* tile_member_dev;
+    int64_t* scal[QG_MAX_EW];   // [groups] host
+    int64_t* scal_dev[QG_MAX_EW];
+    void* cwork_dev;
+    ~QGrouped()
+    {
+        delete[] ud, delete[] ug, delete[] u_in, delete[] up, delete[] m, delete[] tiles, delete[] tile_member;
+        for (int k = 0; k < QG_MAX_EW; ++k) delete[] scal[k];
+    }
 };
 
 #pragma GCC visibility push(hidden)   // internal to the library: nothing here is an exported symbol
@@ -227,6 +248,8 @@ int qg_batched_launches(const QPlanGeom* s, const QBatchGeom* b, bool has_ep);
 bool qg_same_launch_key(const QPlanGeom& x, const QPlanGeom& y);
 inline bool qg_grp_empty(const qgemul_desc& d) { return d.M == 0 || d.N == 0; }
 // the geometry of a grouped plan: G (fresh) and info receive it; info says why a descriptor was refused
-int qg_grouped_geometry(const qgemul_desc* d, int64_t groups, uint32_t flags, QGrouped* G, qgemul_info* info);
+// ev: the ONE element-wise chain of a grouped plan with one (nullptr: none), gep: which of its scalar stages take per-member values
+int qg_grouped_geometry(const qgemul_desc* d, int64_t groups, uint32_t flags, QGrouped* G, qgemul_info* info, const EpView* ev = nullptr,
+                        const qgemul_grouped_ep* gep = nullptr);
 void qg_grouped_member_out(const QGrouped* G, int64_t g, qgemul_grouped_member* out);
 #pragma GCC visibility pop

@@ -81,6 +81,18 @@ inline QGrpTile qg_grp_record(const QGrpShape& s, int32_t w)
     return t;
 }
 
+// The chain pass of a grouped plan with an element-wise chain (k_eltwise_grp / k_approx_grp, qg_eltwise_grp.hip) walks the launch's
+// packed C linearly, one 64 x 64 tile per workgroup, and must know whose per-member scalars a tile takes: out[w] = the member (index
+// in the caller's list) of C tile w IN MEMORY ORDER, w = c_off / c_tile, 4 bytes per workgroup.  out[T], T = qg_grp_tiles(m, n); the
+// members' C tiles are disjoint and cover [0, T) (the planner lays them back to back), so every entry is written exactly once.
+inline void qg_grp_tile_members(const QGrpShape* m, int64_t n, int32_t* out)
+{
+    for (int64_t g = 0; g < n; ++g) {
+        const int64_t w0 = m[g].c_off / m[g].c_tile, cnt = (int64_t)m[g].tiles_m * m[g].tiles_n;
+        for (int64_t w = 0; w < cnt; ++w) out[w0 + w] = m[g].member;
+    }
+}
+
 // out[T], T = qg_grp_tiles(m, n) < 2^31; order[n] is scratch of the caller (member indices).  Members without tiles take none.
 inline void qg_grp_schedule(const QGrpShape* m, int64_t n, int mode, int64_t* order, QGrpTile* out)
 {

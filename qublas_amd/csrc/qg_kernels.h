@@ -182,6 +182,24 @@ QG_HD const QGrpTile* qg_grp_tiles_of(const G&, long) { return nullptr; }
 // n_tiles workgroups, the ten geometries of qg_launch_mfma_bd (a 3 x 3 launch is the pair <3,3> + <2,2 on three-plane storage>,
 // both reading the same records); anything else is hipErrorInvalidValue
 hipError_t qg_launch_mfma_grp(int LA, int LB, const QMfmaGrpArgs& a, int64_t n_tiles, hipStream_t st);
+// An element-wise chain on a grouped plan (qgemul_plan_create_grouped_epx).  C, D and every tensor operand are the members' packed
+// tensors back to back, one index space over the launch, so the chain runs at the launch-wide element index; what differs from member
+// to member is a scalar stage's value: scal[k] != nullptr: stage k takes the raw value scal[k][member] (a table of the plan, one entry
+// per member of the caller's list; a wave-uniform load), nullptr: QEpArgs::scalar[k] for all (QGrpEp: qg_eltwise_args.h).  The new kernels
+// carry this in argument structs of their own: QMfmaArgs, QMfmaGrpArgs, QMfmaEpBdArgs, QEpArgs and QEltwiseArgs are what they were.
+struct QMfmaEpGrpArgs : QMfmaArgs {
+    const QGrpTile* tiles;
+    QGrpEp ge;
+};
+// the QGrpEp of a kernel's argument struct, in place: its table pointers are indexed by the stage number at run time, and a copy
+// would live in scratch (kernels whose arguments have none never evaluate the result)
+template <class G>
+QG_HD auto qg_grp_ep_of(const G& g, int) -> decltype(&g.ge) { return &g.ge; }
+template <class G>
+QG_HD const QGrpEp* qg_grp_ep_of(const G&, long) { return nullptr; }
+// the grouped launch with the chain in the kernel's epilogue (qg_mfma_ep_grp.hip: k_mfma_ep_grp, the body of k_mfma with GRP and EP
+// together): the geometries of qg_launch_mfma_grp, chains the planner has bounded by 32-bit arithmetic
+hipError_t qg_launch_mfma_ep_grp(int LA, int LB, const QMfmaEpGrpArgs& a, int64_t n_tiles, hipStream_t st);
 // one member of a stack the caller has cleared (trailer, row sums): qg_launch_pack without the clearing, as qg_launch_pack_stack
 // packs its members (p.trailer and p.rowsum_off relative to dst, p.offs == 2 for centred operands)
 hipError_t qg_launch_pack_member(const QOperandGeom& g, const QPackedGeom& p, const void* src, void* dst, int check_range, int* range_flag,

@@ -1,6 +1,6 @@
 // qg_mfma_body.h — the body of k_mfma and k_mfma_bd (qg_mfma.hip) and of k_mfma_ep_bd (qg_mfma_ep_bd.hip), included INSIDE the
 // kernels: no include guard, nothing at namespace scope.  In scope where it is included: the kernel argument `QMfmaArgs g` (BD with
-// EP: a QMfmaEpBdArgs; GRP: a QMfmaGrpArgs) and the compile-time constants LA, LB, BK, WGM, WGN, TI, TJ, NSTAGE, ABL, EP, SA, SB, KARA,
+// EP: a QMfmaEpBdArgs; GRP: a QMfmaGrpArgs, with EP a QMfmaEpGrpArgs: k_mfma_ep_grp, qg_mfma_ep_grp.hip) and the compile-time constants LA, LB, BK, WGM, WGN, TI, TJ, NSTAGE, ABL, EP, SA, SB, KARA,
 // KS, BD, GRP (their meaning: the comment in front of k_mfma; GRP: k_mfma_grp, qg_mfma_grp.hip).
     if constexpr (SA == 3 && SB == 3 && ABL == 0) {
         const unsigned ma = qg_plane_mask(g.maskA);
@@ -35,16 +35,21 @@
     int bd_member = 0;       // BD: the member that tile belongs to (wave-uniform)
     int64_t grp_a = 0, grp_b = 0, grp_c = 0, grp_corr = 0;   // GRP: this workgroup's record of the host's schedule (qg_grp.h)
     int grp_nk = 0;
+    int grp_member = 0;      // GRP with EP: the member of the caller's list this workgroup's tile belongs to (wave-uniform)
     if constexpr (GRP) {
         // grouped launch: block bid reads record bid — where its A and B blocks start, where its C tile goes, its k-tile count, its
         // rows of the stack's row sums and its member's K biasA biasB.  One wave-uniform load of 48 bytes; no division, no tile walk
-        static_assert(!GRP || (!BD && KS == 1 && !KARA && ABL == 0 && !EP && TM == 64 && TN == 64), "grouped form: the plain lock-step body on 64 x 64 tiles");
+        static_assert(!GRP || (!BD && KS == 1 && !KARA && ABL == 0 && TM == 64 && TN == 64), "grouped form: the plain lock-step body on 64 x 64 tiles");
         const QGrpTile rec = qg_grp_tiles_of(g, 0)[blockIdx.x];
         grp_a = rec.a_off;
         grp_b = rec.b_off;
         grp_c = rec.c_off;
         grp_corr = rec.corr;
         grp_nk = rec.nk;
+        if constexpr (EP) {   // (wave-uniform; said so: the member indexes the scalar tables, the C offset goes into base pointers)
+            grp_member = __builtin_amdgcn_readfirstlane(rec.member);
+            grp_c = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(rec.c_off >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)rec.c_off));
+        }
         tile_m = (int)((unsigned)rec.row_a / (unsigned)TM);   // (the row sums' rows: tile_m * TM, tile_n * TN)
         tile_n = (int)((unsigned)rec.row_b / (unsigned)TN);
     } else
@@ -299,6 +304,18 @@
                 int32_t v[16];
 #pragma unroll
                 for (int e = 0; e < 16; ++e) v[e] = (int32_t)s[e];
+                if constexpr (GRP) {
+                    // the tile's base is the launch-wide element index already (D and every tensor operand: the members back to back).
+                    // It is wave-uniform and goes into the operands' and D's base pointers; what a lane adds is its index inside the
+                    // tile, below 4096: 32-bit offsets, where 64-bit element indices per run and container cost a third wave per SIMD.
+                    // A per-member scalar stage takes its member's value from the plan's table: a uniform load, nothing per lane
+                    const uint32_t lane0 = (uint32_t)(col * TM + row0);
+                    qg_ep_apply_runs_grp<int32_t, 4>(v, g.ep, g.epa, tile_base, lane0, 8, *qg_grp_ep_of(g, 0), grp_member);
+                    char* Dt = C + tile_base * g.ep.dbytes;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) qg_ep_store_run<int32_t>(Dt + (lane0 + 8u * q) * (uint32_t)g.ep.dbytes, 0, g.ep.dbytes, v + 4 * q);
+                    continue;
+                } else
                 if constexpr (BD) {   // D and per-member operands at the stack-wide index, a shared operand at the member-local one
                     const QBdEp be = qg_bd_ep_of(g, 0);
                     qg_ep_apply_runs_bd<int32_t, 4>(v, g.ep, g.epa, base, 8, (int64_t)bd_member * be.msize, be.shared);

@@ -395,12 +395,29 @@ bool grp_key_equal(const qgemul_desc* d, int64_t groups)
 int64_t up256(int64_t x) { return (x + 255) / 256 * 256; }
 } // namespace
 
-int qgemul_run_grouped(const qgemul_desc* d, int64_t groups, void* const* C, const void* const* A, const void* const* B, const int64_t* lda,
-                       const int64_t* ldb, const int64_t* ldc, const qgemul_opts* o)
+// ev: the group's one element-wise chain (nullptr: none; then gep, E and scalars are not read and C is C); with one, C is D, E[k][g] is
+// member g's tight operand of tensor stage k (one element for a scalar stage that is not per member) and scalars[k] the per-member
+// values of stage k.  The cache key holds the chain and, in the place of a batched chain's shared pattern, the per-member pattern
+static int run_grouped_view(const qgemul_desc* d, int64_t groups, const EpView* ev, const qgemul_grouped_ep* gep, void* const* C, const void* const* A,
+                            const void* const* B, const void* const* const* E, const int64_t* const* scalars, const int64_t* lda, const int64_t* ldb,
+                            const int64_t* ldc, const qgemul_opts* o)
 {
     if (!d || !C || !A || !B || groups < 1 || groups > 0x7fffffffll) return QG_EINVAL;
     qgemul_opts opts = resolve_opts(o);
     if (opts.flags & QG_OPT_ALL_DEVICES) return QG_EUNSUPPORTED;   // (the sharded entry has no grouped form)
+    const qgemul_epilogue* ep = ev ? ev->re : nullptr;
+    if (ep && ep->n_stages > QG_MAX_EW) return QG_EINVAL;
+    qgemul_batched_ep pattern;
+    memset(&pattern, 0, sizeof pattern);
+    for (uint32_t k = 0; ep && k < ep->n_stages; ++k) {
+        const qgemul_ew_stage& s = ep->stage[k];
+        const bool per = gep && gep->scalar_per_member[k];
+        pattern.e_shared[k] = per ? 1 : 0;
+        if (s.op == QG_EW_APPROX) continue;
+        if (per ? (!scalars || !scalars[k]) : (!E || !E[k])) return QG_EINVAL;
+        for (int64_t g = 0; !per && g < groups; ++g)
+            if (!(d[g].M == 0 || d[g].N == 0) && !E[k][s.e_scalar ? 0 : g]) return QG_EINVAL;
+    }
     bool gaps = false;
     for (int64_t g = 0; g < groups; ++g) {
         if (d[g].M == 0 || d[g].N == 0) continue;
@@ -416,11 +433,12 @@ int qgemul_run_grouped(const qgemul_desc* d, int64_t groups, void* const* C, con
         int cur = c.device;
         if (hipGetDevice(&cur) == hipSuccess) opts.device = cur;
     }
-    qg_run_key_set(g_want, d[0], opts.flags, -groups, nullptr, nullptr);
+    qg_run_key_set(g_want, d[0], opts.flags, -groups, ev, ev ? &pattern : nullptr);
     const bool same_plan = c.plan && qg_run_key_equal(c.key, g_want) && grp_key_equal(d, groups) && (opts.device < 0 || opts.device == c.device);
     if (!same_plan) {   // validate before touching the device
         qgemul_info info;
-        if (const int st = qgemul_classify_grouped(d, groups, opts.flags, &info); st != QG_OK) return st;
+        const int st = ev ? qgemul_classify_grouped_epx(d, groups, ep, ev->ax, gep, opts.flags, &info) : qgemul_classify_grouped(d, groups, opts.flags, &info);
+        if (st != QG_OK) return st;
     }
     int st = QG_OK;
     const bool warm = c.ctx && (opts.device < 0 || opts.device == c.device);
@@ -428,7 +446,7 @@ int qgemul_run_grouped(const qgemul_desc* d, int64_t groups, void* const* C, con
     if (warm) QG_HIP(hipSetDevice(c.device));
     if (!same_plan) {
         if (c.plan) { qgemul_plan_destroy(c.plan); c.plan = nullptr; }
-        st = qgemul_plan_create_grouped(c.ctx, d, groups, opts.flags, &c.plan);
+        st = ev ? qgemul_plan_create_grouped_epx(c.ctx, d, groups, ep, ev->ax, gep, opts.flags, &c.plan) : qgemul_plan_create_grouped(c.ctx, d, groups, opts.flags, &c.plan);
         if (st != QG_OK) { c.plan = nullptr; return st; }
         c.key = g_want;
         delete[] g_grp_key.d;
@@ -449,7 +467,9 @@ int qgemul_run_grouped(const qgemul_desc* d, int64_t groups, void* const* C, con
             for (int w = 0; w < 3; ++w) {
                 off[3 * g + w] = tot[w];
                 const qfmt* f = w == 0 ? d[g].a : w == 1 ? d[g].b : d[g].c;
-                if (!empty) tot[w] += up256(qg_member_extent(d[g], w, ld[w]) * (int64_t)qg_host_elem(f, d[g].is_complex).size);
+                // (with a chain the third tensor is D: elements of the chain's destination format)
+                const qfmt fd[2] = {ep ? ep->d : d[g].c[0], ep ? ep->d : d[g].c[1]};
+                if (!empty) tot[w] += up256(qg_member_extent(d[g], w, ld[w]) * (int64_t)qg_host_elem(w == 2 ? fd : f, d[g].is_complex).size);
             }
         }
         void *dA, *dB, *dC, *pA, *pB, *pC;
@@ -461,7 +481,8 @@ int qgemul_run_grouped(const qgemul_desc* d, int64_t groups, void* const* C, con
         void* base[3] = {dA, dB, dC};
         auto bytes_of = [&](int64_t g, int w) {
             const int64_t ld = w == 0 ? (lda ? lda[g] : 0) : w == 1 ? (ldb ? ldb[g] : 0) : (ldc ? ldc[g] : 0);
-            const qfmt* f = w == 0 ? d[g].a : w == 1 ? d[g].b : d[g].c;
+            const qfmt fd[2] = {ep ? ep->d : d[g].c[0], ep ? ep->d : d[g].c[1]};
+            const qfmt* f = w == 0 ? d[g].a : w == 1 ? d[g].b : fd;
             return (size_t)(qg_member_extent(d[g], w, ld) * (int64_t)qg_host_elem(f, d[g].is_complex).size);
         };
         for (int64_t g = 0; g < groups && st == QG_OK; ++g) {
@@ -479,8 +500,37 @@ int qgemul_run_grouped(const qgemul_desc* d, int64_t groups, void* const* C, con
         if (!pa_) { st = QG_EINVAL; break; }
         for (int64_t g = 0; g < groups; ++g)
             for (int w = 0; w < 3; ++w) pa_[w * groups + g] = dptr[3 * g + w];
-        if (!(st = qgemul_pack_grouped(p, QG_OPERAND_A, pa_, lda, pA)) && !(st = qgemul_pack_grouped(p, QG_OPERAND_B, pa_ + groups, ldb, pB)) &&
-            !(st = qgemul_execute_grouped(p, pC, pA, pB)))
+        // the chain's operands: scalars from the caller's one element or into the plan's table, tensors staged and packed member by member
+        qgemul_ep_args ea;
+        memset(&ea, 0, sizeof ea);
+        auto raw = [](const void* q, qfmt f) { return (1 + (int)f.I + (int)f.F) <= 32 ? (int64_t) * (const int32_t*)q : *(const int64_t*)q; };
+        const void** pe_ = ep ? new (std::nothrow) const void*[groups] : nullptr;
+        if (ep && !pe_) st = QG_EINVAL;
+        for (uint32_t k = 0; ep && k < ep->n_stages && st == QG_OK; ++k) {
+            const qgemul_ew_stage& sk = ep->stage[k];
+            if (sk.op == QG_EW_APPROX) continue;
+            if (pattern.e_shared[k]) { st = qgemul_grouped_set_scalars(p, (int)k, scalars[k]); continue; }
+            if (sk.e_scalar) { ea.e_scalar[k] = raw(E[k][0], sk.e); continue; }
+            const qfmt fe[2] = {sk.e, sk.e};
+            const int64_t eb = qg_host_elem(fe, 0).size;
+            int64_t totE = 0;
+            for (int64_t g = 0; g < groups; ++g) totE += d[g].M == 0 || d[g].N == 0 ? 0 : up256(d[g].M * d[g].N * eb);
+            void *dE, *pE;
+            if ((st = cache_buffer(c, 6 + 2 * (int)k, (size_t)totE, &dE)) || (st = cache_buffer(c, 7 + 2 * (int)k, (size_t)qgemul_packed_e_bytes(p, (int)k), &pE))) break;
+            int64_t at = 0;
+            for (int64_t g = 0; g < groups && st == QG_OK; ++g) {
+                pe_[g] = nullptr;
+                if (d[g].M == 0 || d[g].N == 0) continue;
+                pe_[g] = (const char*)dE + at;
+                if (hipMemcpyAsync((void*)pe_[g], E[k][g], (size_t)(d[g].M * d[g].N * eb), hipMemcpyHostToDevice, s) != hipSuccess) st = QG_EHIP;
+                at += up256(d[g].M * d[g].N * eb);
+            }
+            if (st == QG_OK) st = qgemul_pack_e_grouped(p, (int)k, pe_, nullptr, pE);
+            ea.e_packed[k] = pE;
+        }
+        delete[] pe_;
+        if (st == QG_OK && !(st = qgemul_pack_grouped(p, QG_OPERAND_A, pa_, lda, pA)) && !(st = qgemul_pack_grouped(p, QG_OPERAND_B, pa_ + groups, ldb, pB)) &&
+            !(st = ep ? qgemul_execute_grouped_ep(p, pC, pA, pB, &ea) : qgemul_execute_grouped(p, pC, pA, pB)))
             st = qgemul_unpack_c_grouped(p, pC, (void* const*)(pa_ + 2 * groups), ldc);
         delete[] pa_;
         for (int64_t g = 0; g < groups && st == QG_OK; ++g) {
@@ -493,6 +543,23 @@ int qgemul_run_grouped(const qgemul_desc* d, int64_t groups, void* const* C, con
     delete[] dptr;
     if (st == QG_OK && e != hipSuccess) { qg_set_last_hip((int)e); st = QG_EHIP; }
     return st;
+}
+
+int qgemul_run_grouped(const qgemul_desc* d, int64_t groups, void* const* C, const void* const* A, const void* const* B, const int64_t* lda,
+                       const int64_t* ldb, const int64_t* ldc, const qgemul_opts* o)
+{
+    return run_grouped_view(d, groups, nullptr, nullptr, C, A, B, nullptr, nullptr, lda, ldb, ldc, o);
+}
+
+// ... followed by ONE real element-wise chain with per-member scalars: member g is Qgemul<...>(C_g, A_g, B_g), then the chain
+int qgemul_run_grouped_epx(const qgemul_desc* d, int64_t groups, const qgemul_epilogue* ep, const qgemul_approx* const ax[QG_MAX_EW], const qgemul_grouped_ep* gep,
+                           void* const* D, const void* const* A, const void* const* B, const void* const* const E[QG_MAX_EW],
+                           const int64_t* const scalars[QG_MAX_EW], const int64_t* lda, const int64_t* ldb, const int64_t* ldd, const qgemul_opts* o)
+{
+    if (!ep) return QG_EINVAL;
+    static const qgemul_approx* const no_ax[QG_MAX_EW] = {};   // (ax == nullptr: a chain without APPROX stages)
+    const EpView v = {ep, nullptr, nullptr, ax ? ax : no_ax};
+    return run_grouped_view(d, groups, &v, gep, D, A, B, E, scalars, lda, ldb, ldd, o);
 }
 
 // ---- several GPUs in one process: row bands of C, one per entry of the device list (include/qgemul.h) ----

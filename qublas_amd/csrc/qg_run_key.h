@@ -25,7 +25,8 @@ struct QRunKey {
     qgemul_approx* ax;                // QG_MAX_EW tables, allocated while any ax_on[k]
     uint8_t cx_on[QG_MAX_EW];         // stage k carries a CMUL record: cx[k]
     qgemul_cmul cx[QG_MAX_EW];
-    uint8_t e_shared[QG_MAX_EW];      // batched chain: stage k's tensor operand is one tensor for every member
+    uint8_t e_shared[QG_MAX_EW];      // batched chain: stage k's tensor operand is one tensor for every member; grouped chain (batch < 0):
+                                      // scalar stage k takes one value per member (qgemul_grouped_ep::scalar_per_member)
 
     QRunKey() { memset((void*)this, 0, sizeof *this); }
     QRunKey(const QRunKey& o) : QRunKey() { *this = o; }

@@ -126,6 +126,18 @@ def batched_ep(shared=()) -> "qgemul_batched_ep":
     return b
 
 
+class qgemul_grouped_ep(C.Structure):
+    """which scalar stages of a grouped plan's chain take one raw value per member from the plan's table; include/qgemul.h"""
+    _fields_ = [("scalar_per_member", C.c_uint8 * QG_MAX_EW), ("reserved", C.c_uint8 * 4)]
+
+
+def grouped_ep(per_member=()) -> "qgemul_grouped_ep":
+    b = qgemul_grouped_ep()
+    for k, v in enumerate(per_member):
+        b.scalar_per_member[k] = 1 if v else 0
+    return b
+
+
 class qgemul_grouped_member(C.Structure):
     """where member g of a grouped plan lives (include/qgemul.h)"""
     _fields_ = [("in_launch", C.c_int32), ("launches", C.c_int32), ("off", C.c_int64 * 3), ("bytes", C.c_int64 * 3),
