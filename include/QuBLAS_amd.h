@@ -351,9 +351,23 @@ struct Slots { int cmul = QG_CMUL_NONE; Fmt m[8]{}; Fmt prod[2]{}; };
 
 template <class EA, class EB, class MulList> struct slots_of;
 template <class EA, class EB, typename... Tags>
-    requires(!EA::is_complex)
+    requires(!EA::is_complex && !EB::is_complex)
 struct slots_of<EA, EB, TypeList<Tags...>> {
     static constexpr Slots value = [] { Slots s; s.m[0] = merge_mul(EA::fmt, EB::fmt, parse<Tags...>::value); s.prod[0] = s.prod[1] = s.m[0]; return s; }();
+};
+// ONE real and ONE complex operand: Qmul(real, complex) / Qmul(complex, real) are part-wise (QuBLAS.h:3604-3644),
+// re = Qmul<realT...>(x, y.real), im = Qmul<imagT...>(x, y.imag); two bare Qu types as tags are <realT<first>, imagT<second>>
+template <class EA, class EB, typename... Tags>
+    requires(EA::is_complex != EB::is_complex)
+struct slots_of<EA, EB, TypeList<Tags...>> {
+    static constexpr Slots value = [] {
+        Slots s;
+        s.cmul = EA::is_complex ? QG_CMUL_REAL_B : QG_CMUL_REAL_A;
+        s.m[QG_M_RE] = merge_mul(re_fmt<EA>(), re_fmt<EB>(), part_tags<0, Tags...>::value);   // (re_fmt / im_fmt of a real element: its format)
+        s.m[QG_M_IM] = merge_mul(im_fmt<EA>(), im_fmt<EB>(), part_tags<1, Tags...>::value);
+        s.prod[0] = s.m[QG_M_RE]; s.prod[1] = s.m[QG_M_IM];
+        return s;
+    }();
 };
 // the complex multiplier a tag list names, on part formats: f1 = a + bi the first argument, f2 = c + di the second
 template <class MulList> struct cmul_of;
@@ -391,7 +405,7 @@ struct cmul_of<TypeList<TFComplexMul<Args...>>> {
     }
 };
 template <class EA, class EB, class MulList>
-    requires(EA::is_complex)
+    requires(EA::is_complex && EB::is_complex)
 struct slots_of<EA, EB, MulList> {
     static constexpr Slots value = cmul_of<MulList>::slots(re_fmt<EA>(), im_fmt<EA>(), re_fmt<EB>(), im_fmt<EB>());
 };
@@ -443,21 +457,24 @@ qgemul_desc Qgemul_lower_types(std::type_identity<Qu_s<dim<CM, CN>, EC>>, std::t
     constexpr bool ta = pick_ta<Tags...>::value;
     constexpr size_t M = ta ? AC : AR, K = ta ? AR : AC;
     static_assert(M == CM && BN == CN && BKd == K, "Qgemul: C is MxN, A is MxK (KxM when transposed), B is KxN");
-    static_assert(EA::is_complex == EB::is_complex && EA::is_complex == EC::is_complex, "Qgemul: all real or all complex");
+    // real x real -> real; complex x complex, real x complex and complex x real -> complex (the mixed forms: QG_CMUL_REAL_A / _B of qgemul.h)
+    static_assert(EC::is_complex == (EA::is_complex || EB::is_complex), "Qgemul: C is complex exactly when an operand is");
     using add_list = typename pick_add<Tags...>::type;
     using L = levels_of<add_list>;
-    static_assert(EA::is_complex ? L::all_complex : L::all_real, "Qgemul: level types must be complex for complex operands, real otherwise");
+    static_assert(EC::is_complex ? L::all_complex : L::all_real, "Qgemul: level types must be complex for a complex result, real otherwise");
     constexpr Slots s = slots_of<EA, EB, typename pick_mul<Tags...>::type>::value;
     qgemul_desc d{};
     d.abi = QGEMUL_ABI_VERSION;
     d.transA = ta;
-    d.is_complex = EA::is_complex;
+    d.is_complex = EC::is_complex;
     d.cmul = uint8_t(s.cmul);
     d.M = int64_t(M); d.N = int64_t(CN); d.K = int64_t(K);
     d.a[0] = re_fmt<EA>().c(); d.a[1] = im_fmt<EA>().c();
     d.b[0] = re_fmt<EB>().c(); d.b[1] = im_fmt<EB>().c();
     d.c[0] = re_fmt<EC>().c(); d.c[1] = im_fmt<EC>().c();
-    for (int i = 0; i < (s.cmul == QG_CMUL_NONE ? 1 : s.cmul == QG_CMUL_TF ? 8 : 6); ++i) d.mul[i] = s.m[i].c();
+    if constexpr (EC::is_complex && !EA::is_complex) d.a[1] = qfmt{};   // a mixed descriptor's real operand: its format in [0], [1] all zero
+    if constexpr (EC::is_complex && !EB::is_complex) d.b[1] = qfmt{};
+    for (int i = 0; i < (s.cmul == QG_CMUL_NONE ? 1 : s.cmul == QG_CMUL_TF ? 8 : s.cmul == QG_CMUL_BASIC ? 6 : 2); ++i) d.mul[i] = s.m[i].c();
     for (size_t k = K; k > 1; k = (k + 1) / 2) ++d.n_levels;
     Fmt prev[2] = {s.prod[0], s.prod[1]};
     for (uint32_t l = 0; l < d.n_levels; ++l) {
@@ -467,7 +484,7 @@ qgemul_desc Qgemul_lower_types(std::type_identity<Qu_s<dim<CM, CN>, EC>>, std::t
                 buf = L::value[l < L::n ? l : L::n - 1][p];
                 // real: Qadd<T_l> yields T_l; complex: the complex tag is ignored, the add is the default
                 // merge of two equal formats (= that format) and the level buffer converts (QuBLAS.h:4966)
-                add = EA::is_complex ? merge_add(prev[p], prev[p], TagSet{}) : buf;
+                add = EC::is_complex ? merge_add(prev[p], prev[p], TagSet{}) : buf;
             }
             d.level_add[p][l] = add.c();
             d.level[p][l] = buf.c();

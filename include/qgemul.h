@@ -61,7 +61,17 @@ enum {
 };
 
 /* complex multiply algorithm — BasicComplexMul QuBLAS.h:3426-3445, TFComplexMul :3510-3534 */
-enum { QG_CMUL_NONE = 0, QG_CMUL_BASIC = 1, QG_CMUL_TF = 2 };
+enum { QG_CMUL_NONE = 0, QG_CMUL_BASIC = 1, QG_CMUL_TF = 2,
+       /* one REAL and one COMPLEX operand ("Real-Complex Operations", QuBLAS.h:3600-3644): Qmul(real, complex) and
+        * Qmul(complex, real) are part-wise,  re = Qmul<realT...>(a, y.real),  im = Qmul<imagT...>(a, y.imag)  — two bare Qu
+        * types as tags mean <realT<first>, imagT<second>> — so a mixed Qgemul is two real trees that share one operand.
+        * is_complex = 1 (C is complex; level_add / level / c as for any complex descriptor).  The REAL operand's format is
+        * in [0] of its a[] / b[]; its [1] must be all zero (QG_EINVAL otherwise: one descriptor, one spelling).  Its host
+        * element is a plain int32_t / int64_t word (qgemul_info.host_elem_bytes / host_imag_off are per operand).
+        * Served: the plain entry points and qgemul_run.  Element-wise chains, batched and grouped plans and the sharded
+        * run refuse such a descriptor (QG_EUNSUPPORTED, "mixed real-complex"). */
+       QG_CMUL_REAL_A = 3,   /* A real, B and C complex:  p_re = op(A'[i,k] * B[k,j].real),  p_im = op(A'[i,k] * B[k,j].imag) */
+       QG_CMUL_REAL_B = 4 }; /* A and C complex, B real:  p_re = op(A'[i,k].real * B[k,j]),  p_im = op(A'[i,k].imag * B[k,j]) */
 
 /* slots of qgemul_desc.mul[] */
 enum {
@@ -80,7 +90,10 @@ enum {
     QG_T_B = 4,   /* Qmul(cd, b) */
     QG_T_C = 5,   /* Qmul(ba, d) */
     QG_T_RE = 6,  /* Qsub(A, B) */
-    QG_T_IM = 7   /* Qsub(B, C) */
+    QG_T_IM = 7,  /* Qsub(B, C) */
+    /* QG_CMUL_REAL_A / QG_CMUL_REAL_B (QuBLAS.h:3604-3644): the two part-wise products, nothing else */
+    QG_M_RE = 0,  /* Qmul<realT...>(real, complex.real) / (complex.real, real) */
+    QG_M_IM = 1   /* Qmul<imagT...>(real, complex.imag) / (complex.imag, real) */
 };
 
 typedef struct qfmt {
@@ -215,7 +228,7 @@ typedef struct qgemul_info {
     int32_t host_elem_bytes[3]; /* sizeof host element of A, B, C (complex: whole struct) */
     int32_t host_imag_off[3];   /* byte offset of .imag inside a complex host element */
     int64_t packed_bytes[3];    /* device-private packed sizes of A, B, C for this M,N,K */
-    double  ops;                /* 2*M*N*K for real; x3 (TF) or x4 (Basic) real MACs for complex */
+    double  ops;                /* 2*M*N*K for real; x3 (TF) or x4 (Basic) real MACs for complex; x2 for real x complex */
     char    reason[96];         /* why unsupported / why tree */
 } qgemul_info;
 
@@ -230,6 +243,9 @@ enum {
     QG_KERNEL_MFMA_CPLX = 7,    /* class L, complex: four real int8-limb dot products on MFMA + one combine pass */
     QG_KERNEL_GEMV_I32 = 8,     /* class T, N = 1 (batched Qreduce / GEMV), K = 2^p >= 16, 32-bit values: one wave per row (or per 256/K rows) */
     QG_KERNEL_GEMV_I64 = 9,     /* the same with 64-bit tree values on elements of at most 32 storage bits (32-bit words, wide level types) */
+    QG_KERNEL_TREE_RC_I32 = 11, /* class T, one real and one complex operand (QG_CMUL_REAL_A / _B), 32-bit intermediates: two part-wise trees on a shared real value */
+    QG_KERNEL_MFMA_RC = 12,     /* class L, one real and one complex operand: ONE real int8-limb GEMM on the stacked operand (A x [B_re | B_im] or
+                                   [A_re; A_im] x B) into raw 64-bit dot products + one two-product convert pass */
     QG_KERNEL_TREE_I128 = 10    /* class T with intermediates / level formats / C beyond 62 bits (up to 120): the general tree kernel on
                                    128-bit values — the reference's multi-word ArbiInt<N > 64>, QuBLAS.h:566-912; real or complex */
 };

@@ -61,14 +61,23 @@ template <class... Tags> struct mul_with<TypeList<Tags...>> {
 // ---- product sub-operation formats
 template <class EA, class EB, class MulList> struct slots;
 template <class EA, class EB, class... Tags>
-    requires(!EA::is_complex)
+    requires(!EA::is_complex && !EB::is_complex)
 struct slots<EA, EB, TypeList<Tags...>> {
     using prod_t = decltype(Qmul<Tags...>(std::declval<EA>(), std::declval<EB>()));
     static constexpr int cmul = QG_CMUL_NONE;
     static void fill(qgemul_desc& d) { d.mul[QG_MUL_REAL] = fmt_of<prod_t>(); }
 };
+// ONE real and ONE complex operand: the header's own part-wise Qmul(real, complex) / Qmul(complex, real) (QuBLAS.h:3604-3644)
+// names the two product formats (realT / imagT tags, or two bare Qu types)
+template <class EA, class EB, class... Tags>
+    requires(EA::is_complex != EB::is_complex)
+struct slots<EA, EB, TypeList<Tags...>> {
+    using prod_t = decltype(Qmul<Tags...>(std::declval<EA>(), std::declval<EB>()));
+    static constexpr int cmul = EA::is_complex ? QG_CMUL_REAL_B : QG_CMUL_REAL_A;
+    static void fill(qgemul_desc& d) { d.mul[QG_M_RE] = fmt_of<typename prod_t::realType>(); d.mul[QG_M_IM] = fmt_of<typename prod_t::imagType>(); }
+};
 template <class EA, class EB, class... Args>
-    requires(EA::is_complex)
+    requires(EA::is_complex && EB::is_complex)
 struct slots<EA, EB, TypeList<BasicComplexMul<Args...>>> {
     using S = Qmul_s<EA, EB, BasicComplexMul<Args...>>;
     using a_t = typename EA::realType; using b_t = typename EA::imagType;
@@ -89,10 +98,10 @@ struct slots<EA, EB, TypeList<BasicComplexMul<Args...>>> {
     static void fill(qgemul_desc& d) { fill(d.mul); }
 };
 template <class EA, class EB>
-    requires(EA::is_complex)
+    requires(EA::is_complex && EB::is_complex)
 struct slots<EA, EB, TypeList<>> : slots<EA, EB, TypeList<BasicComplexMul<>>> {}; // QuBLAS.h:3422-3424
 template <class EA, class EB, class... Args>
-    requires(EA::is_complex)
+    requires(EA::is_complex && EB::is_complex)
 struct slots<EA, EB, TypeList<TFComplexMul<Args...>>> {
     using S = Qmul_s<EA, EB, TFComplexMul<Args...>>;
     using a_t = typename EA::realType; using b_t = typename EA::imagType;
@@ -156,19 +165,22 @@ qgemul_desc Qgemul_lower_types(std::type_identity<Qu_s<dim<CM, CN>, EC>>, std::t
     constexpr bool ta = pick_ta<Tags...>::value;
     constexpr size_t M = ta ? AC : AR, K = ta ? AR : AC;
     static_assert(M == CM && BN == CN && BK == K, "Qgemul: C is MxN, A is MxK (KxM when transposed), B is KxN");
-    static_assert(EA::is_complex == EB::is_complex && EA::is_complex == EC::is_complex, "Qgemul: all real or all complex");
+    // real x real -> real; complex x complex, real x complex and complex x real -> complex (the mixed forms: QG_CMUL_REAL_A / _B of qgemul.h)
+    static_assert(EC::is_complex == (EA::is_complex || EB::is_complex), "Qgemul: C is complex exactly when an operand is");
     using mul_list = typename pick_mul<Tags...>::type;
     using add_list = typename pick_add<Tags...>::type;
     using S = slots<EA, EB, mul_list>;
     qgemul_desc d{};
     d.abi = QGEMUL_ABI_VERSION;
     d.transA = ta;
-    d.is_complex = EA::is_complex;
+    d.is_complex = EC::is_complex;
     d.cmul = uint8_t(S::cmul);
     d.M = int64_t(M); d.N = int64_t(CN); d.K = int64_t(K);
     d.a[0] = fmt_of<typename parts<EA>::re>(); d.a[1] = fmt_of<typename parts<EA>::im>();
     d.b[0] = fmt_of<typename parts<EB>::re>(); d.b[1] = fmt_of<typename parts<EB>::im>();
     d.c[0] = fmt_of<typename parts<EC>::re>(); d.c[1] = fmt_of<typename parts<EC>::im>();
+    if constexpr (EC::is_complex && !EA::is_complex) d.a[1] = qfmt{};   // a mixed descriptor's real operand: its format in [0], [1] all zero
+    if constexpr (EC::is_complex && !EB::is_complex) d.b[1] = qfmt{};
     S::fill(d);
     for (size_t k = K; k > 1; k = (k + 1) / 2) ++d.n_levels;
     if (d.n_levels) fill_levels<0, typename S::prod_t, add_list>(d);

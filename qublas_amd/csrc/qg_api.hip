@@ -406,8 +406,8 @@ int plan_create_view(qgemul_ctx* c, const qgemul_desc* d, const EpView* ev, uint
     if (hipMemcpyAsync(p->dev_table, &p->an.tree, sizeof(QTreeTable), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
         hipStreamSynchronize(c->stream) != hipSuccess)
         return fail();
-    if (p->info.kernel == QG_KERNEL_MFMA_CPLX) {
-        const size_t ws = (size_t)(2 * p->pa.rows_p) * (size_t)(2 * p->pb.rows_p) * sizeof(int64_t);
+    if (p->info.kernel == QG_KERNEL_MFMA_CPLX || p->info.kernel == QG_KERNEL_MFMA_RC) {   // (a mixed plan's real operand has one part)
+        const size_t ws = (size_t)((d->cmul == QG_CMUL_REAL_A ? 1 : 2) * p->pa.rows_p) * (size_t)((d->cmul == QG_CMUL_REAL_B ? 1 : 2) * p->pb.rows_p) * sizeof(int64_t);
         if (hipMalloc((void**)&p->workspace, ws) != hipSuccess) return fail();
     }
     if (qg_wide_epilogue(p) && hipMalloc((void**)&p->wide_ws, (size_t)(p->pc_c.Mp * p->pc_c.Np) * sizeof(int32_t)) != hipSuccess) return fail();
@@ -488,7 +488,7 @@ static QOperandGeom operand_geom(const qgemul_plan* p, int operand, int64_t ld)
     const QHostElem& h = operand == QG_OPERAND_A ? p->ha : p->hb;
     const qfmt* f = operand == QG_OPERAND_A ? d.a : d.b;
     g.K = d.K;
-    g.parts = d.is_complex ? 2 : 1;
+    g.parts = d.is_complex && d.cmul != (operand == QG_OPERAND_A ? QG_CMUL_REAL_A : QG_CMUL_REAL_B) ? 2 : 1;   // (a mixed descriptor's real operand: plain words)
     g.elem_bytes = h.size;
     for (int q = 0; q < 2; ++q) {
         g.off[q] = h.off[q];
@@ -538,7 +538,8 @@ int qgemul_pack_f64(qgemul_plan* p, int operand, const double* src_dev, int64_t 
         // Qu_s(double) with QuMode<RND::CONV>: the reference's result is an artefact of its multi-word CONV branch
         // (QuBLAS.h:2137-2156 on ArbiInt<2400>); silently returning the arithmetic answer would break bit-exactness
         const qfmt* f = operand == QG_OPERAND_A ? p->desc.a : p->desc.b;
-        for (int q = 0; q < (p->desc.is_complex ? 2 : 1); ++q)
+        const int real_operand = p->desc.cmul == (operand == QG_OPERAND_A ? QG_CMUL_REAL_A : QG_CMUL_REAL_B);
+        for (int q = 0; q < (p->desc.is_complex && !real_operand ? 2 : 1); ++q)
             if (f[q].Q == QG_RND_CONV) return QG_EUNSUPPORTED;
     }
     QG_ON_DEVICE(p->ctx);
@@ -943,6 +944,29 @@ static int execute_kernel(qgemul_plan* p, void* packedC, const void* packedA, co
         QG_HIP(qg_launch_cplx_combine(g, st));
         return QG_OK;
     }
+    case QG_KERNEL_MFMA_RC: {
+        const bool ca = p->desc.cmul == QG_CMUL_REAL_B;   // A is the complex operand
+        QMfmaArgs a = mfma_args(p->pa, p->pb, p->variant, packedA, packedB, p->workspace, 8);
+        a.Mp = (ca ? 2 : 1) * p->pa.rows_p;   // the complex operand's parts stacked along its rows: one real GEMM
+        a.Np = (ca ? 1 : 2) * p->pb.rows_p;
+        a.to_c.identity = 1;  // raw 64-bit dot products
+        QG_HIP(qg_launch_mfma(p->LA, p->LB, a, st));
+        QRcConvert g;
+        g.D = p->workspace;
+        g.C = (char*)packedC;
+        g.M = p->desc.M;
+        g.N = p->desc.N;
+        g.Np = a.Np;
+        g.im_r = ca ? p->pa.rows_p : 0;
+        g.im_c = ca ? 0 : p->pb.rows_p;
+        g.tm = p->cfg.TM;
+        g.tn = p->cfg.TN;
+        g.cbytes = pcg.cbytes;
+        g.to_c[0] = p->an.lin.to_c[0];
+        g.to_c[1] = p->an.lin.to_c[1];
+        QG_HIP(qg_launch_rc_convert(g, st));
+        return QG_OK;
+    }
     case QG_KERNEL_TREE_I32:
         QG_HIP(qg_launch_tree_fast(p->dev_table, p->an.tree.n_levels_k, p->an.split_s, p->an.mul24_ok, p->tc.tree, packedA, packedB, packedC,
                                    p->desc.M, p->desc.N, p->pa.K_p, pcg.cbytes, st));
@@ -958,6 +982,10 @@ static int execute_kernel(qgemul_plan* p, void* packedC, const void* packedA, co
     case QG_KERNEL_TREE_CPLX_I32:
         QG_HIP(qg_launch_tree_cplx_fast(p->dev_table, p->an.tree.n_levels_k, p->tc.cplx, p->desc.cmul == QG_CMUL_TF ? 1 : 0, packedA, packedB, packedC,
                                         p->desc.M, p->desc.N, p->pa.K_p, pcg.cbytes, st));
+        return QG_OK;
+    case QG_KERNEL_TREE_RC_I32:
+        QG_HIP(qg_launch_tree_rc(p->dev_table, p->an.tree.n_levels_k, p->tc.cplx, p->desc.cmul == QG_CMUL_REAL_B ? 1 : 0, packedA, packedB, packedC, p->desc.M,
+                                 p->desc.N, p->pa.K_p, pcg.cbytes, st));
         return QG_OK;
     case QG_KERNEL_TREE_I64:
         if (p->an.tree64_ok && !(p->flags & QG_OPT_GENERIC_TREE)) {

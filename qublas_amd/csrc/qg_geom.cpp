@@ -194,6 +194,9 @@ struct Planner {
     QHostElem* const hc = &out->hc;
     QComposite& comp = out->comp;
     const int parts = d->is_complex ? 2 : 1;
+    // one real and one complex operand (QG_CMUL_REAL_A / QG_CMUL_REAL_B): complex-ness is a property of each operand
+    const bool mixed = d->is_complex && (d->cmul == QG_CMUL_REAL_A || d->cmul == QG_CMUL_REAL_B);
+    const int parts_a = d->is_complex && d->cmul != QG_CMUL_REAL_A ? 2 : 1, parts_b = d->is_complex && d->cmul != QG_CMUL_REAL_B ? 2 : 1;
     int LA = 0, LB = 0, kernel = QG_KERNEL_NONE;
     int64_t centreA = 0, centreB = 0;
     bool centred = false;
@@ -214,21 +217,24 @@ struct Planner {
             info->supported = 0;
             return an->status;
         }
-        out->ha = qg_host_elem(d->a, d->is_complex);
-        out->hb = qg_host_elem(d->b, d->is_complex);
+        out->ha = qg_host_elem(d->a, parts_a == 2);
+        out->hb = qg_host_elem(d->b, parts_b == 2);
         *hc = qg_host_elem(d->c, d->is_complex);
         info->cls = an->cls;
         info->max_bits = an->max_bits;
         info->supported = 1;
-        info->in_bits[0] = storage_bits(d->a, parts);
-        info->in_bits[1] = storage_bits(d->b, parts);
+        info->in_bits[0] = storage_bits(d->a, parts_a);
+        info->in_bits[1] = storage_bits(d->b, parts_b);
         const QHostElem* h[3] = {&out->ha, &out->hb, hc};
         for (int w = 0; w < 3; ++w) {
             info->host_elem_bytes[w] = h[w]->size;
             info->host_imag_off[w] = h[w]->off[1];
         }
         const double mnk = (double)d->M * (double)d->N * (double)d->K;
-        info->ops = !d->is_complex ? 2.0 * mnk : (d->cmul == QG_CMUL_TF ? 6.0 * mnk : 8.0 * mnk);
+        info->ops = !d->is_complex ? 2.0 * mnk : mixed ? 4.0 * mnk : (d->cmul == QG_CMUL_TF ? 6.0 * mnk : 8.0 * mnk);
+        // what a mixed descriptor is refused: the entry points that have no part-wise form yet (include/qgemul.h)
+        if (mixed && ev) return refuse(info, QG_EUNSUPPORTED, "mixed real-complex: no element-wise chain");
+        if (mixed && batch > 0) return refuse(info, QG_EUNSUPPORTED, "mixed real-complex: no batched or grouped plan");
         return QG_OK;
     }
 
@@ -253,8 +259,8 @@ struct Planner {
     {
         LA = qg_limbs_for(d->a[0]);
         LB = qg_limbs_for(d->b[0]);
-        if (d->is_complex) {  // parts are stacked along the row axis and share one limb count
-            const int la2 = qg_limbs_for(d->a[1]), lb2 = qg_limbs_for(d->b[1]);
+        if (d->is_complex) {  // parts are stacked along the row axis and share one limb count (a mixed descriptor's real operand has one part)
+            const int la2 = parts_a == 2 ? qg_limbs_for(d->a[1]) : 0, lb2 = parts_b == 2 ? qg_limbs_for(d->b[1]) : 0;
             if (la2 > LA) LA = la2;
             if (lb2 > LB) LB = lb2;
         }
@@ -289,7 +295,7 @@ struct Planner {
     {
         const int mn = LA < LB ? LA : LB;
         QMfmaCfg plain_cfg = {0, 0, 0, 0};   // what qg_mfma_pick chose for the member alone
-        cfg = qg_mfma_pick(LA, LB, d->M * parts, d->N * parts, (ep ? QG_OPT_LOCKSTEP_TILES : 0u) | flags);   // (the fused / unfused element-wise chain keeps the kernel it was measured on)
+        cfg = qg_mfma_pick(LA, LB, d->M * parts_a, d->N * parts_b, (ep ? QG_OPT_LOCKSTEP_TILES : 0u) | flags);   // (the fused / unfused element-wise chain keeps the kernel it was measured on)
         // batch > 0: the member of a batched plan.  Where k_mfma has a block-diagonal form for it, the tile geometry comes from
         // qg_mfma_pick_batched (the batch's total tile count, the member's padding waste) and out->bd = 1: the packed layouts then belong
         // to the batched plan and may differ from the plain plan of the same descriptor
@@ -304,7 +310,7 @@ struct Planner {
         const QStep& tc = an->lin.to_c[0];
         const bool pp_centred = cfg.variant && !ep && storage_bits(d->c, parts) <= 31 && (tc.identity || (tc.d >= 0 && tc.W <= 30));   // (every single-limb kernel has the 64-bit branch)
         if (cfg.variant && (int64_t)mn * d->K <= (1ll << 17) - 1 && !an->wide && !an->generic_only && !(centred && LA == 1 && LB == 1 && !pp_centred))
-            kernel = d->is_complex ? QG_KERNEL_MFMA_CPLX : ((LA == 1 && LB == 1) ? QG_KERNEL_MFMA_I8 : QG_KERNEL_MFMA_I8_LIMB);
+            kernel = mixed ? QG_KERNEL_MFMA_RC : d->is_complex ? QG_KERNEL_MFMA_CPLX : ((LA == 1 && LB == 1) ? QG_KERNEL_MFMA_I8 : QG_KERNEL_MFMA_I8_LIMB);
         // (one output column whose tree the one-column kernels can walk: those stream A once at HBM rate; a composite plan would read
         // it once per limb group and write slabs — the batched Qreduce of 32-bit words with exact level types stays there)
         else if (!d->is_complex && !(d->N == 1 && (an->gemv_ok || an->gemv_wide_ok) && !(flags & QG_OPT_GENERIC_TREE)) &&
@@ -401,10 +407,15 @@ struct Planner {
             snprintf(info->reason, sizeof info->reason, "exact tree evaluation; one-column kernel steps: %s", qg_form_name(tc.gemv));
         if (kernel == QG_KERNEL_TREE_CPLX_I32)
             snprintf(info->reason, sizeof info->reason, "exact tree evaluation; complex kernel steps: %s", qg_form_name(tc.cplx));
+        if (mixed) {   // the form's name first: qgemul_info.reason says which mixed product this is
+            const char* form = d->cmul == QG_CMUL_REAL_A ? "real x complex" : "complex x real";
+            if (kernel == QG_KERNEL_TREE_RC_I32) snprintf(info->reason, sizeof info->reason, "%s: exact tree evaluation; mixed kernel steps: %s", form, qg_form_name(tc.cplx));
+            else snprintf(info->reason, sizeof info->reason, "%s: exact tree evaluation, part by part%s", form, kernel == QG_KERNEL_TREE_I128 ? ", on 128-bit values" : "");
+        }
         // the 32-bit tree kernels walk a perfect binary tree: their operands are zero-padded along K to 2^n_levels leaves
         // (a node whose right child is a zero leaf / zero subtree is the reference's converting copy of an odd leftover)
         const bool t64 = kernel == QG_KERNEL_TREE_I64 && an->tree64_ok && fast;   // the 2x2-per-lane 64-bit kernel, not the general one
-        const int64_t Kt = (kernel == QG_KERNEL_TREE_I32 || kernel == QG_KERNEL_TREE_CPLX_I32 || kernel == QG_KERNEL_GEMV_I32 || kernel == QG_KERNEL_GEMV_I64 || t64)
+        const int64_t Kt = (kernel == QG_KERNEL_TREE_I32 || kernel == QG_KERNEL_TREE_CPLX_I32 || kernel == QG_KERNEL_TREE_RC_I32 || kernel == QG_KERNEL_GEMV_I32 || kernel == QG_KERNEL_GEMV_I64 || t64)
                                ? ((int64_t)1 << an->tree.n_levels_k) : d->K;   // (n_levels_k: at least 5 levels, qg_plan.h)
         *pa = QPackedGeom{d->M, Kt, info->in_bits[0] <= 32 ? 4 : 8, 0, 0, 0};
         *pb = QPackedGeom{d->N, Kt, info->in_bits[1] <= 32 ? 4 : 8, 0, 0, 0};
@@ -416,8 +427,8 @@ struct Planner {
     // ... bytes of packed A and B: the planes, the plane-mask trailer, a composite plan's sub-operands, the row sums of centred operands
     int packed_ab_bytes()
     {
-        info->packed_bytes[0] = (int64_t)parts * (pa->limbs ? pa->limbs : 1) * pa->rows_p * pa->K_p * pa->cbytes;
-        info->packed_bytes[1] = (int64_t)parts * (pb->limbs ? pb->limbs : 1) * pb->rows_p * pb->K_p * pb->cbytes;
+        info->packed_bytes[0] = (int64_t)parts_a * (pa->limbs ? pa->limbs : 1) * pa->rows_p * pa->K_p * pa->cbytes;
+        info->packed_bytes[1] = (int64_t)parts_b * (pb->limbs ? pb->limbs : 1) * pb->rows_p * pb->K_p * pb->cbytes;
         // multi-limb operands carry their plane mask in a trailer behind the planes (QPackedGeom::trailer)
         if (pa->limbs > 1) { pa->trailer = info->packed_bytes[0]; info->packed_bytes[0] += QG_TRAILER_BYTES; }
         if (pb->limbs > 1) { pb->trailer = info->packed_bytes[1]; info->packed_bytes[1] += QG_TRAILER_BYTES; }
@@ -556,6 +567,9 @@ int qg_plan_geometry(const qgemul_desc* d, uint32_t flags, const EpView* ev, int
     p.three_digit_choice();
     if (p.kernel != QG_KERNEL_NONE) p.limb_layout();
     else p.tree_layout();
+    if (p.kernel == QG_KERNEL_MFMA_RC)
+        snprintf(out->info.reason, sizeof out->info.reason, "%s: linear class, one %d x %d limb GEMM on the stacked operand + two-product convert",
+                 d->cmul == QG_CMUL_REAL_A ? "real x complex" : "complex x real", p.LA, p.LB);
     out->bd = p.bd ? 1 : 0;
     out->info.kernel = p.kernel;
     out->info.limbs[0] = p.LA;
@@ -601,7 +615,8 @@ int qg_plan_launches(const QPlanGeom* p)
     switch (p->info.kernel) {
     case QG_KERNEL_MFMA_I8:
     case QG_KERNEL_MFMA_I8_LIMB: return p->variant != QG_MFMA_RING && qg_wide_epilogue(p) ? 2 : 1;
-    case QG_KERNEL_MFMA_CPLX: return 2;
+    case QG_KERNEL_MFMA_CPLX:
+    case QG_KERNEL_MFMA_RC: return 2;
     default: return 1;
     }
 }

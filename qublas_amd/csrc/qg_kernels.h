@@ -58,6 +58,16 @@ struct QCplxCombine {
     QStep to_c[2];
 };
 hipError_t qg_launch_cplx_combine(const QCplxCombine& g, hipStream_t st);
+// mixed linear class (one real and one complex operand): the two raw dot-product blocks of D (tiled int64: the real operand against
+// the stacked parts of the complex one) converted into packed complex C [2][M][N]; P_im sits im_r rows / im_c columns behind P_re
+struct QRcConvert {
+    const int64_t* D;   // [Mp/tm][Np/tn][tn][tm]
+    char* C;
+    int64_t M, N, Np, im_r, im_c;
+    int32_t tm, tn, cbytes;
+    QStep to_c[2];
+};
+hipError_t qg_launch_rc_convert(const QRcConvert& g, hipStream_t st);
 
 // composite linear plans (operands of more than 3 int8 limbs, or K beyond the int32 accumulators' exact range): the limb-group /
 // k-chunk sub-GEMMs store RAW dot products (int32 for single-limb pairs, int64 otherwise) in slabs of one common packed-C
@@ -106,6 +116,10 @@ hipError_t qg_launch_gemv(const QTreeTable* dev_table, int n_levels, int b_is_bi
 // exact tree evaluation, complex descriptors with K = 2^p >= 32 and 32-bit intermediates
 hipError_t qg_launch_tree_cplx_fast(const QTreeTable* dev_table, int n_levels, QCplxForm form, int tf, const void* A, const void* B, void* C,
                                     int64_t M, int64_t N, int64_t K, int cbytes, hipStream_t st);
+// one real and one complex operand (qg_tree_rc.hip): forms QCF_RUNTIME and QCF_COMPACT; a_complex: A is the complex operand
+// ([2][M][K], B [N][K]), else B ([2][N][K], A [M][K]); C [2][M][N]
+hipError_t qg_launch_tree_rc(const QTreeTable* dev_table, int n_levels, QCplxForm form, int a_complex, const void* A, const void* B, void* C, int64_t M,
+                             int64_t N, int64_t K, int cbytes, hipStream_t st);
 
 // linear class on int8 MFMA with LA x LB limbs (QMfmaCfg, qg_mfma_pick: qg_geom.h)
 struct QMfmaArgs {

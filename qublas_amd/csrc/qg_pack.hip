@@ -378,6 +378,21 @@ __global__ __launch_bounds__(256) void k_cplx_combine(QCplxCombine g)
     store_container(g.C, g.M * g.N + m * g.N + n, g.cbytes, qg_step<int64_t>(im, g.to_c[1]));
 }
 
+// mixed linear class: D = A x [B_re | B_im] or [A_re; A_im] x B raw dot products (tiled int64), two products per output:
+// re = cvt_{c[0]}(P_re), im = cvt_{c[1]}(P_im), one round + overflow per part (each part at the frac of its own operands)
+__global__ __launch_bounds__(256) void k_rc_convert(QRcConvert g)
+{
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= g.M * g.N) return;
+    const int64_t m = idx / g.N, n = idx % g.N;
+    auto D = [&](int64_t r, int64_t c) {
+        const int64_t tn = g.Np / g.tn;
+        return g.D[(((r / g.tm) * tn + c / g.tn) * g.tn + c % g.tn) * g.tm + r % g.tm];
+    };
+    store_container(g.C, m * g.N + n, g.cbytes, qg_step<int64_t>(D(m, n), g.to_c[0]));
+    store_container(g.C, g.M * g.N + m * g.N + n, g.cbytes, qg_step<int64_t>(D(g.im_r + m, g.im_c + n), g.to_c[1]));
+}
+
 // BitStream export (QuBLAS.h:4811-4827): thread = one output element position.  pos -> source element (tensor-level
 // chunk reversal) -> its raw value -> `width` characters, MSB first, element-level chunk reversal -> out[pos*width ...].
 // ASCII: consecutive lanes write consecutive width-byte runs.  Packed: the stream is M*N*width bits; a thread ORs its
@@ -564,6 +579,14 @@ hipError_t qg_launch_cplx_combine(const QCplxCombine& g, hipStream_t st)
     const int64_t n = g.M * g.N;
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_cplx_combine, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g);
+    return hipGetLastError();
+}
+
+hipError_t qg_launch_rc_convert(const QRcConvert& g, hipStream_t st)
+{
+    const int64_t n = g.M * g.N;
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_rc_convert, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g);
     return hipGetLastError();
 }
 

@@ -766,7 +766,16 @@ void qg_analyze(const qgemul_desc* d, QAnalysis* out)
     }
     const int cx = d->is_complex ? 1 : 0;
     const int parts = cx ? 2 : 1;
-    if (cx && d->cmul != QG_CMUL_BASIC && d->cmul != QG_CMUL_TF) { c.fail(QG_EINVAL, "complex descriptor without cmul"); return; }
+    // one real and one complex operand (QG_CMUL_REAL_A / QG_CMUL_REAL_B, QuBLAS.h:3600-3644): two part-wise products on a shared real value
+    const bool mixed = cx && (d->cmul == QG_CMUL_REAL_A || d->cmul == QG_CMUL_REAL_B);
+    const bool real_a = mixed && d->cmul == QG_CMUL_REAL_A;
+    if (cx && !mixed && d->cmul != QG_CMUL_BASIC && d->cmul != QG_CMUL_TF) { c.fail(QG_EINVAL, "complex descriptor without cmul"); return; }
+    if (!cx && (d->cmul == QG_CMUL_REAL_A || d->cmul == QG_CMUL_REAL_B)) { c.fail(QG_EINVAL, "mixed real-complex: C is complex (is_complex = 1)"); return; }
+    if (mixed) {   // the real operand has ONE spelling: its format in [0], [1] all zero (the plan cache compares field by field)
+        const qfmt z = real_a ? d->a[1] : d->b[1];
+        // (pad is no part of a format's meaning: qg_run_key.h)
+        if (z.I || z.F || z.S || z.Q || z.O) { c.fail(QG_EINVAL, "mixed real-complex: [1] of the real operand's format must be zero"); return; }
+    }
     if (!cx && d->cmul != QG_CMUL_NONE) { c.fail(QG_EINVAL, "real descriptor with cmul"); return; }
 
     QTreeTable& T = out->tree;
@@ -786,11 +795,12 @@ void qg_analyze(const qgemul_desc* d, QAnalysis* out)
     T.parts = parts;
 
     for (int p = 0; p < parts; ++p) {
-        if (!fmt_ok(c, d->a[p]) || !fmt_ok(c, d->b[p]) || !fmt_ok(c, d->c[p])) return;
+        const bool has_a = !(real_a && p), has_b = !(mixed && !real_a && p);   // (the real operand of a mixed descriptor has no [1])
+        if ((has_a && !fmt_ok(c, d->a[p])) || (has_b && !fmt_ok(c, d->b[p])) || !fmt_ok(c, d->c[p])) return;
         // operand ELEMENTS are one-word values (int32_t / int64_t host elements); products, sums, levels and C may be multi-word
-        if (sbits(d->a[p]) > 64 || sbits(d->b[p]) > 64) { c.fail(QG_EUNSUPPORTED, "operand element wider than 64 storage bits"); return; }
+        if ((has_a && sbits(d->a[p]) > 64) || (has_b && sbits(d->b[p]) > 64)) { c.fail(QG_EUNSUPPORTED, "operand element wider than 64 storage bits"); return; }
     }
-    const int nslots = !cx ? 1 : (d->cmul == QG_CMUL_TF ? 8 : 6);
+    const int nslots = !cx ? 1 : mixed ? 2 : (d->cmul == QG_CMUL_TF ? 8 : 6);
     for (int i = 0; i < nslots; ++i)
         if (!fmt_ok(c, d->mul[i])) return;
     for (int p = 0; p < parts; ++p)
@@ -808,6 +818,13 @@ void qg_analyze(const qgemul_desc* d, QAnalysis* out)
         Rng pr = mul_rng(a.r, b.r);
         Rng dot = {pr.lo * d->K, pr.hi * d->K};
         out->dot_bits = bits_of(dot.lo) > bits_of(dot.hi) ? bits_of(dot.lo) : bits_of(dot.hi);
+    } else if (mixed) {
+        // re = Qmul<realT...>(x, y.real), im = Qmul<imagT...>(x, y.imag) — or (x.real, y), (x.imag, y) — QuBLAS.h:3604-3644
+        for (int p = 0; p < 2; ++p) {
+            const qfmt fa = d->a[real_a ? 0 : p], fb = d->b[real_a ? p : 0];
+            Val a = {fmt_range(fa), fa}, b = {fmt_range(fb), fb};
+            prod[p] = do_mul(c, a, b, m[p], &T.mul[p]);
+        }
     } else {
         Val a = {fmt_range(d->a[0]), d->a[0]}, b = {fmt_range(d->a[1]), d->a[1]};
         Val cc = {fmt_range(d->b[0]), d->b[0]}, dd = {fmt_range(d->b[1]), d->b[1]};
@@ -871,7 +888,23 @@ void qg_analyze(const qgemul_desc* d, QAnalysis* out)
             if (out->lin.to_c[0].d > 100 || out->lin.to_c[0].d < -100) c.exact = false;
         }
     }
-    if (cx) {
+    if (mixed) {
+        // Mixed linear class.  When both products and every node of both trees are exact, the parts are the plain dot products
+        //   re = sum_k x y.real,  im = sum_k x y.imag   (or x.real y, x.imag y)
+        // at frac Fa + Fb of their own operands: ONE real GEMM on the stacked operand gives both, each then rounded / overflowed ONCE
+        // into C's part by to_c[part] (sh[] stays 0: the parts are never combined).  The limits are those of the complex linear class.
+        auto mag = [](Rng r) { I128 a = r.lo < 0 ? -r.lo : r.lo; return a > r.hi ? a : r.hi; };
+        I128 mx = 0;
+        for (int p = 0; p < 2; ++p) {
+            const qfmt fa = d->a[real_a ? 0 : p], fb = d->b[real_a ? p : 0];
+            out->lin.to_c[p] = make_step((int)fa.F + (int)fb.F, d->c[p], false);
+            if (out->lin.to_c[p].d > 61 || out->lin.to_c[p].d < -61) c.exact = false;
+            const I128 t = mag(fmt_range(fa)) * mag(fmt_range(fb)) * d->K;
+            if (t > mx) mx = t;
+        }
+        out->dot_bits = bits_of(mx);
+        if (out->dot_bits > 62) c.exact = false;
+    } else if (cx) {
         // Complex linear class.  When every sub-operation and tree node is exact, both multipliers reduce to
         //   re = sum_k (a c - b d),  im = sum_k (a d + b c)
         // (TF: A - B = (a+b)c - (c+d)b, B - C = (c+d)b - (b-a)d), each term carrying the power of two of its
@@ -1234,6 +1267,7 @@ void qg_analyze(const qgemul_desc* d, QAnalysis* out)
         if (one) out->gemv_form = lf.O == QG_SAT_ZERO ? QGF_ONE_ZERO : QGF_ONE_TCPL;
         else if (recs) out->gemv_form = rec_clamps ? QGF_REC_CLAMP : QGF_REC_KINDS;   // per-level formats in compact records
     }
+    // (mixed real-complex descriptors: the same conditions admit them to their own 32-bit kernel, qg_tree_rc.hip)
     out->cplx_fast_ok = (cx && !out->wide && !out->generic_only && !copy0 && d->n_levels <= 16 && c.max_bits <= 31 && c.max_fmt_bits <= 31) ? 1 : 0;
     // fixed-mode variant of the complex kernel (BASELINE configuration 5's "RND + SAT"): every sub-operation and every tree
     // step either the identity, or an exact left shift / a rounding shift with RND::POS_INF, followed by SAT::TCPL, so a
@@ -1244,11 +1278,11 @@ void qg_analyze(const qgemul_desc* d, QAnalysis* out)
             return q.identity || (q.d >= -29 && q.d <= 29 && q.O == QG_SAT_TCPL && (q.d <= 0 || q.Q == QG_RND_POS_INF));
         };
         bool all = true;
-        const int ns = d->cmul == QG_CMUL_TF ? 8 : 6;
+        const int ns = mixed ? 2 : d->cmul == QG_CMUL_TF ? 8 : 6;
         for (int i = 0; i < ns; ++i) all = all && ok(T.mul[i].q);
         for (int p = 0; p < 2; ++p)
             for (uint32_t l = 0; l < d->n_levels; ++l) all = all && ok(T.level_add[p][l].q) && ok(T.level_cvt[p][l]);
-        out->cplx_form = all ? QCF_TABLE : QCF_RUNTIME;
+        out->cplx_form = all && !mixed ? QCF_TABLE : QCF_RUNTIME;   // (the mixed kernel has the forms QCF_RUNTIME and QCF_COMPACT)
         // ... and QCF_COMPACT when every step fits the branch-free forms of QFix (qg_plan.h): a rounding that is "add a constant, shift
         // right" — TRN::TCPL (+0; the reference's default QuMode), RND::POS_INF (+2^(d-1)), RND::NEG_INF (+2^(d-1) - 1) — and an
         // overflow that is one clamp — SAT::TCPL (the reference's default OfMode) or SAT::SMGN ([-hi, hi]); the values that
@@ -1269,7 +1303,9 @@ void qg_analyze(const qgemul_desc* d, QAnalysis* out)
             struct Slot { int idx; bool mul; qfmt x, y; };
             const qfmt a = d->a[0], b = d->a[1], cc = d->b[0], dd = d->b[1];
             std::vector<Slot> slots;
-            if (tf) {
+            if (mixed) {   // the two part-wise products on the shared real value
+                slots = {{QG_M_RE, true, a, cc}, {QG_M_IM, true, real_a ? a : b, real_a ? dd : cc}};
+            } else if (tf) {
                 slots = {{QG_T_AB, false, a, b}, {QG_T_CD, false, cc, dd}, {QG_T_BA, false, b, a},
                          {QG_T_A, true, d->mul[QG_T_AB], cc}, {QG_T_B, true, d->mul[QG_T_CD], b}, {QG_T_C, true, d->mul[QG_T_BA], dd},
                          {QG_T_RE, false, d->mul[QG_T_A], d->mul[QG_T_B]}, {QG_T_IM, false, d->mul[QG_T_B], d->mul[QG_T_C]}};
@@ -1342,7 +1378,7 @@ void qg_analyze(const qgemul_desc* d, QAnalysis* out)
                     }
                 if (!kinds || feat <= 0) break;   // plain compact records, or the branching form: the first packing stands
             }
-            if (reg) out->cplx_form = !kinds ? QCF_COMPACT : feat > 0 ? qcf_kinds(feat) : QCF_KINDS;
+            if (reg) out->cplx_form = !kinds ? QCF_COMPACT : mixed ? QCF_RUNTIME : feat > 0 ? qcf_kinds(feat) : QCF_KINDS;
             // QCF_UNIFORM ("one clamp for the whole loop"): the plain compact form where, in addition, every value made in the k loop — the
             // products, their sum / differences and every tree node of both parts — is clamped into ONE range, the sums and the
             // nodes neither shift nor round (equal fraction bits throughout), and the level buffers do not convert.  That is what
@@ -1350,7 +1386,7 @@ void qg_analyze(const qgemul_desc* d, QAnalysis* out)
             // RND::POS_INF / SAT::TCPL inside the loop).  The kernel then keeps (lo, hi) and the products' (t, d) in registers for
             // the whole launch — no record loads, no moves of bounds — and the products' exact left shifts are folded into the
             // staged operand planes: 18 vector instructions per complex MAC instead of 24.8 (TF), 21 instead of 27.4 (Basic).
-            if (reg && out->cplx_form == QCF_COMPACT) {
+            if (reg && out->cplx_form == QCF_COMPACT && !mixed) {
                 const int re = tf ? QG_T_RE : QG_B_RE, im = tf ? QG_T_IM : QG_B_IM;
                 const QFix& r0 = T.fmul[re];
                 bool uni = r0.lo > INT32_MIN && r0.hi < INT32_MAX;
@@ -1501,7 +1537,8 @@ void qg_analyze(const qgemul_desc* d, QAnalysis* out)
     }
     if (!out->linear_ok)
         snprintf(out->reason, sizeof out->reason, "%s",
-                 "a product or tree node may round or overflow: exact tree evaluation");
+                 mixed ? (real_a ? "real x complex: exact tree evaluation, part by part" : "complex x real: exact tree evaluation, part by part")
+                       : "a product or tree node may round or overflow: exact tree evaluation");
     // ring plans: decided on the formats alone (a "wide" unrounded product, 2^62 for int32 operands, is no obstacle: it is never
     // formed).  A descriptor that is exact anyway keeps its exact linear plan, one output column the one-column kernels walk
     // stays with them (they stream A once at HBM rate).
@@ -1522,8 +1559,11 @@ QTreeChoice qg_tree_choice(const QAnalysis* an, const qgemul_desc* d, uint32_t f
     if (an->wide) {
         c.kernel = QG_KERNEL_TREE_I128;
     } else if (d->is_complex) {
-        c.kernel = an->cplx_fast_ok && fast ? QG_KERNEL_TREE_CPLX_I32 : QG_KERNEL_TREE_CPLX;
+        const bool mixed = d->cmul == QG_CMUL_REAL_A || d->cmul == QG_CMUL_REAL_B;
+        c.kernel = an->cplx_fast_ok && fast ? (mixed ? QG_KERNEL_TREE_RC_I32 : QG_KERNEL_TREE_CPLX_I32) : QG_KERNEL_TREE_CPLX;
         c.cplx = rt ? QCF_RUNTIME : an->cplx_form;
+        // (the mixed kernel's run-time-mode form is built for at most 12 levels, qg_tree_rc.hip: longer trees take the general kernel)
+        if (c.kernel == QG_KERNEL_TREE_RC_I32 && c.cplx == QCF_RUNTIME && an->tree.n_levels_k > 12) c.kernel = QG_KERNEL_TREE_CPLX;
         if (ab && no_uniform && (c.cplx == QCF_UNIFORM || c.cplx == QCF_LJ || c.cplx == QCF_PK16)) c.cplx = QCF_COMPACT;
         else if (ab && no_lj && (c.cplx == QCF_LJ || c.cplx == QCF_PK16)) c.cplx = an->cplx_form_base;
         else if (ab && no_pk && c.cplx == QCF_PK16) c.cplx = QCF_LJ;

@@ -269,6 +269,7 @@ int run_view(const qgemul_desc* d, const EpView* ev, void* C, const void* A, con
     qgemul_opts opts = resolve_opts(o);
     if (opts.flags & QG_OPT_ALL_DEVICES) {
         if (ev) return QG_EUNSUPPORTED;
+        if (d->is_complex && (d->cmul == QG_CMUL_REAL_A || d->cmul == QG_CMUL_REAL_B)) return QG_EUNSUPPORTED;   // (mixed real-complex: no sharded form)
         arm_reaper();
         int ndev = 0;
         if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return QG_ENOGPU;
@@ -578,6 +579,8 @@ int qgemul_run_sharded(const qgemul_desc* d, void* C, const void* A, const void*
         qgemul_info info;
         int st = qgemul_classify(d, opts.flags, &info);
         if (st != QG_OK) return st;
+        // mixed real-complex descriptors have no sharded form yet (include/qgemul.h): one device serves them
+        if (d->is_complex && (d->cmul == QG_CMUL_REAL_A || d->cmul == QG_CMUL_REAL_B)) return QG_EUNSUPPORTED;
     }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return QG_ENOGPU;

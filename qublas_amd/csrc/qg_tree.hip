@@ -64,7 +64,13 @@ __device__ __forceinline__ void product(const QTreeTable* __restrict__ t, const 
         return;
     }
     const T a = x[0], b = x[1], c = y[0], d = y[1];
-    if (t->cmul == QG_CMUL_TF) {
+    if (t->cmul == QG_CMUL_REAL_A) {          // real x complex: two part-wise products on the shared real value (QuBLAS.h:3604-3623)
+        out[0] = A::mul(a, c, t->mul[QG_M_RE]);
+        out[1] = A::mul(a, d, t->mul[QG_M_IM]);
+    } else if (t->cmul == QG_CMUL_REAL_B) {   // complex x real (QuBLAS.h:3625-3644)
+        out[0] = A::mul(a, c, t->mul[QG_M_RE]);
+        out[1] = A::mul(b, c, t->mul[QG_M_IM]);
+    } else if (t->cmul == QG_CMUL_TF) {
         T ab = A::add(a, b, t->mul[QG_T_AB]);
         T cd = A::add(c, d, t->mul[QG_T_CD]);
         T ba = A::sub(b, a, t->mul[QG_T_BA]);
@@ -99,6 +105,8 @@ __global__ __launch_bounds__(256) void k_tree_generic(const QTreeTable* __restri
     const int64_t m0 = (int64_t)(blockIdx.x / tiles_n) * TG_T, n0 = (int64_t)(blockIdx.x % tiles_n) * TG_T;
     const int parts = tab->parts;
     const int nl = tab->n_levels;
+    // a mixed descriptor's real operand is packed as ONE plane [rows][K] (its second LDS plane stays zero and is never used)
+    const int parts_a = tab->cmul == QG_CMUL_REAL_A ? 1 : parts, parts_b = tab->cmul == QG_CMUL_REAL_B ? 1 : parts;
 
     T val[2][QG_MAX_LEVELS + 1];
     uint64_t has = 0; // bit l: a pending element of list l (the same for both parts)
@@ -112,8 +120,8 @@ __global__ __launch_bounds__(256) void k_tree_generic(const QTreeTable* __restri
             for (int p = 0; p < parts; ++p) {
                 int64_t va = 0, vb = 0;
                 if (k < K) {
-                    if (m0 + r < M) va = qg_load_c(A, ((int64_t)p * pa.rows_p + m0 + r) * pa.K_p + k, pa.cbytes);
-                    if (n0 + r < N) vb = qg_load_c(B, ((int64_t)p * pb.rows_p + n0 + r) * pb.K_p + k, pb.cbytes);
+                    if (m0 + r < M && p < parts_a) va = qg_load_c(A, ((int64_t)p * pa.rows_p + m0 + r) * pa.K_p + k, pa.cbytes);
+                    if (n0 + r < N && p < parts_b) vb = qg_load_c(B, ((int64_t)p * pb.rows_p + n0 + r) * pb.K_p + k, pb.cbytes);
                 }
                 sA[p][r][kk] = va;
                 sB[p][r][kk] = vb;

@@ -42,6 +42,8 @@ QU_MODES = {"RND::POS_INF": 0, "RND::NEG_INF": 1, "RND::ZERO": 2, "RND::INF": 3,
 OF_MODES = {"SAT::TCPL": 0, "SAT::ZERO": 1, "SAT::SMGN": 2, "WRP::TCPL": 3}
 
 CMUL_NONE, CMUL_BASIC, CMUL_TF = 0, 1, 2
+CMUL_REAL_A, CMUL_REAL_B = 3, 4   # one real and one complex operand (include/qgemul.h): A real / B real; product slots M_RE, M_IM
+M_RE, M_IM = 0, 1
 DESC_LEFTOVER0_COPY = 1   # qgemul_desc.flags (include/qgemul.h)
 DESC_REFERENCE_ARTEFACTS = 2   # opt-in: C of an unsigned WRP::TCPL format with exactly 32 value bits comes out unwrapped, as in the reference
 CLASS_LINEAR, CLASS_TREE = 1, 2
@@ -291,7 +293,37 @@ class TFComplexMul:
     loose: TagLike = None
 
 
-MulArgs = Union[Tags, Qu, BasicComplexMul, TFComplexMul, None]
+@dataclass(frozen=True)
+class RealComplexMul:
+    """QgemulMulArgs of a Qgemul with one real and one complex operand: Qmul<realT<...>, imagT<...>, loose tags...> of the
+    reference's "Real-Complex Operations" (QuBLAS.h:3604-3644).  A part without its own tag sees the loose tags, as in
+    BasicComplexMul; two bare Qu types as tags are RealComplexMul(realT=first, imagT=second) (:3621-3623, :3642-3644)."""
+    realT: TagLike = None
+    imagT: TagLike = None
+    loose: TagLike = None
+
+
+MulArgs = Union[Tags, Qu, BasicComplexMul, TFComplexMul, RealComplexMul, None]
+
+
+def mixed_mul_slots(x: Elem, y: Elem, m: MulArgs) -> Tuple[int, List[Qu]]:
+    """Resolved formats of the two part-wise products of Qmul(real, complex) / Qmul(complex, real), slots M_RE, M_IM."""
+    if m is None:
+        m = RealComplexMul()
+    if isinstance(m, (Tags, Qu)):
+        m = RealComplexMul(loose=m)
+    if isinstance(m, (tuple, list)) and len(m) == 2 and all(isinstance(t, Qu) for t in m):
+        m = RealComplexMul(realT=m[0], imagT=m[1])
+    if not isinstance(m, RealComplexMul):
+        raise ValueError("a real x complex Qgemul takes realT / imagT tags (RealComplexMul), two Qu types, loose tags or nothing")
+    zero = Qu(0, 0, False, 0, 0)
+    if isinstance(y, Qcomplex):
+        re = mul_merge(x, y.real, _pick(m.realT, m.loose))
+        im = mul_merge(x, y.imag, _pick(m.imagT, m.loose))
+        return CMUL_REAL_A, [re, im] + [zero] * 6
+    re = mul_merge(x.real, y, _pick(m.realT, m.loose))
+    im = mul_merge(x.imag, y, _pick(m.imagT, m.loose))
+    return CMUL_REAL_B, [re, im] + [zero] * 6
 
 
 def _pick(own: TagLike, loose: TagLike) -> Tags:
@@ -338,9 +370,10 @@ def lower(A: Elem, B: Elem, Cc: Elem, M: int, N: int, K: int, *,
           transposed_a: bool = False, reference_artefacts: bool = False) -> qgemul_desc:
     """Lower one Qgemul<QgemulAddArgs<add_args…>, QgemulMulArgs<mul_args>, QgemulTransposedA<t>>
     call on element types (A, B, C) and runtime sizes to the C-ABI descriptor."""
-    cx = isinstance(A, Qcomplex)
-    if cx != isinstance(B, Qcomplex) or cx != isinstance(Cc, Qcomplex):
-        raise ValueError("mixed real/complex operands are outside the Qgemul path (SURVEY.md §2)")
+    cx = isinstance(Cc, Qcomplex)
+    mixed = isinstance(A, Qcomplex) != isinstance(B, Qcomplex)
+    if (mixed and not cx) or (not mixed and cx != isinstance(A, Qcomplex)):
+        raise ValueError("operands and C disagree: real x real -> real; complex x complex, real x complex, complex x real -> complex")
     if K < 1 or M < 0 or N < 0:
         raise ValueError("bad shape")
     d = qgemul_desc()
@@ -375,14 +408,15 @@ def lower(A: Elem, B: Elem, Cc: Elem, M: int, N: int, K: int, *,
             d.level[0][l] = d.level[1][l] = t.c()
             prev = t
     else:
-        d.a[0], d.a[1] = A.real.c(), A.imag.c()
-        d.b[0], d.b[1] = B.real.c(), B.imag.c()
+        zero = Qu(0, 0, False, 0, 0)   # [1] of a real operand (a mixed descriptor): all zero
+        d.a[0], d.a[1] = (A.real.c(), A.imag.c()) if isinstance(A, Qcomplex) else (A.c(), zero.c())
+        d.b[0], d.b[1] = (B.real.c(), B.imag.c()) if isinstance(B, Qcomplex) else (B.c(), zero.c())
         d.c[0], d.c[1] = Cc.real.c(), Cc.imag.c()
-        cmul, slots = complex_mul_slots(A, B, mul_args)
+        cmul, slots = mixed_mul_slots(A, B, mul_args) if mixed else complex_mul_slots(A, B, mul_args)
         d.cmul = cmul
         for i, s in enumerate(slots):
             d.mul[i] = s.c()
-        prev = (slots[6], slots[7]) if cmul == CMUL_TF else (slots[4], slots[5])
+        prev = (slots[6], slots[7]) if cmul == CMUL_TF else (slots[4], slots[5]) if cmul == CMUL_BASIC else (slots[M_RE], slots[M_IM])
         for l in range(nl):
             if levels:
                 t = levels[min(l, len(levels) - 1)]
