@@ -58,12 +58,20 @@ def _part(arr: np.ndarray, p: int) -> np.ndarray:
     return np.ascontiguousarray(arr["im" if p else "re"]) if arr.dtype.names else arr
 
 
-def gemm(d: qgemul_desc, A: np.ndarray, B: np.ndarray, *, lda=0, ldb=0, nthreads: int = 4) -> np.ndarray:
-    """C (tight, host layout of the complex C element) of a mixed descriptor, part by part through qoracle_gemm"""
+def gemm(d: qgemul_desc, A: np.ndarray, B: np.ndarray, *, lda=0, ldb=0, rows=(0, 0), cols=(0, 0), nthreads: int = 4,
+         out: np.ndarray | None = None) -> np.ndarray:
+    """C (tight, host layout of the complex C element) of a mixed descriptor, part by part through qoracle_gemm.  rows / cols / out as
+    in qoracle.gemm: only the block rows x cols is evaluated ((0, 0): the whole extent) and written into out, whose other elements keep
+    their values"""
     _, _, ec = elems(d)
-    out = np.zeros(d.M * d.N, dtype=qoracle.host_dtype(ec))
+    if out is None:
+        out = np.zeros(d.M * d.N, dtype=qoracle.host_dtype(ec))
+    r = slice(rows[0], rows[1] if rows[1] > 0 else d.M)   # (an end <= 0: to the end, as in qoracle_gemm)
+    c = slice(cols[0], cols[1] if cols[1] > 0 else d.N)
+    grid = out.reshape(d.N, d.M)
     for p, (name, f) in enumerate((("re", ec.real), ("im", ec.imag))):
-        out[name] = qoracle.gemm(part_desc(d, p), _part(A, p), _part(B, p), f, lda=lda, ldb=ldb, nthreads=nthreads)
+        part = qoracle.gemm(part_desc(d, p), _part(A, p), _part(B, p), f, lda=lda, ldb=ldb, rows=rows, cols=cols, nthreads=nthreads)
+        grid[name][c, r] = part.reshape(d.N, d.M)[c, r]
     return out
 
 

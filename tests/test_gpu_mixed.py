@@ -1,13 +1,15 @@
 """GPU parity of Qgemul with one real and one complex operand (QG_CMUL_REAL_A / QG_CMUL_REAL_B, include/qgemul.h), through the C-ABI.
 Every comparison is byte for byte against tests/mixed_ref.py — part p of the descriptor as a real Qgemul through the oracle —, which
 the CPU tests pin to the reference's own results (tests/golden/ref_mixed_0):
-  * every golden record through qgemul_run and through the resident entry points;
+  * every golden record through qgemul_run and through the resident entry points, and under QG_OPT_RUNTIME_MODES, QG_OPT_GENERIC_TREE
+    and (linear class) QG_OPT_FORCE_TREE;
   * the mixed tree kernel (k_tree_rc: compact steps and, under QG_OPT_RUNTIME_MODES or with modes the compact steps lack, run-time
     modes) and the general kernel's part-wise branch (QG_OPT_GENERIC_TREE), both operand orders: shapes that cross the 32 x 32 and
     16 x 16 tiles in both directions, K below / at / above one 32-leaf chunk with odd leftovers on several
-    levels, 12 and 13 levels, TransposedA;
+    levels, 12 and 13 levels, TransposedA; edge-heavy operands (dist 2) at 33 x 17 x 33 and 65 x 40 x 1000;
   * the linear class (one real limb GEMM on the stacked operand + the two-product convert pass): one-, two- and three-limb operands,
-    parts whose shifts into C differ, 33 x 17 x 40 and 130 x 70 x 200, TransposedA, and the same descriptors under QG_OPT_FORCE_TREE;
+    parts whose shifts into C differ, 33 x 17 x 40 and 130 x 70 x 200, TransposedA, and the same descriptors under QG_OPT_FORCE_TREE
+    (every other tile form of that GEMM: tests/test_gpu_stacked_tiles.py);
   * QG_OPT_CHECK_RANGE, qgemul_execute_host_c and qgemul_time_execute on mixed plans;
   * 128-bit values (a level format of 70 bits) at 9 x 7 x 37;
   * leading dimensions with poison between the columns, qgemul_pack_f64, qgemul_fill_packed against the oracle's generator, the
@@ -25,6 +27,7 @@ import numpy as np
 import pytest
 
 import mixed_ref as R
+from stacked_cases import LINEAR   # (the linear-class elements and tags: shared with tests/test_gpu_stacked_tiles.py)
 from qublas_amd import capi
 from qublas_amd.desc import CLASS_TREE, Qcomplex, Qu, RealComplexMul, RND, SAT, TRN, WRP, Tags, lower
 
@@ -45,6 +48,7 @@ VARIANTS = {
 }
 SHAPES = [(33, 17, k, False) for k in (1, 5, 31, 32, 33, 1000)] + [(65, 40, k, False) for k in (1, 5, 31, 32, 33, 1000)] + \
          [(8, 8, 4096, False), (4, 4, 8192, False), (33, 17, 33, True), (33, 17, 5, True), (65, 40, 1000, True)]
+EDGE_SHAPES = [(33, 17, 33, False), (65, 40, 1000, False)]   # at the edge-heavy operand distribution (dist 2)
 
 
 def mixed_desc(variant, order, M, N, K, ta=False):
@@ -74,6 +78,19 @@ def test_golden_records_one_shot(oracle, j):
     assert exp.tobytes() == R.case_expected(j).tobytes()
     assert R.strong(d, exp) or "saturation" in j["name"]
     assert run(oracle, d, A, B).tobytes() == exp.tobytes(), j["name"]
+
+
+@pytest.mark.parametrize("j", R.cases(), ids=lambda j: j["name"])
+def test_golden_records_second_opinions(oracle, j):
+    """each reference-made record (its default plan runs in test_golden_records_one_shot) on the run-time-mode steps and on the general
+    kernel's part-wise branch, and the linear-class ones on the tree kernels: all must give the reference's C"""
+    d, A, B, _ = R.case_checked(j["name"])
+    exp = R.case_expected(j)
+    flags = [capi.OPT_RUNTIME_MODES, capi.OPT_GENERIC_TREE]
+    if capi.KERNEL_NAMES[capi.classify(d).kernel] == "mfma_rc":
+        flags.append(capi.OPT_FORCE_TREE)
+    for fl in flags:
+        assert run(oracle, d, A, B, flags=fl).tobytes() == exp.tobytes(), (j["name"], fl)
 
 
 def resident(oracle, ctx, d, A, B, flags=0, lda=0, ldb=0, ldc=0):
@@ -116,9 +133,9 @@ def test_golden_records_resident(oracle, j):
 @pytest.mark.parametrize("order", ["ra", "rb"])
 @pytest.mark.parametrize("variant", list(VARIANTS))
 def test_tree_kernels(oracle, variant, order, flags):
-    for M, N, K, ta in SHAPES:
-        d, A, B, exp = checked(variant, order, M, N, K, ta)
-        assert R.strong(d, exp), (variant, M, N, K)
+    for M, N, K, ta, dist in [s + (0,) for s in SHAPES] + [s + (2,) for s in EDGE_SHAPES]:
+        d, A, B, exp = checked(variant, order, M, N, K, ta, dist)
+        assert R.strong(d, exp), (variant, M, N, K, dist)
         info = capi.classify(d, flags)
         # the mixed kernel: compact steps where every step is "add a constant, shift, clamp", run-time modes otherwise (built for at
         # most 12 levels); QG_OPT_GENERIC_TREE and longer run-time-mode trees: the general kernel's part-wise product branch
@@ -128,19 +145,7 @@ def test_tree_kernels(oracle, variant, order, flags):
         if want == "tree_rc_i32":
             assert info.reason.decode().endswith("run-time modes" if runtime else "fixed modes, compact"), info.reason
         got = run(oracle, d, A, B, flags=flags)
-        assert got.tobytes() == exp.tobytes(), (variant, order, flags, M, N, K, ta)
-
-
-# name: (real element, complex element, C, lowering keywords): products with one spare bit and level types that hold every sum, so
-# nothing rounds or overflows before C; C's parts have fewer fraction bits than the products (right shifts of 2 and 1, 3 and 3, 6 and 0)
-LINEAR = {
-    "limb1": (Qu(4, 3), Qcomplex(Qu(4, 3), Qu(4, 1)), Qcomplex(Qu(18, 4), Qu(18, 3)),
-              dict(mul_args=RealComplexMul(realT=Qu(10, 6), imagT=Qu(10, 4)), add_args=[Qcomplex(Qu(18, 6), Qu(18, 4))])),
-    "limb2": (Qu(6, 6), C5, Qcomplex(Qu(22, 6), Qu(22, 0)),
-              dict(mul_args=RealComplexMul(realT=Qu(14, 9), imagT=Qu(14, 3)), add_args=[Qcomplex(Qu(22, 9), Qu(22, 3))])),
-    "limb3": (Qu(8, 8), Qcomplex(Qu(8, 8), Qu(7, 5)), Qcomplex(Qu(26, 10), Qu(25, 13)),
-              dict(mul_args=RealComplexMul(realT=Qu(18, 16), imagT=Qu(17, 13)), add_args=[Qcomplex(Qu(26, 16), Qu(25, 13))])),
-}
+        assert got.tobytes() == exp.tobytes(), (variant, order, flags, M, N, K, ta, dist)
 
 
 @pytest.mark.parametrize("order", ["ra", "rb"])

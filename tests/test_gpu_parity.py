@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import golden_io as G
+from stacked_cases import B8, BL, C5, C8, L8, LW
 from qublas_amd import capi
 from qublas_amd.desc import (CLASS_LINEAR, Qcomplex, Qu, RND, SAT, TRN, WRP, TFComplexMul, BasicComplexMul, Tags,
                              desc_from_dict, lower)
@@ -638,11 +639,7 @@ def test_fast_tree_fixed_mode_variants(oracle, elem, K, dist):
 def test_complex_linear_class_on_mfma(oracle):
     """Complex operands whose BasicComplexMul sub-ops and tree levels are all exact: four real int8-limb dot
     products on MFMA + one combine pass, against the oracle and against the exact tree kernel."""
-    r = Qu(6, 3, True, RND.POS_INF, SAT.TCPL)
-    i = Qu(6, -3, True, RND.POS_INF, SAT.TCPL)
-    c5 = Qcomplex(r, i)
-    BL = BasicComplexMul(acT=Qu(14, 6), bdT=Qu(14, -6), adT=Qu(14, 0), bcT=Qu(14, 0), acbdT=Qu(15, 6), adbcT=Qu(15, 0))
-    lw = Qcomplex(Qu(30, 6), Qu(30, 0))
+    c5, c8, lw, l8 = C5, C8, LW, L8   # (the elements and tags: tests/stacked_cases.py, shared with tests/test_gpu_stacked_tiles.py)
     wide = Qcomplex(Qu(18, 6, True, RND.POS_INF), Qu(18, 6, True, RND.POS_INF))
     narrow = Qcomplex(Qu(9, 2, True, RND.CONV, SAT.SMGN), Qu(7, -1, True, RND.ZERO, WRP.TCPL))
     for ec, shape, ta in ((wide, (200, 130, 512), False), (narrow, (130, 257, 256), True), (c5, (64, 64, 2048), False)):
@@ -651,11 +648,6 @@ def test_complex_linear_class_on_mfma(oracle):
         b = _vs_oracle(oracle, c5, c5, ec, M, N, K, mul_args=BL, add_args=[lw], transposed_a=ta, flags=capi.OPT_FORCE_TREE)
         assert fields_equal(a, b)
     # symmetric 8-bit parts: single limb per part
-    r8 = Qu(4, 3)
-    c8 = Qcomplex(r8, r8)
-    # adbcT needs 11 int bits: ad + bc reaches exactly 2^15 at a=b=c=d=-128, and two of those overflow Qu<10,6> by one LSB
-    B8 = BasicComplexMul(acT=Qu(9, 6), bdT=Qu(9, 6), adT=Qu(9, 6), bcT=Qu(9, 6), acbdT=Qu(11, 6), adbcT=Qu(11, 6))
-    l8 = Qcomplex(Qu(22, 6), Qu(22, 6))
     _vs_oracle(oracle, c8, c8, Qcomplex(Qu(16, 3), Qu(16, 3)), 300, 200, 1024, mul_args=B8, add_args=[l8], expect_kernel="mfma_cplx")
 
 

@@ -23,6 +23,7 @@ from qublas_amd import capi, profmeta  # noqa: E402
 from qublas_amd.desc import (BasicComplexMul, CMUL_NONE, CMUL_REAL_A, QGEMUL_ABI_VERSION, Qcomplex, Qu, RealComplexMul, RND, SAT, lower,  # noqa: E402
                              qgemul_desc)
 
+DEFAULT_SIZE = 2048
 R63 = Qu(6, 3, True, RND.POS_INF, SAT.TCPL)
 C5 = Qcomplex(R63, Qu(6, -3, True, RND.POS_INF, SAT.TCPL))
 
@@ -40,6 +41,22 @@ def part_desc(d, p):
         r.level_add[0][l] = r.level_add[1][l] = d.level_add[p][l]
         r.level[0][l] = r.level[1][l] = d.level[p][l]
     return r
+
+
+def wide_descs(order, S):
+    """(mixed, padded) descriptors of the wide-tag workload: every product with one spare bit, levels and C that hold the sum of S
+    products, so nothing rounds or overflows (the linear class; tests/test_stacked_tile_coverage.py pins the kernel variant it runs on)"""
+    ea, eb = (R63, C5) if order == "ra" else (C5, R63)
+    zp = Qcomplex(R63, R63)   # the real operand as a complex one whose imaginary parts are zero
+    lg = max(1, (S - 1).bit_length())
+    cw = Qcomplex(Qu(15 + lg, 6), Qu(15 + lg, 0))
+    mixed = lower(ea, eb, cw, S, S, S, mul_args=RealComplexMul(realT=Qu(14, 6), imagT=Qu(14, 0)), add_args=[cw])
+    # (Basic on the padded operand: x = a + bi, y = c + di; the products with the (6, -3) part have 0 fraction bits)
+    hi, lo = Qu(14, 6), Qu(14, 0)
+    bm = BasicComplexMul(acT=hi, bdT=lo, adT=lo if order == "ra" else hi, bcT=hi if order == "ra" else lo, acbdT=Qu(15, 6), adbcT=Qu(15, 6))
+    cp = Qcomplex(Qu(16 + lg, 6), Qu(16 + lg, 6))
+    padded = lower(zp if order == "ra" else C5, C5 if order == "ra" else zp, cp, S, S, S, mul_args=bm, add_args=[cp])
+    return mixed, padded
 
 
 class Arm:
@@ -66,7 +83,7 @@ class Arm:
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--size", type=int, default=2048)
+    ap.add_argument("--size", type=int, default=DEFAULT_SIZE)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--orders", default="ra,rb")
@@ -83,15 +100,7 @@ def main():
                 mixed = lower(ea, eb, C5, S, S, S)
                 padded = lower(zp if order == "ra" else C5, C5 if order == "ra" else zp, C5, S, S, S)
             else:
-                # every product with one spare bit, levels and C that hold the sum of S products: nothing rounds or overflows
-                lg = max(1, (S - 1).bit_length())
-                cw = Qcomplex(Qu(15 + lg, 6), Qu(15 + lg, 0))
-                mixed = lower(ea, eb, cw, S, S, S, mul_args=RealComplexMul(realT=Qu(14, 6), imagT=Qu(14, 0)), add_args=[cw])
-                # (Basic on the padded operand: x = a + bi, y = c + di; the products with the (6, -3) part have 0 fraction bits)
-                hi, lo = Qu(14, 6), Qu(14, 0)
-                bm = BasicComplexMul(acT=hi, bdT=lo, adT=lo if order == "ra" else hi, bcT=hi if order == "ra" else lo, acbdT=Qu(15, 6), adbcT=Qu(15, 6))
-                cp = Qcomplex(Qu(16 + lg, 6), Qu(16 + lg, 6))
-                padded = lower(zp if order == "ra" else C5, C5 if order == "ra" else zp, cp, S, S, S, mul_args=bm, add_args=[cp])
+                mixed, padded = wide_descs(order, S)
             arms = {"mixed": Arm(ctx, [mixed]), "padded": Arm(ctx, [padded]), "parts": Arm(ctx, [part_desc(mixed, 0), part_desc(mixed, 1)])}
             for arm in arms.values():   # clock and code-object warm-up
                 arm.time(2, 2)
