@@ -531,6 +531,9 @@ void Qgemul(TC& C, const TA& A, const TB& B)
 //     QgemulBatched<tags...>(C, A, B);      // member b:  Qgemul<tags...>(C[:, :, b], A[:, :, b], B[:, :, b])
 // The column-major index makes the members contiguous at stride rows * cols.  Same tags and same lowering as Qgemul: the
 // descriptor is the one Qgemul lowers for ONE member (qgemul_run_batched, qgemul.h); small linear-class members run as one launch.
+// Qcomplex tensors (and one real, one complex operand) are members like any other:
+//     QgemulRunFlags() |= QG_OPT_BATCHED_STACKED;   // complex / real x complex members of the linear class: one block-diagonal launch
+//                                                   // + one combine pass for the whole batch; without it member by member (mixed: refused)
 template <typename... Tags, size_t CM, size_t CN, size_t CB, size_t AR, size_t AC, size_t AB, size_t BR, size_t BN, size_t BB, class EC, class EA, class EB>
 qgemul_desc QgemulBatched_lower_types(std::type_identity<Qu_s<dim<CM, CN, CB>, EC>>, std::type_identity<Qu_s<dim<AR, AC, AB>, EA>>,
                                       std::type_identity<Qu_s<dim<BR, BN, BB>, EB>>, int64_t* batch, int64_t* strides)

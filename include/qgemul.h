@@ -68,8 +68,9 @@ enum { QG_CMUL_NONE = 0, QG_CMUL_BASIC = 1, QG_CMUL_TF = 2,
         * is_complex = 1 (C is complex; level_add / level / c as for any complex descriptor).  The REAL operand's format is
         * in [0] of its a[] / b[]; its [1] must be all zero (QG_EINVAL otherwise: one descriptor, one spelling).  Its host
         * element is a plain int32_t / int64_t word (qgemul_info.host_elem_bytes / host_imag_off are per operand).
-        * Served: the plain entry points and qgemul_run.  Element-wise chains, batched and grouped plans and the sharded
-        * run refuse such a descriptor (QG_EUNSUPPORTED, "mixed real-complex"). */
+        * Served: the plain entry points and qgemul_run, and batched plans created with QG_OPT_BATCHED_STACKED (linear-class members).
+        * Element-wise chains, every other batched plan, grouped plans and the sharded run refuse such a descriptor (QG_EUNSUPPORTED,
+        * "mixed real-complex"). */
        QG_CMUL_REAL_A = 3,   /* A real, B and C complex:  p_re = op(A'[i,k] * B[k,j].real),  p_im = op(A'[i,k] * B[k,j].imag) */
        QG_CMUL_REAL_B = 4 }; /* A and C complex, B real:  p_re = op(A'[i,k].real * B[k,j]),  p_im = op(A'[i,k].imag * B[k,j]) */
 
@@ -189,10 +190,16 @@ enum {
                                       unsigned formats) — the plain balanced limbs of every round before; result-identical (tests) */
     QG_OPT_LOCKSTEP_TILES = 128u,  /* large single-limb problems: the 64-byte-k-tile kernel whose waves run in lock step
                                     * (k_mfma16) instead of the two-group kernel on 128-byte k-tiles (k_mfma_pp) */
-    /* the highest bit in use.  Chains with an APPROX stage (below): run UNIFORM tables through the general form of the pass too
+    /* Chains with an APPROX stage (below): run UNIFORM tables through the general form of the pass too
      * (segment by segment under a lane mask instead of one Horner loop with a per-lane coefficient); result-identical, for
      * equivalence tests and A/B timing */
-    QG_OPT_APPROX_GENERAL = 4096u
+    QG_OPT_APPROX_GENERAL = 4096u,
+    /* the highest bit in use.  Batched plans (below) whose member is a complex or a real x complex GEMM of the linear class: ONE
+     * block-diagonal MFMA launch over the members' stacked parts plus ONE block-diagonal combine pass (2 launches for the whole
+     * batch) instead of member by member; a mixed member, which a batched plan refuses otherwise, is served in this form.
+     * Result-identical.  Decided at plan time (the packed A and B differ).  Ignored by every other plan: plain and grouped plans,
+     * real, tree-class and composite members, and the _batched_ep entry points */
+    QG_OPT_BATCHED_STACKED = 8192u
 };
 
 /* status codes */
@@ -322,6 +329,11 @@ int qgemul_time_execute(qgemul_plan* p, void* packedC, const void* packedA, cons
  * workgroups walk the block diagonal of the big product.  Everything else (tree class, complex, ring and
  * composite plans, members large enough for the two-group kernels, conversions that take the raw-dot-product pass) runs member
  * by member on the existing path through the same entry points, so every supported descriptor is served.
+ * QG_OPT_BATCHED_STACKED: complex and real x complex members of the linear class whose limb pair has a block-diagonal kernel run
+ * as TWO launches for the whole batch: the block-diagonal GEMM over the members' stacked parts (member blocks of 2 tm x 2 tn tiles;
+ * mixed: tm x 2 tn or 2 tm x tn) into the plan's int64 workspace, and one block-diagonal combine pass (k_stack_combine_bd) into the
+ * members' packed Cs.  Without the flag a mixed member is refused (QG_EUNSUPPORTED) and a complex one runs member
+ * by member.
  * The packed layouts belong to the batched plan (they may differ from the plain plan of the same descriptor); packed C is the
  * members' packed Cs back to back.  qgemul_info.packed_bytes[] of a batched classify / plan are for the whole batch, ops too.
  * A batched plan is destroyed with qgemul_plan_destroy and answers qgemul_plan_info and qgemul_plan_packed_layout (in the one-
@@ -349,6 +361,11 @@ int qgemul_execute_batched(qgemul_plan* p, void* packedC, const void* packedA, c
 int qgemul_time_execute_batched(qgemul_plan* p, void* packedC, const void* packedA, const void* packedB, int warmup, int iters, float* avg_ms);
 int qgemul_run_batched(const qgemul_desc* d, int64_t batch, void* C, const void* A, const void* B, int64_t strideC, int64_t strideA, int64_t strideB,
                        const qgemul_opts* o);
+/* measurement only, a plan in the stacked form (QG_OPT_BATCHED_STACKED): qgemul_time_execute_batched of ONE of its two launches —
+ * launch 0: the block-diagonal GEMM into the plan's workspace, 1: the combine pass over what that workspace holds (execute the plan
+ * once before timing launch 1).  Every other plan, every other launch number: QG_EINVAL */
+int qgemul_time_execute_batched_launch(qgemul_plan* p, void* packedC, const void* packedA, const void* packedB, int launch, int warmup, int iters,
+                                       float* avg_ms);
 
 /* ---- fused element-wise epilogue ----
  * The reference's lazy tensor operators (Qmul/Qadd/Qsub on tensors, QuBLAS.h:3780-3877, front-ends

@@ -26,6 +26,7 @@ OPT_FORCE_TREE, OPT_CHECK_RANGE, OPT_GENERIC_TREE, OPT_RUNTIME_MODES, OPT_FUSED_
 OPT_GENERIC_LAYOUT, OPT_LOCKSTEP_TILES, OPT_ARITHMETIC_CONV, OPT_ALL_DEVICES = 64, 128, 256, 512
 OPT_SCHOOLBOOK_LIMBS = 2048   # 17/18-bit operands: balanced base-256 limbs and 9 products, not three base-64 digits and 6; result-identical
 OPT_APPROX_GENERAL = 4096   # chains with an APPROX stage: uniform tables through the general form of the pass; result-identical
+OPT_BATCHED_STACKED = 8192   # batched plans of complex / real x complex linear-class members: one block-diagonal launch + one combine pass; result-identical
 OPT_BALANCED_LIMBS = 1024   # never centre an operand (x - c in balanced limbs): the plain balanced limbs, result-identical
 OPERAND_A, OPERAND_B, OPERAND_C = 0, 1, 2
 BITS_ASCII, BITS_PACKED = 0, 1
@@ -46,7 +47,7 @@ EXPORTS = [
     "qgemul_classify_epx", "qgemul_plan_create_epx", "qgemul_run_epx", "qgemul_plan_approx_uniform", "qgemul_sizeof", "qgemul_approx_plan_form", "qgemul_apply_epilogue", "qgemul_time_apply_epilogue", "qgemul_packed_c_bytes", "qgemul_pack_c",
     "qgemul_classify_epcx", "qgemul_plan_create_epcx", "qgemul_run_epcx", "qgemul_cmul_plan_form",
     "qgemul_classify_batched", "qgemul_classify_batched_launches", "qgemul_plan_create_batched", "qgemul_plan_batched_launches", "qgemul_pack_batched",
-    "qgemul_unpack_c_batched", "qgemul_execute_batched", "qgemul_time_execute_batched", "qgemul_run_batched",
+    "qgemul_unpack_c_batched", "qgemul_execute_batched", "qgemul_time_execute_batched", "qgemul_time_execute_batched_launch", "qgemul_run_batched",
     "qgemul_classify_batched_epx", "qgemul_classify_batched_epx_launches", "qgemul_plan_create_batched_epx", "qgemul_pack_e_batched", "qgemul_execute_batched_ep",
     "qgemul_time_execute_batched_ep", "qgemul_run_batched_epx",
     "qgemul_classify_grouped", "qgemul_classify_grouped_launches", "qgemul_classify_grouped_member", "qgemul_plan_create_grouped", "qgemul_plan_grouped_launches",
@@ -162,6 +163,7 @@ def lib() -> C.CDLL:
         L.qgemul_unpack_c_batched.argtypes = [vp, vp, vp, i64, i64]
         L.qgemul_execute_batched.argtypes = [vp, vp, vp, vp]
         L.qgemul_time_execute_batched.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(C.c_float)]
+        L.qgemul_time_execute_batched_launch.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
         L.qgemul_run_batched.argtypes = [pd, i64, vp, vp, vp, i64, i64, i64, C.POINTER(qgemul_opts)]
         pbe = C.POINTER(qgemul_batched_ep)
         L.qgemul_classify_batched_epx.argtypes = [pd, i64, pe, pax, pbe, u32, C.POINTER(qgemul_info)]
@@ -779,6 +781,13 @@ class BatchedPlan:
     def time_execute(self, pC: int, pA: int, pB: int, warmup: int, iters: int) -> float:
         ms = C.c_float()
         _chk(lib().qgemul_time_execute_batched(self.h, C.c_void_p(pC), C.c_void_p(pA), C.c_void_p(pB), warmup, iters, C.byref(ms)), "qgemul_time_execute_batched")
+        return ms.value
+
+    def time_execute_launch(self, pC: int, pA: int, pB: int, launch: int, warmup: int, iters: int) -> float:
+        """a plan in the stacked form (OPT_BATCHED_STACKED): ms per run of ONE of its launches, 0 the block-diagonal GEMM, 1 the combine pass"""
+        ms = C.c_float()
+        _chk(lib().qgemul_time_execute_batched_launch(self.h, C.c_void_p(pC), C.c_void_p(pA), C.c_void_p(pB), launch, warmup, iters, C.byref(ms)),
+             "qgemul_time_execute_batched_launch")
         return ms.value
 
     # ---- plans with an element-wise chain (ep is not None) ----

@@ -463,6 +463,7 @@ void qgemul_plan_destroy(qgemul_plan* p)
     delete p->grp;
     hipFree(p->dev_table);
     hipFree(p->workspace);
+    hipFree(p->stack_work);
     hipFree(p->cwork);
     hipFree(p->wide_ws);
     hipFree(p->hostc_pc);
@@ -1163,6 +1164,13 @@ int plan_create_batched_view(qgemul_ctx* c, const qgemul_desc* d, int64_t batch,
             return QG_EHIP;
         }
     }
+    if (b->bd_stack) {   // the stacked form: the raw dot products between its two launches
+        DeviceScope scope(c->device);
+        if (scope.err != hipSuccess || hipMalloc((void**)&b->stack_work, (size_t)(b->stack_ws ? b->stack_ws : 16)) != hipSuccess) {
+            qgemul_plan_destroy(b);
+            return QG_EHIP;
+        }
+    }
     *out = b;
     return QG_OK;
 }
@@ -1185,7 +1193,7 @@ int qgemul_pack_batched(qgemul_plan* p, int operand, const void* src_dev, int64_
     if (ext < 1 || member_stride < ext) return QG_EINVAL;
     qgemul_plan* m = p->member;
     const int64_t eb = operand == QG_OPERAND_A ? p->ha.size : p->hb.size;
-    if (!p->bd) {
+    if (!p->bd && !p->bd_stack) {
         for (int64_t b = 0; b < p->batch; ++b)
             if (const int st = qgemul_pack(m, operand, (const char*)src_dev + b * member_stride * eb, ld, (char*)packed_dev + b * p->mstride[operand]); st != QG_OK) return st;
         return QG_OK;
@@ -1222,12 +1230,48 @@ static QMfmaArgs bd_mfma_args(const qgemul_plan* p, void* packedC, const void* p
     return a;
 }
 
+// the stacked form (QG_OPT_BATCHED_STACKED): the members' stacked parts as ONE block-diagonal GEMM of raw 64-bit dot products into the
+// plan's workspace — member blocks of bd_tm x bd_tn tiles —, then ONE combine pass into the members' packed Cs (qg_combine_bd.hip)
+// which: -1 both launches; 0 / 1: that launch alone (qgemul_time_execute_batched_launch: the measurement of the two shares)
+static int execute_stacked(qgemul_plan* p, void* packedC, const void* packedA, const void* packedB, int which = -1)
+{
+    const qgemul_plan* m = p->member;
+    QG_ON_DEVICE(p->ctx);
+    QMfmaArgs a = mfma_args(p->pa, p->pb, p->variant, packedA, packedB, p->stack_work, 8);
+    a.to_c.identity = 1;
+    a.bd_tm = p->bd_tm;
+    a.bd_tn = p->bd_tn;
+    if (which != 1) QG_HIP(qg_launch_mfma_bd(p->LA, p->LB, a, p->batch, p->ctx->stream));
+    if (which == 0) return QG_OK;
+    QStackCombine g;
+    memset(&g, 0, sizeof g);
+    g.W = p->stack_work;
+    g.C = (char*)packedC;
+    g.M = p->desc.M;
+    g.N = p->desc.N;
+    g.cstride = p->mstride[2];
+    g.tm = (int32_t)(m->pa.rows_p / p->cfg.TM);
+    g.tn = (int32_t)(m->pb.rows_p / p->cfg.TN);
+    g.bd_tm = p->bd_tm;
+    g.bd_tn = p->bd_tn;
+    g.im_r = p->bd_stack == QG_STACK_REAL_B ? g.tm : 0;
+    g.im_c = p->bd_stack == QG_STACK_REAL_A ? g.tn : 0;
+    g.mode = p->bd_stack;
+    g.cbytes = p->pc.cbytes;
+    for (int i = 0; i < 4; ++i) g.sh[i] = m->an.lin.sh[i];
+    g.to_c[0] = m->an.lin.to_c[0];
+    g.to_c[1] = m->an.lin.to_c[1];
+    QG_HIP(qg_launch_stack_combine_bd(g, p->batch, p->ctx->stream));
+    return QG_OK;
+}
+
 int qgemul_execute_batched(qgemul_plan* p, void* packedC, const void* packedA, const void* packedB)
 {
     if (!p || p->batch < 1 || !packedC || !packedA || !packedB) return QG_EINVAL;
     if (p->has_ep) return QG_EINVAL;  // a batched plan with a chain runs through qgemul_execute_batched_ep
     if (p->desc.M == 0 || p->desc.N == 0) return QG_OK;
     qgemul_plan* m = p->member;
+    if (p->bd_stack) return execute_stacked(p, packedC, packedA, packedB);
     if (!p->bd) {
         for (int64_t b = 0; b < p->batch; ++b)
             if (const int st = qgemul_execute(m, (char*)packedC + b * p->mstride[2], (const char*)packedA + b * p->mstride[0], (const char*)packedB + b * p->mstride[1]); st != QG_OK)
@@ -1244,6 +1288,13 @@ int qgemul_time_execute_batched(qgemul_plan* p, void* packedC, const void* packe
 {
     if (p && p->has_ep) return QG_EINVAL;
     return time_execute(p, packedC, packedA, packedB, nullptr, warmup, iters, avg_ms, true);
+}
+
+int qgemul_time_execute_batched_launch(qgemul_plan* p, void* packedC, const void* packedA, const void* packedB, int launch, int warmup, int iters, float* avg_ms)
+{
+    if (!p || p->batch < 1 || !p->bd_stack || !packedC || !packedA || !packedB || !avg_ms || iters < 1 || (launch != 0 && launch != 1)) return QG_EINVAL;
+    if (p->desc.M == 0 || p->desc.N == 0) { *avg_ms = 0; return QG_OK; }
+    return time_calls(p, warmup, iters, avg_ms, [&] { return execute_stacked(p, packedC, packedA, packedB, launch); });
 }
 
 // ---- element-wise chains on batched plans (include/qgemul.h): member b is Qgemul<...>(C_b, A_b, B_b) followed by the chain ----

@@ -99,6 +99,9 @@ struct qgemul_plan : QPlanGeom, QBatchGeom {
     // resource; with a chain, ep / ept / pc (D) / pc_c (C) are the member's, and the block-diagonal pass form's packed C of the whole stack
     // is this plan's cwork
     qgemul_plan* member;
+    // ... in the stacked form (QPlanGeom::bd_stack, QG_OPT_BATCHED_STACKED): the raw dot products between the block-diagonal launch and
+    // the combine pass, QBatchGeom::stack_ws bytes, owned by the batched plan itself
+    int64_t* stack_work;
     // grouped plan (qgemul_plan_create_grouped): batch == -1, so that the plain entry points refuse it as they refuse a batched plan and
     // the batched ones as they refuse a plain plan; everything else is in grp.  With a chain (qgemul_plan_create_grouped_epx): has_ep, ep, ept
     // and has_ax are the group's one chain, the device tables of its APPROX stages are the key plan's (grp->up[grp->key])

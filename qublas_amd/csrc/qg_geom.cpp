@@ -202,6 +202,10 @@ struct Planner {
     bool centred = false;
     QMfmaCfg cfg = {0, 0, 0, 0};
     bool bd = false;                  // batch > 0 and k_mfma has a block-diagonal form for the member: see linear_kernel
+    // QG_OPT_BATCHED_STACKED on a batched plan without a chain (a grouped plan's members come in without the flag): a complex or mixed
+    // member may take the stacked block-diagonal form; stacked: it does (see linear_kernel)
+    const bool want_stack = batch > 0 && (flags & QG_OPT_BATCHED_STACKED) && d->is_complex && !ev;
+    bool stacked = false;
     bool k6 = false, ppl33 = false;   // the six-product kernel / the 3 x 3 body of k_mfma_ppl takes the plan
 
 
@@ -209,6 +213,7 @@ struct Planner {
     int analysis_and_header()
     {
         out->bd = 0;
+        out->bd_stack = QG_STACK_NONE;
         memset(&comp, 0, sizeof comp);
         qg_analyze(d, an);
         memset(info, 0, sizeof *info);
@@ -234,9 +239,11 @@ struct Planner {
         info->ops = !d->is_complex ? 2.0 * mnk : mixed ? 4.0 * mnk : (d->cmul == QG_CMUL_TF ? 6.0 * mnk : 8.0 * mnk);
         // what a mixed descriptor is refused: the entry points that have no part-wise form yet (include/qgemul.h)
         if (mixed && ev) return refuse(info, QG_EUNSUPPORTED, "mixed real-complex: no element-wise chain");
-        if (mixed && batch > 0) return refuse(info, QG_EUNSUPPORTED, "mixed real-complex: no batched or grouped plan");
+        // (under QG_OPT_BATCHED_STACKED the answer waits for the kernel choice: mixed_member_refusal)
+        if (mixed && batch > 0 && !want_stack) return mixed_member_refusal();
         return QG_OK;
     }
+    int mixed_member_refusal() { return refuse(info, QG_EUNSUPPORTED, "mixed real-complex: no batched or grouped plan"); }
 
     // 2 + 3, RING plans (qg_plan.cpp: ring_plan; qg_mfma_ring.hip): product and every level wrap into one signed format of n <= 32 bits,
     // so the tree is the dot product modulo 2^n.  The operands keep their first min(L, limbs) balanced digits, L = ceil(n / 8) — no
@@ -299,7 +306,7 @@ struct Planner {
         // batch > 0: the member of a batched plan.  Where k_mfma has a block-diagonal form for it, the tile geometry comes from
         // qg_mfma_pick_batched (the batch's total tile count, the member's padding waste) and out->bd = 1: the packed layouts then belong
         // to the batched plan and may differ from the plain plan of the same descriptor
-        if (batch > 0 && !d->is_complex && (!ep || !ev->im)) {   // (with a real chain: qgemul_plan_create_batched_epx)
+        if (batch > 0 && (!d->is_complex || want_stack) && (!ep || !ev->im)) {   // (with a real chain: qgemul_plan_create_batched_epx)
             const QMfmaCfg bc = qg_mfma_pick_batched(LA, LB, batch, cfg);
             if (bc.variant) { plain_cfg = cfg; cfg = bc; bd = true; }
         }
@@ -327,6 +334,13 @@ struct Planner {
         }
         // the block-diagonal form takes what ONE launch of a lock-step kernel with its own conversion serves: no composite plan, no
         // raw-dot-product detour (qg_wide_epilogue).  A member without it runs on the plain plan's own geometry
+        // The STACKED form (want_stack): the member's plan is already one real GEMM on stacked parts with an identity epilogue into an
+        // int64 workspace, so the block-diagonal launch takes it as it is, on the 64 x 64 geometry, and the combine pass follows it.
+        // bd itself stays with the real members: nothing that serves their form (grouped plans, chains) sees a stacked member
+        if (bd && want_stack && (kernel == QG_KERNEL_MFMA_CPLX || kernel == QG_KERNEL_MFMA_RC)) {
+            stacked = true;
+            bd = false;
+        }
         if (bd && (comp.on || raw_dot_pass(kernel, tc, an->dot_bits) || (kernel != QG_KERNEL_MFMA_I8 && kernel != QG_KERNEL_MFMA_I8_LIMB))) {
             bd = false;
             if (!comp.on) cfg = plain_cfg;
@@ -563,6 +577,9 @@ int qg_plan_geometry(const qgemul_desc* d, uint32_t flags, const EpView* ev, int
         p.linear_limbs();
         p.linear_kernel();
     }
+    // a mixed member without the stacked form is refused as without QG_OPT_BATCHED_STACKED (nothing but the header of info is filled yet)
+    if (p.mixed && batch > 0 && !p.stacked) return p.mixed_member_refusal();
+    out->bd_stack = !p.stacked ? QG_STACK_NONE : !p.mixed ? QG_STACK_CPLX : d->cmul == QG_CMUL_REAL_A ? QG_STACK_REAL_A : QG_STACK_REAL_B;
     p.packed_c();
     p.three_digit_choice();
     if (p.kernel != QG_KERNEL_NONE) p.limb_layout();
@@ -632,18 +649,29 @@ int64_t qg_member_extent(const qgemul_desc& d, int operand, int64_t ld)
 
 // ---- batched Qgemul: `batch` GEMMs of one descriptor at constant strides (include/qgemul.h) ----
 // the block-diagonal form: the stack's packed geometries, total[] = the stack's bytes; true: beyond the tile / address range
+// The STACKED form (m->bd_stack): an operand of two parts brings both into the stack — a member's packed operand is [part][row tile]
+// ..., so member b owns parts * rows_p / TM consecutive row tiles and the stack's rows_p counts them all —, the launch has bd_tm x bd_tn
+// tiles per member, its raw dot products go into a workspace of 64 x 64 int64 tiles (stack_ws), and packed C keeps the step of the
+// member-by-member form.  Complex plans are never centred (linear_limbs), a mixed plan's real operand included: no row sums.
 static bool batched_stack(const QPlanGeom* m, int64_t batch, QPlanGeom* s, QBatchGeom* b, int64_t total[3])
 {
+    const int64_t parts[2] = {m->bd_stack == QG_STACK_CPLX || m->bd_stack == QG_STACK_REAL_B ? 2 : 1, m->bd_stack == QG_STACK_CPLX || m->bd_stack == QG_STACK_REAL_A ? 2 : 1};
+    const int64_t tm = parts[0] * (m->pa.rows_p / m->cfg.TM), tn = parts[1] * (m->pb.rows_p / m->cfg.TN);
     int64_t tiles = 0;
-    bool over = __builtin_mul_overflow((m->pa.rows_p / m->cfg.TM) * (m->pb.rows_p / m->cfg.TN), batch, &tiles) || tiles > 0x7fffffffll;
+    bool over = __builtin_mul_overflow(tm * tn, batch, &tiles) || tiles > 0x7fffffffll;
+    if (m->bd_stack) {
+        b->bd_tm = (int32_t)tm;
+        b->bd_tn = (int32_t)tn;
+        over |= m->pa.offs != 0 || m->pb.offs != 0 || __builtin_mul_overflow(tiles, (int64_t)m->cfg.TM * m->cfg.TN * 8, &b->stack_ws) || b->stack_ws > (1ll << 60);
+    }
     QPackedGeom* sg[2] = {&s->pa, &s->pb};
     const QPackedGeom* mg[2] = {&m->pa, &m->pb};
     for (int w = 0; w < 2 && !over; ++w) {
         QPackedGeom& g = *sg[w];
         g = *mg[w];
         int64_t planes = 0;
-        over |= __builtin_mul_overflow(g.rows_p, batch, &g.rows_p) || __builtin_mul_overflow((int64_t)g.limbs * g.K_p, g.rows_p, &planes) || planes > (1ll << 60);
-        b->mstride[w] = (int64_t)mg[w]->limbs * mg[w]->rows_p * mg[w]->K_p;
+        over |= __builtin_mul_overflow(g.rows_p * parts[w], batch, &g.rows_p) || __builtin_mul_overflow((int64_t)g.limbs * g.K_p, g.rows_p, &planes) || planes > (1ll << 60);
+        b->mstride[w] = parts[w] * mg[w]->limbs * mg[w]->rows_p * mg[w]->K_p;
         int64_t bytes = planes;
         g.trailer = 0;
         if (g.limbs > 1) { g.trailer = bytes; bytes += QG_TRAILER_BYTES; }   // ONE plane mask: the OR over every member
@@ -653,8 +681,8 @@ static bool batched_stack(const QPlanGeom* m, int64_t batch, QPlanGeom* s, QBatc
         }
         total[w] = bytes;
     }
-    b->mstride[2] = m->info.packed_bytes[2];
-    over |= __builtin_mul_overflow(b->mstride[2], batch, &total[2]);
+    b->mstride[2] = m->bd_stack ? qg_round_up(m->info.packed_bytes[2], 256) : m->info.packed_bytes[2];
+    over |= __builtin_mul_overflow(b->mstride[2], batch, &total[2]) || (m->bd_stack && total[2] > (1ll << 60));
     return over;
 }
 
@@ -668,7 +696,7 @@ int qg_batched_geometry(const qgemul_desc* d, int64_t batch, uint32_t flags, con
     if (st != QG_OK) return st;
     b->batch = batch;
     // the stack has the member's kernel, host elements and packed C (pa / pb: below; an and comp stay the member's alone)
-    s->bd = m->bd, s->LA = m->LA, s->LB = m->LB, s->cfg = m->cfg, s->variant = m->variant;
+    s->bd = m->bd, s->bd_stack = m->bd_stack, s->LA = m->LA, s->LB = m->LB, s->cfg = m->cfg, s->variant = m->variant;
     s->ha = m->ha, s->hb = m->hb, s->hc = m->hc, s->pc = m->pc;
     b->member_launches = qg_plan_launches(m);
     int64_t total[3] = {0, 0, 0};
@@ -699,6 +727,12 @@ int qg_batched_geometry(const qgemul_desc* d, int64_t batch, uint32_t flags, con
         if (ev)
             snprintf(s->info.reason, sizeof s->info.reason, b->bd_fused ? "linear class: %lld members, chain fused into one block-diagonal launch" : "linear class: %lld members, block-diagonal launch + one chain pass over the stack",
                      (long long)batch);
+    } else if (m->bd_stack) {
+        over |= batched_stack(m, batch, s, b, total);
+        // (every batch count fits qgemul_info.reason)
+        if (m->bd_stack == QG_STACK_CPLX) snprintf(s->info.reason, sizeof s->info.reason, "linear class: %lld complex members, one block-diagonal launch + one combine pass", (long long)batch);
+        else if (m->bd_stack == QG_STACK_REAL_A) snprintf(s->info.reason, sizeof s->info.reason, "linear class: %lld real x complex members, block-diagonal launch + combine pass", (long long)batch);
+        else snprintf(s->info.reason, sizeof s->info.reason, "linear class: %lld complex x real members, block-diagonal launch + combine pass", (long long)batch);
     } else {
         for (int w = 0; w < 3; ++w) {
             b->mstride[w] = qg_round_up(m->info.packed_bytes[w], 256);
@@ -721,6 +755,7 @@ int qg_batched_geometry(const qgemul_desc* d, int64_t batch, uint32_t flags, con
 int qg_batched_launches(const QPlanGeom* s, const QBatchGeom* b, bool has_ep)
 {
     if (s->bd) return has_ep && !b->bd_fused ? 2 : 1;
+    if (s->bd_stack) return 2;   // the block-diagonal GEMM and the combine pass
     const int64_t n = b->batch * b->member_launches;
     return n > 0x7fffffffll ? 0x7fffffff : (int)n;
 }
@@ -746,6 +781,7 @@ static int straggler_launches(const QGrouped* G, const QPlanGeom& q, uint32_t fl
 // geometry, a straggler its plain plan's
 static int grouped_distinct(const qgemul_desc* d, int64_t groups, uint32_t flags, const EpView* ev, QGrouped* G, qgemul_info* info)
 {
+    flags &= ~(uint32_t)QG_OPT_BATCHED_STACKED;   // (a batched plan's switch: a grouped plan plans its members as without it)
     // (the comparison of the one-shot cache: qg_run_key.h)
     for (int64_t g = 0; g < groups; ++g) {
         int64_t u = 0;

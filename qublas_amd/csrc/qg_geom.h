@@ -150,14 +150,23 @@ struct QPlanGeom {
     QCGeom pc_c;          // the kernel's own packed C, which only exists in memory (cwork) for the kernels that do not fuse the chain
     QComposite comp;      // composite linear plan (comp.on): limb groups x k-chunks of sub-GEMMs + an exact combine pass
     int bd;               // the member of a batched plan: k_mfma's block-diagonal form takes it (a batched plan: it launches that form)
+    int bd_stack;         // QG_OPT_BATCHED_STACKED, a complex / mixed member of a batched plan: the stacked block-diagonal form takes it
+                          // (QStackMode; bd stays 0: nothing that serves the real form sees such a member)
 };
+// the stacked block-diagonal form: which operands carry two parts, i.e. which source tiles of the workspace one output tile has
+enum QStackMode { QG_STACK_NONE = 0, QG_STACK_CPLX = 1, QG_STACK_REAL_A = 2, QG_STACK_REAL_B = 3 };
 
 // Batched plan (qg_batched_geometry; batch > 0): `batch` GEMMs of one descriptor at constant strides.  Next to it stand two QPlanGeoms:
 // the MEMBER's, and the STACK's, which is the member's with info (packed_bytes of the whole batch) and, in the block-diagonal form
 // (bd: one launch of k_mfma's BD form over the stacked operands), the stack's packed geometries in pa / pb — the member's with
-// batch times the rows, one plane-mask trailer and one row-sum array behind the planes of all members.  bd == 0: member by member.
+// batch times the rows, one plane-mask trailer and one row-sum array behind the planes of all members.  bd == 0: member by member,
+// unless bd_stack (QG_OPT_BATCHED_STACKED): the members' two-part packed operands back to back ([part][row tile][k tile][limb][TM][BK]
+// each; pa / pb.rows_p: ALL rows of the stack, parts included), one plane-mask trailer, no row sums, and the launch's raw dot products
+// in a workspace of stack_ws bytes: bd_tm x bd_tn tiles of 64 x 64 int64 per member, which k_stack_combine_bd turns into packed C.
 struct QBatchGeom {
     int64_t batch;
+    int64_t stack_ws;     // bd_stack: bytes of the workspace between the two launches
+    int32_t bd_tm, bd_tn; // bd_stack: tiles of ONE member in the launch (its parts included)
     int member_launches;  // kernel launches of one member's execute (with a chain: its pass included unless fused)
     int64_t mstride[3];   // the packed operands' stride from member to member
     // element-wise chain (qgemul_plan_create_batched_epx).  e_shared[k]: stage k's tensor operand is ONE M x N tensor for every member;

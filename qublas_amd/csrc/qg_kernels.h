@@ -44,7 +44,8 @@ hipError_t qg_launch_unpack_c(const QCGeom& c, const void* packed, void* dst, hi
 // batched plans, block-diagonal form: `batch` members of geometry g / member (ONE member's packed geometry; limb layout) at
 // src + b * stride_bytes are packed into the row tiles [b * member.rows_p / tr, ...) of the stack `stack` (member with batch times
 // the rows).  What belongs to the STACK is set up once, not per member: the plane-mask trailer (the OR over every member) and
-// the row sums of centred operands, which sit behind the planes of all members.
+// the row sums of centred operands, which sit behind the planes of all members.  A two-part operand (g.parts == 2: the stacked form of
+// a complex / mixed batch) brings both parts of a member, [part][row tile] ..., so `stack` then has parts * batch times the rows.
 hipError_t qg_launch_pack_stack(const QOperandGeom& g, const QPackedGeom& member, const QPackedGeom& stack, int64_t batch, const void* src,
                                 int64_t stride_bytes, void* dst, int check_range, int* range_flag, hipStream_t st, int generic = 0);
 
@@ -68,6 +69,20 @@ struct QRcConvert {
     QStep to_c[2];
 };
 hipError_t qg_launch_rc_convert(const QRcConvert& g, hipStream_t st);
+// stacked batched plans (QG_OPT_BATCHED_STACKED; qg_combine_bd.hip): the block-diagonal launch's workspace -> the members' packed
+// complex Cs.  W: bd_tm x bd_tn tiles of 64 x 64 int64 per member (tile-major, column-major inside a tile); tm x tn: the tiles of ONE
+// part; mode: QStackMode, which fixes bd_tm, bd_tn and where the imaginary product of a mixed member sits (im_r / im_c tiles behind
+// the real one); C: [2][M][N] per member in cbytes containers, cstride bytes from member to member
+struct QStackCombine {
+    const int64_t* W;
+    char* C;
+    int64_t M, N, cstride;
+    int32_t tm, tn, bd_tm, bd_tn, im_r, im_c;
+    int32_t mode, cbytes;
+    int32_t sh[4];
+    QStep to_c[2];
+};
+hipError_t qg_launch_stack_combine_bd(const QStackCombine& g, int64_t batch, hipStream_t st);
 
 // composite linear plans (operands of more than 3 int8 limbs, or K beyond the int32 accumulators' exact range): the limb-group /
 // k-chunk sub-GEMMs store RAW dot products (int32 for single-limb pairs, int64 otherwise) in slabs of one common packed-C

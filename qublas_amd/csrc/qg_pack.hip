@@ -641,7 +641,10 @@ hipError_t qg_launch_pack_member(const QOperandGeom& g, const QPackedGeom& p, co
 hipError_t qg_launch_pack_stack(const QOperandGeom& g, const QPackedGeom& member, const QPackedGeom& stack, int64_t batch, const void* src,
                                 int64_t stride_bytes, void* dst, int check_range, int* range_flag, hipStream_t st, int generic)
 {
-    if (batch < 1 || member.limbs < 1 || member.digit6 || g.parts != 1 || stack.rows_p != member.rows_p * batch) return hipErrorInvalidValue;
+    // (a two-part operand: the stacked form of a complex / mixed batch, whose members bring both parts — [part][row tile] ... each — and
+    // are never centred)
+    if (batch < 1 || member.limbs < 1 || member.digit6 || g.parts < 1 || g.parts > 2 || (g.parts == 2 && stack.offs) || stack.rows_p != g.parts * member.rows_p * batch)
+        return hipErrorInvalidValue;
     // the stack's own trailer and row sums: cleared ONCE; every member then ORs / adds into them
     if (stack.trailer)
         if (hipError_t e = hipMemsetAsync((char*)dst + stack.trailer, 0, QG_TRAILER_BYTES, st); e != hipSuccess) return e;
@@ -649,7 +652,7 @@ hipError_t qg_launch_pack_stack(const QOperandGeom& g, const QPackedGeom& member
         if (hipError_t e = hipMemsetAsync((char*)dst + stack.rowsum_off, 0, (size_t)stack.rows_p * 8, st); e != hipSuccess) return e;
     // member b owns the row tiles [b * rows_p / tr, (b + 1) * rows_p / tr): `planes` contiguous bytes of the stack; the trailer and
     // its row sums are addressed relative to that start (both stay positive: they lie behind the planes of ALL members)
-    const int64_t planes = (int64_t)member.limbs * member.rows_p * member.K_p;
+    const int64_t planes = (int64_t)g.parts * member.limbs * member.rows_p * member.K_p;
     for (int64_t b = 0; b < batch; ++b) {
         QPackedGeom m = member;
         m.trailer = stack.trailer ? stack.trailer - b * planes : 0;

@@ -79,6 +79,22 @@ QG_HD void qg_bd_tile_of(I w, I tmM, I tnN, I& member, I& tile_m, I& tile_n)
     qg_tile_of<8, true>(w % per, tmM, tnN, tile_m, tile_n);
 }
 
+// Stacked batched plans (QG_OPT_BATCHED_STACKED): a member's block of the block-diagonal launch holds the products of its stacked
+// parts, tm x tn tiles per product.  Source tile k of part `part` of the OUTPUT tile (lm, ln), as (row tile, column tile) inside the
+// member's block.  Complex members (cplx; the block is 2 tm x 2 tn): re = P(lm, ln) - P(lm + tm, ln + tn), im = P(lm, ln + tn) +
+// P(lm + tm, ln), k = 0, 1 in this order.  Mixed members: one product per part (k = 0), the imaginary one im_r tile rows / im_c tile
+// columns behind the real one (real x complex: 0, tn; complex x real: tm, 0).
+QG_HD void qg_stack_src_tile(bool cplx, int part, int k, int lm, int ln, int tm, int tn, int im_r, int im_c, int& r, int& c)
+{
+    if (cplx) {
+        r = lm + (k ? tm : 0);
+        c = ln + (k != part ? tn : 0);
+    } else {
+        r = lm + (part ? im_r : 0);
+        c = ln + (part ? im_c : 0);
+    }
+}
+
 // Persistent kernels (grid workgroups, a multiple of 8, each walking a list of tiles): the grid / 8 workgroups of a residue
 // class take the tiles of the class's run round-robin, i.e. in every round a class works on grid / 8 consecutive tiles of the
 // walk.  Workgroup block.x of grid.x owns the tile numbers first + i * step, i < count (count == 0: nothing to do).  A kernel
