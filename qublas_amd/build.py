@@ -10,8 +10,8 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["qg_api.hip", "qg_run.hip", "qg_pack.hip", "qg_combine_bd.hip", "qg_eltwise.hip", "qg_approx.hip", "qg_eltwise_bd.hip", "qg_eltwise_grp.hip", "qg_eltwise_cplx.hip", "qg_tree.hip", "qg_tree_fast.hip", "qg_tree64.hip", "qg_tree_cplx.hip", "qg_tree_rc.hip", "qg_gemv.hip", "qg_mfma.hip", "qg_mfma_ep_bd.hip", "qg_mfma_grp.hip", "qg_mfma_ep_grp.hip", "qg_mfma_pp.hip", "qg_mfma_ppl.hip", "qg_mfma_k6.hip", "qg_mfma_ring.hip", "qg_comm.hip", "qg_plan.cpp", "qg_geom.cpp"]
-HEADERS = ["qg_ops.h", "qg_forms.h", "qg_plan.h", "qg_kernels.h", "qg_geom.h", "qg_tile_walk.h", "qg_grp.h", "qg_mfma_tile.h", "qg_mfma_body.h", "qg_ring.h", "qg_step_all.h", "qg_tree_counter.h", "qg_tree_io.h", "qg_eltwise.h", "qg_eltwise_args.h", "qg_approx.h", "qg_approx_dev.h", "qg_bd_ep.h", "qg_grp_ep.h", "qg_cmul.h", "qg_fix.h", "qg_api_int.h", "qg_run_key.h", os.path.join("..", "..", "include", "qgemul.h")]
+SOURCES = ["qg_api.hip", "qg_run.hip", "qg_pack.hip", "qg_combine_bd.hip", "qg_eltwise.hip", "qg_approx.hip", "qg_eltwise_cplx.hip", "qg_tree.hip", "qg_tree_fast.hip", "qg_tree64.hip", "qg_tree_cplx.hip", "qg_tree_rc.hip", "qg_gemv.hip", "qg_mfma.hip", "qg_mfma_ep_bd.hip", "qg_mfma_grp.hip", "qg_mfma_ep_grp.hip", "qg_mfma_pp.hip", "qg_mfma_ppl.hip", "qg_mfma_k6.hip", "qg_mfma_ring.hip", "qg_comm.hip", "qg_plan.cpp", "qg_geom.cpp"]
+HEADERS = ["qg_ops.h", "qg_forms.h", "qg_plan.h", "qg_kernels.h", "qg_geom.h", "qg_tile_walk.h", "qg_grp.h", "qg_mfma_tile.h", "qg_member_forms.h", "qg_mfma_body.h", "qg_ring.h", "qg_step_all.h", "qg_tree_counter.h", "qg_tree_io.h", "qg_eltwise.h", "qg_eltwise_args.h", "qg_approx.h", "qg_approx_dev.h", "qg_cmul.h", "qg_fix.h", "qg_api_int.h", "qg_run_key.h", os.path.join("..", "..", "include", "qgemul.h")]
 # compile flags of every source (tools/isa_diff.py compiles with the same ones)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result", "-x", "hip"]
 LIB = os.path.join(HERE, "libqugemm.so")

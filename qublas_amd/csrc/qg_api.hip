@@ -639,25 +639,38 @@ static int ep_args_ok(const qgemul_plan* p, const qgemul_ep_args* args)
     return QG_OK;
 }
 
-// the plan's chain as ONE linear pass: packed C (the kernel's own layout and container, pc_c) -> packed D
-static int run_chain_pass(qgemul_plan* p, const void* packedC, void* packedD, const QEpArgs& a, const qgemul_ep_args* args)
+// a chain as ONE linear pass over n elements: packed C (cbytes containers) -> packed D
+static QEltwiseArgs chain_pass_args(const void* packedC, void* packedD, int64_t n, int cbytes, const QEpTable& t, const QEpArgs& a)
 {
-    hipStream_t st = p->ctx->stream;
     QEltwiseArgs g;
     memset(&g, 0, sizeof g);
     g.C = (const char*)packedC;
     g.D = (char*)packedD;
-    g.n = p->pc_c.Mp * p->pc_c.Np;
-    g.cbytes = p->pc_c.cbytes;
-    g.t = p->ept;
+    g.n = n;
+    g.cbytes = cbytes;
+    g.t = t;
     g.a = a;
+    return g;
+}
+
+// ... with APPROX stages: the tables of `owner` (the plan that analysed the chain), the form choice of the caller's plan
+static QApproxArgs approx_pass_args(const QEltwiseArgs& g, const qgemul_plan* owner, uint32_t flags)
+{
+    QApproxArgs x;
+    memset(&x, 0, sizeof x);
+    x.g = g;
+    for (int k = 0; k < QG_MAX_EW; ++k) x.ax[k] = owner->ax_dev[k];
+    x.force_general = (flags & QG_OPT_APPROX_GENERAL) ? 1 : 0;   // result-identical form choice (include/qgemul.h)
+    return x;
+}
+
+// the plan's chain as ONE linear pass: packed C (the kernel's own layout and container, pc_c) -> packed D
+static int run_chain_pass(qgemul_plan* p, const void* packedC, void* packedD, const QEpArgs& a, const qgemul_ep_args* args)
+{
+    hipStream_t st = p->ctx->stream;
+    QEltwiseArgs g = chain_pass_args(packedC, packedD, p->pc_c.Mp * p->pc_c.Np, p->pc_c.cbytes, p->ept, a);
     if (p->has_ax) {
-        QApproxArgs x;
-        memset(&x, 0, sizeof x);
-        x.g = g;
-        for (int k = 0; k < QG_MAX_EW; ++k) x.ax[k] = p->ax_dev[k];
-        x.force_general = (p->flags & QG_OPT_APPROX_GENERAL) ? 1 : 0;   // result-identical form choice (include/qgemul.h)
-        QG_HIP(qg_launch_approx(x, st));
+        QG_HIP(qg_launch_approx(approx_pass_args(g, p, p->flags), st));
         return QG_OK;
     }
     if (p->has_cmul) {
@@ -1079,14 +1092,17 @@ int qgemul_export_bitstream(qgemul_plan* p, const void* packedC, int tensor_chun
     return QG_OK;
 }
 
+// the plan a timing entry point is for (a batched plan's chain is told by the plan; a grouped plan's by the entry point)
+enum TimedPlan { TIMED_PLAIN, TIMED_BATCHED, TIMED_GROUPED, TIMED_GROUPED_EP };
+
 static int time_execute(qgemul_plan* p, void* packedC, const void* packedA, const void* packedB, const qgemul_ep_args* args,
-                        int warmup, int iters, float* avg_ms, int kind = 0)   // kind: 0 a plain plan, 1 a batched one, 2 a grouped one, 3 a grouped one with a chain
+                        int warmup, int iters, float* avg_ms, TimedPlan kind = TIMED_PLAIN)
 {
-    const bool batched = kind == 1;
-    if (!p || !avg_ms || iters < 1 || (kind >= 2 ? !p->grp : (p->batch != 0) != batched)) return QG_EINVAL;
+    const bool batched = kind == TIMED_BATCHED, grouped = kind == TIMED_GROUPED || kind == TIMED_GROUPED_EP;
+    if (!p || !avg_ms || iters < 1 || (grouped ? !p->grp : (p->batch != 0) != batched)) return QG_EINVAL;
     return time_calls(p, warmup, iters, avg_ms, [&] {
-        if (kind == 3) return qgemul_execute_grouped_ep(p, packedC, packedA, packedB, args);
-        if (kind == 2) return qgemul_execute_grouped(p, packedC, packedA, packedB);
+        if (kind == TIMED_GROUPED_EP) return qgemul_execute_grouped_ep(p, packedC, packedA, packedB, args);
+        if (kind == TIMED_GROUPED) return qgemul_execute_grouped(p, packedC, packedA, packedB);
         if (batched) return p->has_ep ? qgemul_execute_batched_ep(p, packedC, packedA, packedB, args) : qgemul_execute_batched(p, packedC, packedA, packedB);
         return p->has_ep ? qgemul_execute_ep(p, packedC, packedA, packedB, args) : qgemul_execute(p, packedC, packedA, packedB);
     });
@@ -1287,7 +1303,7 @@ int qgemul_execute_batched(qgemul_plan* p, void* packedC, const void* packedA, c
 int qgemul_time_execute_batched(qgemul_plan* p, void* packedC, const void* packedA, const void* packedB, int warmup, int iters, float* avg_ms)
 {
     if (p && p->has_ep) return QG_EINVAL;
-    return time_execute(p, packedC, packedA, packedB, nullptr, warmup, iters, avg_ms, true);
+    return time_execute(p, packedC, packedA, packedB, nullptr, warmup, iters, avg_ms, TIMED_BATCHED);
 }
 
 int qgemul_time_execute_batched_launch(qgemul_plan* p, void* packedC, const void* packedA, const void* packedB, int launch, int warmup, int iters, float* avg_ms)
@@ -1384,29 +1400,14 @@ int qgemul_execute_batched_ep(qgemul_plan* p, void* packedD, const void* packedA
     // TWO launches: the block-diagonal kernel as it is into the plan's packed C of the whole stack, then ONE pass over the stack
     const QMfmaArgs a = bd_mfma_args(p, p->cwork, packedA, packedB, p->pc_c.cbytes);
     QG_HIP(qg_launch_mfma_bd(p->LA, p->LB, a, p->batch, st));
-    QEltwiseArgs g;
-    memset(&g, 0, sizeof g);
-    g.C = (const char*)p->cwork;
-    g.D = (char*)packedD;
-    g.n = p->batch * be.msize;
-    g.cbytes = p->pc_c.cbytes;
-    g.t = p->ept;
-    g.a = ea;
+    const QEltwiseArgs g = chain_pass_args(p->cwork, packedD, p->batch * be.msize, p->pc_c.cbytes, p->ept, ea);
     if (p->has_ax) {
-        QApproxBdArgs x;
-        memset(&x, 0, sizeof x);
-        x.x.g = g;
-        for (int k = 0; k < QG_MAX_EW; ++k) x.x.ax[k] = m->ax_dev[k];
-        x.x.force_general = (p->flags & QG_OPT_APPROX_GENERAL) ? 1 : 0;
-        x.bd = be;
+        const QApproxBdArgs x = {approx_pass_args(g, p->member, p->flags), be};
         QG_HIP(qg_launch_approx_bd(x, st));
-        return QG_OK;
+    } else {
+        const QEltwiseBdArgs e = {g, be};
+        QG_HIP(qg_launch_eltwise_bd(e, st));
     }
-    QEltwiseBdArgs e;
-    memset(&e, 0, sizeof e);
-    e.g = g;
-    e.bd = be;
-    QG_HIP(qg_launch_eltwise_bd(e, st));
     return QG_OK;
 }
 
@@ -1414,7 +1415,7 @@ int qgemul_time_execute_batched_ep(qgemul_plan* p, void* packedD, const void* pa
                                    float* avg_ms)
 {
     if (!p || !p->has_ep) return QG_EINVAL;
-    return time_execute(p, packedD, packedA, packedB, args, warmup, iters, avg_ms, true);
+    return time_execute(p, packedD, packedA, packedB, args, warmup, iters, avg_ms, TIMED_BATCHED);
 }
 
 
@@ -1568,6 +1569,20 @@ int qgemul_unpack_c_grouped(qgemul_plan* p, const void* packed_dev, void* const*
     return QG_OK;
 }
 
+// the grouped launch's uniform arguments (what every workgroup shares: the launch key's variant and conversion into C, the stacks'
+// plane masks and row sums) and the schedule; cbytes: the container the kernel stores
+static QMfmaGrpArgs grp_mfma_args(const QGrouped* G, void* packedC, const void* packedA, const void* packedB, int cbytes)
+{
+    const QPlanGeom& k = G->ug[G->key];
+    QMfmaGrpArgs a;
+    memset((void*)&a, 0, sizeof a);
+    (QMfmaArgs&)a = mfma_args(G->sa, G->sb, k.variant, packedA, packedB, packedC, cbytes);
+    a.to_c = k.an.lin.to_c[0];
+    centre_args(a, G->sa, G->sb, packedA, packedB, 0);
+    a.tiles = G->tiles_dev;
+    return a;
+}
+
 int qgemul_execute_grouped(qgemul_plan* p, void* packedC, const void* packedA, const void* packedB)
 {
     if (!p || !p->grp || !packedC || !packedA || !packedB) return QG_EINVAL;
@@ -1576,13 +1591,7 @@ int qgemul_execute_grouped(qgemul_plan* p, void* packedC, const void* packedA, c
     if (G->n_tiles > 0) {
         QG_ON_DEVICE(p->ctx);
         const QPlanGeom& k = G->ug[G->key];
-        QMfmaGrpArgs a;
-        memset((void*)&a, 0, sizeof a);
-        (QMfmaArgs&)a = mfma_args(G->sa, G->sb, k.variant, packedA, packedB, packedC, k.pc.cbytes);
-        a.to_c = k.an.lin.to_c[0];
-        centre_args(a, G->sa, G->sb, packedA, packedB, 0);
-        a.tiles = G->tiles_dev;
-        QG_HIP(qg_launch_mfma_grp(k.LA, k.LB, a, G->n_tiles, p->ctx->stream));
+        QG_HIP(qg_launch_mfma_grp(k.LA, k.LB, grp_mfma_args(G, packedC, packedA, packedB, k.pc.cbytes), G->n_tiles, p->ctx->stream));
     }
     for (int64_t g = 0; g < G->groups; ++g) {
         const QGrpMember& m = G->m[g];
@@ -1595,7 +1604,7 @@ int qgemul_execute_grouped(qgemul_plan* p, void* packedC, const void* packedA, c
 
 int qgemul_time_execute_grouped(qgemul_plan* p, void* packedC, const void* packedA, const void* packedB, int warmup, int iters, float* avg_ms)
 {
-    return time_execute(p, packedC, packedA, packedB, nullptr, warmup, iters, avg_ms, 2);
+    return time_execute(p, packedC, packedA, packedB, nullptr, warmup, iters, avg_ms, TIMED_GROUPED);
 }
 
 // ---- element-wise chains on grouped plans (include/qgemul.h): member g is Qgemul<...>(C_g, A_g, B_g) followed by the chain ----
@@ -1697,12 +1706,7 @@ int qgemul_execute_grouped_ep(qgemul_plan* p, void* packedD, const void* packedA
         for (int s = 0; s < p->ept.n; ++s)
             if (G->per_member[s]) ge.scal[s] = G->scal_dev[s];
         // the launch's uniform arguments: those of qgemul_execute_grouped, with the kernel's own C container
-        QMfmaGrpArgs a;
-        memset((void*)&a, 0, sizeof a);
-        (QMfmaArgs&)a = mfma_args(G->sa, G->sb, k.variant, packedA, packedB, G->fused ? packedD : G->cwork_dev, k.pc_c.cbytes);
-        a.to_c = k.an.lin.to_c[0];
-        centre_args(a, G->sa, G->sb, packedA, packedB, 0);
-        a.tiles = G->tiles_dev;
+        const QMfmaGrpArgs a = grp_mfma_args(G, G->fused ? packedD : G->cwork_dev, packedA, packedB, k.pc_c.cbytes);
         if (G->fused) {
             // ONE launch: the grouped kernel's epilogue runs the chain on the value it has just converted into C's type
             QMfmaEpGrpArgs f;
@@ -1717,29 +1721,12 @@ int qgemul_execute_grouped_ep(qgemul_plan* p, void* packedD, const void* packedA
         } else {
             // TWO launches: the grouped kernel as it is into the plan's packed C of the launch, then ONE pass over its tiles into D
             QG_HIP(qg_launch_mfma_grp(k.LA, k.LB, a, G->n_tiles, st));
-            QEltwiseArgs g;
-            memset(&g, 0, sizeof g);
-            g.C = (const char*)G->cwork_dev;
-            g.D = (char*)packedD;
-            g.n = G->launch_elems;
-            g.cbytes = k.pc_c.cbytes;
-            g.t = k.ept;
-            g.a = ea;
+            const QEltwiseArgs g = chain_pass_args(G->cwork_dev, packedD, G->launch_elems, k.pc_c.cbytes, k.ept, ea);
             if (G->has_ax) {
-                QApproxGrpArgs x;
-                memset(&x, 0, sizeof x);
-                x.x.g = g;
-                for (int s = 0; s < QG_MAX_EW; ++s) x.x.ax[s] = G->up[G->key]->ax_dev[s];
-                x.x.force_general = (p->flags & QG_OPT_APPROX_GENERAL) ? 1 : 0;
-                x.tile_member = G->tile_member_dev;
-                x.ge = ge;
+                const QApproxGrpArgs x = {approx_pass_args(g, G->up[G->key], p->flags), G->tile_member_dev, ge};
                 QG_HIP(qg_launch_approx_grp(x, st));
             } else {
-                QEltwiseGrpArgs e;
-                memset(&e, 0, sizeof e);
-                e.g = g;
-                e.tile_member = G->tile_member_dev;
-                e.ge = ge;
+                const QEltwiseGrpArgs e = {g, G->tile_member_dev, ge};
                 QG_HIP(qg_launch_eltwise_grp(e, st));
             }
         }
@@ -1764,7 +1751,7 @@ int qgemul_time_execute_grouped_ep(qgemul_plan* p, void* packedD, const void* pa
                                    float* avg_ms)
 {
     if (!p || !p->grp || !p->grp->has_ep) return QG_EINVAL;
-    return time_execute(p, packedD, packedA, packedB, args, warmup, iters, avg_ms, 3);
+    return time_execute(p, packedD, packedA, packedB, args, warmup, iters, avg_ms, TIMED_GROUPED_EP);
 }
 
 } // extern "C"

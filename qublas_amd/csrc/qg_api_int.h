@@ -16,8 +16,6 @@
 #include "qg_plan.h"
 #include "qg_approx.h"
 #include "qg_cmul.h"
-#include "qg_bd_ep.h"
-#include "qg_grp_ep.h"
 #include "qg_run_key.h"
 
 #define QG_INTERNAL __attribute__((visibility("hidden")))

@@ -39,6 +39,18 @@ struct QApproxArgs {
     const QApproxTable* ax[QG_MAX_EW];   // device pointers; nullptr for the plain stages
     int32_t force_general, pad_;         // QG_OPT_APPROX_GENERAL: uniform tables run the general form too
 };
+// ... over the stack of a batched plan and over the launch of a grouped plan (QEltwiseBdArgs, QEltwiseGrpArgs: qg_eltwise_args.h)
+struct QApproxBdArgs {
+    QApproxArgs x;
+    QBdEp bd;
+};
+struct QApproxGrpArgs {
+    QApproxArgs x;
+    const int32_t* tile_member;
+    QGrpEp ge;
+};
 #if defined(__HIPCC__)
 hipError_t qg_launch_approx(const QApproxArgs& a, hipStream_t st);
+hipError_t qg_launch_approx_bd(const QApproxBdArgs& a, hipStream_t st);
+hipError_t qg_launch_approx_grp(const QApproxGrpArgs& a, hipStream_t st);
 #endif

@@ -27,18 +27,10 @@ namespace {
 
 static_assert(offsetof(QApproxTable, coef) == offsetof(QApproxTable, thr) + sizeof(int64_t) * QG_MAX_SEG, "thr and coef are copied to LDS as one block");
 
-__device__ __forceinline__ void store_one(char* dst, int64_t idx, int bytes, int64_t v)
-{
-    switch (bytes) {
-    case 1: ((int8_t*)dst)[idx] = (int8_t)v; break;
-    case 2: ((int16_t*)dst)[idx] = (int16_t)v; break;
-    case 4: ((int32_t*)dst)[idx] = (int32_t)v; break;
-    default: ((int64_t*)dst)[idx] = v; break;
-    }
-}
-
-template <class T>
-__global__ __launch_bounds__(256) void k_approx(QApproxArgs a)
+// the pass in k_eltwise's three framings (qg_eltwise.hip: eltwise_pass): src_of(i0) is the lane's operand source, TAIL: n need not be
+// a multiple of 16
+template <class T, bool TAIL, class SrcOf>
+__device__ __forceinline__ void approx_pass(const QApproxArgs& a, SrcOf src_of)
 {
     __shared__ int64_t tabs[QG_MAX_EW][QG_APPROX_LDS_WORDS];
     const QEltwiseArgs& g = a.g;
@@ -49,9 +41,10 @@ __global__ __launch_bounds__(256) void k_approx(QApproxArgs a)
     }
     __syncthreads();
     const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 16;
-    if (i0 >= g.n) return;
-    const bool full = i0 + 16 <= g.n;
+    if (TAIL ? i0 >= g.n : i0 + 16 > g.n) return;
+    const bool full = !TAIL || i0 + 16 <= g.n;
     const int cnt = full ? 16 : (int)(g.n - i0);
+    const auto src = src_of(i0);
     T v[16];
     load16<T>(g.C, i0, g.cbytes, full, cnt, v);
     for (int k = 0; k < g.t.n; ++k) {
@@ -64,9 +57,12 @@ __global__ __launch_bounds__(256) void k_approx(QApproxArgs a)
         T e[16];
         if (s.scalar) {
 #pragma unroll
-            for (int o = 0; o < 16; ++o) e[o] = (T)g.a.scalar[k];
+            for (int o = 0; o < 16; ++o) e[o] = (T)src.scalar(k);
+        } else if (TAIL && !full) {   // (a tail: one GEMM's packed C, no member)
+            load16<T>(g.a.e[k], i0, s.ebytes, false, cnt, e);
         } else {
-            load16<T>(g.a.e[k], i0, s.ebytes, full, cnt, e);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) src.template run<T>(k, q, s.ebytes, e + 4 * q);
         }
         qg_ep_stage<T, 16>(v, e, s);
     }
@@ -78,7 +74,58 @@ __global__ __launch_bounds__(256) void k_approx(QApproxArgs a)
     }
 #pragma unroll
     for (int o = 0; o < 16; ++o)
-        if (o < cnt) store_one(g.D, i0 + o, g.t.dbytes, (int64_t)v[o]);
+        if (o < cnt) qg_ep_store_one(g.D, i0 + o, g.t.dbytes, (int64_t)v[o]);
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void k_approx(QApproxArgs a)
+{
+    approx_pass<T, true>(a, [&](int64_t i0) { return qg_pass_src(a.g, i0); });
+}
+// (the stack form keeps the body it had, instruction for instruction: as approx_pass with the stack's source its code differed and its
+// pass measured up to 1.3 % over the former build's on 256 and 1024 members of 64^3, beyond the spread of the repetitions.  Two of
+// those points stay 1 % over with this body as well — profiles/ep_member_forms_ab.jsonl — so the shared body is not shown to be the cause)
+template <class T>
+__global__ __launch_bounds__(256) void k_approx_bd(QApproxBdArgs a)
+{
+    __shared__ int64_t tabs[QG_MAX_EW][QG_APPROX_LDS_WORDS];
+    const QEltwiseArgs& g = a.x.g;
+    for (int k = 0; k < g.t.n; ++k) {   // (approx_pass's table copy, written out here too: as a shared function it moved four instructions in every approx kernel)
+        if (!a.x.ax[k]) continue;
+        const int64_t* src = a.x.ax[k]->thr;
+        for (int i = threadIdx.x; i < QG_APPROX_LDS_WORDS; i += 256) tabs[k][i] = src[i];
+    }
+    __syncthreads();
+    const int64_t w0 = (int64_t)blockIdx.x * 4096;
+    const int64_t member_off = w0 / a.bd.msize * a.bd.msize;
+    const int64_t i0 = w0 + (int64_t)threadIdx.x * 16;
+    if (i0 + 16 > g.n) return;
+    T v[16];
+    load16<T>(g.C, i0, g.cbytes, true, 16, v);
+    for (int k = 0; k < g.t.n; ++k) {
+        const QEpStage& s = g.t.st[k];
+        if (s.op == QG_EW_APPROX) {
+            approx_stage<T>(v, a.x.ax[k], tabs[k], a.x.force_general || !a.x.ax[k]->uniform);
+            qg_step_all<T, 16>(v, s.cvt);
+            continue;
+        }
+        T e[16];
+        if (s.scalar) {
+#pragma unroll
+            for (int o = 0; o < 16; ++o) e[o] = (T)g.a.scalar[k];
+        } else {
+            load16<T>(g.a.e[k], ((a.bd.shared >> k) & 1u) ? i0 - member_off : i0, s.ebytes, true, 16, e);
+        }
+        qg_ep_stage<T, 16>(v, e, s);
+    }
+    qg_step_all<T, 16>(v, g.t.to_d);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) qg_ep_store_run<T>(g.D, i0 + 4 * q, g.t.dbytes, v + 4 * q);
+}
+template <class T>
+__global__ __launch_bounds__(256) void k_approx_grp(QApproxGrpArgs a)
+{
+    approx_pass<T, false>(a.x, [&](int64_t) { return qg_pass_src(a.x.g, a.ge, a.tile_member); });
 }
 
 } // namespace
@@ -90,5 +137,25 @@ hipError_t qg_launch_approx(const QApproxArgs& a, hipStream_t st)
     if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
     if (a.g.t.bits32) hipLaunchKernelGGL(k_approx<int32_t>, dim3((unsigned)blocks), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(k_approx<int64_t>, dim3((unsigned)blocks), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t qg_launch_approx_bd(const QApproxBdArgs& a, hipStream_t st)
+{
+    const int64_t n = a.x.g.n;
+    if (n <= 0) return hipSuccess;
+    if (!qg_pass_stack_ok(n, a.bd)) return hipErrorInvalidValue;
+    if (a.x.g.t.bits32) hipLaunchKernelGGL(k_approx_bd<int32_t>, dim3((unsigned)(n / 4096)), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_approx_bd<int64_t>, dim3((unsigned)(n / 4096)), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t qg_launch_approx_grp(const QApproxGrpArgs& a, hipStream_t st)
+{
+    const int64_t n = a.x.g.n;
+    if (n <= 0) return hipSuccess;
+    if (!qg_pass_launch_ok(n, a.tile_member)) return hipErrorInvalidValue;
+    if (a.x.g.t.bits32) hipLaunchKernelGGL(k_approx_grp<int32_t>, dim3((unsigned)(n / 4096)), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_approx_grp<int64_t>, dim3((unsigned)(n / 4096)), dim3(256), 0, st, a);
     return hipGetLastError();
 }

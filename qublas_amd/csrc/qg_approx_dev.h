@@ -1,5 +1,5 @@
-// qg_approx_dev.h — device pieces of the passes that run chains with an APPROX stage: k_approx (qg_approx.hip) and its
-// block-diagonal form k_approx_bd (qg_eltwise_bd.hip).  The stage itself is described in qg_approx.hip.
+// qg_approx_dev.h — device pieces of the pass that runs chains with an APPROX stage (qg_approx.hip: k_approx and its member forms
+// k_approx_bd, k_approx_grp), where the stage itself is described.
 #pragma once
 #include "qg_approx.h"
 #include "qg_eltwise.h"

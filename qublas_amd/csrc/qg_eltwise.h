@@ -80,67 +80,72 @@ __device__ __forceinline__ void qg_ep_stage(T (&v)[N], const T (&e)[N], const QE
     qg_step_all<T, N>(v, s.cvt);
 }
 
-// the whole chain on NR runs of 4 consecutive packed elements; run q starts at element index idx0 + q * stride
+// Where a stage's operand comes from.  The stage loop below asks a source two things: stage k's scalar, and run q (4 consecutive
+// packed elements) of stage k's tensor operand.  There are three, one per launch form; a fourth form (say, members addressed through a
+// pointer table) is a fourth struct here with the same two members, and neither the loop nor the stages change.
+//
+// ONE GEMM: the index as given, run q at idx0 + q * stride; the call-wide scalar.
+struct QEpSrcOne {
+    const QEpArgs& a;
+    int64_t idx0, stride;
+    __device__ __forceinline__ int64_t scalar(int k) const { return a.scalar[k]; }
+    template <class T>
+    __device__ __forceinline__ void run(int k, int q, int ebytes, T* out) const { qg_ep_load_run<4, T>(a.e[k], idx0 + q * stride, ebytes, out); }
+};
+// A MEMBER OF A STACK (the block-diagonal forms of a batched plan; QBdEp): idx0 runs over the whole stack; stage k's tensor operand is
+// read there too unless bit k of `shared` is set: a shared operand is one member's tensor, read `member_off` elements lower
+struct QEpSrcStack {
+    const QEpArgs& a;
+    int64_t idx0, stride, member_off;
+    uint32_t shared;
+    __device__ __forceinline__ int64_t scalar(int k) const { return a.scalar[k]; }
+    template <class T>
+    __device__ __forceinline__ void run(int k, int q, int ebytes, T* out) const
+    {
+        const int64_t i0 = ((shared >> k) & 1u) ? idx0 - member_off : idx0;
+        qg_ep_load_run<4, T>(a.e[k], i0 + q * stride, ebytes, out);
+    }
+};
+// A MEMBER OF A GROUPED LAUNCH (QGrpEp): the element index runs over the whole launch, as D and every tensor operand do, and comes in
+// two parts: ubase, wave-uniform (the workgroup's tile), which goes into the operand's base pointer, and the lane's 32-bit index lane0
+// behind it; run q starts at lane0 + q * stride.  A scalar stage with a table takes the table's entry of `member` (wave-uniform, like
+// the table pointer: a scalar load)
+struct QEpSrcGroup {
+    const QEpArgs& a;
+    int64_t ubase;
+    uint32_t lane0, stride;
+    const QGrpEp& ge;
+    int member;
+    __device__ __forceinline__ int64_t scalar(int k) const
+    {
+        const int64_t* tab = ge.scal[k];
+        const int64_t raw = tab ? tab[member] : a.scalar[k];
+        // (wave-uniform by construction; said so, so that the value lives in scalar registers like a call-wide scalar does)
+        return (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(raw >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)raw));
+    }
+    template <class T>
+    __device__ __forceinline__ void run(int k, int q, int ebytes, T* out) const
+    {
+        // (the lane's BYTE offset in 32 bits as well: one register per run instead of a 64-bit pair per run and container)
+        const char* p = a.e[k] + ubase * ebytes;
+        qg_ep_load_run<4, T>(p + (lane0 + q * stride) * (uint32_t)ebytes, 0, ebytes, out);
+    }
+};
+
+// the whole chain on NR runs of 4 consecutive packed elements, the operands from `src`.  (The operand is fetched here, in the loop's
+// own body, and src is taken by reference: as a function of its own the fetch moved the instruction streams of the fused MFMA kernels.)
 // T = int32_t when the planner has bounded the whole chain by 32 bits (QEpTable::bits32), else int64_t
-template <class T, int NR>
-__device__ __forceinline__ void qg_ep_apply_runs(T (&v)[4 * NR], const QEpTable& t, const QEpArgs& a, int64_t idx0, int64_t stride)
+template <class T, int NR, class Src>
+__device__ __forceinline__ void qg_ep_apply_runs(T (&v)[4 * NR], const QEpTable& t, const Src& src)
 {
     for (int k = 0; k < t.n; ++k) {
         T e[4 * NR];
         if (t.st[k].scalar) {
 #pragma unroll
-            for (int o = 0; o < 4 * NR; ++o) e[o] = (T)a.scalar[k];
+            for (int o = 0; o < 4 * NR; ++o) e[o] = (T)src.scalar(k);
         } else {
 #pragma unroll
-            for (int q = 0; q < NR; ++q) qg_ep_load_run<4, T>(a.e[k], idx0 + q * stride, t.st[k].ebytes, e + 4 * q);
-        }
-        qg_ep_stage<T, 4 * NR>(v, e, t.st[k]);
-    }
-    qg_step_all<T, 4 * NR>(v, t.to_d);
-}
-
-// ... in the block-diagonal forms of a batched plan (QBdEp, qg_kernels.h): idx0 runs over the whole stack; stage k's tensor operand
-// is read there too unless bit k of `shared` is set: a shared operand is one member's tensor, read `member_off` elements lower
-template <class T, int NR>
-__device__ __forceinline__ void qg_ep_apply_runs_bd(T (&v)[4 * NR], const QEpTable& t, const QEpArgs& a, int64_t idx0, int64_t stride, int64_t member_off, uint32_t shared)
-{
-    for (int k = 0; k < t.n; ++k) {
-        T e[4 * NR];
-        if (t.st[k].scalar) {
-#pragma unroll
-            for (int o = 0; o < 4 * NR; ++o) e[o] = (T)a.scalar[k];
-        } else {
-            const int64_t i0 = ((shared >> k) & 1u) ? idx0 - member_off : idx0;
-#pragma unroll
-            for (int q = 0; q < NR; ++q) qg_ep_load_run<4, T>(a.e[k], i0 + q * stride, t.st[k].ebytes, e + 4 * q);
-        }
-        qg_ep_stage<T, 4 * NR>(v, e, t.st[k]);
-    }
-    qg_step_all<T, 4 * NR>(v, t.to_d);
-}
-
-// ... of a grouped plan (QGrpEp, qg_eltwise_args.h): the element index runs over the whole launch, as D and every tensor operand do, and
-// comes in two parts: ubase, wave-uniform (the workgroup's tile), which goes into the operand's base pointer, and the lane's 32-bit
-// index lane0 behind it; run q starts at lane0 + q * stride.  A scalar stage with a table takes the table's entry of `member`
-// (wave-uniform, like the table pointer: a scalar load)
-template <class T, int NR>
-__device__ __forceinline__ void qg_ep_apply_runs_grp(T (&v)[4 * NR], const QEpTable& t, const QEpArgs& a, int64_t ubase, uint32_t lane0, uint32_t stride, const QGrpEp& ge, int member)
-{
-    for (int k = 0; k < t.n; ++k) {
-        T e[4 * NR];
-        if (t.st[k].scalar) {
-            const int64_t* tab = ge.scal[k];
-            const int64_t raw = tab ? tab[member] : a.scalar[k];
-            // (wave-uniform by construction; said so, so that the value lives in scalar registers like a call-wide scalar does)
-            const int64_t sc = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(raw >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)raw));
-#pragma unroll
-            for (int o = 0; o < 4 * NR; ++o) e[o] = (T)sc;
-        } else {
-            // (the lane's BYTE offset in 32 bits as well: one register per run instead of a 64-bit pair per run and container)
-            const uint32_t eb = (uint32_t)t.st[k].ebytes;
-            const char* p = a.e[k] + ubase * t.st[k].ebytes;
-#pragma unroll
-            for (int q = 0; q < NR; ++q) qg_ep_load_run<4, T>(p + (lane0 + q * stride) * eb, 0, t.st[k].ebytes, e + 4 * q);
+            for (int q = 0; q < NR; ++q) src.template run<T>(k, q, t.st[k].ebytes, e + 4 * q);
         }
         qg_ep_stage<T, 4 * NR>(v, e, t.st[k]);
     }
@@ -168,4 +173,31 @@ __device__ __forceinline__ void qg_ep_store_run(char* D, int64_t idx, int bytes,
         break;
     }
     }
+}
+
+__device__ __forceinline__ void qg_ep_store_one(char* dst, int64_t idx, int bytes, int64_t v)
+{
+    switch (bytes) {
+    case 1: ((int8_t*)dst)[idx] = (int8_t)v; break;
+    case 2: ((int16_t*)dst)[idx] = (int16_t)v; break;
+    case 4: ((int32_t*)dst)[idx] = (int32_t)v; break;
+    default: ((int64_t*)dst)[idx] = v; break;
+    }
+}
+
+// The sources of the stand-alone passes (qg_eltwise.hip, qg_approx.hip): 4096 consecutive elements per workgroup, 16 per lane from
+// i0 = blockIdx.x * 4096 + threadIdx.x * 16 on, 4 runs of 4.  What differs is how a workgroup finds its member:
+// no member at all (one GEMM's packed C)
+__device__ __forceinline__ QEpSrcOne qg_pass_src(const QEltwiseArgs& g, int64_t i0) { return QEpSrcOne{g.a, i0, 4}; }
+// a stack: a member's packed C is a whole number of 64 x 64 tiles = of workgroups, so a workgroup never straddles two members and its
+// member is the quotient (blockIdx.x * 4096) / msize, wave-uniform
+__device__ __forceinline__ QEpSrcStack qg_pass_src(const QEltwiseArgs& g, const QBdEp& bd, int64_t i0)
+{
+    return QEpSrcStack{g.a, i0, 4, (int64_t)blockIdx.x * 4096 / bd.msize * bd.msize, bd.shared};
+}
+// a grouped launch: the members differ in size, so the member is entry blockIdx.x of the plan's tile -> member table (qg_grp.h:
+// qg_grp_tile_members), a wave-uniform load; nothing per lane depends on the member
+__device__ __forceinline__ QEpSrcGroup qg_pass_src(const QEltwiseArgs& g, const QGrpEp& ge, const int32_t* tile_member)
+{
+    return QEpSrcGroup{g.a, (int64_t)blockIdx.x * 4096, threadIdx.x * 16u, 4, ge, tile_member[blockIdx.x]};
 }

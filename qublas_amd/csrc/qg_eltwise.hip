@@ -4,6 +4,11 @@
 //    (the exact tree kernels).  C, the tensor operands and D share ONE index space (the plan's packed-C layout),
 //    so the pass is linear in memory: every lane handles 16 consecutive elements.  HBM-bound:
 //    (cbytes + sum ebytes + dbytes) bytes per element.
+//  * k_eltwise_bd, k_eltwise_grp: the same pass over the whole stack of a batched plan and over the launch of a grouped plan.  The
+//    block-diagonal / grouped GEMM launch (k_mfma_bd, k_mfma_grp) leaves the members' packed Cs back to back, and D and every
+//    per-member tensor operand have the same layout, so the pass stays linear in memory; a workgroup (4096 elements = one 64 x 64
+//    tile) belongs to one member, and only the operand source (qg_eltwise.h) knows of members.  There is no tail: the element count
+//    is a multiple of 4096 (the launchers check it).  The three kernels are one body, eltwise_pass.
 //  * k_pack_e: a tensor operand in reference layout (column-major M x N, QuBLAS.h:2680-2692) -> that index space
 //    (one launch per part of a complex operand).
 #include <hip/hip_runtime.h>
@@ -13,37 +18,28 @@
 
 namespace {
 
-__device__ __forceinline__ void store_one(char* dst, int64_t idx, int bytes, int64_t v)
+template <class T, class Src>
+__device__ __forceinline__ void chain16(const QEltwiseArgs& g, int64_t i0, const Src& src)
 {
-    switch (bytes) {
-    case 1: ((int8_t*)dst)[idx] = (int8_t)v; break;
-    case 2: ((int16_t*)dst)[idx] = (int16_t)v; break;
-    case 4: ((int32_t*)dst)[idx] = (int32_t)v; break;
-    default: ((int64_t*)dst)[idx] = v; break;
-    }
+    T v[16];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) qg_ep_load_run<4, T>(g.C, i0 + 4 * q, g.cbytes, v + 4 * q);
+    qg_ep_apply_runs<T, 4>(v, g.t, src);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) qg_ep_store_run<T>(g.D, i0 + 4 * q, g.t.dbytes, v + 4 * q);
 }
 
-__global__ __launch_bounds__(256) void k_eltwise(QEltwiseArgs g)
+// the pass: src_of(i0) is the lane's operand source (qg_pass_src, qg_eltwise.h: how the workgroup finds its member); TAIL: n need not
+// be a multiple of 16 (one GEMM's packed C; the member forms cover whole tiles)
+template <bool TAIL, class SrcOf>
+__device__ __forceinline__ void eltwise_pass(const QEltwiseArgs& g, SrcOf src_of)
 {
     // 16 consecutive elements per lane (4 runs of 4): enough independent loads in flight per lane for 1-byte containers too
     const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 16;
-    if (i0 >= g.n) return;
-    if (i0 + 16 <= g.n) {
-        if (g.t.bits32) {
-            int32_t v[16];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) qg_ep_load_run<4, int32_t>(g.C, i0 + 4 * q, g.cbytes, v + 4 * q);
-            qg_ep_apply_runs<int32_t, 4>(v, g.t, g.a, i0, 4);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) qg_ep_store_run<int32_t>(g.D, i0 + 4 * q, g.t.dbytes, v + 4 * q);
-        } else {
-            int64_t v[16];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) qg_ep_load_run<4, int64_t>(g.C, i0 + 4 * q, g.cbytes, v + 4 * q);
-            qg_ep_apply_runs<int64_t, 4>(v, g.t, g.a, i0, 4);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) qg_ep_store_run<int64_t>(g.D, i0 + 4 * q, g.t.dbytes, v + 4 * q);
-        }
+    if (TAIL ? i0 >= g.n : i0 + 16 > g.n) return;
+    if (!TAIL || i0 + 16 <= g.n) {
+        if (g.t.bits32) chain16<int32_t>(g, i0, src_of(i0));
+        else chain16<int64_t>(g, i0, src_of(i0));
         return;
     }
     for (int64_t i = i0; i < g.n; ++i) {   // tail of a packed C whose size is not a multiple of 16
@@ -53,8 +49,21 @@ __global__ __launch_bounds__(256) void k_eltwise(QEltwiseArgs g)
             qg_ep_stage<int64_t, 1>(v, e, g.t.st[k]);
         }
         qg_step_all<int64_t, 1>(v, g.t.to_d);
-        store_one(g.D, i, g.t.dbytes, v[0]);
+        qg_ep_store_one(g.D, i, g.t.dbytes, v[0]);
     }
+}
+
+__global__ __launch_bounds__(256) void k_eltwise(QEltwiseArgs g)
+{
+    eltwise_pass<true>(g, [&](int64_t i0) { return qg_pass_src(g, i0); });
+}
+__global__ __launch_bounds__(256) void k_eltwise_bd(QEltwiseBdArgs a)
+{
+    eltwise_pass<false>(a.g, [&](int64_t i0) { return qg_pass_src(a.g, a.bd, i0); });
+}
+__global__ __launch_bounds__(256) void k_eltwise_grp(QEltwiseGrpArgs a)
+{
+    eltwise_pass<false>(a.g, [&](int64_t) { return qg_pass_src(a.g, a.ge, a.tile_member); });
 }
 
 // host column-major (m fastest) -> packed-C index space; 64 x 64 tile through LDS so that both sides are coalesced.
@@ -80,7 +89,7 @@ __global__ __launch_bounds__(256) void k_pack_e(QCGeom c, int part, const char* 
     for (int i = ty; i < 64; i += 4) {
         const int ml = m_fast ? tx : i, nl = m_fast ? i : tx;
         const int64_t m = tm * 64 + ml, n = tn * 64 + nl;
-        if (m < c.M && n < c.N) store_one(dst, qg_c_index(c, part, m, n), ebytes, tile[ml][nl]);
+        if (m < c.M && n < c.N) qg_ep_store_one(dst, qg_c_index(c, part, m, n), ebytes, tile[ml][nl]);
     }
 }
 
@@ -92,6 +101,22 @@ hipError_t qg_launch_eltwise(const QEltwiseArgs& g, hipStream_t st)
     const int64_t blocks = (g.n + 4095) / 4096;
     if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_eltwise, dim3((unsigned)blocks), dim3(256), 0, st, g);
+    return hipGetLastError();
+}
+
+hipError_t qg_launch_eltwise_bd(const QEltwiseBdArgs& a, hipStream_t st)
+{
+    if (a.g.n <= 0) return hipSuccess;
+    if (!qg_pass_stack_ok(a.g.n, a.bd)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_eltwise_bd, dim3((unsigned)(a.g.n / 4096)), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t qg_launch_eltwise_grp(const QEltwiseGrpArgs& a, hipStream_t st)
+{
+    if (a.g.n <= 0) return hipSuccess;
+    if (!qg_pass_launch_ok(a.g.n, a.tile_member)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_eltwise_grp, dim3((unsigned)(a.g.n / 4096)), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 

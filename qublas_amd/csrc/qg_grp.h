@@ -81,7 +81,7 @@ inline QGrpTile qg_grp_record(const QGrpShape& s, int32_t w)
     return t;
 }
 
-// The chain pass of a grouped plan with an element-wise chain (k_eltwise_grp / k_approx_grp, qg_eltwise_grp.hip) walks the launch's
+// The chain pass of a grouped plan with an element-wise chain (k_eltwise_grp, qg_eltwise.hip; k_approx_grp, qg_approx.hip) walks the launch's
 // packed C linearly, one 64 x 64 tile per workgroup, and must know whose per-member scalars a tile takes: out[w] = the member (index
 // in the caller's list) of C tile w IN MEMORY ORDER, w = c_off / c_tile, 4 bytes per workgroup.  out[T], T = qg_grp_tiles(m, n); the
 // members' C tiles are disjoint and cover [0, T) (the planner lays them back to back), so every entry is written exactly once.

@@ -172,23 +172,16 @@ static_assert(offsetof(QMfmaArgs, bd_tm) == offsetof(QMfmaArgs, kara) + 4 && off
               offsetof(QMfmaArgs, bd_tn) == offsetof(QMfmaArgs, has_ep) + 4 && offsetof(QMfmaArgs, dbg) == offsetof(QMfmaArgs, has_ep) + 8,
               "QMfmaArgs: the block-diagonal fields sit in former padding; no field may move");
 hipError_t qg_launch_mfma(int LA, int LB, const QMfmaArgs& a, hipStream_t st);
-// An element-wise chain on a batched plan (qgemul_plan_create_batched_epx) in its block-diagonal forms: C, D and every per-member
-// tensor operand are the members' packed tensors back to back (one index space over the whole stack); a SHARED operand is ONE
-// member's packed tensor, read at the member-local index  i - member * msize.  msize = elements of one member's packed C (a
-// whole number of 64 x 64 tiles), shared bit k = stage k's tensor operand is shared.  The new kernels carry this in argument
-// structs of their own: QMfmaArgs, QEpArgs and QEltwiseArgs are what they were, so no existing kernel's code moves.
-struct QBdEp {
-    int64_t msize;
-    uint32_t shared, pad_;
-};
+// g itself, as a type-dependent expression (I: any template parameter of the caller).  qg_mfma_body.h is one text for kernels with
+// different argument structs; through this it names a field that only some of them have inside an `if constexpr` branch, which the
+// other kernels discard without looking the field up
+template <int I, class G>
+QG_HD const G& qg_dependent(const G& g) { return g; }
+// An element-wise chain on a batched plan (qgemul_plan_create_batched_epx) in its block-diagonal forms (QBdEp: qg_eltwise_args.h).  The
+// kernels carry it in argument structs of their own: QMfmaArgs, QEpArgs and QEltwiseArgs are what they were, so no other kernel's code moves.
 struct QMfmaEpBdArgs : QMfmaArgs {
     QBdEp bd;
 };
-// the QBdEp of a kernel's argument struct (kernels whose arguments have none never evaluate the result)
-template <class G>
-QG_HD auto qg_bd_ep_of(const G& g, int) -> decltype(g.bd) { return g.bd; }
-template <class G>
-QG_HD QBdEp qg_bd_ep_of(const G&, long) { return QBdEp{0, 0, 0}; }
 // the block-diagonal launch with the chain in the kernel's epilogue (qg_mfma_ep_bd.hip: k_mfma_ep_bd, the body of k_mfma with BD and
 // EP together): the geometries of qg_launch_mfma_bd, chains the planner has bounded by 32-bit arithmetic
 hipError_t qg_launch_mfma_ep_bd(int LA, int LB, const QMfmaEpBdArgs& a, int64_t batch, hipStream_t st);
@@ -203,11 +196,6 @@ hipError_t qg_launch_mfma_bd(int LA, int LB, const QMfmaArgs& a, int64_t batch, 
 struct QMfmaGrpArgs : QMfmaArgs {
     const QGrpTile* tiles;
 };
-// the schedule of a kernel's argument struct (kernels whose arguments have none never evaluate the result)
-template <class G>
-QG_HD auto qg_grp_tiles_of(const G& g, int) -> decltype(g.tiles) { return g.tiles; }
-template <class G>
-QG_HD const QGrpTile* qg_grp_tiles_of(const G&, long) { return nullptr; }
 // n_tiles workgroups, the ten geometries of qg_launch_mfma_bd (a 3 x 3 launch is the pair <3,3> + <2,2 on three-plane storage>,
 // both reading the same records); anything else is hipErrorInvalidValue
 hipError_t qg_launch_mfma_grp(int LA, int LB, const QMfmaGrpArgs& a, int64_t n_tiles, hipStream_t st);
@@ -220,12 +208,6 @@ struct QMfmaEpGrpArgs : QMfmaArgs {
     const QGrpTile* tiles;
     QGrpEp ge;
 };
-// the QGrpEp of a kernel's argument struct, in place: its table pointers are indexed by the stage number at run time, and a copy
-// would live in scratch (kernels whose arguments have none never evaluate the result)
-template <class G>
-QG_HD auto qg_grp_ep_of(const G& g, int) -> decltype(&g.ge) { return &g.ge; }
-template <class G>
-QG_HD const QGrpEp* qg_grp_ep_of(const G&, long) { return nullptr; }
 // the grouped launch with the chain in the kernel's epilogue (qg_mfma_ep_grp.hip: k_mfma_ep_grp, the body of k_mfma with GRP and EP
 // together): the geometries of qg_launch_mfma_grp, chains the planner has bounded by 32-bit arithmetic
 hipError_t qg_launch_mfma_ep_grp(int LA, int LB, const QMfmaEpGrpArgs& a, int64_t n_tiles, hipStream_t st);
@@ -289,6 +271,10 @@ inline bool qg_step_is_shift_clamp(const QStep& q) { return !q.identity && q.O =
 
 // element-wise epilogue as its own pass (kernels that do not fuse it) and the operand packer; see qg_eltwise.h
 hipError_t qg_launch_eltwise(const QEltwiseArgs& g, hipStream_t st);
+// ... over the stack of a batched plan / the launch of a grouped plan (qg_eltwise_args.h); a stack that is no whole number of members
+// of whole workgroups, a launch that is no whole number of tiles or has no tile -> member table: hipErrorInvalidValue
+hipError_t qg_launch_eltwise_bd(const QEltwiseBdArgs& a, hipStream_t st);
+hipError_t qg_launch_eltwise_grp(const QEltwiseGrpArgs& a, hipStream_t st);
 hipError_t qg_launch_pack_e(const QCGeom& c, int part, const void* src, int64_t ld, int stride, int off, int src_bytes, void* dst, int ebytes,
                             hipStream_t st);
 

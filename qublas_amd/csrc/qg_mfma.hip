@@ -21,6 +21,7 @@
 
 #include "qg_eltwise.h"
 #include "qg_kernels.h"
+#include "qg_member_forms.h"
 #include "qg_mfma_tile.h"
 #include "qg_step_all.h"
 
@@ -364,7 +365,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_mfma16(QMfmaArgs g)
             int32_t v[4 * TJ];
 #pragma unroll
             for (int e = 0; e < 4 * TJ; ++e) v[e] = (int32_t)s[e];
-            qg_ep_apply_runs<int32_t, TJ>(v, g.ep, g.epa, base0, (int64_t)16 * TM);
+            qg_ep_apply_runs<int32_t, TJ>(v, g.ep, QEpSrcOne{g.epa, base0, (int64_t)16 * TM});
 #pragma unroll
             for (int j = 0; j < TJ; ++j) qg_ep_store_run<int32_t>(C, base0 + (int64_t)j * 16 * TM, g.ep.dbytes, v + 4 * j);
         } else
@@ -458,24 +459,6 @@ hipError_t launch(const QMfmaArgs& a, hipStream_t st)
     return e;
 }
 
-// the block-diagonal form (k_mfma, BD): batch * bd_tm * bd_tn workgroups; a 3 x 3 launch is the pair <3,3> + <2,2 on 3-plane storage>
-// like launch(), and the plane masks it reads are the STACK's (the OR over every member)
-template <int LA, int LB, int BK, int WGM, int WGN, int TI, int TJ, int NSTAGE>
-hipError_t launch_bd(const QMfmaArgs& a, int64_t batch, hipStream_t st)
-{
-    constexpr int TM = WGM * TI * 32, TN = WGN * TJ * 32;
-    constexpr int STAGE = (LA * TM + LB * TN) * BK;
-    const int64_t blocks = batch * a.bd_tm * a.bd_tn;
-    if (blocks <= 0) return hipSuccess;
-    if (blocks > 0x7fffffffll || a.Kp % BK || a.Mp != batch * a.bd_tm * TM || a.Np != batch * a.bd_tn * TN || a.has_ep || a.kara || a.c_host) return hipErrorInvalidValue;
-    const hipError_t e = qg_launch_lds<k_mfma_bd<LA, LB, BK, WGM, WGN, TI, TJ, NSTAGE>>((unsigned)blocks, 64 * WGM * WGN, NSTAGE * STAGE, st, a);
-    if constexpr (LA == 3 && LB == 3) {
-        if (e == hipSuccess && (a.maskA || a.maskB))
-            return qg_launch_lds<k_mfma_bd<2, 2, BK, WGM, WGN, TI, TJ, NSTAGE, 3, 3>>((unsigned)blocks, 64 * WGM * WGN, NSTAGE * (2 * TM + 2 * TN) * BK, st, a);
-    }
-    return e;
-}
-
 // single limb, KS k groups per workgroup (see k_mfma)
 template <int BK, int WGM, int WGN, int TI, int TJ, int NSTAGE, int KS>
 hipError_t launch_ksplit(const QMfmaArgs& a, hipStream_t st)
@@ -492,24 +475,20 @@ hipError_t launch_ksplit(const QMfmaArgs& a, hipStream_t st)
 
 } // namespace
 
+// the block-diagonal form (k_mfma_bd): batch * bd_tm * bd_tn workgroups, the forms and the 3 x 3 pair of qg_member_forms.h; the plane
+// masks it reads are the STACK's (the OR over every member)
 hipError_t qg_launch_mfma_bd(int LA, int LB, const QMfmaArgs& a, int64_t batch, hipStream_t st)
 {
-    if (LA == 1 && LB == 1) {
-        if (a.variant == QG_MFMA_64_BK128) return launch_bd<1, 1, 128, 2, 2, 1, 1, 3>(a, batch, st);
-        return hipErrorInvalidValue;
-    }
-    if (a.variant != QG_MFMA_LIMB_64) return hipErrorInvalidValue;
-    switch (LA * 10 + LB) {
-    case 12: return launch_bd<1, 2, 64, 2, 2, 1, 1, 3>(a, batch, st);
-    case 21: return launch_bd<2, 1, 64, 2, 2, 1, 1, 3>(a, batch, st);
-    case 22: return launch_bd<2, 2, 64, 2, 2, 1, 1, 3>(a, batch, st);
-    case 13: return launch_bd<1, 3, 64, 2, 2, 1, 1, 3>(a, batch, st);
-    case 31: return launch_bd<3, 1, 64, 2, 2, 1, 1, 3>(a, batch, st);
-    case 23: return launch_bd<2, 3, 64, 2, 2, 1, 1, 3>(a, batch, st);
-    case 32: return launch_bd<3, 2, 64, 2, 2, 1, 1, 3>(a, batch, st);
-    case 33: return launch_bd<3, 3, 64, 2, 2, 1, 1, 3>(a, batch, st);
-    default: return hipErrorInvalidValue;
-    }
+    return qg_member_form(LA, LB, a.variant, [&](auto form) -> hipError_t {
+        using F = decltype(form);
+        const int64_t blocks = batch * a.bd_tm * a.bd_tn;
+        if (blocks <= 0) return hipSuccess;
+        if (blocks > 0x7fffffffll || a.Kp % F::BK || a.Mp != batch * a.bd_tm * F::TM || a.Np != batch * a.bd_tn * F::TN || a.has_ep || a.kara || a.c_host) return hipErrorInvalidValue;
+        return qg_member_launch(form, a, [&](auto k) {
+            using K = decltype(k);
+            return qg_launch_lds<k_mfma_bd<QG_MEMBER_FORM_ARGS(K)>>((unsigned)blocks, K::THREADS, K::LDS, st, a);
+        });
+    });
 }
 
 // QG_ABLATE=1..5 selects diagnostic variants of the two benchmarked kernels (results are WRONG by construction; used only

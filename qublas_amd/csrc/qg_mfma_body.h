@@ -1,4 +1,4 @@
-// qg_mfma_body.h — the body of k_mfma and k_mfma_bd (qg_mfma.hip) and of k_mfma_ep_bd (qg_mfma_ep_bd.hip), included INSIDE the
+// qg_mfma_body.h — the body of k_mfma and k_mfma_bd (qg_mfma.hip), k_mfma_ep_bd (qg_mfma_ep_bd.hip), k_mfma_grp (qg_mfma_grp.hip) and k_mfma_ep_grp (qg_mfma_ep_grp.hip), included INSIDE the
 // kernels: no include guard, nothing at namespace scope.  In scope where it is included: the kernel argument `QMfmaArgs g` (BD with
 // EP: a QMfmaEpBdArgs; GRP: a QMfmaGrpArgs, with EP a QMfmaEpGrpArgs: k_mfma_ep_grp, qg_mfma_ep_grp.hip) and the compile-time constants LA, LB, BK, WGM, WGN, TI, TJ, NSTAGE, ABL, EP, SA, SB, KARA,
 // KS, BD, GRP (their meaning: the comment in front of k_mfma; GRP: k_mfma_grp, qg_mfma_grp.hip).
@@ -40,7 +40,7 @@
         // grouped launch: block bid reads record bid — where its A and B blocks start, where its C tile goes, its k-tile count, its
         // rows of the stack's row sums and its member's K biasA biasB.  One wave-uniform load of 48 bytes; no division, no tile walk
         static_assert(!GRP || (!BD && KS == 1 && !KARA && ABL == 0 && TM == 64 && TN == 64), "grouped form: the plain lock-step body on 64 x 64 tiles");
-        const QGrpTile rec = qg_grp_tiles_of(g, 0)[blockIdx.x];
+        const QGrpTile rec = qg_dependent<LA>(g).tiles[blockIdx.x];   // (a field of the grouped kernels' argument structs only: qg_dependent, qg_kernels.h)
         grp_a = rec.a_off;
         grp_b = rec.b_off;
         grp_c = rec.c_off;
@@ -310,17 +310,17 @@
                     // tile, below 4096: 32-bit offsets, where 64-bit element indices per run and container cost a third wave per SIMD.
                     // A per-member scalar stage takes its member's value from the plan's table: a uniform load, nothing per lane
                     const uint32_t lane0 = (uint32_t)(col * TM + row0);
-                    qg_ep_apply_runs_grp<int32_t, 4>(v, g.ep, g.epa, tile_base, lane0, 8, *qg_grp_ep_of(g, 0), grp_member);
+                    qg_ep_apply_runs<int32_t, 4>(v, g.ep, QEpSrcGroup{g.epa, tile_base, lane0, 8, qg_dependent<LA>(g).ge, grp_member});
                     char* Dt = C + tile_base * g.ep.dbytes;
 #pragma unroll
                     for (int q = 0; q < 4; ++q) qg_ep_store_run<int32_t>(Dt + (lane0 + 8u * q) * (uint32_t)g.ep.dbytes, 0, g.ep.dbytes, v + 4 * q);
                     continue;
                 } else
                 if constexpr (BD) {   // D and per-member operands at the stack-wide index, a shared operand at the member-local one
-                    const QBdEp be = qg_bd_ep_of(g, 0);
-                    qg_ep_apply_runs_bd<int32_t, 4>(v, g.ep, g.epa, base, 8, (int64_t)bd_member * be.msize, be.shared);
+                    const QBdEp be = qg_dependent<LA>(g).bd;
+                    qg_ep_apply_runs<int32_t, 4>(v, g.ep, QEpSrcStack{g.epa, base, 8, (int64_t)bd_member * be.msize, be.shared});
                 } else
-                qg_ep_apply_runs<int32_t, 4>(v, g.ep, g.epa, base, 8);
+                qg_ep_apply_runs<int32_t, 4>(v, g.ep, QEpSrcOne{g.epa, base, 8});
 #pragma unroll
                 for (int q = 0; q < 4; ++q) qg_ep_store_run<int32_t>(C, base + 8 * q, g.ep.dbytes, v + 4 * q);
             } else   // (written out, not qg_store_run4 with a run-time container size: as a function it moves this kernel's instruction stream)

@@ -16,6 +16,7 @@
 
 #include "qg_eltwise.h"
 #include "qg_kernels.h"
+#include "qg_member_forms.h"
 #include "qg_mfma_tile.h"
 #include "qg_step_all.h"
 
@@ -32,44 +33,21 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_mfma_ep_bd(QMfmaEpBdArgs g)
 #include "qg_mfma_body.h"
 }
 
-// batch * bd_tm * bd_tn workgroups; a 3 x 3 launch is the pair <3,3> + <2,2 on 3-plane storage> of launch_bd (qg_mfma.hip), and
-// both partners carry the chain: the one the stack's plane masks select stores D
-template <int LA, int LB, int BK, int WGM, int WGN, int TI, int TJ, int NSTAGE>
-hipError_t launch_ep_bd(const QMfmaEpBdArgs& a, int64_t batch, hipStream_t st)
-{
-    constexpr int TM = WGM * TI * 32, TN = WGN * TJ * 32;
-    constexpr int STAGE = (LA * TM + LB * TN) * BK;
-    const int64_t blocks = batch * a.bd_tm * a.bd_tn;
-    if (blocks <= 0) return hipSuccess;
-    if (blocks > 0x7fffffffll || a.Kp % BK || a.Mp != batch * a.bd_tm * TM || a.Np != batch * a.bd_tn * TN || !a.has_ep || !a.ep.bits32 || a.kara || a.c_host ||
-        a.bd.msize != (int64_t)a.bd_tm * a.bd_tn * TM * TN)
-        return hipErrorInvalidValue;
-    const hipError_t e = qg_launch_lds<k_mfma_ep_bd<LA, LB, BK, WGM, WGN, TI, TJ, NSTAGE>>((unsigned)blocks, 64 * WGM * WGN, NSTAGE * STAGE, st, a);
-    if constexpr (LA == 3 && LB == 3) {
-        if (e == hipSuccess && (a.maskA || a.maskB))
-            return qg_launch_lds<k_mfma_ep_bd<2, 2, BK, WGM, WGN, TI, TJ, NSTAGE, 3, 3>>((unsigned)blocks, 64 * WGM * WGN, NSTAGE * (2 * TM + 2 * TN) * BK, st, a);
-    }
-    return e;
-}
-
 } // namespace
 
+// batch * bd_tm * bd_tn workgroups, the forms and the 3 x 3 pair of qg_member_forms.h; both partners carry the chain
 hipError_t qg_launch_mfma_ep_bd(int LA, int LB, const QMfmaEpBdArgs& a, int64_t batch, hipStream_t st)
 {
-    if (LA == 1 && LB == 1) {
-        if (a.variant == QG_MFMA_64_BK128) return launch_ep_bd<1, 1, 128, 2, 2, 1, 1, 3>(a, batch, st);
-        return hipErrorInvalidValue;
-    }
-    if (a.variant != QG_MFMA_LIMB_64) return hipErrorInvalidValue;
-    switch (LA * 10 + LB) {
-    case 12: return launch_ep_bd<1, 2, 64, 2, 2, 1, 1, 3>(a, batch, st);
-    case 21: return launch_ep_bd<2, 1, 64, 2, 2, 1, 1, 3>(a, batch, st);
-    case 22: return launch_ep_bd<2, 2, 64, 2, 2, 1, 1, 3>(a, batch, st);
-    case 13: return launch_ep_bd<1, 3, 64, 2, 2, 1, 1, 3>(a, batch, st);
-    case 31: return launch_ep_bd<3, 1, 64, 2, 2, 1, 1, 3>(a, batch, st);
-    case 23: return launch_ep_bd<2, 3, 64, 2, 2, 1, 1, 3>(a, batch, st);
-    case 32: return launch_ep_bd<3, 2, 64, 2, 2, 1, 1, 3>(a, batch, st);
-    case 33: return launch_ep_bd<3, 3, 64, 2, 2, 1, 1, 3>(a, batch, st);
-    default: return hipErrorInvalidValue;
-    }
+    return qg_member_form(LA, LB, a.variant, [&](auto form) -> hipError_t {
+        using F = decltype(form);
+        const int64_t blocks = batch * a.bd_tm * a.bd_tn;
+        if (blocks <= 0) return hipSuccess;
+        if (blocks > 0x7fffffffll || a.Kp % F::BK || a.Mp != batch * a.bd_tm * F::TM || a.Np != batch * a.bd_tn * F::TN || !a.has_ep || !a.ep.bits32 || a.kara || a.c_host ||
+            a.bd.msize != (int64_t)a.bd_tm * a.bd_tn * F::TM * F::TN)
+            return hipErrorInvalidValue;
+        return qg_member_launch(form, a, [&](auto k) {
+            using K = decltype(k);
+            return qg_launch_lds<k_mfma_ep_bd<QG_MEMBER_FORM_ARGS(K)>>((unsigned)blocks, K::THREADS, K::LDS, st, a);
+        });
+    });
 }

@@ -19,6 +19,7 @@
 
 #include "qg_eltwise.h"
 #include "qg_kernels.h"
+#include "qg_member_forms.h"
 #include "qg_mfma_tile.h"
 #include "qg_step_all.h"
 
@@ -35,42 +36,18 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_mfma_grp(QMfmaGrpArgs g)
 #include "qg_mfma_body.h"
 }
 
-// n_tiles workgroups; a 3 x 3 launch is the pair <3,3> + <2,2 on 3-plane storage> of launch_bd (qg_mfma.hip): both read the same
-// records (the stored stride of a block is SA-based, and the host computed the offsets from the stored planes), and the plane masks
-// they choose by are the launch's (the OR over every member)
-template <int LA, int LB, int BK, int WGM, int WGN, int TI, int TJ, int NSTAGE>
-hipError_t launch_grp(const QMfmaGrpArgs& a, int64_t n_tiles, hipStream_t st)
-{
-    constexpr int TM = WGM * TI * 32, TN = WGN * TJ * 32;
-    constexpr int STAGE = (LA * TM + LB * TN) * BK;
-    if (n_tiles <= 0) return hipSuccess;
-    if (n_tiles > 0x7fffffffll || !a.tiles || a.has_ep || a.kara || a.c_host) return hipErrorInvalidValue;
-    const hipError_t e = qg_launch_lds<k_mfma_grp<LA, LB, BK, WGM, WGN, TI, TJ, NSTAGE>>((unsigned)n_tiles, 64 * WGM * WGN, NSTAGE * STAGE, st, a);
-    if constexpr (LA == 3 && LB == 3) {
-        if (e == hipSuccess && (a.maskA || a.maskB))
-            return qg_launch_lds<k_mfma_grp<2, 2, BK, WGM, WGN, TI, TJ, NSTAGE, 3, 3>>((unsigned)n_tiles, 64 * WGM * WGN, NSTAGE * (2 * TM + 2 * TN) * BK, st, a);
-    }
-    return e;
-}
-
 } // namespace
 
+// n_tiles workgroups, the forms and the 3 x 3 pair of qg_member_forms.h: both partners read the same records (the stored stride of a
+// block is SA-based, and the host computed the offsets from the stored planes), and the plane masks they choose by are the launch's
 hipError_t qg_launch_mfma_grp(int LA, int LB, const QMfmaGrpArgs& a, int64_t n_tiles, hipStream_t st)
 {
-    if (LA == 1 && LB == 1) {
-        if (a.variant == QG_MFMA_64_BK128) return launch_grp<1, 1, 128, 2, 2, 1, 1, 3>(a, n_tiles, st);
-        return hipErrorInvalidValue;
-    }
-    if (a.variant != QG_MFMA_LIMB_64) return hipErrorInvalidValue;
-    switch (LA * 10 + LB) {
-    case 12: return launch_grp<1, 2, 64, 2, 2, 1, 1, 3>(a, n_tiles, st);
-    case 21: return launch_grp<2, 1, 64, 2, 2, 1, 1, 3>(a, n_tiles, st);
-    case 22: return launch_grp<2, 2, 64, 2, 2, 1, 1, 3>(a, n_tiles, st);
-    case 13: return launch_grp<1, 3, 64, 2, 2, 1, 1, 3>(a, n_tiles, st);
-    case 31: return launch_grp<3, 1, 64, 2, 2, 1, 1, 3>(a, n_tiles, st);
-    case 23: return launch_grp<2, 3, 64, 2, 2, 1, 1, 3>(a, n_tiles, st);
-    case 32: return launch_grp<3, 2, 64, 2, 2, 1, 1, 3>(a, n_tiles, st);
-    case 33: return launch_grp<3, 3, 64, 2, 2, 1, 1, 3>(a, n_tiles, st);
-    default: return hipErrorInvalidValue;
-    }
+    return qg_member_form(LA, LB, a.variant, [&](auto form) -> hipError_t {
+        if (n_tiles <= 0) return hipSuccess;
+        if (n_tiles > 0x7fffffffll || !a.tiles || a.has_ep || a.kara || a.c_host) return hipErrorInvalidValue;
+        return qg_member_launch(form, a, [&](auto k) {
+            using K = decltype(k);
+            return qg_launch_lds<k_mfma_grp<QG_MEMBER_FORM_ARGS(K)>>((unsigned)n_tiles, K::THREADS, K::LDS, st, a);
+        });
+    });
 }

@@ -66,12 +66,23 @@ def chains(cq: Qu):
     }
 
 
+def branch_chains(cq: Qu):
+    """APPROX chains for the branches of the pass kernels k_approx_bd / k_approx_grp that chains 5_* leave out (those are 64-bit with a
+    shared bias, or 32-bit without a scalar stage): 32-bit arithmetic with a scalar stage and a shared tensor operand, and 64-bit
+    arithmetic with per-member tensor operands only.  Kept out of chains(): the plan tests walk that list"""
+    act_in = [Ew("mul", S34, Tags(24, 8), scalar=True, into=Qu(24, 8)), Ew("add", B106, into=X312)]
+    return {
+        "6_act_scalar_32bit": ([Ew("mul", S34, scalar=True), Ew("add", B106, into=X312), Approx(UNIFORM2)], X312, [0, 1, 0]),
+        "6_act_member_operand_wide": (act_in + [Approx(UNIFORM2)], Qu(1, 10, True, RND.CONV, SAT.TCPL), [0, 0, 0]),
+    }
+
+
 def lowered(fmt, shape, chain):
     """(descriptor, epilogue, tables, stages, C type, D type, shared flags) of one case"""
     ea, eb, ec, kw, ta, _ = FORMATS[fmt]
     M, N, K = shape
     d = lower(ea, eb, ec, M, N, K, transposed_a=ta, **kw)
-    stages, dq, shared = chains(ec)[chain]
+    stages, dq, shared = {**chains(ec), **branch_chains(ec)}[chain]
     ep, tabs = lower_epilogue_x(ec, stages, dq)
     return d, ep, tabs, stages, ec, dq, shared
 

@@ -54,7 +54,7 @@ class Chain:
     @classmethod
     def named(cls, fmt, name, per_member=None):
         ec = X.FORMATS[fmt][2]
-        stages, dq, _ = X.chains(ec)[name]
+        stages, dq, _ = {**X.chains(ec), **X.branch_chains(ec)}[name]
         return cls(ec, stages, dq, per_member)
 
 

@@ -35,7 +35,10 @@ def report(tmp_path_factory):
     r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-x", "hip", "-c", SRC, "-o", obj,
                         "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
-    return parse(r.stderr)
+    # (the file holds the member forms k_approx_bd and k_approx_grp too: tests/test_batched_ep_resources.py, test_grouped_ep_resources.py)
+    every = parse(r.stderr)
+    assert all(re.search(r"\dk_approx(_bd|_grp)?I[il]E", k) for k in every) and len(every) == 6, sorted(every)   # nothing else lives in the file
+    return {k: v for k, v in every.items() if re.search(r"\dk_approxI", k)}
 
 
 def check(kernels):

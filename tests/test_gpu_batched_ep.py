@@ -165,7 +165,9 @@ def oracle_members(oracle, d, ec, stages, dq, mA, mB, ops, nthreads=8):
 CASES = ([(f, "1_scale_shared_bias") for f in sorted(X.FORMATS)] +
          [(f, c) for f in ("e43_c1byte", "e88_3x3", "q78_centred") for c in ("2_member_sub_shared_mul_wide", "4_four_stages_1_2_4_8_bytes")] +
          [(f, "3_no_stage_narrow_sat") for f in ("e43_c1byte", "e88_3x3", "e88_x_e43_3x1_c16", "e88_3x3_tn_c16")] +
-         [(f, c) for f in ("e43_c1byte", "e88_3x3_c16") for c in ("5_act_uniform", "5_act_general", "5_act_member_operand")])
+         [(f, c) for f in ("e43_c1byte", "e88_3x3_c16") for c in ("5_act_uniform", "5_act_general", "5_act_member_operand")] +
+         # k_approx_bd's remaining branches: 32-bit with a scalar and a SHARED operand, 64-bit with per-member operands only
+         [("e43_c1byte", "6_act_scalar_32bit"), ("e88_3x3_c16", "6_act_scalar_32bit"), ("e88_3x3_c16", "6_act_member_operand_wide")])
 
 
 @pytest.mark.parametrize("shape", X.SHAPES, ids=lambda s: "x".join(map(str, s)))
@@ -184,6 +186,8 @@ def test_chain_forms_vs_oracle_and_plain_plan(ctx, oracle, fmt, chain, shape):
     fusable = X.bits32(d, ep, tabs) and not X.has_approx(stages)
     if chain == "1_scale_shared_bias":
         assert fusable == (fmt == "e43_c1byte" or fmt.endswith("_c16")), fmt          # (32-bit chain wherever C has at most 32 storage bits)
+    if chain.startswith("6_"):
+        assert X.bits32(d, ep, tabs) == chain.endswith("_32bit") and not fusable
     if chain.startswith(("2_", "4_", "5_")):
         assert not fusable or chain == "5_act_member_operand"
     for batch in X.BATCHES:

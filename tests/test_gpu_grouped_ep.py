@@ -92,6 +92,35 @@ def test_chain_forms_vs_oracle_and_plain_loop(ctx, oracle, fmt, chain):
     assert forms == {0: (0, 2), FUSED: ((1, 1) if fusable else (0, 2)), UNFUSED: (0, 2)}
 
 
+@pytest.mark.parametrize("fmt", ["e43_c1byte", "e88_3x3_c16"])
+@pytest.mark.parametrize("chain,table", [("6_act_scalar_32bit", True), ("6_act_scalar_32bit", False), ("5_act_uniform", False)],
+                         ids=["32bit_table", "32bit_call_wide", "64bit_call_wide"])
+def test_approx_pass_arithmetic_and_scalar_source(ctx, oracle, fmt, chain, table):
+    """k_approx_grp<int32_t / int64_t> with the scalar from the plan's table or call-wide: the branches that chain 5_act_uniform above
+    (64-bit, table) leaves out.  Three members; oracle == plain loop == pass form, byte for byte"""
+    ch = G.Chain.named(fmt, chain)
+    members = [G.fmt_member(oracle, fmt, s, ch, seed=300 + 7 * i, dist=i % 2) for i, s in enumerate([(64, 64, 1), (3, 5, 7), (129, 130, 65)])]
+    assert X.bits32(members[0].d, ch.ep, ch.tabs) == chain.endswith("_32bit") and not G.fusable(members)
+    for i, m in enumerate(members):
+        m.scal = [None if s is None else (5 * i - 23 + k if table else 11 - k) for k, s in enumerate(m.scal)]
+    if table:
+        assert check_forms(ctx, oracle, members, want_in=[1, 1, 1]) == {0: (0, 2), FUSED: (0, 2), UNFUSED: (0, 2)}
+        return
+    exp = [m.expected(oracle) for m in members]
+    dev = G.Device(ctx, oracle, members)
+    try:
+        same(G.run_plain_loop(ctx, oracle, dev), exp, "plain loop")
+        for flags in (0, UNFUSED):
+            run = G.GroupedRun(ctx, dev, flags, per_member=[0] * len(ch.stages), e_scalar=[0 if s is None else s for s in members[0].scal])
+            try:
+                same(run.run(), exp, ("grouped", flags))
+                assert (run.plan.fuses(), run.plan.launches) == (0, 2)
+            finally:
+                run.close()
+    finally:
+        dev.close()
+
+
 def test_per_member_scalars_swap_and_reset(ctx, oracle):
     """every member has a distinct value; swapping two members' values swaps exactly their results; set_scalars after a first execute
     changes the next execute's D; a stage with scalar_per_member = 0 uses e_scalar[k]"""
