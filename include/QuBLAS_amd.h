@@ -534,6 +534,7 @@ void Qgemul(TC& C, const TA& A, const TB& B)
 // Qcomplex tensors (and one real, one complex operand) are members like any other:
 //     QgemulRunFlags() |= QG_OPT_BATCHED_STACKED;   // complex / real x complex members of the linear class: one block-diagonal launch
 //                                                   // + one combine pass for the whole batch; without it member by member (mixed: refused)
+//     QgemulRunFlags() |= QG_OPT_BATCHED_TREE;      // tree-class members on the tiled 32-bit tree kernels (K <= 4096): one launch for the whole batch
 template <typename... Tags, size_t CM, size_t CN, size_t CB, size_t AR, size_t AC, size_t AB, size_t BR, size_t BN, size_t BB, class EC, class EA, class EB>
 qgemul_desc QgemulBatched_lower_types(std::type_identity<Qu_s<dim<CM, CN, CB>, EC>>, std::type_identity<Qu_s<dim<AR, AC, AB>, EA>>,
                                       std::type_identity<Qu_s<dim<BR, BN, BB>, EB>>, int64_t* batch, int64_t* strides)

@@ -194,12 +194,18 @@ enum {
      * (segment by segment under a lane mask instead of one Horner loop with a per-lane coefficient); result-identical, for
      * equivalence tests and A/B timing */
     QG_OPT_APPROX_GENERAL = 4096u,
-    /* the highest bit in use.  Batched plans (below) whose member is a complex or a real x complex GEMM of the linear class: ONE
+    /* Batched plans (below) whose member is a complex or a real x complex GEMM of the linear class: ONE
      * block-diagonal MFMA launch over the members' stacked parts plus ONE block-diagonal combine pass (2 launches for the whole
      * batch) instead of member by member; a mixed member, which a batched plan refuses otherwise, is served in this form.
      * Result-identical.  Decided at plan time (the packed A and B differ).  Ignored by every other plan: plain and grouped plans,
      * real, tree-class and composite members, and the _batched_ep entry points */
-    QG_OPT_BATCHED_STACKED = 8192u
+    QG_OPT_BATCHED_STACKED = 8192u,
+    /* the highest bit in use.  Batched plans (below) whose member runs on a tiled 32-bit tree kernel (qgemul_info.kernel
+     * QG_KERNEL_TREE_I32 or QG_KERNEL_TREE_CPLX_I32) with a tree of at most 12 levels (K <= 4096): ONE launch of that kernel's batched
+     * twin for the whole batch instead of one launch per member.  Result-identical, and the packed layouts are the unflagged plan's:
+     * plans with and without the flag are interchangeable on the same packed buffers.  Ignored by every other plan: plain and
+     * grouped plans, members on any other kernel, deeper trees, and the _batched_ep entry points */
+    QG_OPT_BATCHED_TREE = 16384u
 };
 
 /* status codes */
@@ -334,6 +340,9 @@ int qgemul_time_execute(qgemul_plan* p, void* packedC, const void* packedA, cons
  * mixed: tm x 2 tn or 2 tm x tn) into the plan's int64 workspace, and one block-diagonal combine pass (k_stack_combine_bd) into the
  * members' packed Cs.  Without the flag a mixed member is refused (QG_EUNSUPPORTED) and a complex one runs member
  * by member.
+ * QG_OPT_BATCHED_TREE: tree-class members on the tiled 32-bit tree kernels (real and complex; trees of at most 12 levels) run as ONE
+ * launch of batch x tiles workgroups, each working on one tile of one member exactly as the member's own launch would (DESIGN.md
+ * 5.2f).  Packed operands and packed C are the member-by-member form's.  Without the flag such a batch runs member by member.
  * The packed layouts belong to the batched plan (they may differ from the plain plan of the same descriptor); packed C is the
  * members' packed Cs back to back.  qgemul_info.packed_bytes[] of a batched classify / plan are for the whole batch, ops too.
  * A batched plan is destroyed with qgemul_plan_destroy and answers qgemul_plan_info and qgemul_plan_packed_layout (in the one-

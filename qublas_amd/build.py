@@ -10,8 +10,10 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["qg_api.hip", "qg_run.hip", "qg_pack.hip", "qg_combine_bd.hip", "qg_eltwise.hip", "qg_approx.hip", "qg_eltwise_cplx.hip", "qg_tree.hip", "qg_tree_fast.hip", "qg_tree64.hip", "qg_tree_cplx.hip", "qg_tree_rc.hip", "qg_gemv.hip", "qg_mfma.hip", "qg_mfma_ep_bd.hip", "qg_mfma_grp.hip", "qg_mfma_ep_grp.hip", "qg_mfma_pp.hip", "qg_mfma_ppl.hip", "qg_mfma_k6.hip", "qg_mfma_ring.hip", "qg_comm.hip", "qg_plan.cpp", "qg_geom.cpp"]
-HEADERS = ["qg_ops.h", "qg_forms.h", "qg_plan.h", "qg_kernels.h", "qg_geom.h", "qg_tile_walk.h", "qg_grp.h", "qg_mfma_tile.h", "qg_member_forms.h", "qg_mfma_body.h", "qg_ring.h", "qg_step_all.h", "qg_tree_counter.h", "qg_tree_io.h", "qg_eltwise.h", "qg_eltwise_args.h", "qg_approx.h", "qg_approx_dev.h", "qg_cmul.h", "qg_fix.h", "qg_api_int.h", "qg_run_key.h", os.path.join("..", "..", "include", "qgemul.h")]
+SOURCES = ["qg_api.hip", "qg_run.hip", "qg_pack.hip", "qg_combine_bd.hip", "qg_eltwise.hip", "qg_approx.hip", "qg_eltwise_cplx.hip", "qg_tree.hip", "qg_tree_fast.hip", "qg_tree_fast_bd.hip", "qg_tree64.hip", "qg_tree_cplx.hip", "qg_tree_cplx_bd.hip", "qg_tree_rc.hip", "qg_gemv.hip", "qg_mfma.hip", "qg_mfma_ep_bd.hip", "qg_mfma_grp.hip", "qg_mfma_ep_grp.hip", "qg_mfma_pp.hip", "qg_mfma_ppl.hip", "qg_mfma_k6.hip", "qg_mfma_ring.hip", "qg_comm.hip", "qg_plan.cpp", "qg_geom.cpp"]
+HEADERS = ["qg_ops.h", "qg_forms.h", "qg_plan.h", "qg_kernels.h", "qg_geom.h", "qg_tile_walk.h", "qg_grp.h", "qg_mfma_tile.h", "qg_member_forms.h", "qg_mfma_body.h", "qg_ring.h", "qg_step_all.h", "qg_tree_counter.h", "qg_tree_io.h", "qg_tree_bd.h", "qg_eltwise.h", "qg_eltwise_args.h", "qg_approx.h", "qg_approx_dev.h", "qg_cmul.h", "qg_fix.h", "qg_api_int.h", "qg_run_key.h", os.path.join("..", "..", "include", "qgemul.h")]
+# a unit that compiles another unit's text again (the batched twins of the tree kernels: qg_tree_bd.h)
+INCLUDED_UNITS = {"qg_tree_fast_bd.hip": ["qg_tree_fast.hip"], "qg_tree_cplx_bd.hip": ["qg_tree_cplx.hip"]}
 # compile flags of every source (tools/isa_diff.py compiles with the same ones)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result", "-x", "hip"]
 LIB = os.path.join(HERE, "libqugemm.so")
@@ -39,7 +41,7 @@ def build(force: bool = False, verbose: bool = False, diag: bool = False) -> str
         src = os.path.join(CSRC, s)
         obj = os.path.join(objdir, s.rsplit(".", 1)[0] + ".o")
         objs.append(obj)
-        if force or _stale(obj, [src] + hdrs):
+        if force or _stale(obj, [src] + [os.path.join(CSRC, u) for u in INCLUDED_UNITS.get(s, [])] + hdrs):
             cmd = [hipcc] + FLAGS + ["-c", src, "-o", obj] + (["-DQG_DIAG"] if diag else [])
             if verbose:
                 print(" ".join(cmd), flush=True)

@@ -26,6 +26,7 @@ OPT_FORCE_TREE, OPT_CHECK_RANGE, OPT_GENERIC_TREE, OPT_RUNTIME_MODES, OPT_FUSED_
 OPT_GENERIC_LAYOUT, OPT_LOCKSTEP_TILES, OPT_ARITHMETIC_CONV, OPT_ALL_DEVICES = 64, 128, 256, 512
 OPT_SCHOOLBOOK_LIMBS = 2048   # 17/18-bit operands: balanced base-256 limbs and 9 products, not three base-64 digits and 6; result-identical
 OPT_APPROX_GENERAL = 4096   # chains with an APPROX stage: uniform tables through the general form of the pass; result-identical
+OPT_BATCHED_TREE = 16384   # batched plans of tree-class members on the tiled 32-bit tree kernels (at most 12 levels): one launch for the whole batch; result-identical
 OPT_BATCHED_STACKED = 8192   # batched plans of complex / real x complex linear-class members: one block-diagonal launch + one combine pass; result-identical
 OPT_BALANCED_LIMBS = 1024   # never centre an operand (x - c in balanced limbs): the plain balanced limbs, result-identical
 OPERAND_A, OPERAND_B, OPERAND_C = 0, 1, 2

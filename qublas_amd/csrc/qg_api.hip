@@ -1288,6 +1288,16 @@ int qgemul_execute_batched(qgemul_plan* p, void* packedC, const void* packedA, c
     if (p->desc.M == 0 || p->desc.N == 0) return QG_OK;
     qgemul_plan* m = p->member;
     if (p->bd_stack) return execute_stacked(p, packedC, packedA, packedB);
+    if (p->bd_tree) {   // QG_OPT_BATCHED_TREE: ONE launch of the member's tree kernel's batched twin, the members at their packed strides
+        QG_ON_DEVICE(p->ctx);
+        if (m->info.kernel == QG_KERNEL_TREE_I32)
+            QG_HIP(qg_launch_tree_fast_bd(m->dev_table, m->an.tree.n_levels_k, m->an.split_s, m->an.mul24_ok, m->tc.tree, packedA, packedB, packedC, m->desc.M,
+                                          m->desc.N, m->pa.K_p, m->pc.cbytes, p->batch, p->mstride, p->ctx->stream));
+        else
+            QG_HIP(qg_launch_tree_cplx_fast_bd(m->dev_table, m->an.tree.n_levels_k, m->tc.cplx, m->desc.cmul == QG_CMUL_TF ? 1 : 0, packedA, packedB, packedC,
+                                               m->desc.M, m->desc.N, m->pa.K_p, m->pc.cbytes, p->batch, p->mstride, p->ctx->stream));
+        return QG_OK;
+    }
     if (!p->bd) {
         for (int64_t b = 0; b < p->batch; ++b)
             if (const int st = qgemul_execute(m, (char*)packedC + b * p->mstride[2], (const char*)packedA + b * p->mstride[0], (const char*)packedB + b * p->mstride[1]); st != QG_OK)

@@ -214,6 +214,7 @@ struct Planner {
     {
         out->bd = 0;
         out->bd_stack = QG_STACK_NONE;
+        out->bd_tree = 0;
         memset(&comp, 0, sizeof comp);
         qg_analyze(d, an);
         memset(info, 0, sizeof *info);
@@ -686,6 +687,17 @@ static bool batched_stack(const QPlanGeom* m, int64_t batch, QPlanGeom* s, QBatc
     return over;
 }
 
+// QG_OPT_BATCHED_TREE: the tiles of ONE member in the one launch of its tree kernel's batched twin (qg_tree_bd.h), 0 where the member
+// has none: any kernel but the two tiled 32-bit ones, a tree of more than 12 levels (only the 12-level instantiations have a twin)
+static int64_t tree_bd_tiles(const QPlanGeom* m, const qgemul_desc* d, uint32_t flags)
+{
+    const int k = m->info.kernel;
+    if ((k != QG_KERNEL_TREE_I32 && k != QG_KERNEL_TREE_CPLX_I32) || m->an.tree.n_levels_k > QG_TREE_BD_MAX_LEVELS) return 0;
+    const bool rows64 = k == QG_KERNEL_TREE_I32 || qg_tree_choice(&m->an, d, flags, false).cplx == QCF_PK16;
+    const int64_t tm = rows64 ? QG_TREE_TILE_M : QG_TREE_CPLX_TILE_M;
+    return ((d->M + tm - 1) / tm) * ((d->N + QG_TREE_TILE_N - 1) / QG_TREE_TILE_N);
+}
+
 int qg_batched_geometry(const qgemul_desc* d, int64_t batch, uint32_t flags, const EpView* ev, const qgemul_batched_ep* bep, QPlanGeom* m, QPlanGeom* s, QBatchGeom* b)
 {
     if (!d || batch < 1) return QG_EINVAL;
@@ -741,6 +753,15 @@ int qg_batched_geometry(const qgemul_desc* d, int64_t batch, uint32_t flags, con
         s->pa = m->pa;
         s->pb = m->pb;
         if (ev) snprintf(s->info.reason, sizeof s->info.reason, "chain member by member: %.70s", m->info.reason);
+        // the one-launch tree form, on request and without a chain: the layout above is its layout too; more workgroups than a grid
+        // holds: member by member
+        const int64_t tiles = (flags & QG_OPT_BATCHED_TREE) && !ev ? tree_bd_tiles(m, d, flags) : 0;
+        if (tiles > 0 && tiles <= 0x7fffffffll / batch) {
+            m->bd_tree = s->bd_tree = (int)tiles;
+            const char* steps = strstr(m->info.reason, "; ");   // ("exact tree evaluation; <tree | complex> kernel steps: <form>")
+            // (the prefix is no longer than the one it replaces: the longest step-form name still fits qgemul_info.reason)
+            snprintf(s->info.reason, sizeof s->info.reason, "batch in one launch; %.74s", steps ? steps + 2 : m->info.reason);
+        }
     }
     if (over) {
         s->info.supported = 0;
@@ -756,6 +777,7 @@ int qg_batched_launches(const QPlanGeom* s, const QBatchGeom* b, bool has_ep)
 {
     if (s->bd) return has_ep && !b->bd_fused ? 2 : 1;
     if (s->bd_stack) return 2;   // the block-diagonal GEMM and the combine pass
+    if (s->bd_tree) return 1;    // the tree kernel's batched twin
     const int64_t n = b->batch * b->member_launches;
     return n > 0x7fffffffll ? 0x7fffffff : (int)n;
 }
@@ -781,7 +803,7 @@ static int straggler_launches(const QGrouped* G, const QPlanGeom& q, uint32_t fl
 // geometry, a straggler its plain plan's
 static int grouped_distinct(const qgemul_desc* d, int64_t groups, uint32_t flags, const EpView* ev, QGrouped* G, qgemul_info* info)
 {
-    flags &= ~(uint32_t)QG_OPT_BATCHED_STACKED;   // (a batched plan's switch: a grouped plan plans its members as without it)
+    flags &= ~(uint32_t)(QG_OPT_BATCHED_STACKED | QG_OPT_BATCHED_TREE);   // (a batched plan's switches: a grouped plan plans its members as without them)
     // (the comparison of the one-shot cache: qg_run_key.h)
     for (int64_t g = 0; g < groups; ++g) {
         int64_t u = 0;

@@ -152,7 +152,11 @@ struct QPlanGeom {
     int bd;               // the member of a batched plan: k_mfma's block-diagonal form takes it (a batched plan: it launches that form)
     int bd_stack;         // QG_OPT_BATCHED_STACKED, a complex / mixed member of a batched plan: the stacked block-diagonal form takes it
                           // (QStackMode; bd stays 0: nothing that serves the real form sees such a member)
+    int bd_tree;          // QG_OPT_BATCHED_TREE, a member of a batched plan on the tiled 32-bit tree kernels: the tiles of ONE member in the
+                          // one launch of the kernel's batched twin (qg_tree_bd.h); 0: not that form
 };
+// tiles of the tiled 32-bit tree kernels (qg_tree_fast.hip; qg_tree_cplx.hip: 32 rows, its packed 16-bit form 64)
+enum { QG_TREE_TILE_M = 64, QG_TREE_TILE_N = 32, QG_TREE_CPLX_TILE_M = 32, QG_TREE_BD_MAX_LEVELS = 12 };
 // the stacked block-diagonal form: which operands carry two parts, i.e. which source tiles of the workspace one output tile has
 enum QStackMode { QG_STACK_NONE = 0, QG_STACK_CPLX = 1, QG_STACK_REAL_A = 2, QG_STACK_REAL_B = 3 };
 

@@ -120,6 +120,14 @@ hipError_t qg_launch_tree_generic(const QTreeTable* dev_table, int parts, const 
 hipError_t qg_launch_tree_fast(const QTreeTable* dev_table, int n_levels, int split_s, int mul24, QTreeForm form, const void* A, const void* B,
                                void* C, int64_t M, int64_t N, int64_t K, int cbytes, hipStream_t st);
 
+// the batched twins of the two (QG_OPT_BATCHED_TREE; qg_tree_fast_bd.hip, qg_tree_cplx_bd.hip): `batch` members of one descriptor in ONE
+// launch of batch x tiles workgroups, member b's packed A, B, C at stride[0..2] * b bytes behind member 0's; the checks of the plain
+// launchers, and an unknown form, more than 12 levels or more than 2^31 - 1 workgroups is hipErrorInvalidValue
+hipError_t qg_launch_tree_fast_bd(const QTreeTable* dev_table, int n_levels, int split_s, int mul24, QTreeForm form, const void* A, const void* B,
+                                  void* C, int64_t M, int64_t N, int64_t K, int cbytes, int64_t batch, const int64_t stride[3], hipStream_t st);
+hipError_t qg_launch_tree_cplx_fast_bd(const QTreeTable* dev_table, int n_levels, QCplxForm form, int tf, const void* A, const void* B, void* C,
+                                       int64_t M, int64_t N, int64_t K, int cbytes, int64_t batch, const int64_t stride[3], hipStream_t st);
+
 // exact tree evaluation, real descriptors with 5..16 levels and 64-bit values (A, B packed as int32 or int64, K = 2^n_levels)
 hipError_t qg_launch_tree64(const QTreeTable* dev_table, int n_levels, const void* A, const void* B, void* C, int64_t M, int64_t N,
                             int64_t K, int abytes, int bbytes, int cbytes, hipStream_t st);

@@ -24,6 +24,7 @@
 #include "qg_kernels.h"
 #include "qg_step_all.h"
 #include "qg_tile_walk.h"
+#include "qg_tree_bd.h"
 #include "qg_tree_counter.h"
 #include "qg_tree_io.h"
 
@@ -187,6 +188,11 @@ struct QTreeCplxArgs {
     int64_t M, N, K;
     int32_t cbytes;
 };
+// the batched twins' arguments (QG_TREE_BD: qg_tree_cplx_bd.hip compiles this file's text again, qg_tree_bd.h): A, B, C of member 0 and the
+// walk over the members; QTreeCplxArgs is what it was
+struct QTreeCplxArgsBd : QTreeCplxArgs {
+    QTreeBdWalk bd;
+};
 
 // Occupancy: the compact forms are bound by how well the other waves cover a wave's scalar-load round trips, so they are compiled
 // for one wave per SIMD more than their natural register count gives (4 at MAXL 12, 3 at MAXL 16; 10-20 spilled registers outside
@@ -194,8 +200,9 @@ struct QTreeCplxArgs {
 template <int MODE, bool TF>
 constexpr bool cplx_dense_waves = MODE >= QCF_COMPACT && (TF || (MODE != QCF_KINDS && !(MODE >= QCF_KINDS_R && ((MODE - 8) & 2))));   // (no SAT::ZERO kinds)
 template <int MAXL, int MODE, bool TF>   // TF: TFComplexMul (3 multiplications), else BasicComplexMul (4)
-__global__ __launch_bounds__(256, ((cplx_dense_waves<MODE, TF>) ? (MAXL == 12 ? 4 : 3) : 1)) void k_tree_cplx(QTreeCplxArgs g)
+__global__ __launch_bounds__(256, ((cplx_dense_waves<MODE, TF>) ? (MAXL == 12 ? 4 : 3) : 1)) void QG_TREE_KERNEL(k_tree_cplx)(QG_TREE_PARAM(QTreeCplxArgs))
 {
+    QG_TREE_MEMBER(QTreeCplxArgs);
     constexpr int NP = TF ? 3 : 2;   // LDS planes per operand
     constexpr int RW = TF ? 2 : 4;   // leaves per LDS read: with three planes, 8-byte reads keep 24 registers of operands live where 16-byte reads keep 48
     // planes: BasicComplexMul {a, b} / {c, d}; TFComplexMul {a+b, b, b-a} / {c, c+d, d} — the three additions in front of
@@ -210,7 +217,7 @@ __global__ __launch_bounds__(256, ((cplx_dense_waves<MODE, TF>) ? (MAXL == 12 ? 
     // tile rows, so neighbouring blocks re-use A rows and B columns in L2
     const int64_t tiles_n = (g.N + TNB - 1) / TNB, tiles_m = (g.M + TMB - 1) / TMB;
     int64_t tile_m, tile_n;
-    qg_tile_of<16, true>(qg_xcd_block<int64_t>(blockIdx.x, tiles_m * tiles_n), tiles_m, tiles_n, tile_m, tile_n);
+    qg_tile_of<16, true>(QG_TREE_BLOCK(tiles_m * tiles_n), tiles_m, tiles_n, tile_m, tile_n);
     const int64_t m0 = tile_m * TMB, n0 = tile_n * TNB;
     const int nl = tab->n_levels_k;   // (a tree shorter than 5 levels is continued with identity levels: qg_plan.h)
     // QCF_UNIFORM ("one clamp for the whole loop", qg_plan.cpp): ONE range for every value of the k loop and no shift / rounding at the
@@ -499,8 +506,9 @@ constexpr int TM16 = 64;    // rows of C per block (16 thread rows x 4)
 constexpr int PKP = 18;     // dwords per A-plane row: 16 + 2 (8-byte reads stay aligned)
 
 template <int MAXL, bool TF>
-__global__ __launch_bounds__(256, 3) void k_tree_cplx_pk16(QTreeCplxArgs g)
+__global__ __launch_bounds__(256, 3) void QG_TREE_KERNEL(k_tree_cplx_pk16)(QG_TREE_PARAM(QTreeCplxArgs))
 {
+    QG_TREE_MEMBER(QTreeCplxArgs);
     constexpr int NP = TF ? 3 : 2;
     __shared__ __attribute__((aligned(16))) int sA[NP][TM16][PKP];       // [plane][row][k / 2]: (k even, k odd)
     __shared__ __attribute__((aligned(16))) int sB[NP][TNB / 2][PITCH];  // [plane][column pair][k]: (column p, column p + 16)
@@ -509,7 +517,7 @@ __global__ __launch_bounds__(256, 3) void k_tree_cplx_pk16(QTreeCplxArgs g)
     const int tx = tid & 15, ty = tid >> 4;
     const int64_t tiles_n = (g.N + TNB - 1) / TNB, tiles_m = (g.M + TM16 - 1) / TM16;
     int64_t tile_m, tile_n;   // XCD-aware block order (qg_tile_walk.h), as k_tree_cplx
-    qg_tile_of<16, true>(qg_xcd_block<int64_t>(blockIdx.x, tiles_m * tiles_n), tiles_m, tiles_n, tile_m, tile_n);
+    qg_tile_of<16, true>(QG_TREE_BLOCK(tiles_m * tiles_n), tiles_m, tiles_n, tile_m, tile_n);
     const int64_t m0 = tile_m * TM16, n0 = tile_n * TNB;
     const int nl = tab->n_levels_k;
     const int s16 = tab->lj16.s;
@@ -663,27 +671,43 @@ __global__ __launch_bounds__(256, 3) void k_tree_cplx_pk16(QTreeCplxArgs g)
 
 } // namespace
 
+// the leaves of the form switch launch this compilation's kernels: the 12- and 16-level instantiations by the tree's depth, or
+// (QG_TREE_BD) the batched twins of the 12-level ones over the walk's workgroups
+#ifdef QG_TREE_BD
+using QTreeCplxLaunchArgs = QTreeCplxArgsBd;
+template <int MODE>
+static hipError_t launch_cplx(int, int tf, int64_t, hipStream_t st, const QTreeCplxArgsBd& g)
+{
+    return tf ? qg_tree_bd_launch(k_tree_cplx_bd<12, MODE, true>, st, g) : qg_tree_bd_launch(k_tree_cplx_bd<12, MODE, false>, st, g);
+}
+static hipError_t launch_cplx_pk16(int, int tf, int64_t, hipStream_t st, const QTreeCplxArgsBd& g)
+{
+    return tf ? qg_tree_bd_launch(k_tree_cplx_pk16_bd<12, true>, st, g) : qg_tree_bd_launch(k_tree_cplx_pk16_bd<12, false>, st, g);
+}
+#else
+using QTreeCplxLaunchArgs = QTreeCplxArgs;
+static hipError_t launch_cplx_pk16(int n_levels, int tf, int64_t blocks, hipStream_t st, const QTreeCplxArgs& g)
+{
+    return tf ? qg_launch_by_levels(n_levels, k_tree_cplx_pk16<12, true>, k_tree_cplx_pk16<16, true>, blocks, st, g)
+              : qg_launch_by_levels(n_levels, k_tree_cplx_pk16<12, false>, k_tree_cplx_pk16<16, false>, blocks, st, g);
+}
 template <int MODE>
 static hipError_t launch_cplx(int n_levels, int tf, int64_t blocks, hipStream_t st, const QTreeCplxArgs& g)
 {
     return tf ? qg_launch_by_levels(n_levels, k_tree_cplx<12, MODE, true>, k_tree_cplx<16, MODE, true>, blocks, st, g)
               : qg_launch_by_levels(n_levels, k_tree_cplx<12, MODE, false>, k_tree_cplx<16, MODE, false>, blocks, st, g);
 }
+#endif
 
-hipError_t qg_launch_tree_cplx_fast(const QTreeTable* dev_table, int n_levels, QCplxForm form, int tf, const void* A, const void* B, void* C, int64_t M,
-                                    int64_t N, int64_t K, int cbytes, hipStream_t st)
+// one form switch for both compilations
+static hipError_t launch_tree_cplx_form(QCplxForm form, int tf, int n_levels, int64_t blocks, hipStream_t st, const QTreeCplxLaunchArgs& g)
 {
-    int64_t blocks;   // (the packed form's tiles have 64 rows)
-    if (const hipError_t e = qg_tree_blocks(M, N, K, n_levels, form == QCF_PK16 ? TM16 : TMB, TNB, blocks); e != hipSuccess || blocks == 0) return e;
-    QTreeCplxArgs g{dev_table, (const int32_t*)A, (const int32_t*)B, (char*)C, M, N, K, cbytes};
     switch (form) {
     case QCF_RUNTIME: return launch_cplx<QCF_RUNTIME>(n_levels, tf, blocks, st, g);
     case QCF_TABLE: return launch_cplx<QCF_TABLE>(n_levels, tf, blocks, st, g);
     case QCF_COMPACT: return launch_cplx<QCF_COMPACT>(n_levels, tf, blocks, st, g);
     case QCF_KINDS: return launch_cplx<QCF_KINDS>(n_levels, tf, blocks, st, g);
-    case QCF_PK16:
-        return tf ? qg_launch_by_levels(n_levels, k_tree_cplx_pk16<12, true>, k_tree_cplx_pk16<16, true>, blocks, st, g)
-                  : qg_launch_by_levels(n_levels, k_tree_cplx_pk16<12, false>, k_tree_cplx_pk16<16, false>, blocks, st, g);
+    case QCF_PK16: return launch_cplx_pk16(n_levels, tf, blocks, st, g);
     case QCF_LJ: return launch_cplx<QCF_LJ>(n_levels, tf, blocks, st, g);
     case QCF_UNIFORM: return launch_cplx<QCF_UNIFORM>(n_levels, tf, blocks, st, g);
     case QCF_KINDS_R: return launch_cplx<QCF_KINDS_R>(n_levels, tf, blocks, st, g);
@@ -695,3 +719,27 @@ hipError_t qg_launch_tree_cplx_fast(const QTreeTable* dev_table, int n_levels, Q
     }
     return hipErrorInvalidValue;
 }
+
+#ifdef QG_TREE_BD
+static_assert(TMB == QG_TREE_CPLX_TILE_M && TM16 == QG_TREE_TILE_M && TNB == QG_TREE_TILE_N, "qg_batched_geometry (qg_geom.cpp) counts these tiles");
+
+hipError_t qg_launch_tree_cplx_fast_bd(const QTreeTable* dev_table, int n_levels, QCplxForm form, int tf, const void* A, const void* B, void* C, int64_t M,
+                                       int64_t N, int64_t K, int cbytes, int64_t batch, const int64_t stride[3], hipStream_t st)
+{
+    int64_t blocks;   // (the packed form's tiles have 64 rows)
+    if (const hipError_t e = qg_tree_blocks(M, N, K, n_levels, form == QCF_PK16 ? TM16 : TMB, TNB, blocks); e != hipSuccess || blocks == 0 || batch == 0) return e;
+    if (n_levels > 12 || batch < 0 || batch > 0x7fffffffll / blocks) return hipErrorInvalidValue;
+    QTreeCplxArgsBd g{{dev_table, (const int32_t*)A, (const int32_t*)B, (char*)C, M, N, K, cbytes},
+                      {stride[0], stride[1], stride[2], (uint32_t)blocks, (uint32_t)(batch * blocks)}};
+    return launch_tree_cplx_form(form, tf, n_levels, blocks, st, g);
+}
+#else
+hipError_t qg_launch_tree_cplx_fast(const QTreeTable* dev_table, int n_levels, QCplxForm form, int tf, const void* A, const void* B, void* C, int64_t M,
+                                    int64_t N, int64_t K, int cbytes, hipStream_t st)
+{
+    int64_t blocks;   // (the packed form's tiles have 64 rows)
+    if (const hipError_t e = qg_tree_blocks(M, N, K, n_levels, form == QCF_PK16 ? TM16 : TMB, TNB, blocks); e != hipSuccess || blocks == 0) return e;
+    QTreeCplxArgs g{dev_table, (const int32_t*)A, (const int32_t*)B, (char*)C, M, N, K, cbytes};
+    return launch_tree_cplx_form(form, tf, n_levels, blocks, st, g);
+}
+#endif

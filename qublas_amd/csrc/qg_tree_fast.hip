@@ -22,6 +22,7 @@
 #include "qg_kernels.h"
 #include "qg_step_all.h"
 #include "qg_tile_walk.h"
+#include "qg_tree_bd.h"
 #include "qg_tree_counter.h"
 #include "qg_tree_io.h"
 
@@ -118,6 +119,11 @@ struct QTreeFastArgs {
     int32_t cbytes;
     int32_t split_s;    // SPLIT: rounding shift of the product (= bits split off B)
 };
+// the batched twins' arguments (QG_TREE_BD: qg_tree_fast_bd.hip compiles this file's text again, qg_tree_bd.h): A, B, C of member 0 and the
+// walk over the members; QTreeFastArgs is what it was
+struct QTreeFastArgsBd : QTreeFastArgs {
+    QTreeBdWalk bd;
+};
 
 // MODE: the step form, QTreeForm (qg_forms.h).  The one-format forms (QTF_ONE_*) are the default-tag shapes (configurations 1 and 3
 // as literally configured), whose leaf needs no separate rounding step.  QTF_LJ: the operands are staged with the factors that
@@ -140,8 +146,9 @@ struct QTreeFastArgs {
     } while (0)
 
 template <bool SPLIT, bool MUL24, int MAXL, int MODE>
-__global__ __launch_bounds__(256) void k_tree_fast(QTreeFastArgs g)
+__global__ __launch_bounds__(256) void QG_TREE_KERNEL(k_tree_fast)(QG_TREE_PARAM(QTreeFastArgs))
 {
+    QG_TREE_MEMBER(QTreeFastArgs);
     __shared__ __attribute__((aligned(16))) int sA[TMB][PITCH];
     __shared__ __attribute__((aligned(16))) int sBh[TNB][PITCH];
     __shared__ __attribute__((aligned(16))) int sBl[SPLIT ? TNB : 1][PITCH];
@@ -152,7 +159,7 @@ __global__ __launch_bounds__(256) void k_tree_fast(QTreeFastArgs g)
     // tile rows, so neighbouring blocks re-use A rows and B columns in L2
     const int64_t tiles_n = (g.N + TNB - 1) / TNB, tiles_m = (g.M + TMB - 1) / TMB;
     // (the group walk is qg_tile_of<16, true> written out: the call moves the instruction stream of two instantiations)
-    const int64_t bid = qg_xcd_block<int64_t>(blockIdx.x, tiles_m * tiles_n);
+    const int64_t bid = QG_TREE_BLOCK(tiles_m * tiles_n);
     constexpr int64_t GMT = 16;
     const int64_t grp = bid / (GMT * tiles_n), first_m = grp * GMT;
     const int64_t gsz = (tiles_m - first_m) < GMT ? (tiles_m - first_m) : GMT;
@@ -432,8 +439,9 @@ constexpr int PKP = 18;   // dwords per sA16 row (16 + 2: 8-byte reads stay alig
     } while (0)
 
 template <int MAXL, int HYB = 0, bool UNS = false>   // UNS: unsigned formats (qg_fix.h); HYB 1: formats of fewer than 16 bits; 2: exactly 16 (no bits below the unit in a half: nothing to clear, ever)
-__global__ __launch_bounds__(256) void k_tree_pk16(QTreeFastArgs g)
+__global__ __launch_bounds__(256) void QG_TREE_KERNEL(k_tree_pk16)(QG_TREE_PARAM(QTreeFastArgs))
 {
+    QG_TREE_MEMBER(QTreeFastArgs);
     __shared__ __attribute__((aligned(16))) int sA[TMB][HYB ? PITCH : PKP];              // [row][k / 2]: (k even, k odd); HYB: [row][k] of 32-bit values
     __shared__ __attribute__((aligned(16))) int sB[HYB ? TNB : TNB / 2][PITCH];          // [column pair][k]: (column p, column p + 16); HYB: [column][k]
     const QTreeTable* __restrict__ tab = g.tab;
@@ -441,7 +449,7 @@ __global__ __launch_bounds__(256) void k_tree_pk16(QTreeFastArgs g)
     const int tx = tid & 15, ty = tid >> 4;
     const int64_t tiles_n = (g.N + TNB - 1) / TNB, tiles_m = (g.M + TMB - 1) / TMB;
     int64_t tile_m, tile_n;   // XCD-aware block order (qg_tile_walk.h), as k_tree_fast
-    qg_tile_of<16, true>(qg_xcd_block<int64_t>(blockIdx.x, tiles_m * tiles_n), tiles_m, tiles_n, tile_m, tile_n);
+    qg_tile_of<16, true>(QG_TREE_BLOCK(tiles_m * tiles_n), tiles_m, tiles_n, tile_m, tile_n);
     const int64_t m0 = tile_m * TMB, n0 = tile_n * TNB;
     const int nl = tab->n_levels_k;
     const int s16 = HYB ? tab->lj.s - 16 : tab->lj16.s, ea = HYB ? tab->lj.e[0] : tab->lj16.e[0], eb = HYB ? tab->lj.e[1] : tab->lj16.e[1];
@@ -557,15 +565,32 @@ __global__ __launch_bounds__(256) void k_tree_pk16(QTreeFastArgs g)
 
 } // namespace
 
+// the leaves of the form switch launch this compilation's kernels: the 12- and 16-level instantiations by the tree's depth, or
+// (QG_TREE_BD) the batched twins of the 12-level ones over the walk's workgroups
+#ifdef QG_TREE_BD
+using QTreeFastLaunchArgs = QTreeFastArgsBd;
+template <bool SPLIT, bool MUL24, int MODE>
+static hipError_t launch_tf(int, int64_t, hipStream_t st, const QTreeFastArgsBd& g)
+{
+    return qg_tree_bd_launch(k_tree_fast_bd<SPLIT, MUL24, 12, MODE>, st, g);
+}
+template <int HYB, bool UNS>
+static hipError_t launch_pk16(int, int64_t, hipStream_t st, const QTreeFastArgsBd& g)
+{
+    return qg_tree_bd_launch(k_tree_pk16_bd<12, HYB, UNS>, st, g);
+}
+#else
+using QTreeFastLaunchArgs = QTreeFastArgs;
 template <bool SPLIT, bool MUL24, int MODE>
 static hipError_t launch_tf(int n_levels, int64_t blocks, hipStream_t st, const QTreeFastArgs& g)
 {
     return qg_launch_by_levels(n_levels, k_tree_fast<SPLIT, MUL24, 12, MODE>, k_tree_fast<SPLIT, MUL24, 16, MODE>, blocks, st, g);
 }
+#endif
 
 // the forms that split the product at its rounding shift where it needs one (QAnalysis::split_s)
 template <bool SPLIT>
-static hipError_t launch_tf_split(QTreeForm form, int mul24, int n_levels, int64_t blocks, hipStream_t st, const QTreeFastArgs& g)
+static hipError_t launch_tf_split(QTreeForm form, int mul24, int n_levels, int64_t blocks, hipStream_t st, const QTreeFastLaunchArgs& g)
 {
     switch (form) {
     case QTF_ONE_ZERO: return launch_tf<SPLIT, true, QTF_ONE_ZERO>(n_levels, blocks, st, g);
@@ -578,18 +603,17 @@ static hipError_t launch_tf_split(QTreeForm form, int mul24, int n_levels, int64
     }
 }
 
+#ifndef QG_TREE_BD
 template <int HYB, bool UNS>
 static hipError_t launch_pk16(int n_levels, int64_t blocks, hipStream_t st, const QTreeFastArgs& g)
 {
     return qg_launch_by_levels(n_levels, k_tree_pk16<12, HYB, UNS>, k_tree_pk16<16, HYB, UNS>, blocks, st, g);
 }
+#endif
 
-hipError_t qg_launch_tree_fast(const QTreeTable* dev_table, int n_levels, int split_s, int mul24, QTreeForm form, const void* A, const void* B,
-                               void* C, int64_t M, int64_t N, int64_t K, int cbytes, hipStream_t st)
+// one form switch for both compilations
+static hipError_t launch_tree_fast_form(QTreeForm form, int mul24, int split_s, int n_levels, int64_t blocks, hipStream_t st, const QTreeFastLaunchArgs& g)
 {
-    int64_t blocks;
-    if (const hipError_t e = qg_tree_blocks(M, N, K, n_levels, TMB, TNB, blocks); e != hipSuccess || blocks == 0) return e;
-    QTreeFastArgs g{dev_table, (const int32_t*)A, (const int32_t*)B, (char*)C, M, N, K, cbytes, split_s};
     // (the word forms form exact 64-bit products; the others are built for 24-bit multiplies, except the run-time-mode form)
     if (!mul24 && form != QTF_RUNTIME && !(form >= QTF_WORD && form <= QTF_WORD_WRAP)) return hipErrorInvalidValue;
     switch (form) {
@@ -610,3 +634,27 @@ hipError_t qg_launch_tree_fast(const QTreeTable* dev_table, int n_levels, int sp
         return split_s > 0 ? launch_tf_split<true>(form, mul24, n_levels, blocks, st, g) : launch_tf_split<false>(form, mul24, n_levels, blocks, st, g);
     }
 }
+
+#ifdef QG_TREE_BD
+static_assert(TMB == QG_TREE_TILE_M && TNB == QG_TREE_TILE_N, "qg_batched_geometry (qg_geom.cpp) counts these tiles");
+
+hipError_t qg_launch_tree_fast_bd(const QTreeTable* dev_table, int n_levels, int split_s, int mul24, QTreeForm form, const void* A, const void* B,
+                                  void* C, int64_t M, int64_t N, int64_t K, int cbytes, int64_t batch, const int64_t stride[3], hipStream_t st)
+{
+    int64_t blocks;
+    if (const hipError_t e = qg_tree_blocks(M, N, K, n_levels, TMB, TNB, blocks); e != hipSuccess || blocks == 0 || batch == 0) return e;
+    if (n_levels > 12 || batch < 0 || batch > 0x7fffffffll / blocks) return hipErrorInvalidValue;
+    QTreeFastArgsBd g{{dev_table, (const int32_t*)A, (const int32_t*)B, (char*)C, M, N, K, cbytes, split_s},
+                      {stride[0], stride[1], stride[2], (uint32_t)blocks, (uint32_t)(batch * blocks)}};
+    return launch_tree_fast_form(form, mul24, split_s, n_levels, blocks, st, g);
+}
+#else
+hipError_t qg_launch_tree_fast(const QTreeTable* dev_table, int n_levels, int split_s, int mul24, QTreeForm form, const void* A, const void* B,
+                               void* C, int64_t M, int64_t N, int64_t K, int cbytes, hipStream_t st)
+{
+    int64_t blocks;
+    if (const hipError_t e = qg_tree_blocks(M, N, K, n_levels, TMB, TNB, blocks); e != hipSuccess || blocks == 0) return e;
+    QTreeFastArgs g{dev_table, (const int32_t*)A, (const int32_t*)B, (char*)C, M, N, K, cbytes, split_s};
+    return launch_tree_fast_form(form, mul24, split_s, n_levels, blocks, st, g);
+}
+#endif

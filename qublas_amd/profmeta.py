@@ -23,13 +23,13 @@ FAMILY_SOURCES = {
     "mfma_i8": ["qg_mfma.hip", "qg_mfma_pp.hip", "qg_mfma_ring.hip", "qg_ring.h", "qg_step_all.h"],
     "mfma_i8_limb": ["qg_mfma.hip", "qg_mfma_ppl.hip", "qg_mfma_k6.hip", "qg_mfma_ring.hip", "qg_ring.h", "qg_step_all.h"],
     "mfma_cplx": ["qg_mfma.hip", "qg_mfma_ppl.hip", "qg_step_all.h", "qg_pack.hip"],
-    "tree_i32": ["qg_tree_fast.hip", "qg_tree_counter.h", "qg_tree_io.h", "qg_step_all.h", "qg_fix.h", "qg_forms.h"],
+    "tree_i32": ["qg_tree_fast.hip", "qg_tree_bd.h", "qg_tree_counter.h", "qg_tree_io.h", "qg_step_all.h", "qg_fix.h", "qg_forms.h"],
     "tree_i64": ["qg_tree64.hip", "qg_tree.hip", "qg_tree_counter.h", "qg_tree_io.h"],
     "tree_i128": ["qg_tree.hip", "qg_tree_io.h"],
     "tree_cplx": ["qg_tree.hip", "qg_tree_io.h"],
     "mfma_rc": ["qg_mfma.hip", "qg_mfma_ppl.hip", "qg_step_all.h", "qg_pack.hip"],
     "tree_rc_i32": ["qg_tree_rc.hip", "qg_tree_counter.h", "qg_tree_io.h", "qg_fix.h", "qg_forms.h"],
-    "tree_cplx_i32": ["qg_tree_cplx.hip", "qg_tree_counter.h", "qg_tree_io.h", "qg_fix.h", "qg_forms.h"],
+    "tree_cplx_i32": ["qg_tree_cplx.hip", "qg_tree_bd.h", "qg_tree_counter.h", "qg_tree_io.h", "qg_fix.h", "qg_forms.h"],
     "gemv_i32": ["qg_gemv.hip", "qg_tree_io.h", "qg_fix.h", "qg_forms.h"],
     "gemv_i64": ["qg_gemv.hip", "qg_tree_io.h", "qg_fix.h", "qg_forms.h"],
 }
