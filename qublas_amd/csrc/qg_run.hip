@@ -1,6 +1,10 @@
-// qg_run.hip — the one-shot calls of include/qgemul.h (qgemul_run*, qgemul_run_batched*, qgemul_run_sharded): host tensors in, host
-// tensor out, one synchronous call.  Every single-device entry point fills a RunRequest and goes through run_one_shot.
+// qg_run.hip — the one-shot calls of include/qgemul.h (qgemul_run*, qgemul_run_batched*, qgemul_run_grouped*, qgemul_run_sharded):
+// host tensors in, host tensors out, one synchronous call.  The plain and batched entry points fill a RunRequest and go through
+// run_one_shot, the grouped ones fill a GroupedRequest and go through run_grouped; both get the thread's cached plan from
+// acquire_plan, their six operand buffers from cache_operand_buffers and their one synchronisation from finish.  The band loop of
+// qgemul_run_sharded installs its plans with acquire_plan's second half, install_plan.
 #include <atomic>
+#include <memory>
 
 #include "qg_api_int.h"
 
@@ -26,7 +30,7 @@ thread_local RunCache g_run;
 enum { QG_MAX_SHARDS = 16 };
 thread_local RunCache g_shard[QG_MAX_SHARDS];
 thread_local hipEvent_t g_shard_ev[QG_MAX_SHARDS] = {};
-thread_local QRunKey g_want;   // the key of the request at hand (kept between calls: its APPROX tables are on the heap)
+thread_local QRunKey g_want;   // the key of the request at hand (kept between calls: its APPROX tables and descriptor list are on the heap)
 // What a thread has cached is released when the thread ends (worker threads that call Qgemul<>() and exit must not leak a stream
 // and device buffers each).  For the main thread this runs inside exit() BEFORE any static object — HIP's included — is torn down.
 std::atomic<bool> g_shutting_down{false};
@@ -119,6 +123,61 @@ qgemul_opts resolve_opts(const qgemul_opts* o)
     return opts;
 }
 
+// ---- the cache protocol, once ----
+// the cache's plan is the one `want` names, or it goes and create(ctx, &plan) makes that one; a failed create leaves the cache without
+// a plan.  (The caller has made the cache's device current.)
+template <class Create>
+int install_plan(RunCache& c, const QRunKey& want, Create create)
+{
+    if (c.plan && qg_run_key_equal(c.key, want)) return QG_OK;
+    if (c.plan) { qgemul_plan_destroy(c.plan); c.plan = nullptr; }
+    const int st = create(c.ctx, &c.plan);
+    if (st != QG_OK) c.plan = nullptr; else c.key = want;
+    return st;
+}
+
+// The calling thread's one-plan cache serves the request `want` on `device` (< 0: the caller's current one).  classify() is the
+// request's host-only validation: it runs unless the cached plan is the request's, and its status is reported before a device is
+// touched, so descriptor errors come out without a GPU.
+template <class Classify, class Create>
+int acquire_plan(RunCache& c, int device, const QRunKey& want, Classify classify, Create create)
+{
+    if (device < 0 && c.ctx) {   // "current device": follow hipSetDevice calls the caller made between two calls
+        int cur = c.device;
+        if (hipGetDevice(&cur) == hipSuccess) device = cur;
+    }
+    const bool warm = c.ctx && (device < 0 || device == c.device);
+    int st = QG_OK;
+    if (!(warm && c.plan && qg_run_key_equal(c.key, want)) && (st = classify())) return st;
+    if ((st = cache_context(c, device))) return st;   // (another device: everything the cache held is gone)
+    if (warm) QG_HIP(hipSetDevice(c.device));
+    return install_plan(c, want, create);
+}
+
+// slots 0-5 of the cache: host-layout A, B and C (or D) of the given sizes, and the plan's packed A, B and C
+struct OperandBuffers { void *dA, *dB, *dC, *pA, *pB, *pC; };
+int cache_operand_buffers(RunCache& c, size_t bytesA, size_t bytesB, size_t bytesC, OperandBuffers& b)
+{
+    const int64_t* packed = c.plan->info.packed_bytes;
+    int st;
+    if ((st = cache_buffer(c, 0, bytesA, &b.dA)) || (st = cache_buffer(c, 1, bytesB, &b.dB)) || (st = cache_buffer(c, 2, bytesC, &b.dC)) ||
+        (st = cache_buffer(c, 3, (size_t)packed[0], &b.pA)) || (st = cache_buffer(c, 4, (size_t)packed[1], &b.pB)) || (st = cache_buffer(c, 5, (size_t)packed[2], &b.pC)))
+        return st;
+    return QG_OK;
+}
+
+// Everything a call queues goes on the context's stream; ONE synchronisation ends the call, also after a failure mid-way (the source
+// buffers are the caller's and the call is synchronous, so they stay valid until then).  st: what queueing returned; the first error counts
+int finish(RunCache& c, int st)
+{
+    const hipError_t e = hipStreamSynchronize(c.ctx->stream);
+    if (st == QG_OK && e != hipSuccess) { qg_set_last_hip((int)e); st = QG_EHIP; }
+    return st;
+}
+
+// the raw value of a chain's scalar operand: one host element of format f
+int64_t raw_scalar(const void* q, qfmt f) { return (1 + (int)f.I + (int)f.F) <= 32 ? (int64_t) * (const int32_t*)q : *(const int64_t*)q; }
+
 // One single-device one-shot call.  batch == 0: the plain call (strides unused); batch > 0: `batch` members at constant strides.
 // ev: the element-wise chain (nullptr: none) with its operands E; bep / strideE: a batched chain's shared and per-member operands.
 struct RunRequest {
@@ -144,7 +203,6 @@ int stage_chain_operands(RunCache& c, const RunRequest& r, qgemul_ep_args& ea)
     hipStream_t s = c.ctx->stream;
     int st = QG_OK;
     memset(&ea, 0, sizeof ea);
-    auto raw = [](const void* q, qfmt f) { return (1 + (int)f.I + (int)f.F) <= 32 ? (int64_t) * (const int32_t*)q : *(const int64_t*)q; };
     for (uint32_t k = 0; k < ep->n_stages; ++k) {
         const qgemul_ew_stage& sr = ep->stage[k];
         const qgemul_ew_stage* si = ev->im ? &ev->im->stage[k] : nullptr;
@@ -154,13 +212,13 @@ int stage_chain_operands(RunCache& c, const RunRequest& r, qgemul_ep_args& ea)
         if (!t_re && !t_im) {
             // scalar operand: one element ({re, im} for a complex one); a real scalar feeds both parts, except where the
             // imaginary part's stage takes the zero of the operand's type (real - complex, QuBLAS.h:3686)
-            if (sr.op != QG_EW_PASS) ea.e_scalar[k] = raw(r.E[k], sr.e);
+            if (sr.op != QG_EW_PASS) ea.e_scalar[k] = raw_scalar(r.E[k], sr.e);
             if (si && si->op != QG_EW_PASS) {
                 if (cplx) {
                     const qfmt f[2] = {sr.e, si->e};
-                    ea.e_scalar_im[k] = raw((const char*)r.E[k] + qg_host_elem(f, 1).off[1], si->e);
+                    ea.e_scalar_im[k] = raw_scalar((const char*)r.E[k] + qg_host_elem(f, 1).off[1], si->e);
                 } else {
-                    ea.e_scalar_im[k] = si->op == QG_EW_MUL ? raw(r.E[k], si->e) : 0;
+                    ea.e_scalar_im[k] = si->op == QG_EW_MUL ? raw_scalar(r.E[k], si->e) : 0;
                 }
             }
             continue;
@@ -180,86 +238,67 @@ int stage_chain_operands(RunCache& c, const RunRequest& r, qgemul_ep_args& ea)
     return QG_OK;
 }
 
+// what run_one_shot queues on the cache's stream: upload, pack, the chain's operands, execute, unpack, download
+int queue_one_shot(RunCache& c, const RunRequest& r)
+{
+    const qgemul_desc* d = r.d;
+    const bool ep = r.ev != nullptr;
+    const int64_t batch = r.batch;
+    const qgemul_opts& opts = r.opts;
+    qgemul_plan* p = c.plan;
+    hipStream_t s = c.ctx->stream;
+    int st = QG_OK;
+    // host elements of one member (the plain call: of the whole operand) and, from there, of all of them
+    const int64_t extA = qg_member_extent(*d, QG_OPERAND_A, opts.lda), extB = qg_member_extent(*d, QG_OPERAND_B, opts.ldb), extC = qg_member_extent(*d, QG_OPERAND_C, opts.ldc);
+    if (extA < 1 || extB < 1 || extC < 1) return QG_EINVAL;
+    const int64_t more = batch > 0 ? batch - 1 : 0;
+    const size_t bytesA = (size_t)(more * r.strideA + extA) * p->ha.size;
+    const size_t bytesB = (size_t)(more * r.strideB + extB) * p->hb.size;
+    const size_t bytesC = (size_t)(more * r.strideC + extC) * p->hc.size;
+    OperandBuffers b;
+    if ((st = cache_operand_buffers(c, bytesA, bytesB, bytesC, b))) return st;
+    if (hipMemcpyAsync(b.dA, r.A, bytesA, hipMemcpyHostToDevice, s) != hipSuccess || hipMemcpyAsync(b.dB, r.B, bytesB, hipMemcpyHostToDevice, s) != hipSuccess) return QG_EHIP;
+    // the caller's C may have gaps between columns (ldc > M) and between members: those bytes stay as they are
+    const bool gaps = (opts.ldc && opts.ldc != d->M) || (batch > 0 && r.strideC != d->M * d->N);
+    if (gaps && hipMemcpyAsync(b.dC, r.C, bytesC, hipMemcpyHostToDevice, s) != hipSuccess) return QG_EHIP;
+    if (batch > 0) {
+        if ((st = qgemul_pack_batched(p, QG_OPERAND_A, b.dA, opts.lda, r.strideA, b.pA)) || (st = qgemul_pack_batched(p, QG_OPERAND_B, b.dB, opts.ldb, r.strideB, b.pB))) return st;
+    } else {
+        if ((st = qgemul_pack(p, QG_OPERAND_A, b.dA, opts.lda, b.pA)) || (st = qgemul_pack(p, QG_OPERAND_B, b.dB, opts.ldb, b.pB))) return st;
+    }
+    const bool host_c = !batch && !ep && stores_host_c(p);   // the kernel's epilogue writes the reference layout: no packed C, no unpack pass
+    if (host_c) {
+        if ((st = qgemul_execute_host_c(p, b.dC, opts.ldc, b.pA, b.pB))) return st;
+    } else if (!ep) {
+        if ((st = batch > 0 ? qgemul_execute_batched(p, b.pC, b.pA, b.pB) : qgemul_execute(p, b.pC, b.pA, b.pB))) return st;
+    } else {
+        qgemul_ep_args ea;
+        if ((st = stage_chain_operands(c, r, ea))) return st;
+        if ((st = batch > 0 ? qgemul_execute_batched_ep(p, b.pC, b.pA, b.pB, &ea) : qgemul_execute_ep(p, b.pC, b.pA, b.pB, &ea))) return st;
+    }
+    if (!host_c && (st = batch > 0 ? qgemul_unpack_c_batched(p, b.pC, b.dC, opts.ldc, r.strideC) : qgemul_unpack_c(p, b.pC, b.dC, opts.ldc))) return st;
+    return hipMemcpyAsync(r.C, b.dC, bytesC, hipMemcpyDeviceToHost, s) == hipSuccess ? QG_OK : QG_EHIP;
+}
+
 int run_one_shot(const RunRequest& r)
 {
     const qgemul_desc* d = r.d;
     const EpView* ev = r.ev;
-    const qgemul_epilogue* ep = ev ? ev->re : nullptr;
     const int64_t batch = r.batch;
-    qgemul_opts opts = r.opts;
+    const uint32_t flags = r.opts.flags;
+    qgemul_info info;
+    auto classify = [&] { return batch > 0 ? classify_batched_view(d, batch, ev, r.bep, flags, &info, nullptr) : classify_view(d, ev, flags, &info); };
+    auto create = [&](qgemul_ctx* ctx, qgemul_plan** out) { return batch > 0 ? plan_create_batched_view(ctx, d, batch, ev, r.bep, flags, out) : plan_create_view(ctx, d, ev, flags, out); };
+    // the last argument check, shared by every entry point: each stage's operand is there (a stage count the classifier will refuse is
+    // read as far as the struct goes)
+    for (uint32_t k = 0; ev && k < ev->re->n_stages && k < QG_MAX_EW; ++k)
+        if (ev->re->stage[k].op != QG_EW_APPROX && (!r.E || !r.E[k])) return QG_EINVAL;   // (an APPROX stage reads no operand)
+    if (d->M == 0 || d->N == 0) return classify();   // nothing to compute: the request's own status, no device touched
     arm_reaper();
     RunCache& c = g_run;
-    if (opts.device < 0 && c.ctx) {   // "current device": follow hipSetDevice calls the caller made between two calls
-        int cur = c.device;
-        if (hipGetDevice(&cur) == hipSuccess) opts.device = cur;
-    }
-    qg_run_key_set(g_want, *d, opts.flags, batch, ev, r.bep);
-    const bool same_plan = c.plan && qg_run_key_equal(c.key, g_want) && (opts.device < 0 || opts.device == c.device);
-    if (!same_plan) {
-        // validate before touching the device so that descriptor errors are reported without a GPU
-        qgemul_info info;
-        const int st = batch > 0 ? classify_batched_view(d, batch, ev, r.bep, opts.flags, &info, nullptr) : classify_view(d, ev, opts.flags, &info);
-        if (st != QG_OK) return st;
-    }
-    if (ep)
-        for (uint32_t k = 0; k < ep->n_stages; ++k)
-            if (ep->stage[k].op != QG_EW_APPROX && (!r.E || !r.E[k])) return QG_EINVAL;   // (an APPROX stage reads no operand)
-    if (d->M == 0 || d->N == 0) return QG_OK;
-    int st = QG_OK;
-    const bool warm = c.ctx && (opts.device < 0 || opts.device == c.device);
-    if ((st = cache_context(c, opts.device))) return st;
-    if (warm) QG_HIP(hipSetDevice(c.device));
-    if (!same_plan) {
-        if (c.plan) { qgemul_plan_destroy(c.plan); c.plan = nullptr; }
-        st = batch > 0 ? plan_create_batched_view(c.ctx, d, batch, ev, r.bep, opts.flags, &c.plan) : plan_create_view(c.ctx, d, ev, opts.flags, &c.plan);
-        if (st != QG_OK) { c.plan = nullptr; return st; }
-        c.key = g_want;
-    }
-    qgemul_plan* p = c.plan;
-    void *dA, *dB, *dC, *pA, *pB, *pC;
-    do {
-        // host elements of one member (the plain call: of the whole operand) and, from there, of all of them
-        const int64_t extA = qg_member_extent(*d, QG_OPERAND_A, opts.lda), extB = qg_member_extent(*d, QG_OPERAND_B, opts.ldb), extC = qg_member_extent(*d, QG_OPERAND_C, opts.ldc);
-        if (extA < 1 || extB < 1 || extC < 1) { st = QG_EINVAL; break; }
-        const int64_t more = batch > 0 ? batch - 1 : 0;
-        const size_t bytesA = (size_t)(more * r.strideA + extA) * p->ha.size;
-        const size_t bytesB = (size_t)(more * r.strideB + extB) * p->hb.size;
-        const size_t bytesC = (size_t)(more * r.strideC + extC) * p->hc.size;
-        if ((st = cache_buffer(c, 0, bytesA, &dA)) || (st = cache_buffer(c, 1, bytesB, &dB)) || (st = cache_buffer(c, 2, bytesC, &dC)) ||
-            (st = cache_buffer(c, 3, (size_t)p->info.packed_bytes[0], &pA)) || (st = cache_buffer(c, 4, (size_t)p->info.packed_bytes[1], &pB)) ||
-            (st = cache_buffer(c, 5, (size_t)p->info.packed_bytes[2], &pC)))
-            break;
-        hipStream_t s = c.ctx->stream;
-        // everything below is queued on the context's stream; ONE synchronisation at the end (the source buffers are the
-        // caller's and the call is synchronous, so they stay valid until then)
-        if (hipMemcpyAsync(dA, r.A, bytesA, hipMemcpyHostToDevice, s) != hipSuccess || hipMemcpyAsync(dB, r.B, bytesB, hipMemcpyHostToDevice, s) != hipSuccess) { st = QG_EHIP; break; }
-        // the caller's C may have gaps between columns (ldc > M) and between members: those bytes stay as they are
-        const bool gaps = (opts.ldc && opts.ldc != d->M) || (batch > 0 && r.strideC != d->M * d->N);
-        if (gaps && hipMemcpyAsync(dC, r.C, bytesC, hipMemcpyHostToDevice, s) != hipSuccess) { st = QG_EHIP; break; }
-        if (batch > 0) {
-            if ((st = qgemul_pack_batched(p, QG_OPERAND_A, dA, opts.lda, r.strideA, pA)) || (st = qgemul_pack_batched(p, QG_OPERAND_B, dB, opts.ldb, r.strideB, pB))) break;
-        } else {
-            if ((st = qgemul_pack(p, QG_OPERAND_A, dA, opts.lda, pA)) || (st = qgemul_pack(p, QG_OPERAND_B, dB, opts.ldb, pB))) break;
-        }
-        if (!batch && !ep && stores_host_c(p)) {
-            // the kernel's epilogue writes the reference layout: no packed C, no unpack pass
-            if ((st = qgemul_execute_host_c(p, dC, opts.ldc, pA, pB))) break;
-            if (hipMemcpyAsync(r.C, dC, bytesC, hipMemcpyDeviceToHost, s) != hipSuccess) { st = QG_EHIP; break; }
-            break;
-        }
-        if (!ep) {
-            if ((st = batch > 0 ? qgemul_execute_batched(p, pC, pA, pB) : qgemul_execute(p, pC, pA, pB))) break;
-        } else {
-            qgemul_ep_args ea;
-            if ((st = stage_chain_operands(c, r, ea))) break;
-            if ((st = batch > 0 ? qgemul_execute_batched_ep(p, pC, pA, pB, &ea) : qgemul_execute_ep(p, pC, pA, pB, &ea))) break;
-        }
-        if ((st = batch > 0 ? qgemul_unpack_c_batched(p, pC, dC, opts.ldc, r.strideC) : qgemul_unpack_c(p, pC, dC, opts.ldc))) break;
-        if (hipMemcpyAsync(r.C, dC, bytesC, hipMemcpyDeviceToHost, s) != hipSuccess) { st = QG_EHIP; break; }
-    } while (0);
-    const hipError_t e = hipStreamSynchronize(c.ctx->stream);
-    if (st == QG_OK && e != hipSuccess) { qg_set_last_hip((int)e); st = QG_EHIP; }
-    return st;
+    qg_run_key_set(g_want, *d, flags, batch, ev, r.bep);
+    if (const int st = acquire_plan(c, r.opts.device, g_want, classify, create)) return st;
+    return finish(c, queue_one_shot(c, r));
 }
 
 // the plain call: QG_OPT_ALL_DEVICES goes to the sharded entry (without a chain: the element-wise chain runs on one device)
@@ -290,6 +329,180 @@ int batched_args_ok(const qgemul_desc& d, const qgemul_opts& opts, int64_t strid
     const int64_t extA = qg_member_extent(d, QG_OPERAND_A, opts.lda), extB = qg_member_extent(d, QG_OPERAND_B, opts.ldb), extC = qg_member_extent(d, QG_OPERAND_C, opts.ldc);
     if (extA < 1 || extB < 1 || extC < 1 || strideA < extA || strideB < extB || strideC < extC) return QG_EINVAL;
     return QG_OK;
+}
+
+// ---- the grouped one-shot call: `groups` GEMMs of different shapes, beside run_one_shot ----
+// The plan lives in the calling thread's one-plan cache like every other one-shot plan; its key holds the WHOLE descriptor list.
+// ev: the group's one element-wise chain (nullptr: none; then gep, E and scalars are not read and C is C); with one, C is D, E[k][g] is
+// member g's tight operand of tensor stage k (one element for a scalar stage that is not per member) and scalars[k] the per-member
+// values of stage k
+struct GroupedRequest {
+    const qgemul_desc* d;
+    int64_t groups;
+    const EpView* ev;
+    const qgemul_grouped_ep* gep;
+    void* const* C;   // (with a chain: D)
+    const void* const *A, *const *B;
+    const void* const* const* E;
+    const int64_t* const* scalars;
+    const int64_t *lda, *ldb, *ldc;
+};
+bool empty_member(const qgemul_desc& d) { return d.M == 0 || d.N == 0; }
+
+// The host-only argument checks, made before anything else.  per: which scalar stages take a value per member, as 0 / 1 over the chain's
+// stages (the cache key's and the layout's form of gep); gaps: a leading dimension of C leaves bytes between columns
+int grouped_args_ok(const GroupedRequest& r, const qgemul_opts& opts, qgemul_grouped_ep& per, bool& gaps)
+{
+    const qgemul_desc* d = r.d;
+    if (!d || !r.C || !r.A || !r.B || r.groups < 1 || r.groups > 0x7fffffffll) return QG_EINVAL;
+    if (opts.flags & QG_OPT_ALL_DEVICES) return QG_EUNSUPPORTED;   // (the sharded entry has no grouped form)
+    const qgemul_epilogue* ep = r.ev ? r.ev->re : nullptr;
+    if (ep && ep->n_stages > QG_MAX_EW) return QG_EINVAL;
+    memset(&per, 0, sizeof per);
+    for (uint32_t k = 0; ep && k < ep->n_stages; ++k) {
+        const qgemul_ew_stage& s = ep->stage[k];
+        per.scalar_per_member[k] = r.gep && r.gep->scalar_per_member[k] ? 1 : 0;
+        if (s.op == QG_EW_APPROX) continue;
+        if (per.scalar_per_member[k] ? (!r.scalars || !r.scalars[k]) : (!r.E || !r.E[k])) return QG_EINVAL;
+        for (int64_t g = 0; !per.scalar_per_member[k] && g < r.groups; ++g)
+            if (!empty_member(d[g]) && !r.E[k][s.e_scalar ? 0 : g]) return QG_EINVAL;
+    }
+    gaps = false;
+    for (int64_t g = 0; g < r.groups; ++g) {
+        if (empty_member(d[g])) continue;   // (skipped everywhere: its pointers may be null)
+        if (!r.C[g] || !r.A[g] || !r.B[g]) return QG_EINVAL;
+        if (qg_member_extent(d[g], QG_OPERAND_A, r.lda ? r.lda[g] : 0) < 1 || qg_member_extent(d[g], QG_OPERAND_B, r.ldb ? r.ldb[g] : 0) < 1 ||
+            qg_member_extent(d[g], QG_OPERAND_C, r.ldc ? r.ldc[g] : 0) < 1)
+            return QG_EINVAL;
+        gaps |= r.ldc && r.ldc[g] && r.ldc[g] != d[g].M;
+    }
+    return QG_OK;
+}
+
+// Where the members' host-layout tensors stand on the device: per tensor (A, B, C or D, then the chain's tensor operand of stage k at
+// 3 + k) the members back to back in that tensor's buffer, every start 256-byte aligned.  Computed once; the uploads, the entry points'
+// pointer arrays and the download read it.  An empty member, and every member of a stage without a tensor operand, has 0 bytes.
+struct GroupedLayout {
+    enum { NT = 3 + QG_MAX_EW };
+    struct Span { int64_t off, bytes; };
+    int64_t groups = 0;
+    std::unique_ptr<Span[]> span;        // [t * groups + g]
+    std::unique_ptr<const void*[]> ptr;  // [t * groups + g]: the member's device address once place() has the buffer (0 bytes: nullptr)
+    int64_t total[NT] = {};
+    const Span& at(int t, int64_t g) const { return span[t * groups + g]; }
+    const void** ptrs(int t) const { return &ptr[t * groups]; }
+    void place(int t, void* base)
+    {
+        for (int64_t g = 0; g < groups; ++g) ptr[t * groups + g] = at(t, g).bytes ? (const char*)base + at(t, g).off : nullptr;
+    }
+};
+bool grouped_layout(GroupedLayout& L, const GroupedRequest& r, const qgemul_grouped_ep& per)
+{
+    const qgemul_epilogue* ep = r.ev ? r.ev->re : nullptr;
+    const int64_t n = L.groups = r.groups;
+    L.span.reset(new (std::nothrow) GroupedLayout::Span[GroupedLayout::NT * n]);
+    L.ptr.reset(new (std::nothrow) const void*[GroupedLayout::NT * n]());
+    if (!L.span || !L.ptr) return false;
+    const int64_t* const ld[3] = {r.lda, r.ldb, r.ldc};
+    for (int t = 0; t < GroupedLayout::NT; ++t) {
+        const qgemul_ew_stage* sk = t >= 3 && ep && (uint32_t)(t - 3) < ep->n_stages ? &ep->stage[t - 3] : nullptr;
+        const bool tensor = t < 3 || (sk && sk->op != QG_EW_APPROX && !sk->e_scalar && !per.scalar_per_member[t - 3]);
+        for (int64_t g = 0; g < n; ++g) {
+            const qgemul_desc& m = r.d[g];
+            int64_t bytes = 0;
+            if (tensor && !empty_member(m)) {
+                if (t < 3) {
+                    // (with a chain the third tensor is D: elements of the chain's destination format)
+                    const qfmt fd[2] = {ep ? ep->d : m.c[0], ep ? ep->d : m.c[1]};
+                    const qfmt* f = t == 0 ? m.a : t == 1 ? m.b : fd;
+                    bytes = qg_member_extent(m, t, ld[t] ? ld[t][g] : 0) * (int64_t)qg_host_elem(f, m.is_complex).size;
+                } else {
+                    const qfmt fe[2] = {sk->e, sk->e};
+                    bytes = m.M * m.N * (int64_t)qg_host_elem(fe, 0).size;   // (stage operands are tight)
+                }
+            }
+            L.span[t * n + g] = {L.total[t], bytes};
+            L.total[t] += (bytes + 255) / 256 * 256;
+        }
+    }
+    return true;
+}
+
+// the grouped chain's operands: scalars from the caller's one element into ea or per member into the plan's table, tensors up to the
+// device member by member (slots 6 + 2k) and packed (slots 7 + 2k)
+int stage_grouped_chain_operands(RunCache& c, const GroupedRequest& r, const qgemul_grouped_ep& per, GroupedLayout& L, qgemul_ep_args& ea)
+{
+    const qgemul_epilogue* ep = r.ev->re;
+    qgemul_plan* p = c.plan;
+    hipStream_t s = c.ctx->stream;
+    int st = QG_OK;
+    memset(&ea, 0, sizeof ea);
+    for (uint32_t k = 0; k < ep->n_stages; ++k) {
+        const qgemul_ew_stage& sk = ep->stage[k];
+        if (sk.op == QG_EW_APPROX) continue;
+        if (per.scalar_per_member[k]) {
+            if ((st = qgemul_grouped_set_scalars(p, (int)k, r.scalars[k]))) return st;
+            continue;
+        }
+        if (sk.e_scalar) { ea.e_scalar[k] = raw_scalar(r.E[k][0], sk.e); continue; }
+        const int t = 3 + (int)k;
+        void *dE, *pE;
+        if ((st = cache_buffer(c, 6 + 2 * (int)k, (size_t)L.total[t], &dE)) || (st = cache_buffer(c, 7 + 2 * (int)k, (size_t)qgemul_packed_e_bytes(p, (int)k), &pE))) return st;
+        L.place(t, dE);
+        for (int64_t g = 0; g < L.groups; ++g)
+            if (L.at(t, g).bytes && hipMemcpyAsync((void*)L.ptrs(t)[g], r.E[k][g], (size_t)L.at(t, g).bytes, hipMemcpyHostToDevice, s) != hipSuccess) return QG_EHIP;
+        if ((st = qgemul_pack_e_grouped(p, (int)k, L.ptrs(t), nullptr, pE))) return st;
+        ea.e_packed[k] = pE;
+    }
+    return QG_OK;
+}
+
+// what run_grouped queues on the cache's stream: upload, the chain's operands, pack, execute, unpack, download
+int queue_grouped(RunCache& c, const GroupedRequest& r, const qgemul_grouped_ep& per, bool gaps)
+{
+    qgemul_plan* p = c.plan;
+    hipStream_t s = c.ctx->stream;
+    int st = QG_OK;
+    GroupedLayout L;
+    if (!grouped_layout(L, r, per)) return QG_EINVAL;
+    OperandBuffers b;
+    if ((st = cache_operand_buffers(c, (size_t)L.total[0], (size_t)L.total[1], (size_t)L.total[2], b))) return st;
+    void* const base[3] = {b.dA, b.dB, b.dC};
+    const void* const* const host[3] = {r.A, r.B, (const void* const*)r.C};
+    for (int t = 0; t < 3; ++t) {
+        L.place(t, base[t]);
+        if (t == 2 && !gaps) continue;   // C goes up only where a leading dimension leaves bytes between columns: they stay as they are
+        for (int64_t g = 0; g < L.groups; ++g)
+            if (L.at(t, g).bytes && hipMemcpyAsync((void*)L.ptrs(t)[g], host[t][g], (size_t)L.at(t, g).bytes, hipMemcpyHostToDevice, s) != hipSuccess) return QG_EHIP;
+    }
+    qgemul_ep_args ea;
+    if (r.ev && (st = stage_grouped_chain_operands(c, r, per, L, ea))) return st;
+    if ((st = qgemul_pack_grouped(p, QG_OPERAND_A, L.ptrs(0), r.lda, b.pA)) || (st = qgemul_pack_grouped(p, QG_OPERAND_B, L.ptrs(1), r.ldb, b.pB)) ||
+        (st = r.ev ? qgemul_execute_grouped_ep(p, b.pC, b.pA, b.pB, &ea) : qgemul_execute_grouped(p, b.pC, b.pA, b.pB)) ||
+        (st = qgemul_unpack_c_grouped(p, b.pC, (void* const*)L.ptrs(2), r.ldc)))
+        return st;
+    for (int64_t g = 0; g < L.groups; ++g)
+        if (L.at(2, g).bytes && hipMemcpyAsync(r.C[g], L.ptrs(2)[g], (size_t)L.at(2, g).bytes, hipMemcpyDeviceToHost, s) != hipSuccess) return QG_EHIP;
+    return QG_OK;
+}
+
+int run_grouped(const GroupedRequest& r, const qgemul_opts* o)
+{
+    const qgemul_opts opts = resolve_opts(o);
+    qgemul_grouped_ep per;
+    bool gaps;
+    if (const int st = grouped_args_ok(r, opts, per, gaps)) return st;
+    const EpView* ev = r.ev;
+    qgemul_info info;
+    auto classify = [&] { return ev ? qgemul_classify_grouped_epx(r.d, r.groups, ev->re, ev->ax, r.gep, opts.flags, &info) : qgemul_classify_grouped(r.d, r.groups, opts.flags, &info); };
+    auto create = [&](qgemul_ctx* ctx, qgemul_plan** out) {
+        return ev ? qgemul_plan_create_grouped_epx(ctx, r.d, r.groups, ev->re, ev->ax, r.gep, opts.flags, out) : qgemul_plan_create_grouped(ctx, r.d, r.groups, opts.flags, out);
+    };
+    arm_reaper();
+    RunCache& c = g_run;
+    qg_run_key_set_grouped(g_want, r.d, r.groups, opts.flags, ev, &per);
+    if (const int st = acquire_plan(c, opts.device, g_want, classify, create)) return st;
+    return finish(c, queue_grouped(c, r, per, gaps));
 }
 } // namespace
 
@@ -377,179 +590,11 @@ int qgemul_run_batched_epx(const qgemul_desc* d, int64_t batch, const qgemul_epi
 }
 
 // ---- grouped Qgemul: `groups` GEMMs of different shapes (include/qgemul.h) ----
-// The plan lives in the calling thread's one-plan cache, keyed on the WHOLE descriptor list: g_grp_key holds the list the cached
-// plan was made from, and the cache's QRunKey marks the plan as a grouped one (batch = -groups: no plain or batched request has it).
-namespace {
-struct GrpKey {
-    qgemul_desc* d = nullptr;
-    int64_t n = 0;
-    ~GrpKey() { delete[] d; }
-};
-thread_local GrpKey g_grp_key;
-bool grp_key_equal(const qgemul_desc* d, int64_t groups)
-{
-    if (g_grp_key.n != groups || !g_grp_key.d) return false;
-    for (int64_t g = 0; g < groups; ++g)
-        if (!same_desc(g_grp_key.d[g], d[g])) return false;
-    return true;
-}
-int64_t up256(int64_t x) { return (x + 255) / 256 * 256; }
-} // namespace
-
-// ev: the group's one element-wise chain (nullptr: none; then gep, E and scalars are not read and C is C); with one, C is D, E[k][g] is
-// member g's tight operand of tensor stage k (one element for a scalar stage that is not per member) and scalars[k] the per-member
-// values of stage k.  The cache key holds the chain and, in the place of a batched chain's shared pattern, the per-member pattern
-static int run_grouped_view(const qgemul_desc* d, int64_t groups, const EpView* ev, const qgemul_grouped_ep* gep, void* const* C, const void* const* A,
-                            const void* const* B, const void* const* const* E, const int64_t* const* scalars, const int64_t* lda, const int64_t* ldb,
-                            const int64_t* ldc, const qgemul_opts* o)
-{
-    if (!d || !C || !A || !B || groups < 1 || groups > 0x7fffffffll) return QG_EINVAL;
-    qgemul_opts opts = resolve_opts(o);
-    if (opts.flags & QG_OPT_ALL_DEVICES) return QG_EUNSUPPORTED;   // (the sharded entry has no grouped form)
-    const qgemul_epilogue* ep = ev ? ev->re : nullptr;
-    if (ep && ep->n_stages > QG_MAX_EW) return QG_EINVAL;
-    qgemul_batched_ep pattern;
-    memset(&pattern, 0, sizeof pattern);
-    for (uint32_t k = 0; ep && k < ep->n_stages; ++k) {
-        const qgemul_ew_stage& s = ep->stage[k];
-        const bool per = gep && gep->scalar_per_member[k];
-        pattern.e_shared[k] = per ? 1 : 0;
-        if (s.op == QG_EW_APPROX) continue;
-        if (per ? (!scalars || !scalars[k]) : (!E || !E[k])) return QG_EINVAL;
-        for (int64_t g = 0; !per && g < groups; ++g)
-            if (!(d[g].M == 0 || d[g].N == 0) && !E[k][s.e_scalar ? 0 : g]) return QG_EINVAL;
-    }
-    bool gaps = false;
-    for (int64_t g = 0; g < groups; ++g) {
-        if (d[g].M == 0 || d[g].N == 0) continue;
-        if (!C[g] || !A[g] || !B[g]) return QG_EINVAL;
-        if (qg_member_extent(d[g], QG_OPERAND_A, lda ? lda[g] : 0) < 1 || qg_member_extent(d[g], QG_OPERAND_B, ldb ? ldb[g] : 0) < 1 ||
-            qg_member_extent(d[g], QG_OPERAND_C, ldc ? ldc[g] : 0) < 1)
-            return QG_EINVAL;
-        gaps |= ldc && ldc[g] && ldc[g] != d[g].M;
-    }
-    arm_reaper();
-    RunCache& c = g_run;
-    if (opts.device < 0 && c.ctx) {
-        int cur = c.device;
-        if (hipGetDevice(&cur) == hipSuccess) opts.device = cur;
-    }
-    qg_run_key_set(g_want, d[0], opts.flags, -groups, ev, ev ? &pattern : nullptr);
-    const bool same_plan = c.plan && qg_run_key_equal(c.key, g_want) && grp_key_equal(d, groups) && (opts.device < 0 || opts.device == c.device);
-    if (!same_plan) {   // validate before touching the device
-        qgemul_info info;
-        const int st = ev ? qgemul_classify_grouped_epx(d, groups, ep, ev->ax, gep, opts.flags, &info) : qgemul_classify_grouped(d, groups, opts.flags, &info);
-        if (st != QG_OK) return st;
-    }
-    int st = QG_OK;
-    const bool warm = c.ctx && (opts.device < 0 || opts.device == c.device);
-    if ((st = cache_context(c, opts.device))) return st;
-    if (warm) QG_HIP(hipSetDevice(c.device));
-    if (!same_plan) {
-        if (c.plan) { qgemul_plan_destroy(c.plan); c.plan = nullptr; }
-        st = ev ? qgemul_plan_create_grouped_epx(c.ctx, d, groups, ep, ev->ax, gep, opts.flags, &c.plan) : qgemul_plan_create_grouped(c.ctx, d, groups, opts.flags, &c.plan);
-        if (st != QG_OK) { c.plan = nullptr; return st; }
-        c.key = g_want;
-        delete[] g_grp_key.d;
-        g_grp_key.d = new (std::nothrow) qgemul_desc[groups];
-        g_grp_key.n = g_grp_key.d ? groups : 0;
-        for (int64_t g = 0; g < g_grp_key.n; ++g) g_grp_key.d[g] = d[g];
-    }
-    qgemul_plan* p = c.plan;
-    // the members' host-layout tensors back to back on the device, every start 256-byte aligned
-    int64_t* off = new (std::nothrow) int64_t[3 * groups + 3];
-    const void** dptr = new (std::nothrow) const void*[3 * groups];
-    do {
-        if (!off || !dptr) { st = QG_EINVAL; break; }
-        int64_t tot[3] = {0, 0, 0};
-        for (int64_t g = 0; g < groups; ++g) {
-            const bool empty = d[g].M == 0 || d[g].N == 0;
-            const int64_t ld[3] = {lda ? lda[g] : 0, ldb ? ldb[g] : 0, ldc ? ldc[g] : 0};
-            for (int w = 0; w < 3; ++w) {
-                off[3 * g + w] = tot[w];
-                const qfmt* f = w == 0 ? d[g].a : w == 1 ? d[g].b : d[g].c;
-                // (with a chain the third tensor is D: elements of the chain's destination format)
-                const qfmt fd[2] = {ep ? ep->d : d[g].c[0], ep ? ep->d : d[g].c[1]};
-                if (!empty) tot[w] += up256(qg_member_extent(d[g], w, ld[w]) * (int64_t)qg_host_elem(w == 2 ? fd : f, d[g].is_complex).size);
-            }
-        }
-        void *dA, *dB, *dC, *pA, *pB, *pC;
-        if ((st = cache_buffer(c, 0, (size_t)tot[0], &dA)) || (st = cache_buffer(c, 1, (size_t)tot[1], &dB)) || (st = cache_buffer(c, 2, (size_t)tot[2], &dC)) ||
-            (st = cache_buffer(c, 3, (size_t)p->info.packed_bytes[0], &pA)) || (st = cache_buffer(c, 4, (size_t)p->info.packed_bytes[1], &pB)) ||
-            (st = cache_buffer(c, 5, (size_t)p->info.packed_bytes[2], &pC)))
-            break;
-        hipStream_t s = c.ctx->stream;
-        void* base[3] = {dA, dB, dC};
-        auto bytes_of = [&](int64_t g, int w) {
-            const int64_t ld = w == 0 ? (lda ? lda[g] : 0) : w == 1 ? (ldb ? ldb[g] : 0) : (ldc ? ldc[g] : 0);
-            const qfmt fd[2] = {ep ? ep->d : d[g].c[0], ep ? ep->d : d[g].c[1]};
-            const qfmt* f = w == 0 ? d[g].a : w == 1 ? d[g].b : fd;
-            return (size_t)(qg_member_extent(d[g], w, ld) * (int64_t)qg_host_elem(f, d[g].is_complex).size);
-        };
-        for (int64_t g = 0; g < groups && st == QG_OK; ++g) {
-            const bool empty = d[g].M == 0 || d[g].N == 0;
-            for (int w = 0; w < 3; ++w) dptr[3 * g + w] = empty ? nullptr : (const char*)base[w] + off[3 * g + w];
-            if (empty) continue;
-            if (hipMemcpyAsync((void*)dptr[3 * g], A[g], bytes_of(g, 0), hipMemcpyHostToDevice, s) != hipSuccess ||
-                hipMemcpyAsync((void*)dptr[3 * g + 1], B[g], bytes_of(g, 1), hipMemcpyHostToDevice, s) != hipSuccess ||
-                (gaps && hipMemcpyAsync((void*)dptr[3 * g + 2], C[g], bytes_of(g, 2), hipMemcpyHostToDevice, s) != hipSuccess))   // (bytes between columns stay)
-                st = QG_EHIP;
-        }
-        if (st != QG_OK) break;
-        // (the pointer arrays of the entry points: one per operand)
-        const void** pa_ = new (std::nothrow) const void*[3 * groups];
-        if (!pa_) { st = QG_EINVAL; break; }
-        for (int64_t g = 0; g < groups; ++g)
-            for (int w = 0; w < 3; ++w) pa_[w * groups + g] = dptr[3 * g + w];
-        // the chain's operands: scalars from the caller's one element or into the plan's table, tensors staged and packed member by member
-        qgemul_ep_args ea;
-        memset(&ea, 0, sizeof ea);
-        auto raw = [](const void* q, qfmt f) { return (1 + (int)f.I + (int)f.F) <= 32 ? (int64_t) * (const int32_t*)q : *(const int64_t*)q; };
-        const void** pe_ = ep ? new (std::nothrow) const void*[groups] : nullptr;
-        if (ep && !pe_) st = QG_EINVAL;
-        for (uint32_t k = 0; ep && k < ep->n_stages && st == QG_OK; ++k) {
-            const qgemul_ew_stage& sk = ep->stage[k];
-            if (sk.op == QG_EW_APPROX) continue;
-            if (pattern.e_shared[k]) { st = qgemul_grouped_set_scalars(p, (int)k, scalars[k]); continue; }
-            if (sk.e_scalar) { ea.e_scalar[k] = raw(E[k][0], sk.e); continue; }
-            const qfmt fe[2] = {sk.e, sk.e};
-            const int64_t eb = qg_host_elem(fe, 0).size;
-            int64_t totE = 0;
-            for (int64_t g = 0; g < groups; ++g) totE += d[g].M == 0 || d[g].N == 0 ? 0 : up256(d[g].M * d[g].N * eb);
-            void *dE, *pE;
-            if ((st = cache_buffer(c, 6 + 2 * (int)k, (size_t)totE, &dE)) || (st = cache_buffer(c, 7 + 2 * (int)k, (size_t)qgemul_packed_e_bytes(p, (int)k), &pE))) break;
-            int64_t at = 0;
-            for (int64_t g = 0; g < groups && st == QG_OK; ++g) {
-                pe_[g] = nullptr;
-                if (d[g].M == 0 || d[g].N == 0) continue;
-                pe_[g] = (const char*)dE + at;
-                if (hipMemcpyAsync((void*)pe_[g], E[k][g], (size_t)(d[g].M * d[g].N * eb), hipMemcpyHostToDevice, s) != hipSuccess) st = QG_EHIP;
-                at += up256(d[g].M * d[g].N * eb);
-            }
-            if (st == QG_OK) st = qgemul_pack_e_grouped(p, (int)k, pe_, nullptr, pE);
-            ea.e_packed[k] = pE;
-        }
-        delete[] pe_;
-        if (st == QG_OK && !(st = qgemul_pack_grouped(p, QG_OPERAND_A, pa_, lda, pA)) && !(st = qgemul_pack_grouped(p, QG_OPERAND_B, pa_ + groups, ldb, pB)) &&
-            !(st = ep ? qgemul_execute_grouped_ep(p, pC, pA, pB, &ea) : qgemul_execute_grouped(p, pC, pA, pB)))
-            st = qgemul_unpack_c_grouped(p, pC, (void* const*)(pa_ + 2 * groups), ldc);
-        delete[] pa_;
-        for (int64_t g = 0; g < groups && st == QG_OK; ++g) {
-            if (d[g].M == 0 || d[g].N == 0) continue;
-            if (hipMemcpyAsync(C[g], dptr[3 * g + 2], bytes_of(g, 2), hipMemcpyDeviceToHost, s) != hipSuccess) st = QG_EHIP;
-        }
-    } while (0);
-    const hipError_t e = hipStreamSynchronize(c.ctx->stream);
-    delete[] off;
-    delete[] dptr;
-    if (st == QG_OK && e != hipSuccess) { qg_set_last_hip((int)e); st = QG_EHIP; }
-    return st;
-}
-
 int qgemul_run_grouped(const qgemul_desc* d, int64_t groups, void* const* C, const void* const* A, const void* const* B, const int64_t* lda,
                        const int64_t* ldb, const int64_t* ldc, const qgemul_opts* o)
 {
-    return run_grouped_view(d, groups, nullptr, nullptr, C, A, B, nullptr, nullptr, lda, ldb, ldc, o);
+    const GroupedRequest r = {d, groups, nullptr, nullptr, C, A, B, nullptr, nullptr, lda, ldb, ldc};
+    return run_grouped(r, o);
 }
 
 // ... followed by ONE real element-wise chain with per-member scalars: member g is Qgemul<...>(C_g, A_g, B_g), then the chain
@@ -560,7 +605,8 @@ int qgemul_run_grouped_epx(const qgemul_desc* d, int64_t groups, const qgemul_ep
     if (!ep) return QG_EINVAL;
     static const qgemul_approx* const no_ax[QG_MAX_EW] = {};   // (ax == nullptr: a chain without APPROX stages)
     const EpView v = {ep, nullptr, nullptr, ax ? ax : no_ax};
-    return run_grouped_view(d, groups, &v, gep, D, A, B, E, scalars, lda, ldb, ldd, o);
+    const GroupedRequest r = {d, groups, &v, gep, D, A, B, E, scalars, lda, ldb, ldd};
+    return run_grouped(r, o);
 }
 
 // ---- several GPUs in one process: row bands of C, one per entry of the device list (include/qgemul.h) ----
@@ -571,9 +617,7 @@ int qgemul_run_sharded(const qgemul_desc* d, void* C, const void* A, const void*
 {
     if (!d || !C || !A || !B || !devices || n < 1 || n > QG_MAX_SHARDS) return QG_EINVAL;
     arm_reaper();
-    qgemul_opts opts;
-    memset(&opts, 0, sizeof opts);
-    if (o) opts = *o;
+    qgemul_opts opts = resolve_opts(o);   // (opts.device is not read below: the device list names the devices)
     opts.flags &= ~(uint32_t)QG_OPT_ALL_DEVICES;
     {   // validate the whole problem before touching a device (a band of an unsupported descriptor is unsupported too)
         qgemul_info info;
@@ -636,12 +680,7 @@ int qgemul_run_sharded(const qgemul_desc* d, void* C, const void* A, const void*
         qgemul_desc bd = *d;
         bd.M = rows[i];
         qg_run_key_set(g_want, bd, opts.flags, 0, nullptr, nullptr);   // the band's plain plan
-        if (!(c.plan && qg_run_key_equal(c.key, g_want))) {
-            if (c.plan) { qgemul_plan_destroy(c.plan); c.plan = nullptr; }
-            st = qgemul_plan_create(c.ctx, &bd, opts.flags, &c.plan);
-            if (st != QG_OK) { c.plan = nullptr; break; }
-            c.key = g_want;
-        }
+        if ((st = install_plan(c, g_want, [&](qgemul_ctx* ctx, qgemul_plan** out) { return qgemul_plan_create(ctx, &bd, opts.flags, out); }))) break;
         qgemul_plan* p = c.plan;
         hipStream_t s = c.ctx->stream;
         const size_t ea = (size_t)p->ha.size, eb = (size_t)p->hb.size;

@@ -11,13 +11,16 @@
 // an element-wise chain as the planner sees it: a real chain (im == nullptr) or the two part chains of a complex one
 struct EpView { const qgemul_epilogue* re; const qgemul_epilogue* im; const uint8_t* e_cplx; const qgemul_approx* const* ax; const qgemul_epilogue_cplx* epc; const qgemul_cmul* const* cx; };
 
-// The key of a cached plan: every input the plan was made from.  qg_run_key_set writes EVERY field — what a request does not have is
+// The key of a cached plan: every input the plan was made from.  The setters write EVERY field — what a request does not have is
 // written as zero / off —, so no field keeps an earlier plan's value, and qg_run_key_equal needs no knowledge of which entry point
-// stored the key.  The tables of APPROX stages (2.3 KB each) live on the heap, present only while a stage carries one.
+// stored the key.  The tables of APPROX stages (2.3 KB each) and a grouped request's descriptor list live on the heap, present only
+// while a stage carries a table / the request is a grouped one.
 struct QRunKey {
-    qgemul_desc d;
+    qgemul_desc d;                    // the plain or batched request's descriptor (a grouped request: zero, its descriptors are `member`)
     uint32_t flags;
-    int64_t batch;                    // 0: a plain plan; > 0: a batched plan of that many members
+    int64_t batch;                    // 0: not a batched plan; > 0: a batched plan of that many members
+    int64_t groups;                   // 0: not a grouped plan; > 0: a grouped plan of that many members
+    qgemul_desc* member;              // the group's descriptors in list order: `groups` entries, allocated while groups > 0
     uint8_t has_ep, ep_cplx;          // a chain; ... of a complex GEMM (both part chains)
     qgemul_epilogue part[2];          // a real chain is part[0]
     uint8_t e_complex[QG_MAX_EW];
@@ -25,23 +28,28 @@ struct QRunKey {
     qgemul_approx* ax;                // QG_MAX_EW tables, allocated while any ax_on[k]
     uint8_t cx_on[QG_MAX_EW];         // stage k carries a CMUL record: cx[k]
     qgemul_cmul cx[QG_MAX_EW];
-    uint8_t e_shared[QG_MAX_EW];      // batched chain: stage k's tensor operand is one tensor for every member; grouped chain (batch < 0):
-                                      // scalar stage k takes one value per member (qgemul_grouped_ep::scalar_per_member)
+    uint8_t e_shared[QG_MAX_EW];            // batched chain: stage k's tensor operand is one tensor for every member
+    uint8_t scalar_per_member[QG_MAX_EW];   // grouped chain: scalar stage k takes one value per member
 
     QRunKey() { memset((void*)this, 0, sizeof *this); }
     QRunKey(const QRunKey& o) : QRunKey() { *this = o; }
-    ~QRunKey() { delete[] ax; }
+    ~QRunKey() { delete[] ax; delete[] member; }
     QRunKey& operator=(const QRunKey& o)
     {
         if (this == &o) return *this;
-        qgemul_approx* mine = ax;
+        const Heap mine = heap();
         memcpy((void*)this, (const void*)&o, sizeof *this);
-        ax = mine;
+        keep(mine);
         const qgemul_approx* from[QG_MAX_EW];
         for (int k = 0; k < QG_MAX_EW; ++k) from[k] = ax_on[k] ? &o.ax[k] : nullptr;
         tables(from);
+        members(o.member, o.groups);
         return *this;
     }
+    // what this key owns on the heap, carried over a memset / memcpy of the whole object (groups: the length `member` is allocated at)
+    struct Heap { qgemul_approx* ax; qgemul_desc* member; int64_t groups; };
+    Heap heap() const { return {ax, member, groups}; }
+    void keep(const Heap& h) { ax = h.ax; member = h.member; groups = h.groups; }
     // this key's own copy of the tables that ax_on names (none: no allocation)
     void tables(const qgemul_approx* const* from)
     {
@@ -52,15 +60,29 @@ struct QRunKey {
         for (int k = 0; k < QG_MAX_EW; ++k)
             if (ax_on[k]) ax[k] = *from[k];
     }
+    // this key's own copy of a group's n descriptors (n == 0, a request that is not grouped: no allocation)
+    void members(const qgemul_desc* from, int64_t n)
+    {
+        if (n != groups) {
+            delete[] member;
+            member = nullptr;   // (the key stays whole if the allocation throws)
+            groups = 0;
+            if (n) member = new qgemul_desc[n];
+            groups = n;
+        }
+        for (int64_t g = 0; g < n; ++g) member[g] = from[g];
+    }
 };
 
-// ev: the chain (nullptr: none); bep: which tensor operands of a batched chain are shared (nullptr: none)
-inline void qg_run_key_set(QRunKey& key, const qgemul_desc& d, uint32_t flags, int64_t batch, const EpView* ev, const qgemul_batched_ep* bep)
+// The one body of the two setters below.  d: `groups` descriptors of a grouped request, one otherwise (groups == 0)
+inline void qg_run_key_write(QRunKey& key, const qgemul_desc* d, int64_t groups, uint32_t flags, int64_t batch, const EpView* ev, const qgemul_batched_ep* bep,
+                             const qgemul_grouped_ep* gep)
 {
-    qgemul_approx* mine = key.ax;
+    const QRunKey::Heap mine = key.heap();
     memset((void*)&key, 0, sizeof key);
-    key.ax = mine;
-    key.d = d;
+    key.keep(mine);
+    if (!groups) key.d = *d;
+    key.members(d, groups);
     key.flags = flags;
     key.batch = batch;
     if (ev) {
@@ -78,6 +100,18 @@ inline void qg_run_key_set(QRunKey& key, const qgemul_desc& d, uint32_t flags, i
     }
     key.tables(ev ? ev->ax : nullptr);
     if (bep) memcpy(key.e_shared, bep->e_shared, sizeof key.e_shared);
+    if (gep) memcpy(key.scalar_per_member, gep->scalar_per_member, sizeof key.scalar_per_member);
+}
+
+// a plain (batch == 0) or batched request.  ev: the chain (nullptr: none); bep: which tensor operands of a batched chain are shared (nullptr: none)
+inline void qg_run_key_set(QRunKey& key, const qgemul_desc& d, uint32_t flags, int64_t batch, const EpView* ev, const qgemul_batched_ep* bep)
+{
+    qg_run_key_write(key, &d, 0, flags, batch, ev, bep, nullptr);
+}
+// a grouped request of groups >= 1 members.  ev: the group's one chain (nullptr: none); gep: which of its scalar stages take a value per member (nullptr: none)
+inline void qg_run_key_set_grouped(QRunKey& key, const qgemul_desc* d, int64_t groups, uint32_t flags, const EpView* ev, const qgemul_grouped_ep* gep)
+{
+    qg_run_key_write(key, d, groups, flags, 0, ev, nullptr, gep);
 }
 
 // Field by field: padding and reserved bytes of a caller's struct are not part of its meaning, and a descriptor that was not built
@@ -128,7 +162,9 @@ inline bool same_cmul(const qgemul_cmul& x, const qgemul_cmul& y)
 
 inline bool qg_run_key_equal(const QRunKey& x, const QRunKey& y)
 {
-    if (x.flags != y.flags || x.batch != y.batch || x.has_ep != y.has_ep || x.ep_cplx != y.ep_cplx || !same_desc(x.d, y.d)) return false;
+    if (x.flags != y.flags || x.batch != y.batch || x.groups != y.groups || x.has_ep != y.has_ep || x.ep_cplx != y.ep_cplx || !same_desc(x.d, y.d)) return false;
+    for (int64_t g = 0; g < x.groups; ++g)
+        if (!same_desc(x.member[g], y.member[g])) return false;
     if (x.has_ep && !same_epilogue(x.part[0], y.part[0])) return false;
     if (x.ep_cplx && (!same_epilogue(x.part[1], y.part[1]) || memcmp(x.e_complex, y.e_complex, sizeof x.e_complex))) return false;
     for (int k = 0; k < QG_MAX_EW; ++k) {
@@ -136,7 +172,7 @@ inline bool qg_run_key_equal(const QRunKey& x, const QRunKey& y)
         if (x.ax_on[k] && !same_approx(x.ax[k], y.ax[k])) return false;
         if (x.cx_on[k] && !same_cmul(x.cx[k], y.cx[k])) return false;
     }
-    return !memcmp(x.e_shared, y.e_shared, sizeof x.e_shared);
+    return !memcmp(x.e_shared, y.e_shared, sizeof x.e_shared) && !memcmp(x.scalar_per_member, y.scalar_per_member, sizeof x.scalar_per_member);
 }
 
 #pragma GCC visibility pop

@@ -1,5 +1,6 @@
 // The one-shot calls' plan key (qublas_amd/csrc/qg_run_key.h) on its own, under AddressSanitizer + UndefinedBehaviorSanitizer
-// (tests/test_run_key.py builds and runs this).  One descriptor, every kind of request an entry point of qgemul_run* can make.
+// (tests/test_run_key.py builds and runs this).  One descriptor and one group of three, every kind of request an entry point of
+// qgemul_run* can make.
 #include <stdio.h>
 
 #include "../../qublas_amd/csrc/qg_run_key.h"
@@ -18,22 +19,21 @@ static void put(qfmt& dst, qfmt v) { dst.I = v.I; dst.F = v.F; dst.S = v.S; dst.
 // assigned one by one — padding, reserved bytes and the entries beyond n_levels / n_stages / n_seg / n_coef keep the poison
 struct Inputs {
     qgemul_desc d;
+    qgemul_desc g[3];              // the members of a group: d's formats at three shapes, g[0] = d
     qgemul_epilogue ep;
     qgemul_approx t1, t2;          // t2: one coefficient differs
     qgemul_epilogue_cplx epc;
     qgemul_cmul basic, tf;
-    qgemul_batched_ep shared, per_member;
+    qgemul_batched_ep shared, per_member, shared0;   // shared0: the bit pattern of per0 below
+    qgemul_grouped_ep per_none, per0;                // no scalar stage per member; stage 0 per member
 
     void fill(int poison)
     {
         memset((void*)this, poison, sizeof *this);
-        d.abi = QGEMUL_ABI_VERSION; d.transA = 0; d.is_complex = 0; d.cmul = QG_CMUL_NONE; d.flags = 0;
-        d.M = 65; d.N = 33; d.K = 100; d.n_levels = 7;
-        for (int p = 0; p < 2; ++p) {
-            put(d.a[p], fmt(7, 8, 1, 5, 0)); put(d.b[p], fmt(7, 8, 1, 5, 0)); put(d.c[p], fmt(12, 8, 1, 5, 0));
-            for (uint32_t l = 0; l < d.n_levels; ++l) { put(d.level_add[p][l], fmt(20 + (int)l, 10, 1, 5, 0)); put(d.level[p][l], fmt(21 + (int)l, 10, 1, 5, 0)); }
-        }
-        for (int i = 0; i < 8; ++i) put(d.mul[i], fmt(14 + i, 16, 1, 5, 0));
+        desc(d, 65, 33, 100);
+        desc(g[0], 65, 33, 100);
+        desc(g[1], 3, 5, 7);
+        desc(g[2], 33, 17, 64);
         chain(ep, 0);
         chain(epc.part[0], 0);
         chain(epc.part[1], 1);
@@ -43,7 +43,20 @@ struct Inputs {
         basic.cmul = QG_CMUL_BASIC;
         tf.cmul = QG_CMUL_TF;
         for (int i = 0; i < 8; ++i) { put(basic.mul[i], fmt(10 + i, 6, 1, 5, 0)); put(tf.mul[i], fmt(10 + i, 6, 1, 5, 0)); }
-        for (int k = 0; k < QG_MAX_EW; ++k) { shared.e_shared[k] = k == 1; per_member.e_shared[k] = 0; }
+        for (int k = 0; k < QG_MAX_EW; ++k) {
+            shared.e_shared[k] = k == 1; per_member.e_shared[k] = 0; shared0.e_shared[k] = k == 0;
+            per_none.scalar_per_member[k] = 0; per0.scalar_per_member[k] = k == 0;
+        }
+    }
+    static void desc(qgemul_desc& d, int64_t M, int64_t N, int64_t K)
+    {
+        d.abi = QGEMUL_ABI_VERSION; d.transA = 0; d.is_complex = 0; d.cmul = QG_CMUL_NONE; d.flags = 0;
+        d.M = M; d.N = N; d.K = K; d.n_levels = 7;
+        for (int p = 0; p < 2; ++p) {
+            put(d.a[p], fmt(7, 8, 1, 5, 0)); put(d.b[p], fmt(7, 8, 1, 5, 0)); put(d.c[p], fmt(12, 8, 1, 5, 0));
+            for (uint32_t l = 0; l < d.n_levels; ++l) { put(d.level_add[p][l], fmt(20 + (int)l, 10, 1, 5, 0)); put(d.level[p][l], fmt(21 + (int)l, 10, 1, 5, 0)); }
+        }
+        for (int i = 0; i < 8; ++i) put(d.mul[i], fmt(14 + i, 16, 1, 5, 0));
     }
     // MUL by a scalar, ADD of a tensor, then a third stage (the one that carries a table or a record in the kinds that have one)
     static void chain(qgemul_epilogue& e, int part)
@@ -69,9 +82,14 @@ struct Inputs {
     }
 };
 
-enum Kind { PLAIN, CHAIN, CHAIN_T1, CHAIN_T2, CPLX, CPLX_BASIC, CPLX_TF, BATCH2, BATCH7, BCHAIN_SHARED, BCHAIN_MEMBER, BCHAIN_MEMBER_T1, NKIND };
+enum Kind { PLAIN, CHAIN, CHAIN_T1, CHAIN_T2, CPLX, CPLX_BASIC, CPLX_TF, BATCH1, BATCH2, BATCH7, BCHAIN_SHARED, BCHAIN_MEMBER, BCHAIN_MEMBER_T1,
+            GROUP1, GROUP3, GROUP3_LAST_K, GROUP3_ORDER, GCHAIN, GCHAIN_PER0, BCHAIN3_SHARED0, NKIND };
 static const char* const NAME[NKIND] = {"plain", "chain", "chain+table1", "chain+table2", "complex chain", "complex chain+CMUL basic", "complex chain+CMUL TF",
-                                        "batched 2", "batched 7", "batched chain shared", "batched chain per member", "batched chain per member+table1"};
+                                        "batched 1", "batched 2", "batched 7", "batched chain shared", "batched chain per member", "batched chain per member+table1",
+                                        "group of one", "group of three", "group of three, last K changed", "group of three, another order", "grouped chain",
+                                        "grouped chain, stage 0 per member", "batched 3 chain, stage 0 shared"};
+// the requests that hold the most: (c) sets and assigns every kind over each of them
+static const int LARGEST[2] = {BCHAIN_MEMBER_T1, GCHAIN_PER0};
 
 // the key as the entry point of that kind builds it (qg_run.hip)
 static void key_of(int kind, const Inputs& in, QRunKey& key)
@@ -84,6 +102,10 @@ static void key_of(int kind, const Inputs& in, QRunKey& key)
     const EpView ren = {&in.ep, nullptr, nullptr, none};
     const EpView cp = {&in.epc.part[0], &in.epc.part[1], in.epc.e_complex};
     const EpView cpx = {&in.epc.part[0], &in.epc.part[1], in.epc.e_complex, nullptr, &in.epc, cx};
+    // (the lists are copies: their padding and unused levels are those of `in`)
+    const qgemul_desc one[1] = {in.d}, three[3] = {in.g[0], in.g[1], in.g[2]}, order[3] = {in.g[2], in.g[0], in.g[1]};
+    qgemul_desc last_k[3] = {in.g[0], in.g[1], in.g[2]};
+    last_k[2].K = 65;   // (three[0] and the count stay)
     switch (kind) {
     case PLAIN: qg_run_key_set(key, in.d, 0, 0, nullptr, nullptr); break;
     case CHAIN: qg_run_key_set(key, in.d, 0, 0, &re, nullptr); break;
@@ -92,11 +114,19 @@ static void key_of(int kind, const Inputs& in, QRunKey& key)
     case CPLX: qg_run_key_set(key, in.d, 0, 0, &cp, nullptr); break;
     case CPLX_BASIC:
     case CPLX_TF: qg_run_key_set(key, in.d, 0, 0, &cpx, nullptr); break;
+    case BATCH1: qg_run_key_set(key, in.d, 0, 1, nullptr, nullptr); break;
     case BATCH2: qg_run_key_set(key, in.d, 0, 2, nullptr, nullptr); break;
     case BATCH7: qg_run_key_set(key, in.d, 0, 7, nullptr, nullptr); break;
     case BCHAIN_SHARED: qg_run_key_set(key, in.d, 0, 7, &ren, &in.shared); break;
     case BCHAIN_MEMBER: qg_run_key_set(key, in.d, 0, 7, &ren, &in.per_member); break;
     case BCHAIN_MEMBER_T1: qg_run_key_set(key, in.d, 0, 7, &rex, &in.per_member); break;
+    case GROUP1: qg_run_key_set_grouped(key, one, 1, 0, nullptr, &in.per_none); break;
+    case GROUP3: qg_run_key_set_grouped(key, three, 3, 0, nullptr, &in.per_none); break;
+    case GROUP3_LAST_K: qg_run_key_set_grouped(key, last_k, 3, 0, nullptr, &in.per_none); break;
+    case GROUP3_ORDER: qg_run_key_set_grouped(key, order, 3, 0, nullptr, &in.per_none); break;
+    case GCHAIN: qg_run_key_set_grouped(key, three, 3, 0, &ren, &in.per_none); break;
+    case GCHAIN_PER0: qg_run_key_set_grouped(key, three, 3, 0, &ren, &in.per0); break;
+    case BCHAIN3_SHARED0: qg_run_key_set(key, in.g[0], 0, 3, &ren, &in.shared0); break;   // (the batched twin of GCHAIN_PER0: same count, same bit pattern)
     }
 }
 
@@ -129,20 +159,22 @@ int main()
     for (int i = 0; i < NKIND; ++i)
         for (int j = 0; j < NKIND; ++j)
             if (i != j) expect(!qg_run_key_equal(a[i], b[j]), "kinds conflated", i, j);
-    // (c) no field keeps an earlier plan's value: set over the largest request, and assigned over it
-    for (int k = 0; k < NKIND; ++k) {
-        QRunKey over, assigned;
-        key_of(BCHAIN_MEMBER_T1, copy, over);
-        key_of(CPLX_TF, copy, assigned);
-        assigned = over;
-        expect(qg_run_key_equal(assigned, a[BCHAIN_MEMBER_T1]), "assignment", BCHAIN_MEMBER_T1, BCHAIN_MEMBER_T1);
-        key_of(k, first, over);
-        assigned = a[k];
-        expect(qg_run_key_equal(over, a[k]) && qg_run_key_equal(a[k], over), "set over a larger request", k, BCHAIN_MEMBER_T1);
-        expect(qg_run_key_equal(assigned, a[k]) && qg_run_key_equal(a[k], assigned), "assigned over a larger request", k, BCHAIN_MEMBER_T1);
-        for (int j = 0; j < NKIND; ++j)
-            if (j != k) expect(!qg_run_key_equal(over, b[j]) && !qg_run_key_equal(b[j], over), "set over a larger request conflates", k, j);
-    }
+    // (c) no field keeps an earlier plan's value: set over each of the largest requests, and assigned over it (a plain key over a
+    // grouped one drops the list, a group of one over a group of three shortens it)
+    for (int big : LARGEST)
+        for (int k = 0; k < NKIND; ++k) {
+            QRunKey over, assigned;
+            key_of(big, copy, over);
+            key_of(CPLX_TF, copy, assigned);
+            assigned = over;
+            expect(qg_run_key_equal(assigned, a[big]), "assignment", big, big);
+            key_of(k, first, over);
+            assigned = a[k];
+            expect(qg_run_key_equal(over, a[k]) && qg_run_key_equal(a[k], over), "set over a larger request", k, big);
+            expect(qg_run_key_equal(assigned, a[k]) && qg_run_key_equal(a[k], assigned), "assigned over a larger request", k, big);
+            for (int j = 0; j < NKIND; ++j)
+                if (j != k) expect(!qg_run_key_equal(over, b[j]) && !qg_run_key_equal(b[j], over), "set over a larger request conflates", k, j);
+        }
     // flags and every size are part of the key
     {
         QRunKey f;

@@ -183,6 +183,32 @@ def test_no_cpu_fallback():
     assert (out == 77).all()
 
 
+def test_one_shot_calls_classify_before_a_device_is_touched():
+    """The plain, the batched and the grouped one-shot call alike (qg_run.hip: acquire_plan): a descriptor or a list the classifier
+    rejects returns the classifier's status, not QG_ENOGPU; a valid request returns QG_ENOGPU and leaves the output buffers as they were."""
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("GPU present")
+    e = Qu(4, 3)
+    good = lower(e, e, e, 64, 64, 64)
+    bad = lower(e, e, e, 64, 64, 64, add_args=[Qu(5, 3, OfMode=4)])     # (test_rejections: a TCPL_SAT level whose sums leave the format)
+    want = capi.QG_EUNSUPPORTED
+    assert capi.classify_status(bad)[0] == want and capi.classify_batched_status(bad, 3)[0] == want and capi.classify_grouped_status([good, bad, good])[0] == want
+    assert capi.classify_status(good)[0] == capi.classify_batched_status(good, 3)[0] == capi.classify_grouped_status([good] * 3)[0] == capi.QG_OK
+    n = 64 * 64
+    A = np.zeros(3 * n, np.int32)
+    out = [np.full(3 * n, 77, np.int32)] + [np.full(n, 77, np.int32) for _ in range(3)]
+
+    def statuses(d, descs):
+        with pytest.raises(capi.QgemulError) as ei:
+            capi.run(d, out[0], A, A)
+        return [ei.value.status, capi.run_batched_status(d, 3, out[0], A, A, n, n, n), capi.run_grouped_status(descs, out[1:], [A] * 3, [A] * 3)]
+
+    assert statuses(bad, [good, bad, good]) == [want] * 3
+    assert statuses(good, [good] * 3) == [capi.QG_ENOGPU] * 3
+    assert all((o == 77).all() for o in out)
+
+
 def test_int32_kernels_need_32bit_formats():
     """Values may be small while a declared format is wide: the 32-bit tree kernels keep every format's
     bounds in 32-bit registers, so the planner must fall back to the 64-bit kernels (found on the GPU:

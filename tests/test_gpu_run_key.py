@@ -1,20 +1,24 @@
 """One thread, one cached plan, every kind of one-shot call in turn (qublas_amd/csrc/qg_run.hip: run_one_shot; qg_run_key.h: the key
 the cached plan is recognised by).  Each single-feature test alternates two kinds at most; a key that conflated two others — a
-batched plan taken for a plain one, a table or a CMUL record ignored, a shared operand taken for a per-member one — would return
+batched plan taken for a plain one, a table or a CMUL record ignored, a shared operand taken for a per-member one, a group taken for
+its first member or for the batch of its count, one member's K or the per-member pattern of a grouped chain ignored — would return
 another plan's results without an error, and only a walk over all kinds, forwards and backwards, sees it."""
 import numpy as np
 import pytest
 
 import batched_ep_cases as X
 import cmul_ref as R
+import grouped_ep_cases as GE
 import test_gpu_batched as TB
 import test_gpu_batched_ep as TE
 import test_gpu_cmul as TC
+import test_gpu_grouped as TG
 from qublas_amd import capi
 from qublas_amd.desc import Approx, Ew, EwC, Qu, lower, lower_epilogue, lower_epilogue_cplx_x, lower_epilogue_x
 
 pytestmark = pytest.mark.gpu
 POISON = X.POISON
+GROUP = [(65, 33, 100), (3, 5, 7), (33, 17, 64)]   # the members of the grouped requests; the first is the walk's plain shape
 
 
 def poisoned(n, dtype):
@@ -94,12 +98,41 @@ def requests(oracle):
         out.append((name, lambda o, ops=ops, strideE=strideE: capi.run_batched_epx(d, 3, ep, None, o, A, B, ops.host, sC, sA, sB, strideE), (2 * sC + extC, ddt),
                     TE.expected_buffer(oracle, d, dq, 3, exp, sC).tobytes()))
     assert exp_per[0].tobytes() != exp_shared[0].tobytes()
+
+    # grouped, the members' outputs back to back in the one buffer.  Behind the batched chains the same chain on a group, with one
+    # scalar for all and with stage 0 per member; then a group without a chain, and the same with only the LAST member's K changed
+    def views(o, members):
+        ends = np.cumsum([m.ext[2] for m in members])
+        return [o[e - m.ext[2]:e] for m, e in zip(members, ends)]
+
+    gchain = GE.Chain.named("q78_centred", "1_scale_shared_bias")
+    assert bytes(gchain.ep) == bytes(ep)
+    gm = [GE.fmt_member(oracle, "q78_centred", s, gchain, seed=880 + i, dist=1 if i == 0 else 0) for i, s in enumerate(GROUP)]
+    wide = 2                                        # the scalar for all; per member: 3, 4, 5
+    for i, m in enumerate(gm):
+        m.scal = [3 + i, None]
+    exp_wide, exp_own = [m.values(oracle, [wide, None]) for m in gm], [m.values(oracle) for m in gm]
+    assert all(w.tobytes() != o.tobytes() for w, o in zip(exp_wide, exp_own))
+    E1 = [m.E[1] for m in gm]
+    for name, pm, E0, S0, exp in (("run_grouped_epx one scalar", [0, 0], np.asarray([wide], dtype=oracle.host_dtype(stages[0].e)), None, exp_wide),
+                                  ("run_grouped_epx stage 0 per member", [1, 0], None, [m.scal[0] for m in gm], exp_own)):
+        out.append((name, lambda o, pm=pm, E0=E0, S0=S0: capi.run_grouped_epx([m.d for m in gm], gchain.ep, gchain.tabs, pm, views(o, gm), [m.A for m in gm],
+                                                                             [m.B for m in gm], [E0, E1], [S0, None]),
+                    (sum(m.ext[2] for m in gm), ddt), b"".join(e.tobytes() for e in exp)))
+    g3 = [TG.fmt_member(oracle, "q78_centred", s, seed=890 + i, dist=1 if i == 0 else 0) for i, s in enumerate(GROUP)]
+    g3k = g3[:2] + [TG.fmt_member(oracle, "q78_centred", GROUP[2][:2] + (65,), seed=892, dist=0)]
+    assert g3k[0].d is g3[0].d
+    for name, ms in (("run_grouped", g3), ("run_grouped last K", g3k)):
+        out.append((name, lambda o, ms=ms: capi.run_grouped([m.d for m in ms], views(o, ms), [m.A for m in ms], [m.B for m in ms]),
+                    (sum(m.ext[2] for m in ms), cdt), b"".join(m.expected(oracle).tobytes() for m in ms)))
+    # ... and, in front of the plain call, the group that holds the plain call's descriptor alone
+    out.insert(0, ("run_grouped [d]", lambda o: capi.run_grouped([d], [o], [mA[0]], [mB[0]]), (extC, cdt), TB.expected_buffer(oracle, d, ec, 1, Cx[:1], 0).tobytes()))
     return out
 
 
 def test_one_thread_alternates_every_entry_kind(oracle):
     reqs = requests(oracle)
-    assert len(reqs) == 10
+    assert len(reqs) == 15
     try:
         for name, call, (n, dtype), exp in reqs + reqs[::-1]:
             got = poisoned(n, dtype)

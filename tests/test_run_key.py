@@ -1,11 +1,16 @@
 """The one-shot calls' plan key (qublas_amd/csrc/qg_run_key.h: QRunKey, qg_run_key_set, qg_run_key_equal) under AddressSanitizer +
 UndefinedBehaviorSanitizer on the CPU.  The header has no HIP types, so the host compiler builds tests/san/run_key_driver.cpp with it
-alone.  For one descriptor the driver builds the key of every kind of request (plain, real chain, with one APPROX table and with
-another, complex chain, with a CMUL record and with another, batched at two counts, batched chain with a stage shared and per
-member) and checks that
-  (a) a key equals the key built from copies of its inputs whose padding, reserved bytes and unused entries differ,
-  (b) two different kinds never compare equal, in either order,
-  (c) a key set (or assigned) over one that held a larger request equals a freshly built one."""
+alone.  For one descriptor and one group of three the driver builds the key of every kind of request (plain, real chain, with one
+APPROX table and with another, complex chain, with a CMUL record and with another, batched at one, two and seven members, batched
+chain with a stage shared and per member; a group of one, of three, the three with only the last member's K changed and in another
+order, a grouped chain without and with a scalar stage per member, and the batched chain of the same count whose shared flags have
+that same bit pattern) and checks that
+  (a) a key equals the key built from copies of its inputs whose padding, reserved bytes and unused entries differ — the entries
+      of a group's descriptor list included,
+  (b) two different kinds never compare equal, in either order (a group of one, the plain request and a batch of one among them),
+  (c) a key set (or assigned) over one that held a larger request — the largest batched chain, and the grouped chain — equals a
+      freshly built one: a plain key over a grouped one drops the list, a group of one over a group of three shortens it.
+Leak detection is on: the key owns its APPROX tables and its descriptor list."""
 import os
 import subprocess
 

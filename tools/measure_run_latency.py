@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Wall time of the one-shot drop-in call qgemul_run (host buffers in, host buffers out) for small and large problems.
-Needs an MI355X."""
+"""Wall time of the one-shot drop-in call qgemul_run (host buffers in, host buffers out) for small and large problems, and of the
+batched and the grouped one-shot call on three small members.  Needs an MI355X."""
 import json
 import os
 import sys
@@ -27,3 +27,22 @@ for S, kw, reps in ((4, dict(mul_args=E88, add_args=[E88]), 200), (64, dict(mul_
         capi.run(d, C, A, B)
     dt = (time.perf_counter() - t0) / reps
     print(json.dumps({"S": S, "kernel": capi.KERNEL_NAMES[capi.classify(d).kernel], "ms_per_call": dt * 1e3}), flush=True)
+
+# the batched and the grouped one-shot call on small members: int<7,8> operands, two limbs each, every member in the one launch
+Q78 = Qu(7, 8)
+GROUP = [(65, 33, 100), (3, 5, 7), (33, 17, 64)]
+descs = [lower(Q78, Q78, Qu(20, 8), M, N, K, mul_args=Tags(15, 16), add_args=[Qu(28, 16)]) for M, N, K in GROUP]
+As = [rng.integers(Q78.raw_min, Q78.raw_max + 1, M * K, dtype=np.int32) for M, N, K in GROUP]
+Bs = [rng.integers(Q78.raw_min, Q78.raw_max + 1, K * N, dtype=np.int32) for M, N, K in GROUP]
+Cs = [np.zeros(M * N, dtype=np.int32) for M, N, K in GROUP]
+M, N, K = GROUP[0]
+A3, B3, C3 = np.concatenate([As[0]] * 3), np.concatenate([Bs[0]] * 3), np.zeros(3 * M * N, dtype=np.int32)
+calls = (("batched 3 x (65,33,100)", capi.classify_batched_status(descs[0], 3)[1], lambda: capi.run_batched(descs[0], 3, C3, A3, B3, M * N, M * K, K * N)),
+         ("grouped (65,33,100) (3,5,7) (33,17,64)", capi.classify_grouped_status(descs)[1], lambda: capi.run_grouped(descs, Cs, As, Bs)))
+for name, info, call in calls:
+    call()
+    t0 = time.perf_counter()
+    for _ in range(200):
+        call()
+    dt = (time.perf_counter() - t0) / 200
+    print(json.dumps({"call": name, "kernel": capi.KERNEL_NAMES[info.kernel], "ms_per_call": dt * 1e3}), flush=True)
