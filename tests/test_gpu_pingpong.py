@@ -2,7 +2,9 @@
 alternating on the matrix cores.  Every case runs the whole matrix through it AND through the lock-step kernel it replaced
 (QG_OPT_LOCKSTEP_TILES, k_mfma16 on 64-byte k-tiles: different packing, tiles and pipeline) and compares all outputs, then a
 block against the oracle.  Shapes cover one and two k-tiles (the prologue's clamped refills), odd numbers of k-tiles, ragged
-M / N / K (padding inside the packed tiles), every C container and every QuMode x OfMode of the one conversion."""
+M / N / K (padding inside the packed tiles), every C container and ten C formats on generator data.  Every QuMode and OfMode of the one
+conversion at C's ties and bounds, in every tile and lane position, is pinned by tests/test_gpu_linear_c.py (sites pp, pp_cent_u8,
+wide_pp and k256)."""
 import numpy as np
 import pytest
 
